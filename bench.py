@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scan-pair registrations/s on the BASELINE.json workload (synthetic 1M-point pair, 1xMI355X per rank).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one alignPointClouds-equivalent (lgr_align_dev: voxel downsample -> k-NN normals -> FPFH -> brute-force
@@ -25,6 +25,9 @@ Rank 0 prints ONE JSON line with the contract keys plus
                    compared values and of bit mismatches (each oracle stage is fed with the HIP output of the stage
                    before), the sampled matcher queries (index and distance bits), and whether the staged chain equals
                    the timed one-call pipeline.  `--verify` forces this leg even with --no-cpu-baseline.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's lgr_result) as DIR/<name>.npy, so that two
+builds run with the same arguments (same seeded pair, same parameters) can be compared output for output.
 """
 import argparse
 import json
@@ -80,7 +83,14 @@ def parse():
                     help="lgr_ctx_options.arithmetic: fast (default) or PCL's own FPFH weighting order and rounding steps (include/lgr.h)")
     ap.add_argument("--match-opt", action="append", default=[], metavar="FIELD=VALUE",
                     help="lgr_match_options override for ablations / profiles (e.g. coarse_rejection=0); never changes results")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the result of the last timed step (rank 0's pair) as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.dry_run or args.job):
+        ap.error("--dump-outputs writes the headline step's result; --dry-run and --job have none")
+    return args
 
 
 def fan_out(args):
@@ -296,6 +306,20 @@ def _usable_cores():
         except Exception:
             continue
     return cores
+
+
+# the computed fields of lgr_result (include/lgr.h); time_cs, time_te and stage_ms are timings and differ from run to run
+RESULT_SCALARS = ("iterations", "converged", "n_inliers", "metric", "best_metric_before_refit", "best_iteration", "num_rejections",
+                  "estimated_iters", "n_correspondences")
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: `res` (the lgr_result of the last timed step) as out_dir/transformation.npy (4x4 float32, row major) and one
+    out_dir/<field>.npy per computed scalar (float64 0-d arrays; exact for the int32 counts and the float32 metrics)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "transformation.npy"), res.matrix())
+    for name in RESULT_SCALARS:
+        np.save(os.path.join(out_dir, name + ".npy"), np.array(getattr(res, name), np.float64))
 
 
 def _bits(a):
@@ -616,6 +640,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
 
     if rank == 0:
         n_dir = 1 if args.matching == "one_sided" else 2

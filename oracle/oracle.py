@@ -85,8 +85,9 @@ _ref = None
 def ref_utils(build_if_possible=True):
     """The reference's own std-only translation units (src/utils.cpp, src/csv_parser.cpp + headers) behind the extern "C"
     shim oracle/ref/ref_utils_shim.cpp -> oracle/_ref/liblgr_ref_utils.so (recipe: `make -C oracle ref`; needs
-    /root/reference, so it is built in the authoring container and travels to the GPU box as a built file).
-    Returns the ctypes library or None when it is neither present nor buildable."""
+    /root/reference, so it is built in the authoring container only).  tests/golden/make_ref_fixtures.py records its outputs
+    into tests/golden/ref_utils.json, which is what the tests read.  Returns the ctypes library or None when it is neither
+    present nor buildable."""
     global _ref
     if _ref is None:
         if not os.path.exists(_REF_SO) and build_if_possible and os.path.isdir("/root/reference/include"):

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -51,3 +52,28 @@ def test_bench_single_context_mode():
     assert r.returncode == 0, r.stderr[-3000:]
     d = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][0]
     assert d["host"]["threads_per_rank"] == 1 and d["host"]["helper_contexts"] == 0 and d["result"]["converged"] == 1
+
+
+def test_bench_dump_outputs_is_the_timed_result(tmp_path):
+    """--dump-outputs DIR: the last timed step's lgr_result as DIR/<name>.npy (float32 / float64), the same as the JSON line reports; two
+    runs with different step counts compute the same pair and write identical files."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for steps in ("2", "1"):
+        out = tmp_path / ("steps" + steps)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", "1", "--points", "200000",
+                            "--no-cpu-baseline", "--no-stage-rooflines", "--no-matcher-extremes", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][0]
+        assert d["steps"] == int(steps) and d["ms_per_step"] > 0
+        files = {f.name: np.load(f) for f in out.iterdir()}
+        assert set(files) == {"transformation.npy"} | {n + ".npy" for n in ("iterations", "converged", "n_inliers", "metric", "best_metric_before_refit",
+                                                                           "best_iteration", "num_rejections", "estimated_iters", "n_correspondences")}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert files["transformation.npy"].shape == (4, 4) and sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+        for k in ("converged", "iterations", "n_correspondences", "n_inliers"):
+            assert files[k + ".npy"] == d["result"][k], k
+        dumps.append(files)
+    for k, a in dumps[0].items():
+        np.testing.assert_array_equal(a, dumps[1][k], err_msg=k)

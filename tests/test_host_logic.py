@@ -163,6 +163,15 @@ def test_bench_rejects_world_size_mismatch():
     assert r.returncode != 0 and not out
 
 
+def test_bench_rejects_bad_step_counts_and_dump_without_headline_step(tmp_path):
+    """--steps is the number of timed steps (ms_per_step divides by it): fewer than one is refused, as is --dump-outputs with a mode that
+    runs no headline step -- before any rank or GPU is touched."""
+    for argv in (("--steps", "0"), ("--warmup", "-1"), ("--dump-outputs", str(tmp_path / "out"))):
+        r, out = _run_bench("--gpus", "1", "--dry-run", *argv)
+        assert r.returncode == 2 and not out and "error" in r.stderr, argv
+    assert not (tmp_path / "out").exists()
+
+
 def test_bench_force_collective_one_rank_group():
     """--force-collective: a one-rank process group is formed without a launcher and the record all-gather goes through it (gloo here;
     the -m gpu twin in tests/test_gpu_bench_ranks.py runs the same code on RCCL)."""
