@@ -12,6 +12,7 @@
  *     error); nothing throws across the ABI.  "not converged" is NOT an error: see lgr_result.converged.
  *   - point  : 12 floats, pcl::PointXYZINormal layout {x,y,z,1 | nx,ny,nz,0 | intensity,curvature,pad,pad} (48 B)
  *   - fpfh   : 33 floats (pcl::FPFHSignature33, 132 B, row-major M x 33)
+ *   - shot   : 352 floats (pcl::SHOT352::descriptor, 1408 B, row-major M x 352); frames 9 floats (pcl::ReferenceFrame)
  *   - corr   : lgr_corr (include/common.h:120-127 Correspondence), 16 B
  *   - T      : 16 floats COLUMN-major (Eigen::Matrix4f default)
  *   - host entry points (no suffix) borrow caller memory for the duration of the call, upload, run the device
@@ -104,7 +105,7 @@ typedef struct {
     int32_t estimated_iters;
     int32_t n_correspondences;
     double  time_cs, time_te;    /* seconds, device-synchronised wall time */
-    float   stage_ms[12];        /* 0 downsample 1 normals 2 fpfh 3 match 4 filter 5 ransac 6 refit (hipEvent) */
+    float   stage_ms[12];        /* 0 downsample 1 normals 2 fpfh (the descriptor stage: FPFH or SHOT) 3 match 4 filter 5 ransac 6 refit (hipEvent) */
 } lgr_result;
 
 typedef struct lgr_ctx lgr_ctx;
@@ -253,6 +254,19 @@ int lgr_normals_knn_dev(lgr_ctx*, float* d_pts, int n, const float* d_surf, int 
  * more than 2^32 / 48 - 2 surface points (32-bit row offsets into the SPFH table). */
 int lgr_fpfh(lgr_ctx*, const float* kps, int m, const float* surf, int n, float radius, float* out_m_x_33);
 int lgr_fpfh_dev(lgr_ctx*, const float* d_kps, int m, const float* d_surf, int n, float radius, float* d_out);
+/* ---- SHOT352 (include/common.h estimateFeatures<SHOT>: pcl::SHOTEstimationOMP<PointXYZINormal, PointXYZINormal, SHOT352> with
+ *      pcl::SHOTLocalReferenceFrameEstimation at the same radius on the same surface) ----
+ * lrf rows: 9 floats per key point, x, y, z axes (pcl::ReferenceFrame); NaN rows where no frame exists (fewer than 5 neighbours that
+ * differ from the key point, a non-finite key point).  shot rows: 352 floats (pcl::SHOT352::descriptor); NaN rows for a NaN frame,
+ * fewer than 5 neighbours (the key point itself counted) or a non-finite key point.  lrf == NULL: the frames are estimated, else
+ * the given frames are used; out_lrf (optional) receives the frames used.  Neighbours in ascending (squared distance, index) order,
+ * the eigen-decomposition and acos / atan2 are the canonical ones of DESIGN.md section 4 (csrc/lgr_shot_math.h). */
+int lgr_shot_lrf(lgr_ctx*, const float* kps, int m, const float* surf, int n, float radius, float* out_m_x_9);
+int lgr_shot_lrf_dev(lgr_ctx*, const float* d_kps, int m, const float* d_surf, int n, float radius, float* d_out_m_x_9);
+int lgr_shot(lgr_ctx*, const float* kps, int m, const float* surf, int n, float radius, const float* lrf_or_null,
+             float* out_m_x_352, float* out_lrf_or_null);
+int lgr_shot_dev(lgr_ctx*, const float* d_kps, int m, const float* d_surf, int n, float radius, const float* d_lrf_or_null,
+                 float* d_out_m_x_352, float* d_out_lrf_or_null);
 /* Device self-check of the FPFH weighting kernel's reciprocal (v_rcp_f32 + one Newton step in place of the IEEE division sequence;
  * include/common.h:322-332 -> pcl::FPFHEstimation::weightPointSPFHSignature's 1.0f / dists[idx]): every float whose bit pattern lies in
  * [lo_bits, hi_bits] goes through both; out2[0] = values where they differ (must be 0 on [1e-36, 1e36], the range the kernel uses it on),
@@ -270,6 +284,14 @@ int lgr_match_bf_dev(lgr_ctx*, const float* d_q33, int mq, const float* d_t33, i
 /* both directions in one MFMA pass (what LeftToRight/Cluster matchers need, include/matching.h:431-432,495-496) */
 int lgr_match_bf2_dev(lgr_ctx*, const float* d_a33, int ma, const float* d_b33, int mb, int block,
                       int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
+/* ---- include/matching.h:373-376 matchBF<SHOT>(query, train, params): the contract of lgr_match_bf on M x 352 rows (OpenCV 4.5.1's
+ *      normL2Sqr lane order for n = 352: 22 blocks of 16, no tail; ties: the later bf block, then the lower index; NaN rows never
+ *      match).  An exact dense scan: every (query, train) distance is the canonical one. ---- */
+int lgr_match_shot(lgr_ctx*, const float* q352, int mq, const float* t352, int mt, int block, int32_t* idx, float* dist);
+int lgr_match_shot_dev(lgr_ctx*, const float* d_q352, int mq, const float* d_t352, int mt, int block, int32_t* d_idx, float* d_dist);
+/* both directions from one pass over the (a, b) distances */
+int lgr_match2_shot_dev(lgr_ctx*, const float* d_a352, int ma, const float* d_b352, int mb, int block,
+                        int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
 /* ---- include/matching.h:373-376 matchFLANN<FPFH>(query_features, train_features, parameters), randomness 1 (:565-592):
  *      pcl::KdTreeFLANN is an exact search, so the nearest row is the one matchBF finds (the reference's own test asserts that,
  *      tests/flann_bf_matcher.h:82-83); what differs is the reported distance: sqrt of FLANN's L2_Simple (sequential sum of
@@ -334,6 +356,27 @@ int lgr_filter_dev(lgr_ctx*, int matching_id, const float* d_src, int ns, const 
 int lgr_correspondences(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, lgr_corr* out, int* n_out);
 int lgr_correspondences_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params*, lgr_corr* d_out, int* n_out /* host */);
 
+/* ---- the descriptor of the correspondence search (AlignmentParameters.descriptor_id / lrf_id, include/common.h:148) ----
+ * A struct of its own so that lgr_params keeps its revision-5 layout.  NULL = FPFH: lgr_correspondences_ex*(..., NULL) and
+ * lgr_align_ex*(..., NULL) are lgr_correspondences* and lgr_align*.  SHOT is built for the brute-force matcher only: SHOT with
+ * use_bfmatcher = 0, with has_guess, or on a context whose arithmetic is LGR_ARITH_PCL returns LGR_ERR_UNSUPPORTED (the
+ * arithmetic modes differ in the FPFH weighting only and mean nothing for SHOT; the SHOT stage has one arithmetic).  lrf_id
+ * matters to SHOT only (FPFH never reads it, as in the reference): LGR_LRF_DEFAULT is built, the reference's 'gravity' and 'gt' frames
+ * (src/common.cpp:693-755) return LGR_ERR_UNSUPPORTED, other values LGR_ERR_INVALID_ARG.
+ * lgr_result.stage_ms[2] ("fpfh") carries the descriptor stage, whichever descriptor ran. */
+enum { LGR_DESCRIPTOR_FPFH = 0, LGR_DESCRIPTOR_SHOT = 1 };
+enum { LGR_LRF_DEFAULT = 0, LGR_LRF_GRAVITY = 1, LGR_LRF_GT = 2 };   /* gravity / gt: LGR_ERR_UNSUPPORTED */
+typedef struct {
+    int32_t descriptor_id;   /* LGR_DESCRIPTOR_FPFH / LGR_DESCRIPTOR_SHOT */
+    int32_t lrf_id;          /* LGR_LRF_DEFAULT (SHOT only) */
+    int32_t reserved[6];     /* 0 */
+} lgr_feature_params;
+void lgr_default_feature_params(lgr_feature_params* f);      /* FPFH, default frames */
+int lgr_correspondences_ex(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, const lgr_feature_params*,
+                           lgr_corr* out, int* n_out);
+int lgr_correspondences_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params*, const lgr_feature_params*,
+                               lgr_corr* d_out, int* n_out /* host */);
+
 /* ---- include/sac_prerejective_omp.h:21-56 SampleConsensusPrerejectiveOMP(src,tgt,corrs,params).align() ----
  * final_mask (optional): c bytes, inlier mask of the refit transform */
 int lgr_ransac(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
@@ -374,6 +417,11 @@ int lgr_refit_svd_dev(lgr_ctx*, const float* d_src, const float* d_tgt, const lg
  *      alignRansac (:14-19) is lgr_ransac; alignGror (:21-35) via params.alignment_id ---- */
 int lgr_align(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, lgr_result*);
 int lgr_align_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params*, lgr_result* /* host */);
+
+/* lgr_align with the descriptor of lgr_feature_params (NULL: FPFH, i.e. lgr_align) */
+int lgr_align_ex(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, const lgr_feature_params*, lgr_result*);
+int lgr_align_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params*, const lgr_feature_params*,
+                     lgr_result* /* host */);
 
 /* ---- alignGror(src, tgt, correspondences, parameters) (src/alignment.cpp:21-35) =
  *      pcl::registration::GRORInitialAlignment::computeTransformation (include/gror/ia_gror.hpp:367-415) with

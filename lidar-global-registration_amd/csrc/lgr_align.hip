@@ -170,6 +170,13 @@ static int filter_core(lgr_ctx* ctx, int matching_id, int ns, const int32_t* d_i
 
 static void tick(lgr_ctx* ctx, int i) { (void) hipEventRecord(ctx->ev[i], ctx->stream); }
 
+// the descriptor of the correspondence search (lgr_feature_params): its row length and its feature stage
+static int desc_len(int descriptor) { return descriptor == LGR_DESCRIPTOR_SHOT ? 352 : 33; }
+static int descriptor_dev(lgr_ctx* ctx, int descriptor, const float* kps, int m, const float* surf, int n, float radius, float* out) {
+    if (descriptor == LGR_DESCRIPTOR_SHOT) return lgr_shot_dev(ctx, kps, m, surf, n, radius, nullptr, out, nullptr);
+    return lgr_fpfh_dev(ctx, kps, m, surf, n, radius, out);
+}
+
 // ---- multi-scale matching (feature_radius unset): include/matching.h:176-262 (initialize) and :264-352
 // (match_multiscale).  The heavy stages (5-NN, down-sampling chain, normals, FPFH, brute-force matching per level) run on
 // the device; the per-key-point level assignment (log2f/sqrtf of the reference's host arithmetic, level pruning) and
@@ -180,7 +187,7 @@ struct MsSide {
     int min_l2 = INT_MAX, max_l2 = INT_MIN;
     std::vector<std::vector<int>> lists;   // per scale: key-point indices
     std::vector<size_t> feat_off;          // per scale: row offset into the feature buffer
-    float* feat = nullptr;                 // device, sum(rows) x 33
+    float* feat = nullptr;                 // device, sum(rows) x D (D = 33 FPFH, 352 SHOT)
     int32_t* d_lists = nullptr;            // device copy of the lists, concatenated like feat_off
     std::vector<float> xyz;                // host copy of the key points (3 floats each) for the vote
 };
@@ -192,7 +199,8 @@ __global__ void gather_rows12_kernel(const float* __restrict__ pts, const int32_
 }
 
 static int ms_initialize(lgr_ctx* ctx, MsSide& st, int side, const float* d_pcd, int n, const float* d_kps, int n_kps, float iss_radius,
-                         const lgr_params* p, const float* vp, float* ms) {
+                         const lgr_params* p, int descriptor, const float* vp, float* ms) {
+    const int D = desc_len(descriptor);
     st.n_kps = n_kps; st.iss_radius = iss_radius;
     const int k = 5;
     LGR_CHECK(ctx, n >= k, LGR_ERR_INVALID_ARG);
@@ -233,13 +241,13 @@ static int ms_initialize(lgr_ctx* ctx, MsSide& st, int side, const float* d_pcd,
     st.feat_off.assign(nr_scales + 1, 0);
     for (int i = 0; i < nr_scales; ++i) st.feat_off[i + 1] = st.feat_off[i] + st.lists[i].size();
     const size_t rows = st.feat_off[nr_scales];
-    LGR_TRY(lgr_ws_t(ctx, side == 0 ? WS_MS_FEAT_S : WS_MS_FEAT_T, rows * 33 + 1, &st.feat));
+    LGR_TRY(lgr_ws_t(ctx, side == 0 ? WS_MS_FEAT_S : WS_MS_FEAT_T, rows * D + 1, &st.feat));
     LGR_TRY(lgr_ws_t(ctx, side == 0 ? WS_MS_LIST_S : WS_MS_LIST_T, rows + 1, &st.d_lists));
     for (int i = 0; i < nr_scales; ++i)
         if (!st.lists[i].empty())
             LGR_HIP(ctx, hipMemcpyAsync(st.d_lists + st.feat_off[i], st.lists[i].data(), st.lists[i].size() * 4, hipMemcpyHostToDevice, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // :228-261 per scale: down-sample the previous level's cloud, normals, FPFH of the level's key points
+    // :228-261 per scale: down-sample the previous level's cloud, normals, descriptors of the level's key points
     float *bufA, *bufB, *sub;
     LGR_TRY(lgr_ws_t(ctx, side == 0 ? WS_PIPE_SURF_S : WS_PIPE_SURF_T, (size_t) n * 12, &bufA));
     LGR_TRY(lgr_ws_t(ctx, WS_MS_SURF2, (size_t) n * 12, &bufB));
@@ -259,7 +267,7 @@ static int ms_initialize(lgr_ctx* ctx, MsSide& st, int side, const float* d_pcd,
         const int m = (int) st.lists[i].size();
         if (m) {
             gather_rows12_kernel<<<cdiv((long long) m * 12, 256), 256, 0, ctx->stream>>>(d_kps, st.d_lists + st.feat_off[i], m, sub);
-            LGR_TRY(lgr_fpfh_dev(ctx, sub, m, out, nd, search_radius, st.feat + st.feat_off[i] * 33));
+            LGR_TRY(descriptor_dev(ctx, descriptor, sub, m, out, nd, search_radius, st.feat + st.feat_off[i] * D));
         }
         tick(ctx, 3);
         LGR_HIP(ctx, hipEventSynchronize(ctx->ev[3]));
@@ -317,8 +325,12 @@ static void inverse4(const float* m16, float* out16) {
 
 // the matcher dispatch of match_multiscale (include/matching.h:294-312): guess -> matchLocal in both directions (the inverse guess
 // for train -> query, :296), else bf -> matchBF (one MFMA pass serves both directions), else matchFLANN
-static int match_dispatch(lgr_ctx* ctx, const lgr_params* p, const float* a_pts, const float* fa, int ma, const float* b_pts, const float* fb, int mb,
+static int match_dispatch(lgr_ctx* ctx, const lgr_params* p, int descriptor, const float* a_pts, const float* fa, int ma, const float* b_pts, const float* fb, int mb,
                           bool need_ba, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
+    if (descriptor == LGR_DESCRIPTOR_SHOT) {   // (checked on entry: SHOT runs the brute-force matcher only)
+        if (need_ba) return lgr_match2_shot_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d, ba_i, ba_d);
+        return lgr_match_shot_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d);
+    }
     if (p->has_guess) {
         LGR_TRY(lgr_match_local_dev(ctx, a_pts, ma, b_pts, mb, fa, fb, p->guess, p->match_search_radius, ab_i, ab_d));
         if (need_ba) {
@@ -337,11 +349,12 @@ static int match_dispatch(lgr_ctx* ctx, const lgr_params* p, const float* a_pts,
 }
 
 static int ms_match_tables(lgr_ctx* ctx, const float* const* clouds, const int* sizes, const float* const* kclouds, const int* ksizes,
-                           const lgr_params* p, int32_t* d_ij, float* d_dij, int32_t* d_ji, float* d_dji, float* ms) {
+                           const lgr_params* p, int descriptor, int32_t* d_ij, float* d_dij, int32_t* d_ji, float* d_dji, float* ms) {
+    const int D = desc_len(descriptor);
     MsSide st[2];
     for (int c = 0; c < 2; ++c) {
         const float* vp = c == 0 ? (p->has_vp_src ? p->vp_src : nullptr) : (p->has_vp_tgt ? p->vp_tgt : nullptr);
-        LGR_TRY(ms_initialize(ctx, st[c], c, clouds[c], sizes[c], kclouds[c], ksizes[c], c == 0 ? p->iss_radius_src : p->iss_radius_tgt, p, vp, ms));
+        LGR_TRY(ms_initialize(ctx, st[c], c, clouds[c], sizes[c], kclouds[c], ksizes[c], c == 0 ? p->iss_radius_src : p->iss_radius_tgt, p, descriptor, vp, ms));
     }
     tick(ctx, 4);
     const bool need_ji = p->matching_id != LGR_MATCH_ONE_SIDED;
@@ -359,8 +372,8 @@ static int ms_match_tables(lgr_ctx* ctx, const float* const* clouds, const int* 
         LGR_TRY(lgr_ws_t(ctx, WS_MS_RES, (size_t) 2 * (ma + mb) + 4, &r));
         int32_t *ab_i = r, *ba_i = r + ma;
         float *ab_d = (float*) (r + ma + mb), *ba_d = ab_d + ma;
-        const float* fa = st[0].feat + st[0].feat_off[ia] * 33;
-        const float* fb = st[1].feat + st[1].feat_off[ib] * 33;
+        const float* fa = st[0].feat + st[0].feat_off[ia] * D;
+        const float* fb = st[1].feat + st[1].feat_off[ib] * D;
         const float *pa = nullptr, *pb = nullptr;
         if (p->has_guess) {   // matchLocal works on the level's key-point sub-clouds (kps_multiscale, include/matching.h:243)
             float* sub;
@@ -369,7 +382,7 @@ static int ms_match_tables(lgr_ctx* ctx, const float* const* clouds, const int* 
             gather_rows12_kernel<<<cdiv((long long) mb * 12, 256), 256, 0, ctx->stream>>>(kclouds[1], st[1].d_lists + st[1].feat_off[ib], mb, sub + (size_t) ma * 12);
             pa = sub; pb = sub + (size_t) ma * 12;
         }
-        LGR_TRY(match_dispatch(ctx, p, pa, fa, ma, pb, fb, mb, need_ji, ab_i, ab_d, ba_i, ba_d));
+        LGR_TRY(match_dispatch(ctx, p, descriptor, pa, fa, ma, pb, fb, mb, need_ji, ab_i, ab_d, ba_i, ba_d));
         std::vector<int32_t> h((size_t) 2 * (ma + mb));
         LGR_HIP(ctx, hipMemcpyAsync(h.data(), r, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -409,11 +422,41 @@ __global__ void finalize_kernel(lgr_corr* __restrict__ corr, int n, const int32_
     corr[i].index_match = kt[corr[i].index_match];
 }
 
+extern "C" void lgr_default_feature_params(lgr_feature_params* f) {
+    if (!f) return;
+    memset(f, 0, sizeof(*f));
+    f->descriptor_id = LGR_DESCRIPTOR_FPFH;
+    f->lrf_id = LGR_LRF_DEFAULT;
+}
+
+// the descriptor a feature-parameter struct selects, checked against the rest of the configuration (NULL: FPFH)
+static int feature_descriptor(lgr_ctx* ctx, const lgr_params* p, const lgr_feature_params* f, int* descriptor) {
+    *descriptor = LGR_DESCRIPTOR_FPFH;
+    if (!f) return LGR_OK;
+    LGR_CHECK(ctx, f->descriptor_id == LGR_DESCRIPTOR_FPFH || f->descriptor_id == LGR_DESCRIPTOR_SHOT, LGR_ERR_UNSUPPORTED);
+    if (f->descriptor_id == LGR_DESCRIPTOR_SHOT) {    // the frames matter to SHOT only (FPFH never reads lrf_id, include/common.h:366,407)
+        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT || f->lrf_id == LGR_LRF_GRAVITY || f->lrf_id == LGR_LRF_GT, LGR_ERR_INVALID_ARG);
+        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT, LGR_ERR_UNSUPPORTED);
+        LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);     // matchFLANN / matchLocal are built for FPFH only
+        LGR_CHECK(ctx, ctx->opt.arithmetic != LGR_ARITH_PCL, LGR_ERR_UNSUPPORTED);  // the arithmetic modes are FPFH weightings
+    }
+    *descriptor = f->descriptor_id;
+    return LGR_OK;
+}
+
 extern "C" int lgr_correspondences_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p,
                                        lgr_corr* d_out, int* n_out) {
+    return lgr_correspondences_ex_dev(ctx, d_src, ns, d_tgt, nt, p, nullptr, d_out, n_out);
+}
+
+extern "C" int lgr_correspondences_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p,
+                                          const lgr_feature_params* fp, lgr_corr* d_out, int* n_out) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (d_src || ns == 0) && (d_tgt || nt == 0) && p && n_out && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
+    int descriptor;
+    LGR_TRY(feature_descriptor(ctx, p, fp, &descriptor));
+    const int D = desc_len(descriptor);
     if (ns < 2 || nt < 2) { *n_out = 0; return LGR_OK; }   // nothing to match (the reference ends with an empty correspondence list)
     LGR_CHECK(ctx, d_out != nullptr, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, p->randomness == 1, LGR_ERR_UNSUPPORTED);        // data/test.yaml:14 "currently only 1 is supported"
@@ -461,8 +504,8 @@ extern "C" int lgr_correspondences_dev(lgr_ctx* ctx, const float* d_src, int ns,
     ns = ksizes[0]; nt = ksizes[1];
     float* feat[2];
     float* surf[2];
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_S, (size_t) ns * 33, &feat[0]));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_T, (size_t) nt * 33, &feat[1]));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_S, (size_t) ns * D, &feat[0]));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_T, (size_t) nt * D, &feat[1]));
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_S, (size_t) sizes[0] * 12, &surf[0]));
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_T, (size_t) sizes[1] * 12, &surf[1]));
     float ms[3] = {0, 0, 0};
@@ -492,7 +535,7 @@ extern "C" int lgr_correspondences_dev(lgr_ctx* ctx, const float* d_src, int ns,
         if (rc != LGR_OK) { ctx->err = ctx->aux2->err; return rc; }
     }
     if (multiscale) {
-        LGR_TRY(ms_match_tables(ctx, clouds, sizes, kclouds, ksizes, p, ij, dij, ji, dji, ms));
+        LGR_TRY(ms_match_tables(ctx, clouds, sizes, kclouds, ksizes, p, descriptor, ij, dij, ji, dji, ms));
     } else {
     // The two clouds' feature stages are independent until the matcher: the source cloud runs on this context, the target cloud
     // on a second context (own stream and workspace) driven by a second host thread, so that the ~20 host read-backs per cloud
@@ -509,7 +552,7 @@ extern "C" int lgr_correspondences_dev(lgr_ctx* ctx, const float* d_src, int ns,
         tick(cx, 2);
         // :243-246 re-estimates the normals of the key-point COPY; FPFH reads only the surface normals
         // (include/common.h:329), so that step has no observable effect and is not executed.
-        LGR_TRY(lgr_fpfh_dev(cx, kclouds[c], ksizes[c], surf[c], nd, search_radius, feat[c]));            // :248
+        LGR_TRY(descriptor_dev(cx, descriptor, kclouds[c], ksizes[c], surf[c], nd, search_radius, feat[c]));   // :248
         tick(cx, 3);
         LGR_HIP(cx, hipEventSynchronize(cx->ev[3]));
         float t;
@@ -521,7 +564,7 @@ extern "C" int lgr_correspondences_dev(lgr_ctx* ctx, const float* d_src, int ns,
     // The source cloud is done first (this thread): the matcher's query-side half (clustering, assignment, sort) runs right behind
     // its features, under the target cloud's feature kernels on the second context.
     const bool both_dirs = p->matching_id != LGR_MATCH_ONE_SIDED;
-    const bool prepare_query = p->use_bfmatcher && !p->has_guess;   // match_dispatch: the brute-force matcher will be called
+    const bool prepare_query = p->use_bfmatcher && !p->has_guess && descriptor == LGR_DESCRIPTOR_FPFH;   // match_dispatch: the FPFH brute-force matcher will be called
     struct PrepGuard { lgr_ctx* c; ~PrepGuard() { lgr_match_prepare_cancel(c); } } prep_guard{ctx};
     LGR_TRY(lgr_run_pair(ctx,
         [&](lgr_ctx* cx) {
@@ -538,7 +581,7 @@ extern "C" int lgr_correspondences_dev(lgr_ctx* ctx, const float* d_src, int ns,
         if (sum > 0.f) for (int s = 0; s < 3; ++s) ms[s] *= wall / sum;
     }
     tick(ctx, 4);
-    LGR_TRY(match_dispatch(ctx, p, kclouds[0], feat[0], ns, kclouds[1], feat[1], nt, p->matching_id != LGR_MATCH_ONE_SIDED, ij, dij, ji, dji));
+    LGR_TRY(match_dispatch(ctx, p, descriptor, kclouds[0], feat[0], ns, kclouds[1], feat[1], nt, p->matching_id != LGR_MATCH_ONE_SIDED, ij, dij, ji, dji));
     }
     tick(ctx, 5);
     if (tables_guard.armed) {
@@ -558,6 +601,11 @@ extern "C" int lgr_correspondences_dev(lgr_ctx* ctx, const float* d_src, int ns,
 }
 
 extern "C" int lgr_correspondences(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, lgr_corr* out, int* n_out) {
+    return lgr_correspondences_ex(ctx, src, ns, tgt, nt, p, nullptr, out, n_out);
+}
+
+extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
+                                      lgr_corr* out, int* n_out) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (src || ns == 0) && (tgt || nt == 0) && p && n_out && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
@@ -571,19 +619,26 @@ extern "C" int lgr_correspondences(lgr_ctx* ctx, const float* src, int ns, const
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));
     LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
     LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_TRY(lgr_correspondences_dev(ctx, ds, ns, dt, nt, p, dc, n_out));
+    LGR_TRY(lgr_correspondences_ex_dev(ctx, ds, ns, dt, nt, p, fp, dc, n_out));
     if (*n_out) LGR_HIP(ctx, hipMemcpyAsync(out, dc, (size_t) *n_out * 16, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LGR_OK;
 }
 
 extern "C" int lgr_align_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, lgr_result* res) {
+    return lgr_align_ex_dev(ctx, d_src, ns, d_tgt, nt, p, nullptr, res);
+}
+
+extern "C" int lgr_align_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
+                                lgr_result* res) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (d_src || ns == 0) && (d_tgt || nt == 0) && p && res && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
     // alignTeaser throws in the reference (src/alignment.cpp:40)
     LGR_CHECK(ctx, p->alignment_id == LGR_ALIGN_RANSAC || p->alignment_id == LGR_ALIGN_GROR, LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, p->n_samples >= 3 && p->n_samples <= 8, LGR_ERR_UNSUPPORTED);   // (lgr_ransac.hip instantiates its kernels for 3..8)
+    int descriptor;
+    LGR_TRY(feature_descriptor(ctx, p, fp, &descriptor));
     if (ns < 2 || nt < 2) {
         // a cloud without two points gives no correspondences; the reference then leaves the identity, not converged
         // (selectCorrespondences refuses fewer than n_samples, src/sac_prerejective_omp.cpp:36-42)
@@ -596,7 +651,7 @@ extern "C" int lgr_align_dev(lgr_ctx* ctx, const float* d_src, int ns, const flo
     lgr_corr* dc;
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));
     int c = 0;
-    LGR_TRY(lgr_correspondences_dev(ctx, d_src, ns, d_tgt, nt, p, dc, &c));
+    LGR_TRY(lgr_correspondences_ex_dev(ctx, d_src, ns, d_tgt, nt, p, fp, dc, &c));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     double time_cs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     tick(ctx, 7);
@@ -621,15 +676,20 @@ extern "C" int lgr_align_dev(lgr_ctx* ctx, const float* d_src, int ns, const flo
 }
 
 extern "C" int lgr_align(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, lgr_result* res) {
+    return lgr_align_ex(ctx, src, ns, tgt, nt, p, nullptr, res);
+}
+
+extern "C" int lgr_align_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
+                            lgr_result* res) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (src || ns == 0) && (tgt || nt == 0) && p && res && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
-    if (ns < 2 || nt < 2) return lgr_align_dev(ctx, nullptr, 0, nullptr, 0, p, res);   // identity, not converged
+    if (ns < 2 || nt < 2) return lgr_align_ex_dev(ctx, nullptr, 0, nullptr, 0, p, fp, res);   // identity, not converged
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, &ds));
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, &dt));
     LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
     LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    return lgr_align_dev(ctx, ds, ns, dt, nt, p, res);
+    return lgr_align_ex_dev(ctx, ds, ns, dt, nt, p, fp, res);
 }

@@ -121,6 +121,7 @@ enum {
     WS_PIPE_CORR, WS_PIPE_KNN_S, WS_PIPE_KNN_T, WS_PIPE_FLAGS, WS_PIPE_MISC, WS_PIPE_KIDX_S, WS_PIPE_KIDX_T, WS_PIPE_KPS_S, WS_PIPE_KPS_T,
     WS_MS_KNN_I, WS_MS_KNN_D, WS_MS_LIST_S, WS_MS_LIST_T, WS_MS_SUB, WS_MS_FEAT_S, WS_MS_FEAT_T, WS_MS_SURF2, WS_MS_RES, WS_PLANE_VISITED, WS_PLANE_CLAIMED, WS_PLANE_OUT, WS_LOCAL_G, WS_SORT_TMP, WS_MATCH_BOX, WS_RANSAC_GHIST,
     WS_HOST_A, WS_HOST_B, WS_HOST_C, WS_HOST_D, WS_HOST_E, WS_HOST_F,
+    WS_SHOT_PACK_A, WS_SHOT_PACK_B, WS_SHOT_KEYS,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 112, "grow lgr_ctx::ws");

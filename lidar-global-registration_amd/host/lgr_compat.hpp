@@ -5,20 +5,21 @@
 //   include/correspondence_search.h:9-28  CorrespondenceSearch, FeatureBasedCorrespondenceSearch
 //   include/sac_prerejective_omp.h:21-56  SampleConsensusPrerejectiveOMP
 //   include/downsample.h:32               downsamplePointCloud
-//   include/common.h:322-332              estimateFeatures<FPFH>
-//   include/matching.h:373-376            matchBF<FPFH>
+//   include/common.h:322-332, 360-370     estimateFeatures<FPFH>, estimateFeatures<SHOT>
+//   include/matching.h:373-376            matchBF<FPFH>, matchBF<SHOT>
 //   include/transformation.h:6-7          estimateOptimalRigidTransformation
 //   include/hypotheses.h:10-12            updateHypotheses
 //   src/common.cpp:531-547, 644-655       calculateSmoothedDensities, estimateNormalsPoints
 //
 // The reference passes pcl::PointCloud<pcl::PointXYZINormal> / pcl::FPFHSignature33 / Eigen::Matrix4f.  Neither PCL
 // nor Eigen exists in this image, so the shim is written against three tiny layout-compatible types (lgr::PointN is
-// the 48-byte PointXYZINormal, lgr::FPFH the 132-byte signature, lgr::Matrix4f a column-major 4x4).  A maintainer of
-// the reference defines LGR_COMPAT_POINT_T / LGR_COMPAT_FPFH_T / LGR_COMPAT_MATRIX4F_T to the real types before
+// the 48-byte PointXYZINormal, lgr::FPFH the 132-byte signature, lgr::SHOT the 1444-byte pcl::SHOT352, lgr::Matrix4f a column-major
+// 4x4).  A maintainer of the reference defines LGR_COMPAT_POINT_T / LGR_COMPAT_FPFH_T / LGR_COMPAT_SHOT_T / LGR_COMPAT_MATRIX4F_T to the real types before
 // including this header: every access below is either `.points`, `.size()`, `.data()` or a
 // reinterpret of the contiguous storage, which the real types provide with the same layout.
 #pragma once
 #include <array>
+#include <cctype>
 #include <cstring>
 #include <memory>
 #include <optional>
@@ -51,6 +52,13 @@ using FPFH = LGR_COMPAT_FPFH_T;
 #endif
 static_assert(sizeof(FPFH) == 132, "FPFH must be 33 floats");
 
+#ifndef LGR_COMPAT_SHOT_T
+struct SHOT { float descriptor[352]; float rf[9]; };   // pcl::SHOT352
+#else
+using SHOT = LGR_COMPAT_SHOT_T;
+#endif
+static_assert(sizeof(SHOT) == 1444, "SHOT must be the 1444-byte pcl::SHOT352 layout (352 + 9 floats)");
+
 #ifndef LGR_COMPAT_MATRIX4F_T
 struct Matrix4f {   // column-major like Eigen::Matrix4f
     float m[16];
@@ -75,6 +83,7 @@ template <class T> struct Cloud {   // the subset of pcl::PointCloud<T> the path
 };
 using PointNCloud = Cloud<PointN>;
 using FPFHCloud = Cloud<FPFH>;
+using SHOTCloud = Cloud<SHOT>;
 
 // include/common.h:120-127
 struct Correspondence {
@@ -205,19 +214,52 @@ inline void estimateFeatures<FPFH>(const PointNCloud::ConstPtr& pcd, const Point
     features->width = (unsigned) pcd->size();
 }
 
+// SHOT frames (src/common.cpp:693-755 estimateReferenceFrames, lrf_id compared in lower case): "gt" and "gravity" are not built on the
+// device path; any other id is the default frame, as in the reference (which warns and falls back)
+inline bool lrf_is_default(std::string id) {
+    for (char& c : id) c = (char) std::tolower((unsigned char) c);
+    return id != "gt" && id != "gravity";
+}
+// include/common.h:360-370 estimateFeatures<SHOT>: SHOTEstimationOMP with the frames of estimateReferenceFrames
+template <>
+inline void estimateFeatures<SHOT>(const PointNCloud::ConstPtr& pcd, const PointNCloud::ConstPtr& surface, SHOTCloud::Ptr& features,
+                                   float radius_search, const AlignmentParameters& parameters) {
+    if (!lrf_is_default(parameters.lrf_id)) throw std::runtime_error("lgr: lrf '" + parameters.lrf_id + "' is not built on the device path");
+    const int m = (int) pcd->size();
+    std::vector<float> rows((size_t) m * 352), frames((size_t) m * 9);
+    check(lgr_shot(context(), raw(*pcd), m, raw(*surface), (int) surface->size(), radius_search, nullptr, rows.data(), frames.data()),
+          "estimateFeatures<SHOT>");
+    features->points.resize(m);
+    for (int i = 0; i < m; ++i) {
+        std::memcpy(features->points[i].descriptor, rows.data() + (size_t) i * 352, 352 * sizeof(float));
+        std::memcpy(features->points[i].rf, frames.data() + (size_t) i * 9, 9 * sizeof(float));
+    }
+    features->width = (unsigned) m;
+}
+
 // ---- include/matching.h:373-376 (randomness = 1)
 template <class FeatureT>
 inline std::vector<MultivaluedCorrespondence> matchBF(const typename Cloud<FeatureT>::ConstPtr& query_features,
                                                       const typename Cloud<FeatureT>::ConstPtr& train_features,
                                                       const AlignmentParameters& parameters) {
-    static_assert(sizeof(FeatureT) == 132, "only FPFH is built on this path");
+    static_assert(sizeof(FeatureT) == 132 || sizeof(FeatureT) == 1444, "only FPFH and SHOT are built on this path");
     if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness != 1 is not supported (data/test.yaml:14)");
     int mq = (int) query_features->size(), mt = (int) train_features->size();
     std::vector<int32_t> idx(mq);
     std::vector<float> dist(mq);
-    check(lgr_match_bf(context(), reinterpret_cast<const float*>(query_features->points.data()), mq,
-                       reinterpret_cast<const float*>(train_features->points.data()), mt, parameters.bf_block_size, idx.data(), dist.data()),
-          "matchBF");
+    if constexpr (sizeof(FeatureT) == 1444) {   // SHOT352: the 352 descriptor floats of every row, without the frame
+        auto rows = [](const Cloud<FeatureT>& c) {
+            std::vector<float> r(c.size() * 352);
+            for (std::size_t i = 0; i < c.size(); ++i) std::memcpy(r.data() + i * 352, &c.points[i], 352 * sizeof(float));
+            return r;
+        };
+        const std::vector<float> q = rows(*query_features), t = rows(*train_features);
+        check(lgr_match_shot(context(), q.data(), mq, t.data(), mt, parameters.bf_block_size, idx.data(), dist.data()), "matchBF");
+    } else {
+        check(lgr_match_bf(context(), reinterpret_cast<const float*>(query_features->points.data()), mq,
+                           reinterpret_cast<const float*>(train_features->points.data()), mt, parameters.bf_block_size, idx.data(), dist.data()),
+              "matchBF");
+    }
     std::vector<MultivaluedCorrespondence> out(mq);
     for (int i = 0; i < mq; ++i)
         if (idx[i] >= 0) { out[i].match_indices.push_back(idx[i]); out[i].distances.push_back(dist[i]); }
@@ -305,12 +347,21 @@ public:
         : src_(std::move(src)), tgt_(std::move(tgt)), parameters_(std::move(parameters)) {}
     CorrespondencesPtr calculateCorrespondences() override {
         // key points: "iss" or every point (src/common.cpp:657-691; other ids fall back to every point there too)
-        if (parameters_.descriptor_id != "fpfh") throw std::runtime_error("lgr: only descriptor 'fpfh' is built on the device path");
+        // descriptor: "fpfh" or "shot" (the struct default, include/common.h:148).  The frames matter to SHOT only (FPFH never reads lrf_id,
+        // include/common.h:366,407): "gt" / "gravity" give LGR_ERR_UNSUPPORTED there, every other id is the default frame.
+        lgr_feature_params f;
+        lgr_default_feature_params(&f);
+        if (parameters_.descriptor_id == "shot") {
+            f.descriptor_id = LGR_DESCRIPTOR_SHOT;
+            if (!lrf_is_default(parameters_.lrf_id)) f.lrf_id = LGR_LRF_GRAVITY;
+        } else if (parameters_.descriptor_id != "fpfh") {
+            throw std::runtime_error("lgr: only descriptors 'fpfh' and 'shot' are built on the device path");
+        }
         lgr_params a = to_abi(parameters_);
         auto out = std::make_shared<Correspondences>(src_->size());
         int n = 0;
-        check(lgr_correspondences(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(), &a,
-                                  reinterpret_cast<lgr_corr*>(out->data()), &n), "calculateCorrespondences");
+        check(lgr_correspondences_ex(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(), &a, &f,
+                                     reinterpret_cast<lgr_corr*>(out->data()), &n), "calculateCorrespondences");
         out->resize(n);
         return out;
     }

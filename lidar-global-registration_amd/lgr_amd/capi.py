@@ -23,6 +23,9 @@ KEYPOINT_ANY, KEYPOINT_ISS = 0, 1
 SCORE_CONSTANT, SCORE_MAE, SCORE_MSE, SCORE_EXP = 0, 1, 2, 3
 ALIGN_RANSAC, ALIGN_GROR = 0, 1
 ORDER_REFERENCE, ORDER_CANONICAL = 0, 1
+DESCRIPTOR_FPFH, DESCRIPTOR_SHOT = 0, 1
+LRF_DEFAULT = 0
+ERR_UNSUPPORTED = -5
 
 CORR_DTYPE = np.dtype([("index_query", "<i4"), ("index_match", "<i4"), ("distance", "<f4"), ("threshold", "<f4")])
 
@@ -75,6 +78,20 @@ LIBM_ACOSF, LIBM_ATANF, LIBM_ATAN2F, LIBM_SINF, LIBM_COSF = 0, 1, 2, 3, 4
 
 
 FORMAT_AUTO, FORMAT_F32, FORMAT_F16, FORMAT_F16R = -1, 0, 1, 2
+
+
+class FeatureParams(C.Structure):
+    """lgr_feature_params: the descriptor of the correspondence search (AlignmentParameters.descriptor_id / lrf_id)."""
+    _fields_ = [("descriptor_id", C.c_int32), ("lrf_id", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+def feature_params(descriptor="fpfh", lrf_id=LRF_DEFAULT):
+    """descriptor: 'fpfh' / 'shot' (or the LGR_DESCRIPTOR_* value)."""
+    f = FeatureParams()
+    _lib.lgr_default_feature_params(C.byref(f))
+    f.descriptor_id = {"fpfh": DESCRIPTOR_FPFH, "shot": DESCRIPTOR_SHOT}.get(descriptor, descriptor)
+    f.lrf_id = int(lrf_id)
+    return f
 
 
 class LgrError(RuntimeError):
@@ -442,6 +459,52 @@ class Context:
         self.check(_lib.lgr_fpfh_dev(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius), _ptr(out)))
         return out
 
+    def shot_lrf(self, kps, surf, radius):
+        """SHOT local reference frames: cuda float32 [m, 9] (x, y, z axes; NaN rows where no frame exists)."""
+        out = self.empty((kps.shape[0], 9), self.torch.float32)
+        self.check(_lib.lgr_shot_lrf_dev(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius), _ptr(out)))
+        return out
+
+    def shot(self, kps, surf, radius, lrf=None, with_lrf=False):
+        """SHOT352 rows: cuda float32 [m, 352]; lrf (cuda [m, 9]) = given frames, None = estimated.  with_lrf: also the frames used."""
+        out = self.empty((kps.shape[0], 352), self.torch.float32)
+        lo = self.empty((kps.shape[0], 9), self.torch.float32) if with_lrf else None
+        self.check(_lib.lgr_shot_dev(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius),
+                                     _ptr(None if lrf is None else lrf.contiguous()), _ptr(out), _ptr(lo)))
+        return (out, lo) if with_lrf else out
+
+    def shot_host(self, kps, surf, radius, lrf=None):
+        kps = np.ascontiguousarray(kps, np.float32); surf = np.ascontiguousarray(surf, np.float32)
+        out = np.zeros((kps.shape[0], 352), np.float32)
+        lo = np.zeros((kps.shape[0], 9), np.float32)
+        lrf = None if lrf is None else np.ascontiguousarray(lrf, np.float32)
+        self.check(_lib.lgr_shot(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius), _ptr(lrf), _ptr(out), _ptr(lo)))
+        return out, lo
+
+    def match_shot(self, q, t, block=10000):
+        """exact matchBF on [m, 352] rows: (idx int32 [mq], dist float32 [mq])."""
+        torch = self.torch
+        q = q.contiguous(); t = t.contiguous()
+        idx = self.empty((q.shape[0],), torch.int32)
+        dist = self.empty((q.shape[0],), torch.float32)
+        self.check(_lib.lgr_match_shot_dev(self.h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match2_shot(self, a, b, block=10000):
+        torch = self.torch
+        a = a.contiguous(); b = b.contiguous()
+        ab_i = self.empty((a.shape[0],), torch.int32); ab_d = self.empty((a.shape[0],), torch.float32)
+        ba_i = self.empty((b.shape[0],), torch.int32); ba_d = self.empty((b.shape[0],), torch.float32)
+        self.check(_lib.lgr_match2_shot_dev(self.h, _ptr(a), a.shape[0], _ptr(b), b.shape[0], int(block),
+                                            _ptr(ab_i), _ptr(ab_d), _ptr(ba_i), _ptr(ba_d)))
+        return ab_i, ab_d, ba_i, ba_d
+
+    def match_shot_host(self, q, t, block=10000):
+        q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
+        idx = np.zeros(q.shape[0], np.int32); dist = np.zeros(q.shape[0], np.float32)
+        self.check(_lib.lgr_match_shot(self.h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
     def fpfh_host(self, kps, surf, radius):
         kps = np.ascontiguousarray(kps, np.float32); surf = np.ascontiguousarray(surf, np.float32)
         out = np.zeros((kps.shape[0], 33), np.float32)
@@ -458,11 +521,17 @@ class Context:
         self._join()
         return out[: n.value].cpu().numpy().view(CORR_DTYPE).reshape(-1)
 
-    def correspondences(self, src, tgt, params):
+    def correspondences(self, src, tgt, params, descriptor="fpfh"):
+        """descriptor: 'fpfh' (lgr_correspondences_dev) or 'shot' / a FeatureParams (lgr_correspondences_ex_dev)."""
         out = self.empty((src.shape[0], 4), self.torch.int32)
         n = C.c_int(0)
-        self.check(_lib.lgr_correspondences_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params),
-                                                _ptr(out), C.byref(n)))
+        if isinstance(descriptor, str) and descriptor == "fpfh":
+            self.check(_lib.lgr_correspondences_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params),
+                                                    _ptr(out), C.byref(n)))
+        else:
+            f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+            self.check(_lib.lgr_correspondences_ex_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params),
+                                                       C.byref(f), _ptr(out), C.byref(n)))
         return out[: n.value]
 
     def stage_ms(self):
@@ -560,13 +629,24 @@ class Context:
         self.check(_lib.lgr_refit_svd_dev(self.h, _ptr(src), _ptr(tgt), _ptr(corr), corr.shape[0], _ptr(mask), T))
         return np.array(T, np.float32).reshape(4, 4).T.copy()
 
-    def align(self, src, tgt, params):
+    def align(self, src, tgt, params, descriptor="fpfh"):
+        """descriptor: 'fpfh' (lgr_align_dev) or 'shot' / a FeatureParams (lgr_align_ex_dev)."""
         res = Result()
-        self.check(_lib.lgr_align_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(res)))
+        if isinstance(descriptor, str) and descriptor == "fpfh":
+            self.check(_lib.lgr_align_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(res)))
+        else:
+            f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+            self.check(_lib.lgr_align_ex_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
+                                             C.byref(res)))
         return res
 
-    def align_host(self, src, tgt, params):
+    def align_host(self, src, tgt, params, descriptor="fpfh"):
         src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
         res = Result()
-        self.check(_lib.lgr_align(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(res)))
+        if isinstance(descriptor, str) and descriptor == "fpfh":
+            self.check(_lib.lgr_align(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(res)))
+        else:
+            f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+            self.check(_lib.lgr_align_ex(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
+                                         C.byref(res)))
         return res

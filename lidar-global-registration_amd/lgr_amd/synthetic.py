@@ -177,3 +177,26 @@ def make_correspondence_problem(n_pts=20000, c=5000, inlier_frac=0.4, sigma=0.01
     corr["distance"] = rng.uniform(0, 50, c).astype(np.float32)
     corr["threshold"] = thr
     return dict(src=make_points(src), tgt=make_points(tgt), corr=corr, T_gt=T)
+
+
+# tests/point2plane_distance.cpp:29-58 of the reference: its ground-truth transform and corner scene
+CORNER_GT = np.array([[0.0803703, -0.996763, -0.00201846, 1.2143], [0.996758, 0.080377, -0.00349969, -6.13404],
+                      [0.00365057, -0.00173067, 0.999992, -1.17221], [0, 0, 0, 1]], np.float32)
+
+
+def make_corner_scene(n=100, shift=5):
+    """The reference's end-to-end scene: three orthogonal n x n lattices (spacing 2), the target shifted by 1 in-plane, the source moved
+    by CORNER_GT^-1 (emplace_back order of :33-40).  Returns (src, tgt, vp_src, vp_tgt); normals are left to the caller (:66-67)."""
+    ij = np.stack(np.meshgrid(np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 2).astype(np.float64)
+    i, j = ij[:, 0], ij[:, 1]
+    z = np.zeros_like(i)
+    s = np.stack([np.stack([2 * i, 2 * j, z], 1), np.stack([shift + 2 * i, z, shift + 2 * j], 1),
+                  np.stack([z, 2 * shift + 2 * i, 2 * shift + 2 * j], 1)], 1).reshape(-1, 3)
+    t = np.stack([np.stack([2 * i + 1, 2 * j, z], 1), np.stack([shift + 2 * i, z, shift + 2 * j + 1], 1),
+                  np.stack([z, 2 * shift + 2 * i + 1, 2 * shift + 2 * j], 1)], 1).reshape(-1, 3)
+    gi = np.linalg.inv(CORNER_GT).astype(np.float64)
+    src = make_points((s @ gi[:3, :3].T + gi[:3, 3]).astype(np.float32))
+    tgt = make_points(t.astype(np.float32))
+    vp_tgt = np.full(3, 2.0 * n, np.float32)
+    vp_src = (CORNER_GT[:3, :3].T.astype(np.float64) @ (vp_tgt - CORNER_GT[:3, 3]).astype(np.float64)).astype(np.float32)
+    return src, tgt, vp_src, vp_tgt
