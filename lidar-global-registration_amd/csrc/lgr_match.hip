@@ -411,7 +411,7 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
     }
     // The sorted copies are for the exact rerank (and the f32 ball bounds): with the f16 formats nothing before the MFMA passes reads them, so
     // they are gathered UNDER pass 0 (launch_sorted_copies, called where that pass is queued: the set-up phase in front of it is bound by
-    // HBM -- 3.1 GB of column operands -- and the passes are not).
+    // HBM -- 2.1 GB of column operands -- and the passes are not).
     bool sorted_launched = false;
     auto launch_sorted_copies = [&](bool behind_main) -> int {
         if (sorted_launched) return LGR_OK;
@@ -479,16 +479,28 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
         ex.quad = 2.f;
         if (rot) {
             // Helmert coordinates are computed in f32: |dy| <= 10.4 u |x'| per vector (prefix sums of <= 11 terms, one
-            // rounded constant) -> 20.8 u (x + y)^2 on d2, 0.13 of the unit 4 g40 (x + y)^2; the dropped energy is absolute
-            ex.quad = 2.2f;
-            ex.abs = (float) ((double) ex.abs + 4.0 * (double) drop2 * 1.0001);
+            // rounded constant) -> 20.8 u (x + y)^2 on d2, 0.13 of the unit 4 g40 (x + y)^2; the dropped energy is absolute.
+            // Norms: the rotated format stores a norm as TWO f16 terms against c0 = a_norm[0] (pack16_kernel): n1 = rn(N / c0),
+            // r1 = N - c0 n1 (exact), n2 = rn(r1 / c0), error e = r1 - c0 n2, with N = |x'|^2 2^2s <= N_max <= 2^15 c0 (so n1 is finite):
+            //   n1 normal (N >= 2^-14 c0):  |r1| <= 2^-11 N;  n1 subnormal: |r1| <= 2^-25 c0 (half the f16 subnormal spacing 2^-24, times c0);
+            //   n2 (|r1 / c0| <= 16):       |e| <= 2^-11 |r1| + 2^-25 c0  ->  |e| <= 2^-22 N + 2^-25 c0 (1 + 2^-11);
+            //   should the MFMA flush subnormal f16 inputs (hipcc's default mode keeps them), a flushed n2 loses |r1| < 2^-14 c0, a flushed
+            //   n1 (with n2) N + |e| < 2^-14 c0 (1 + 2^-11) -- so, whatever the mode, per norm  |e| <= 2^-22 N + 2^-14 c0 (1 + 2^-10).
+            // All products c0 n are exact in the f32 accumulator.  Both norms, back in d2 units (x 2^-2s): 2^-22 (|a'|^2 + |b'|^2) + 2^-13 c0 2^-2s.
+            //   relative part: 2^-22 (x^2 + y^2) <= 2^-22 (x + y)^2 = 0.025 of the unit 4 g40 (x + y)^2 (9.54e-6) -> quad + 0.03;
+            //   absolute part: c0 < 2^-14 N_max by the choice of e1 (or c0 = 1), so 2^-13 c0 2^-2s < 2^-27 max |x - c|^2 -- it replaces the
+            //   three-term expansion's 2^-13 (a_norm[2] + ..) 2^-2s above (whose relative part, 2^-33 N, sat inside the doubled quad).
+            ex.quad = 2.23f;
+            ex.abs = (float) ((2.0 * std::ldexp(1.0, -14) * (double) sc.a_norm[0] * (1.0 + std::ldexp(1.0, -10)) * (double) sc.inv_s2) * 1.01
+                              + 4.0 * (double) drop2 * 1.0001);
         }
     }
     g_last_stats.f16 = f16 ? (rot ? 2 : 1) : 0;
-    const int KS = !f16 ? OpFmt<FMT_F32>::KS : rot ? OpFmt<FMT_F16R>::KS : OpFmt<FMT_F16>::KS;
+    const int KS = !f16 ? OpFmt<FMT_F32>::KS : rot ? OpFmt<FMT_F16R>::KS : OpFmt<FMT_F16>::KS;   // MFMA steps of a tile
+    const int NF = !f16 ? OpFmt<FMT_F32>::NF : rot ? OpFmt<FMT_F16R>::NF : OpFmt<FMT_F16>::NF;   // fragments stored per tile and side
     const size_t frag_bytes = f16 ? sizeof(f16x8) : sizeof(float);
-    const size_t a_op_bytes = (size_t) ta * KS * 64 * frag_bytes;
-    const size_t bset_stride = (size_t) tb * KS * 64;   // fragments per column set
+    const size_t a_op_bytes = (size_t) ta * NF * 64 * frag_bytes;
+    const size_t bset_stride = (size_t) tb * NF * 64;   // fragments per column set
     char *Aop, *Bop;
     LGR_TRY(lgr_ws_t(ctx, WS_MATCH_ROWMIN, a_op_bytes + 256, &Aop));
     const size_t b_op_bytes = KCL * bset_stride * frag_bytes;
@@ -534,11 +546,11 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
         LGR_HIP(ctx, hipMemcpyAsync(leaf_g0, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    // The column (train-side) operands -- 16 sets, 3 GB at 1M rows, the longest piece of the set-up -- are packed on a third stream:
+    // The column (train-side) operands -- 16 sets, 2.1 GB at 1M rows, the longest piece of the set-up -- are packed on a third stream:
     // nothing before the first MFMA pass reads them (the bounds of pass 0 need the ROW operands, the packed leaf centres and the
     // boxes), so that chain runs beside the packing instead of behind it.  sB is joined in launch_mfma.
     // (It starts BEHIND the row operands' packing: side by side the two packing kernels share the HBM write bandwidth and the row
-    // operands, which the bounds wait for, take as long as the 3 GB of column sets.)
+    // operands, which the bounds wait for, take as long as the 2.1 GB of column sets.)
     hipStream_t sB = ctx->stream;
     if (f16) LGR_TRY(lgr_ctx_stream3(ctx, &sB));
     DrainOnExit drain_sB{sB, ctx->stream};   // (the third stream: column operands, table initialisation)
@@ -571,7 +583,7 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
     const size_t o_cop = pcarve((size_t) KCL * ((n_leaves + TILE) / TILE) * 7 * 64 * sizeof(f16x8));   // the leaf centres as packed train rows
     if (prune) LGR_TRY(lgr_ws_t(ctx, WS_MATCH_PRUNE, poff, &pb));
     const int n_cpad = pad_to(n_leaves, TILE);
-    const size_t cset_stride = (size_t) (n_cpad / TILE) * KS * 64;
+    const size_t cset_stride = (size_t) (n_cpad / TILE) * NF * 64;
     bool early_b = false;   // ev[27] on sB: workspace cleared (+ centres packed, f16 formats)
     if (prune) {
         if (sB != ctx->stream) {
@@ -599,7 +611,7 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
         if (rot) pack16_kernel<true><<<cdiv(ma_pad, 256), 256, 0, ctx->stream>>>(d_a, A.perm, ma_pad, 0, cen, A.blkcl, sc, (_Float16*) Aop, nAp, shellA);
         else pack16_kernel<false><<<cdiv(ma_pad, 256), 256, 0, ctx->stream>>>(d_a, A.perm, ma_pad, 0, cen, A.blkcl, sc, (_Float16*) Aop, nAp, shellA);
     }
-    // the column operands (f16 formats: 3 GB at 1M, HBM-write bound) and their group maxima, on the third stream behind the row operands.  (Round 5
+    // the column operands (f16 formats: 2.1 GB at 1M, HBM-write bound) and their group maxima, on the third stream behind the row operands.  (Round 5
     // measured the alternatives: behind lb_mfma_kernel -- which then runs alone in 0.18 ms instead of 0.85 -- box_lb_kernel crawls beside the
     // packing instead (0.07 -> 0.92 ms); behind the near kernels, with pass 0's stage selection from assign_kernel's distances so that
     // mask_kernel need not wait for the column norms: mask_kernel crawls (0.4 -> 1.04 ms) and pass 0 starts 0.1 ms later than with this order.)
@@ -791,10 +803,10 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
             } else {
                 float* nC = (float*) (pb + o_cnrm);
                 f16x8* Cop = (f16x8*) (pb + o_cop);
-                if (rot) lb_mfma_kernel<OpFmt<FMT_F16R>::KS><<<n_rb, LBM_THREADS, 0, cx->stream>>>((const f16x8*) Aop, Cop, cset_stride, out_scale, A.blkcl, nAp, nC, ex,
-                                                                                                  B.r2max, B.leaf_count, n_leaves, n_cpad, LBsq);
-                else lb_mfma_kernel<OpFmt<FMT_F16>::KS><<<n_rb, LBM_THREADS, 0, cx->stream>>>((const f16x8*) Aop, Cop, cset_stride, out_scale, A.blkcl, nAp, nC, ex,
-                                                                                              B.r2max, B.leaf_count, n_leaves, n_cpad, LBsq);
+                if (rot) lb_mfma_kernel<FMT_F16R><<<n_rb, LBM_THREADS, 0, cx->stream>>>((const f16x8*) Aop, Cop, cset_stride, out_scale, A.blkcl, nAp, nC, ex,
+                                                                                       B.r2max, B.leaf_count, n_leaves, n_cpad, LBsq);
+                else lb_mfma_kernel<FMT_F16><<<n_rb, LBM_THREADS, 0, cx->stream>>>((const f16x8*) Aop, Cop, cset_stride, out_scale, A.blkcl, nAp, nC, ex,
+                                                                                   B.r2max, B.leaf_count, n_leaves, n_cpad, LBsq);
             }
             LGR_HIP(cx, hipGetLastError());
             return (int) LGR_OK;

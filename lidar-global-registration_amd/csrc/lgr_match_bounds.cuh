@@ -76,11 +76,11 @@ __global__ __launch_bounds__(256) void lb_kernel(const float* __restrict__ Asort
 
 // The same table from the packed f16 operands (f16 formats): the leaf centres are packed like train rows (one copy per column set,
 // pack16_kernel with role 1), a workgroup multiplies the 8 row tiles of its block with the centre tiles of the block's set on the
-// matrix cores and keeps the row minimum -- 6 (7) MFMA steps per 32 x 32 (row, centre) tile instead of 33 packed FMAs per pair.
+// matrix cores and keeps the row minimum -- 6 (7) MFMA steps on 4 (7) stored fragments per 32 x 32 (row, centre) tile instead of 33 packed FMAs per pair.
 // The filtered value is within eps(x, y) of |a - c|^2 (x = largest |a'| of the block, y = |c'|: the matcher's own proven bound),
 // so  dmin - eps  is a valid lower bound of the smallest distance; eps is ~1e-5 (x + y)^2, far below what the bound is used for.
 constexpr int LBM_THREADS = 512, LBM_CHUNK = 4;   // 8 waves = the 8 row tiles of a block; centre tiles go through LDS 4 at a time, double buffered
-template <int KS>
+template <int FMT>
 __global__ __launch_bounds__(LBM_THREADS) void lb_mfma_kernel(const f16x8* __restrict__ Ap, const f16x8* __restrict__ Cp, size_t cset_stride /* fragments */,
                                                               float out_scale, const int* __restrict__ blkcl, const float* __restrict__ nA,
                                                               const float* __restrict__ nC /* [KCL][n_cpad] */, EpsExtra ex,
@@ -88,8 +88,9 @@ __global__ __launch_bounds__(LBM_THREADS) void lb_mfma_kernel(const f16x8* __res
                                                               float* __restrict__ LBsq) {
     // (round 5: the chunks arrive by LDS-DMA, the next one while the current one is multiplied -- staged through registers, every 16-byte piece
     //  of a chunk waited for its own memory round trip, six in a row per chunk: 0.62 ms for 0.09 ms worth of MFMAs, on the matcher's critical chain)
-    constexpr int CH_BLOCKS = LBM_CHUNK * KS;   // 1 KB blocks per chunk
-    __shared__ __attribute__((aligned(16))) f16x8 cs[2][LBM_CHUNK * KS * 64];
+    constexpr int NF = OpFmt<FMT>::NF;          // stored fragments per tile (OpFmt: the chain reads them in its own order)
+    constexpr int CH_BLOCKS = LBM_CHUNK * NF;   // 1 KB blocks per chunk
+    __shared__ __attribute__((aligned(16))) f16x8 cs[2][LBM_CHUNK * NF * 64];
     __shared__ int dmin_s[MAXLEAF + TILE];
     __shared__ float xw[LBM_THREADS / 64];
     const int rb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
@@ -103,15 +104,15 @@ __global__ __launch_bounds__(LBM_THREADS) void lb_mfma_kernel(const f16x8* __res
         for (int o = 32; o > 0; o >>= 1) n2 = fmaxf(n2, __shfl_xor(n2, o));
         if (lane == 0) xw[wave] = n2;
     }
-    f16x8 a[KS];
+    f16x8 a[NF];
     const int row_tile = rb * (BLOCK_ROWS / TILE) + wave;
 #pragma unroll
-    for (int kk = 0; kk < KS; ++kk) a[kk] = Ap[((size_t) row_tile * KS + kk) * 64 + lane];
+    for (int kk = 0; kk < NF; ++kk) a[kk] = Ap[((size_t) row_tile * NF + kk) * 64 + lane];
     const f16x8* Cset = Cp + (size_t) p * cset_stride;
     const int n_ct = n_cpad / TILE, n_ch = (n_ct + LBM_CHUNK - 1) / LBM_CHUNK;
     auto issue = [&](int ch) {   // wave w copies the 1 KB blocks w, w + 8, ... of chunk ch
-        const int nblk = min(LBM_CHUNK, n_ct - ch * LBM_CHUNK) * KS;
-        const char* src = reinterpret_cast<const char*>(Cset + (size_t) ch * LBM_CHUNK * KS * 64);
+        const int nblk = min(LBM_CHUNK, n_ct - ch * LBM_CHUNK) * NF;
+        const char* src = reinterpret_cast<const char*>(Cset + (size_t) ch * LBM_CHUNK * NF * 64);
         char* dst = reinterpret_cast<char*>(&cs[ch & 1][0]);
         for (int blk = wave; blk < nblk; blk += LBM_THREADS / 64)
             __builtin_amdgcn_global_load_lds((const void*) (src + blk * 1024 + lane * 16), (__attribute__((address_space(3))) void*) (dst + blk * 1024), 16, 0, 0);
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(LBM_THREADS) void lb_mfma_kernel(const f16x8* __res
             if (t >= nt) break;   // (uniform)
             f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int kk = 0; kk < KS; ++kk) acc = mfma_step(a[kk], cb[(t * KS + kk) * 64 + lane], acc);
+            for (int kk = 0; kk < OpFmt<FMT>::KS; ++kk) acc = mfma_step(a[OpFmt<FMT>::fa(kk)], cb[(t * NF + OpFmt<FMT>::fb(kk)) * 64 + lane], acc);
             // minimum over the wave's 32 rows, on the bit patterns (a negative value -- a distance within eps of zero -- stays
             // negative under the signed-integer order, whichever negative it is; it ends as a bound of 0 below)
             int m = min(__float_as_int(acc[0]), __float_as_int(acc[1]));

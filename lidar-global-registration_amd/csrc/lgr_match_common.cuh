@@ -67,15 +67,36 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 //      = 105, padded to 112 = 7 steps, fragment = 8 halves (lane l: row l & 31, k = 16 * step + 8 * (l >> 5) + j).
 // F16R: the same on 30 coordinates.  Every 11-bin block of an FPFH row sums to 100, so differences of rows have no component
 //      along the block's all-ones direction; in a Helmert basis of the block that direction is one coordinate, the other
-//      10 carry the whole distance.  K = 3 * 30 + 6 = 96 = 6 steps (-1/7 of the MFMA work, LDS reads and operand bytes).
+//      10 carry the whole distance.  K = 96 = 6 steps (-1/7 of the MFMA work).  Each side STORES only four fragments (NF):
+//      the rows' h1 part meets both column parts and the columns' h1 part both row parts, so the chain reuses them --
+//          steps 0-1: A01 = h1(-2 x') | c0, a1    x  B01 = h1(x') | b1, c0    a1.b1 + the leading norm terms (coarse d2~)
+//          steps 2-3: A01 (again)                 x  B23 = h2(x') | b2, 0     a1.b2 + the columns' second norm term
+//          steps 4-5: A45 = h2(-2 x') | 0, a2     x  B01 (again)              a2.b1 + the rows' second norm term
+//      (norms as two-term expansions against one constant c0, pack16_kernel): 2/3 of the operand bytes of six stored fragments.
 //      Used only when the dropped coordinates are (numerically) constant over both sets; their largest measured energy
 //      enters the error bound, so any input stays exact (match_impl, "rot").
+// KS = MFMA steps of a tile, NF = fragments stored per 32-row tile and side; step kk multiplies A fragment fa(kk) by B fragment fb(kk).
 enum { FMT_F32 = 0, FMT_F16 = 1, FMT_F16R = 2 };
 template <int FMT> struct OpFmt;
-template <> struct OpFmt<FMT_F32> { typedef float frag; static constexpr int KS = 17; };
-template <> struct OpFmt<FMT_F16> { typedef f16x8 frag; static constexpr int KS = 7; };
-template <> struct OpFmt<FMT_F16R> { typedef f16x8 frag; static constexpr int KS = 6; };
-struct F16Scale { float s_mul; float inv_s2; float a_norm[3]; };   // 2^s, 2^-2s, the three a-side norm-slot constants
+template <> struct OpFmt<FMT_F32> {
+    typedef float frag; static constexpr int KS = 17, NF = 17;
+    static constexpr int fa(int kk) { return kk; }
+    static constexpr int fb(int kk) { return kk; }
+};
+template <> struct OpFmt<FMT_F16> {
+    typedef f16x8 frag; static constexpr int KS = 7, NF = 7;
+    static constexpr int fa(int kk) { return kk; }
+    static constexpr int fb(int kk) { return kk; }
+};
+template <> struct OpFmt<FMT_F16R> {
+    typedef f16x8 frag; static constexpr int KS = 6, NF = 4;
+    static constexpr int fa(int kk) { return kk < 4 ? (kk & 1) : kk - 2; }   // A01 A01 A45: 0 1 0 1 2 3
+    static constexpr int fb(int kk) { return kk < 4 ? kk : kk - 4; }         // B01 B23 B01: 0 1 2 3 0 1
+};
+static_assert(OpFmt<FMT_F16R>::fa(0) == 0 && OpFmt<FMT_F16R>::fb(0) == 0 && OpFmt<FMT_F16R>::fa(1) == 1 && OpFmt<FMT_F16R>::fb(1) == 1,
+              "the first two steps are the coarse d2~ (stored fragments 0 and 1 of both sides)");
+// 2^s, 2^-2s, the a-side norm-slot constants (plain format: three terms against a_norm[0..2]; rotated: two terms against a_norm[0])
+struct F16Scale { float s_mul; float inv_s2; float a_norm[3]; };
 
 // Coarse rejection (rotated format, passes that have upper bounds; DESIGN.md 3b "coarse rejection").  After the first two
 // MFMA steps of a 32 x 32 tile the accumulator holds  c = |a'|^2_lead + |b'|^2_lead - 2 a1.b1  (scaled by 2^2s): the

@@ -29,6 +29,14 @@ __device__ unsigned long long g_prof[16];
 #endif
 __device__ __forceinline__ f32x16 mfma_step(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 mfma_step(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+// the KS-step chain of one 32 x 32 tile on the NF stored fragments of each side: step kk multiplies A fragment fa(kk) by B fragment
+// fb(kk) (OpFmt; the rotated format reuses two of its four fragments per side)
+template <int FMT>
+__device__ __forceinline__ f32x16 mfma_chain(const typename OpFmt<FMT>::frag (&a)[OpFmt<FMT>::NF], const typename OpFmt<FMT>::frag (&b)[OpFmt<FMT>::NF], f32x16 acc) {
+#pragma unroll
+    for (int kk = 0; kk < OpFmt<FMT>::KS; ++kk) acc = mfma_step(a[OpFmt<FMT>::fa(kk)], b[OpFmt<FMT>::fb(kk)], acc);
+    return acc;
+}
 
 template <bool COLDIR, int FMT, bool CO /* coarse rejection (rotated format, CoarseArgs set) */>
 #ifndef LGR_MM_OCC_CO
@@ -49,8 +57,8 @@ __global__ __launch_bounds__(NTHR, CO ? LGR_MM_OCC_CO : LGR_MM_OCC) void match_m
     constexpr bool COARSE = CO, use_coarse = CO;
     unsigned n_tested = 0u, n_rejected = 0u, n_skipped = 0u;   // wave-uniform tile counts
     typedef typename OpFmt<FMT>::frag frag;
-    constexpr int KS = OpFmt<FMT>::KS;
-    constexpr int STAGE_FRAGS = STAGE_TILES * KS * 64;
+    constexpr int NF = OpFmt<FMT>::NF;   // stored fragments per tile (the chain has OpFmt<FMT>::KS steps)
+    constexpr int STAGE_FRAGS = STAGE_TILES * NF * 64;
     constexpr int STAGE_VEC4 = STAGE_FRAGS * (int) sizeof(frag) / 16;   // 16-byte pieces per stage
     // ONE __shared__ object: with a second one beside the LDS-DMA staging array hipcc waits vmcnt(0) before the first
     // ds_read of every stage, i.e. for the DMA of the NEXT stage it has just issued (cdna_hip_programming.md, projection GEMM
@@ -139,11 +147,11 @@ __global__ __launch_bounds__(NTHR, CO ? LGR_MM_OCC_CO : LGR_MM_OCC) void match_m
             PROF_CNT(9);
             col_dirty = true;
             const int row_tile = rb * (BLOCK_ROWS / TILE) + wave * RW;
-            const frag* Bset = Bp + (size_t) blkcl[rb] * bset_stride + (size_t) col_tile0 * KS * 64;
+            const frag* Bset = Bp + (size_t) blkcl[rb] * bset_stride + (size_t) col_tile0 * NF * 64;
             // A fragments (coalesced 256-B loads) and the |a'|^2 of the 16 rows each lane's accumulators cover
-            frag a[KS];
+            frag a[NF];
 #pragma unroll
-            for (int kk = 0; kk < KS; ++kk) a[kk] = Ap[((size_t) row_tile * KS + kk) * 64 + lane];
+            for (int kk = 0; kk < NF; ++kk) a[kk] = Ap[((size_t) row_tile * NF + kk) * 64 + lane];
             f32x16 nav = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             if (!F16) {   // f32 operands: |a'|^2 through the accumulator input (the f16 format carries it in K slots)
 #pragma unroll
@@ -300,7 +308,7 @@ __global__ __launch_bounds__(NTHR, CO ? LGR_MM_OCC_CO : LGR_MM_OCC) void match_m
             // two column tiles per epilogue (one v_min3 per accumulator pair for the row minima, 8 fewer vector
             // instructions per tile): +13 % at 4 waves/SIMD (spills), -1.4 % at 2 waves/SIMD.
             auto compute = [&](int st, int buf, int nxt) {
-                frag b[KS];
+                frag b[NF];
                 if (COARSE && use_coarse) {
                     // Coarse sweep: the first two steps of a tile give a coarse d2~ (see CoarseArgs); tiles with an element
                     // under the stage threshold are only RECORDED here (kept[ct] bit st) and finished after the sweep,
@@ -372,15 +380,13 @@ __global__ __launch_bounds__(NTHR, CO ? LGR_MM_OCC_CO : LGR_MM_OCC) void match_m
                     return;
                 }
 #pragma unroll
-                for (int kk = 0; kk < KS; ++kk) b[kk] = Bs[buf][kk * 64 + lane];
+                for (int kk = 0; kk < NF; ++kk) b[kk] = Bs[buf][kk * 64 + lane];
 #pragma unroll
                 for (int ct = 0; ct < STAGE_TILES; ++ct) {
-                    f32x16 acc = mfma_step(a[0], b[0], nav);
-#pragma unroll
-                    for (int kk = 1; kk < KS; ++kk) acc = mfma_step(a[kk], b[kk], acc);
+                    f32x16 acc = mfma_chain<FMT>(a, b, nav);
                     if (ct + 1 < STAGE_TILES) {
 #pragma unroll
-                        for (int kk = 0; kk < KS; ++kk) b[kk] = Bs[buf][((ct + 1) * KS + kk) * 64 + lane];
+                        for (int kk = 0; kk < NF; ++kk) b[kk] = Bs[buf][((ct + 1) * NF + kk) * 64 + lane];
                     }
                     epilogue(acc, st, ct, nxt);
                 }
@@ -398,7 +404,7 @@ __global__ __launch_bounds__(NTHR, CO ? LGR_MM_OCC_CO : LGR_MM_OCC) void match_m
                 auto dma_coarse = [&]() {
                     const int s_ = __builtin_ctz(to_issue);
                     to_issue &= to_issue - 1u;
-                    const char* src = reinterpret_cast<const char*>(Bset + (size_t) s_ * STAGE_FRAGS + (size_t) ((wave >> 1) * KS + (wave & 1)) * 64);
+                    const char* src = reinterpret_cast<const char*>(Bset + (size_t) s_ * STAGE_FRAGS + (size_t) ((wave >> 1) * NF + (wave & 1)) * 64);
                     char* dst = reinterpret_cast<char*>(smem) + (issued % CO_NB) * (CO_FRAGS * (int) sizeof(frag)) + wave * 1024;
                     __builtin_amdgcn_global_load_lds((const void*) (src + lane * 16), (__attribute__((address_space(3))) void*) dst, 16, 0, 0);
                     ++issued;
@@ -499,13 +505,11 @@ __global__ __launch_bounds__(NTHR, CO ? LGR_MM_OCC_CO : LGR_MM_OCC) void match_m
                         const int grp = __builtin_amdgcn_readfirstlane(tg_s[ks_ * STAGE_TILES + ct]);
                         if (grp != prev_grp && prev_grp >= 0) flush_rows(prev_grp);
                         prev_grp = grp;
-                        const frag* bsrc = Bset + (size_t) ks_ * STAGE_FRAGS + (size_t) ct * KS * 64 + lane;
-                        frag b[KS];
+                        const frag* bsrc = Bset + (size_t) ks_ * STAGE_FRAGS + (size_t) ct * NF * 64 + lane;
+                        frag b[NF];
 #pragma unroll
-                        for (int kk = 0; kk < KS; ++kk) b[kk] = bsrc[kk * 64];
-                        f32x16 acc = mfma_step(a[0], b[0], nav);
-#pragma unroll
-                        for (int kk = 1; kk < KS; ++kk) acc = mfma_step(a[kk], b[kk], acc);
+                        for (int kk = 0; kk < NF; ++kk) b[kk] = bsrc[kk * 64];
+                        const f32x16 acc = mfma_chain<FMT>(a, b, nav);
                         row_min1(acc);
                         col_min(acc, ks_, ct);
                     }

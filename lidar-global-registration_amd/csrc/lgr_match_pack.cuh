@@ -40,12 +40,15 @@ __global__ void pack_kernel(const float* __restrict__ X, const int* __restrict__
     }
 }
 
-// f16-split operands (OpFmt<true>).  Same roles / sets / nrm output as pack_kernel; P holds f16x8 fragments:
-// fragment (tile, step, lane) at ((set * tiles + tile) * 7 + step) * 64 + lane, lane = row | (khalf << 5).
-// Concatenated K index c: [0,33) a1.b1, [33,66) a1.b2, [66,99) a2.b1, 99..104 norm slots, rest 0.
-// rows: h = split(-2 x' 2^s);  cols: h = split(x' 2^s);  a norm enters as the three-term f16 expansion of
-// N = |x'|^2 2^2s against the constants A1..A3 on the other side (N = A1 B1 + A2 B2 + A3 B3 up to 2^-33 N or the f16
-// flush limit).
+// f16-split operands (OpFmt<FMT_F16 / FMT_F16R>).  Same roles / sets / nrm output as pack_kernel; P holds f16x8 fragments:
+// fragment (tile, f, lane) at ((set * tiles + tile) * NF + f) * 64 + lane, lane = row | (khalf << 5).
+// Plain format (NF = 7 = KS): concatenated K index c: [0,33) a1.b1, [33,66) a1.b2, [66,99) a2.b1, 99..104 norm slots, rest 0;
+// a norm enters as the three-term f16 expansion of N = |x'|^2 2^2s against the constants A1..A3 on the other side
+// (N = A1 B1 + A2 B2 + A3 B3 up to 2^-33 N or the f16 flush limit).
+// Rotated format (NF = 4 stored fragments, KS = 6 steps: OpFmt<FMT_F16R>): stored K index c of a row / column:
+// [0,30) h1, 30..31 norm slots, [32,62) h2, 62..63 norm slots; a norm is the two-term expansion N ~ c0 (n1 + n2) against
+// the one constant c0 = a_norm[0] (error bound: match_impl, "rot").
+// rows: h = split(-2 x' 2^s);  cols: h = split(x' 2^s).
 // Helmert coordinates of one 11-bin block: y_k = (x_0 + .. + x_{k-1} - k x_k) / sqrt(k (k + 1)), k = 1..10 (orthonormal, all
 // orthogonal to (1,..,1)); *u = (x_0 + .. + x_10) / sqrt(11) is the dropped coordinate.
 __device__ __forceinline__ void helmert11(const float* __restrict__ x, float* __restrict__ y, float* u) {
@@ -100,11 +103,11 @@ __global__ __launch_bounds__(256) void pack16_kernel(const float* __restrict__ X
     float y[30], u0, u1, u2;
     if (ROT) { helmert11(v, y, &u0); helmert11(v + 11, y + 10, &u1); helmert11(v + 22, y + 20, &u2); }
     if (!in_range) continue;
-    constexpr int nd = ROT ? 30 : 33, ks = ROT ? OpFmt<FMT_F16R>::KS : OpFmt<FMT_F16>::KS;
+    constexpr int nd = ROT ? 30 : 33, nf = ROT ? OpFmt<FMT_F16R>::NF : OpFmt<FMT_F16>::NF;
     int tile = pos >> 5, r = pos & 31;
-    // the row's K = 16 ks halves are assembled in registers (all indices are compile-time constants) and leave as
-    // 2 ks 16-byte pieces: piece (step, khalf) of row r sits at fragment (step * 64 + khalf * 32 + r)
-    _Float16 hv[ks * 16];
+    // the row's K = 16 nf stored halves are assembled in registers (all indices are compile-time constants) and leave as
+    // 2 nf 16-byte pieces: piece (f, khalf) of row r sits at fragment (f * 64 + khalf * 32 + r)
+    _Float16 hv[nf * 16];
     auto put = [&](int cidx, _Float16 h) { hv[cidx] = h; };
     const float mul = role == 0 ? -2.0f * sc.s_mul : sc.s_mul;
     float n2m = n2;                           // the norm the MFMA chain must see: of the operand coordinates
@@ -114,46 +117,64 @@ __global__ __launch_bounds__(256) void pack16_kernel(const float* __restrict__ X
         for (int k = 0; k < 30; ++k) n2m = n2m + y[k] * y[k];
     }
     // K order.  Plain format: [0,nd) a1.b1, [nd,2nd) a1.b2, [2nd,3nd) a2.b1, then the six norm slots.  Rotated format: the
-    // first two MFMA steps (K slots 0..31) hold a1.b1 and the leading norm terms -- a coarse d2~ the kernel tests before
-    // it spends the other four steps on a tile (match_mfma, "coarse rejection") -- then [32,62) a1.b2, [62,92) a2.b1 and
-    // the four remaining norm terms.
-    constexpr int o12 = ROT ? 32 : nd, o21 = ROT ? 62 : 2 * nd;
+    // stored fragments 0-1 (K slots 0..31) hold h1 and the leading norm term, 2-3 (K slots 32..63) h2 and the second norm
+    // term; the chain pairs them as h1.h1, h1.h2, h2.h1 (OpFmt<FMT_F16R>), and its first two steps -- a1.b1 and the leading
+    // norm terms -- are a coarse d2~ the kernels test before they spend the other four steps on a tile (match_mfma, "coarse rejection").
+    constexpr int o12 = ROT ? 32 : nd, o21 = ROT ? 32 : 2 * nd;
 #pragma unroll
     for (int k = 0; k < nd; ++k) {
         float x = (ROT ? y[k] : v[k]) * mul;  // exact (power of two)
         _Float16 h1 = (_Float16) x;           // round to nearest
         _Float16 h2 = (_Float16) (x - (float) h1);
-        if (role == 0) { put(k, h1); put(o12 + k, h1); put(o21 + k, h2); }
+        if (ROT) { put(k, h1); put(o12 + k, h2); }
+        else if (role == 0) { put(k, h1); put(o12 + k, h1); put(o21 + k, h2); }
         else { put(k, h1); put(o12 + k, h2); put(o21 + k, h1); }
     }
-    // norm slots: 3 nd .. 3 nd + 2 carry |b'|^2 (expansion on the column side, constants on the row side), the next three
-    // |a'|^2 the other way round, so d2~ 2^2s = |b'|^2 - 2 a'.b' + |a'|^2 comes out of the MFMA chain with C = 0
+    // norm slots, so that d2~ 2^2s = |b'|^2 - 2 a'.b' + |a'|^2 comes out of the MFMA chain with C = 0
     const bool rows = role == 0;
     const _Float16 c0 = (_Float16) sc.a_norm[0], c1 = (_Float16) sc.a_norm[1], c2 = (_Float16) sc.a_norm[2];
-    _Float16 b1, b2, b3;
-    if (o >= 0) {
-        float N = n2m * (sc.s_mul * sc.s_mul);
-        b1 = (_Float16) (N / sc.a_norm[0]);
-        float r1 = __builtin_fmaf(-sc.a_norm[0], (float) b1, N);
-        b2 = (_Float16) (r1 / sc.a_norm[1]);
-        float r2 = __builtin_fmaf(-sc.a_norm[1], (float) b2, r1);
-        b3 = (_Float16) (r2 / sc.a_norm[2]);
-    } else {
-        b1 = (_Float16) __uint_as_float(0x7f800000u); b2 = (_Float16) 0.f; b3 = (_Float16) 0.f;   // padding: +inf
-    }
-    // columns: [expansion | constants], rows: [constants | expansion]
+    const float N = n2m * (sc.s_mul * sc.s_mul);
     if (ROT) {
-        put(30, rows ? c0 : b1); put(31, rows ? b1 : c0);
-        put(92, rows ? c1 : b2); put(93, rows ? c2 : b3); put(94, rows ? b2 : c1); put(95, rows ? b3 : c2);
+        // two terms against c0: n1 = f16(N / c0) -- the same leading term as the three-term expansion, so the coarse d2~ of a
+        // row is what it was -- and n2 = f16((N - c0 n1) / c0).  Stored:
+        //     rows    [0,32): h1 | c0, n1     [32,64): h2 | 0, n2
+        //     columns [0,32): h1 | n1, c0     [32,64): h2 | n2, 0
+        // so the row norm meets c0 in steps 0-1 (n1) and 4-5 (n2), the column norm in steps 0-1 (n1) and 2-3 (n2), and the
+        // zero slots meet the other side's n1 (steps 4-5: columns' n1 x rows' 0; steps 2-3: rows' n1 x columns' 0).  A padding
+        // position (or a norm the f16 terms cannot hold) therefore keeps n1 FINITE -- the largest f16, 65504 -- and puts +inf
+        // into n2: 0 x inf would make the product NaN.  Its full d2~ is +inf as before; its coarse d2~ (steps 0-1) is >= 65504 c0,
+        // about 2 N_max, instead of +inf -- above the thresholds of any real data, and a tile kept on it ends at +inf: it can cost
+        // a tile, never change a minimum.
+        _Float16 n1 = (_Float16) 65504.f, n2 = (_Float16) __uint_as_float(0x7f800000u);
+        if (o >= 0 && N / sc.a_norm[0] < 65504.f) {
+            n1 = (_Float16) (N / sc.a_norm[0]);
+            const float r1 = __builtin_fmaf(-sc.a_norm[0], (float) n1, N);   // exact
+            n2 = (_Float16) (r1 / sc.a_norm[0]);
+        }
+        const _Float16 z = (_Float16) 0.f;
+        put(30, rows ? c0 : n1); put(31, rows ? n1 : c0);
+        put(62, rows ? z : n2); put(63, rows ? n2 : z);
     } else {
+        _Float16 b1, b2, b3;
+        if (o >= 0) {
+            b1 = (_Float16) (N / sc.a_norm[0]);
+            float r1 = __builtin_fmaf(-sc.a_norm[0], (float) b1, N);
+            b2 = (_Float16) (r1 / sc.a_norm[1]);
+            float r2 = __builtin_fmaf(-sc.a_norm[1], (float) b2, r1);
+            b3 = (_Float16) (r2 / sc.a_norm[2]);
+        } else {
+            b1 = (_Float16) __uint_as_float(0x7f800000u); b2 = (_Float16) 0.f; b3 = (_Float16) 0.f;   // padding: +inf
+        }
+        // 3 nd .. 3 nd + 2 carry |b'|^2 (expansion on the column side, constants on the row side), the next three |a'|^2 the
+        // other way round: columns [expansion | constants], rows [constants | expansion]
         put(3 * nd + 0, rows ? c0 : b1); put(3 * nd + 1, rows ? c1 : b2); put(3 * nd + 2, rows ? c2 : b3);
         put(3 * nd + 3, rows ? b1 : c0); put(3 * nd + 4, rows ? b2 : c1); put(3 * nd + 5, rows ? b3 : c2);
 #pragma unroll
-        for (int cidx = 3 * nd + 6; cidx < ks * 16; ++cidx) put(cidx, (_Float16) 0.f);
+        for (int cidx = 3 * nd + 6; cidx < nf * 16; ++cidx) put(cidx, (_Float16) 0.f);
     }
-    f16x8* base = reinterpret_cast<f16x8*>(P) + ((size_t) set * (n_pad / TILE) + tile) * ks * 64;
+    f16x8* base = reinterpret_cast<f16x8*>(P) + ((size_t) set * (n_pad / TILE) + tile) * nf * 64;
 #pragma unroll
-    for (int piece = 0; piece < 2 * ks; ++piece) {
+    for (int piece = 0; piece < 2 * nf; ++piece) {
         f16x8 w;
 #pragma unroll
         for (int j = 0; j < 8; ++j) w[j] = hv[piece * 8 + j];

@@ -701,7 +701,7 @@ constexpr int RF_THREADS = 256;
 #ifndef RF_OCC
 #define RF_OCC 4   // waves per SIMD of rerank_refilter (round 5: the allocator took 154 VGPRs and two; the kernel waits on barriers and tile loads 64 % of its wave cycles)
 #endif
-template <bool ROWDIR, int KS>
+template <bool ROWDIR, int FMT>
 __global__ __launch_bounds__(RF_THREADS) __attribute__((amdgpu_waves_per_eu(RF_OCC, RF_OCC))) void rerank_refilter(RefilterArgs ra, const unsigned* __restrict__ item_g, const unsigned* __restrict__ item_q, unsigned n_items,
                                                               int n_groups, int q_pad, int t_pad, int group_size, const int* __restrict__ starts,
                                                               const float* __restrict__ nQ, const int* __restrict__ blkclQ, const float* __restrict__ nQ_sets,
@@ -729,11 +729,12 @@ __global__ __launch_bounds__(RF_THREADS) __attribute__((amdgpu_waves_per_eu(RF_O
     // run is chosen for the whole workgroup and its train tiles go through LDS once for all four waves (every wave fetching
     // its own copy made the kernel a re-reader of operand tiles: 5-6 GB per launch at 1M).  A wave without items in the run
     // only joins the barriers.
-    __shared__ __attribute__((aligned(16))) f16x8 tile_s[KS * 64];
+    constexpr int NF = OpFmt<FMT>::NF;   // stored fragments per tile; A (rows) is the MFMA's first operand in both directions
+    __shared__ __attribute__((aligned(16))) f16x8 tile_s[NF * 64];
     __shared__ unsigned long long runkey_s[RF_THREADS / 64];
     // XCD-aware block order (round 5): the items are sorted by group, a group's ~700 items are five or six consecutive blocks -- which the
-    // hardware spreads over as many XCDs, each L2 fetching the group's 192 KB of fragments for itself (2.2 GB of HBM-side traffic per launch at
-    // 3.2 TB/s: the kernel's bound).  XCD x takes the contiguous block range [x per, (x + 1) per): a group's blocks run back to back on one L2.
+    // hardware spreads over as many XCDs, each L2 fetching the group's 128 KB of fragments for itself (2.2 GB of HBM-side traffic per launch at
+    // 3.2 TB/s with six stored fragments, about a third less with four: the kernel's bound).  XCD x takes the contiguous block range [x per, (x + 1) per): a group's blocks run back to back on one L2.
     const int n_blk = (int) ((n_items + 32u * (RF_THREADS / 64) - 1u) / (32u * (RF_THREADS / 64)));
     const int blk = (int) (blockIdx.x & 7u) * ((n_blk + 7) >> 3) + (int) (blockIdx.x >> 3);
     if (blk >= n_blk) return;
@@ -751,7 +752,7 @@ __global__ __launch_bounds__(RF_THREADS) __attribute__((amdgpu_waves_per_eu(RF_O
     }
     const unsigned long long my_key = have ? (((unsigned long long) my_g << 8) | (unsigned) my_p) : ~0ull;
     bool todo = have;
-    constexpr int PIECES = KS * 64;   // 16-byte pieces of a train tile
+    constexpr int PIECES = NF * 64;   // 16-byte pieces of a train tile
     for (;;) {
         // the run of this round: all pending items of the workgroup with the smallest pending (group, cluster)
         {
@@ -776,7 +777,7 @@ __global__ __launch_bounds__(RF_THREADS) __attribute__((amdgpu_waves_per_eu(RF_O
         const bool act = todo && my_key == rk;
         todo = todo && !act;
         const bool wave_on = __ballot(act) != 0ull;
-        f16x8 qf[KS];
+        f16x8 qf[NF];
         // Pre-test of a tile (round 5): about one pair per query passes in the whole launch, so nearly every 32 x 32 tile ends with nothing to emit --
         // but the exact test below is sixteen multiply / subtract / compare / ballot / branch groups per tile, the bulk of the kernel's vector
         // instructions.  bound = (thr + eps) / out_scale, inflated by 1e-6 (its own roundings and the exact test's are worth 3e-7): whatever the
@@ -789,9 +790,9 @@ __global__ __launch_bounds__(RF_THREADS) __attribute__((amdgpu_waves_per_eu(RF_O
             }
             // the queries' fragments: lane (c, half) reads the 8 halves of its query for every K step
             const f16x8* src = ROWDIR ? ra.Ap : ra.Bp + (size_t) p * ra.bset_stride;
-            const size_t o = ((size_t) (my_q >> 5) * KS) * 64 + (my_q & 31) + 32 * half;
+            const size_t o = ((size_t) (my_q >> 5) * NF) * 64 + (my_q & 31) + 32 * half;
 #pragma unroll
-            for (int kk = 0; kk < KS; ++kk) qf[kk] = src[o + (size_t) kk * 64];
+            for (int kk = 0; kk < NF; ++kk) qf[kk] = src[o + (size_t) kk * 64];
             auto inflate = [&](float t) {   // (thr + eps) / out_scale, rounded up; -inf stays -inf, NaN keeps the tile
                 const float b = t / ra.out_scale;
                 return b >= 0.f ? b * 1.000001f + 1e-30f : (b < 0.f ? b * 0.999999f + 1e-30f : __uint_as_float(0x7f800000u));
@@ -809,7 +810,7 @@ __global__ __launch_bounds__(RF_THREADS) __attribute__((amdgpu_waves_per_eu(RF_O
         // train tiles: fetched by the whole workgroup (the next one into registers while the current one is consumed), one LDS copy
         f16x8 nx0, nx1;
         auto fetch = [&](int t0) {
-            const f16x8* tb = tsrc + (size_t) (t0 >> 5) * KS * 64;
+            const f16x8* tb = tsrc + (size_t) (t0 >> 5) * NF * 64;
             nx0 = tb[threadIdx.x];
             if ((int) threadIdx.x + RF_THREADS < PIECES) nx1 = tb[threadIdx.x + RF_THREADS];
         };
@@ -823,9 +824,10 @@ __global__ __launch_bounds__(RF_THREADS) __attribute__((amdgpu_waves_per_eu(RF_O
             if (!wave_on) continue;
             f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                const f16x8 tf = tile_s[kk * 64 + lane];
-                acc = ROWDIR ? mfma_step(qf[kk], tf, acc) : mfma_step(tf, qf[kk], acc);
+            for (int kk = 0; kk < OpFmt<FMT>::KS; ++kk) {
+                const int fq = ROWDIR ? OpFmt<FMT>::fa(kk) : OpFmt<FMT>::fb(kk), ft = ROWDIR ? OpFmt<FMT>::fb(kk) : OpFmt<FMT>::fa(kk);
+                const f16x8 tf = tile_s[ft * 64 + lane];
+                acc = ROWDIR ? mfma_step(qf[fq], tf, acc) : mfma_step(tf, qf[fq], acc);
             }
             // ROWDIR: acc[r] = (query row (r&3) + 8 (r>>2) + 4 half, train column c); COLDIR: (train row ..., query column c)
             {
@@ -1122,8 +1124,8 @@ int run_rerank(lgr_ctx* ctx, EpsExtra ex, CompView comp, const float* table, int
             LGR_HIP(ctx, hipMemsetAsync(n_pairs, 0, 4, ctx->stream));
             const int rf_grid = ((cdiv(n_items, 32 * (RF_THREADS / 64)) + 7) >> 3) << 3;   // (a multiple of 8: the kernel's XCD-aware block order)
 #define LGR_RF_ARGS ra, item_g2, item_q2, n_items, n_groups, q_pad, ts.n_pad, group_size, starts, nQ, qs.blkcl, nQ_sets, gmax, cl_of_group, ex, thr, cap, n_pairs, pair_q, pair_t
-            if (ra.ks == 6) rerank_refilter<ROWDIR, 6><<<rf_grid, RF_THREADS, 0, ctx->stream>>>(LGR_RF_ARGS);
-            else rerank_refilter<ROWDIR, 7><<<rf_grid, RF_THREADS, 0, ctx->stream>>>(LGR_RF_ARGS);
+            if (ra.ks == OpFmt<FMT_F16R>::KS) rerank_refilter<ROWDIR, FMT_F16R><<<rf_grid, RF_THREADS, 0, ctx->stream>>>(LGR_RF_ARGS);
+            else rerank_refilter<ROWDIR, FMT_F16><<<rf_grid, RF_THREADS, 0, ctx->stream>>>(LGR_RF_ARGS);
 #undef LGR_RF_ARGS
             LGR_HIP(ctx, hipMemcpyAsync(h + 8, n_pairs, 4, hipMemcpyDeviceToHost, ctx->stream));
             LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));

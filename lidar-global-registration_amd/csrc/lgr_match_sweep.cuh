@@ -56,8 +56,8 @@ __global__ __launch_bounds__(NTHR, SW_OCC) void match_sweep(const f16x8* __restr
                                                             const unsigned short* __restrict__ ucol16 /* [mb_pad] or nullptr */,
                                                             uint2* __restrict__ kept_out, unsigned long long* __restrict__ kept_count /* 64 bits: never wraps below the capacity */, unsigned kept_cap) {
     typedef f16x8 frag;
-    constexpr int KS = OpFmt<FMT_F16R>::KS;
-    constexpr int STAGE_FRAGS = STAGE_TILES * KS * 64;
+    constexpr int NF = OpFmt<FMT_F16R>::NF;   // stored fragments per tile (the sweep reads the first two: the coarse steps)
+    constexpr int STAGE_FRAGS = STAGE_TILES * NF * 64;
     constexpr int CO_FRAGS = STAGE_TILES * 2 * 64, CO_NB = 6, CO_D = 4;   // ring slot (fragments), slots, stages in flight (as match_mfma)
     static_assert(CO_D == 4 && CO_NB == CO_D + 2, "the counted waits below are written for two pairs of stages in flight");
     static_assert(WAVES == 2 * STAGE_TILES, "one coarse piece per wave");
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(NTHR, SW_OCC) void match_sweep(const f16x8* __restr
             const unsigned mask = mk[0] | mk[1];   // uniform over the workgroup
             if (!mask) continue;
             const int set = blkcl[rbA];
-            const frag* Bset = Bp + (size_t) set * bset_stride + (size_t) col_tile0 * KS * 64;
+            const frag* Bset = Bp + (size_t) set * bset_stride + (size_t) col_tile0 * NF * 64;
             int row_tile[2];
             frag a0[2], a1[2];
             int t_lane[2][2];       // [block][q >> 6]: coarse threshold of tile q = 4 stage + ct in lane q & 63 (column side + error term)
@@ -115,8 +115,8 @@ __global__ __launch_bounds__(NTHR, SW_OCC) void match_sweep(const f16x8* __restr
             for (int r = 0; r < SW_RB; ++r) {
                 row_tile[r] = (rbA + r) * (BLOCK_ROWS / TILE) + wave;
                 const int rt = mk[r] ? row_tile[r] : row_tile[0];   // (a block that sits the visit out: any valid address)
-                a0[r] = Ap[((size_t) rt * KS + 0) * 64 + lane];
-                a1[r] = Ap[((size_t) rt * KS + 1) * 64 + lane];
+                a0[r] = Ap[((size_t) rt * NF + 0) * 64 + lane];
+                a1[r] = Ap[((size_t) rt * NF + 1) * 64 + lane];
                 t_lane[r][0] = t_lane[r][1] = IINF; e_lane[r][0] = e_lane[r][1] = 0.f; trow[r] = 0.f;
                 skipm[r][0] = skipm[r][1] = 0ull;
 #pragma unroll
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(NTHR, SW_OCC) void match_sweep(const f16x8* __restr
             auto dma_coarse = [&]() {
                 const int s_ = __builtin_ctz(to_issue);
                 to_issue &= to_issue - 1u;
-                const char* src = reinterpret_cast<const char*>(Bset + (size_t) s_ * STAGE_FRAGS + (size_t) ((wave >> 1) * KS + (wave & 1)) * 64);
+                const char* src = reinterpret_cast<const char*>(Bset + (size_t) s_ * STAGE_FRAGS + (size_t) ((wave >> 1) * NF + (wave & 1)) * 64);
                 char* dst = reinterpret_cast<char*>(smem) + (issued % CO_NB) * (CO_FRAGS * (int) sizeof(frag)) + wave * 1024;
 #ifndef LGR_EXP_SWEEP_NODMA   // (timing ablations, tools/exp_sweep_ablate.sh: wrong results)
                 __builtin_amdgcn_global_load_lds((const void*) (src + lane * 16), (__attribute__((address_space(3))) void*) dst, 16, 0, 0);
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(64 * TL_WAVES) void match_tiles(const f16x8* __rest
                                                              int* __restrict__ rowmin, int* __restrict__ colmin, const uint2* __restrict__ kept,
                                                              const unsigned long long* __restrict__ kept_count, unsigned kept_cap) {
     typedef f16x8 frag;
-    constexpr int KS = OpFmt<FMT_F16R>::KS;
+    constexpr int NF = OpFmt<FMT_F16R>::NF;
     constexpr int IINF = 0x7f800000;
     const int lane = threadIdx.x & 63, half = lane >> 5;
     if (*kept_count > (unsigned long long) kept_cap) return;   // overflow: the fused kernel repeats the whole pass
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(64 * TL_WAVES) void match_tiles(const f16x8* __rest
     const unsigned n_waves = gridDim.x * TL_WAVES, w_id = blockIdx.x * TL_WAVES + (threadIdx.x >> 6);
     const int rg_blocks = rg_rows / BLOCK_ROWS;
     const f32x16 nav = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    frag a[KS];
+    frag a[NF];
     unsigned cur_rt = 0xffffffffu;
     for (unsigned e0 = w_id * TL_RUN; e0 < n; e0 += n_waves * TL_RUN) {
         for (unsigned e = e0; e < min(n, e0 + TL_RUN); ++e) {
@@ -333,15 +333,13 @@ __global__ __launch_bounds__(64 * TL_WAVES) void match_tiles(const f16x8* __rest
             if (rt != cur_rt) {
                 cur_rt = rt;
 #pragma unroll
-                for (int kk = 0; kk < KS; ++kk) a[kk] = Ap[((size_t) rt * KS + kk) * 64 + lane];
+                for (int kk = 0; kk < NF; ++kk) a[kk] = Ap[((size_t) rt * NF + kk) * 64 + lane];
             }
-            const frag* bsrc = Bp + (size_t) blkcl[rb] * bset_stride + (size_t) ct * KS * 64 + lane;
-            frag b[KS];
+            const frag* bsrc = Bp + (size_t) blkcl[rb] * bset_stride + (size_t) ct * NF * 64 + lane;
+            frag b[NF];
 #pragma unroll
-            for (int kk = 0; kk < KS; ++kk) b[kk] = bsrc[kk * 64];
-            f32x16 acc = mfma_step(a[0], b[0], nav);
-#pragma unroll
-            for (int kk = 1; kk < KS; ++kk) acc = mfma_step(a[kk], b[kk], acc);
+            for (int kk = 0; kk < NF; ++kk) b[kk] = bsrc[kk * 64];
+            const f32x16 acc = mfma_chain<FMT_F16R>(a, b, nav);
             // column minima: the 16 registers of a lane are 16 rows of one column; the two lane halves hold the other 16 rows of the same column
             if (COLDIR) {
                 int cm = min(__float_as_int(acc[0]), __float_as_int(acc[1]));
