@@ -13,6 +13,7 @@
  *   - point  : 12 floats, pcl::PointXYZINormal layout {x,y,z,1 | nx,ny,nz,0 | intensity,curvature,pad,pad} (48 B)
  *   - fpfh   : 33 floats (pcl::FPFHSignature33, 132 B, row-major M x 33)
  *   - shot   : 352 floats (pcl::SHOT352::descriptor, 1408 B, row-major M x 352); frames 9 floats (pcl::ReferenceFrame)
+ *   - rops   : 135 floats (RoPS135::histogram, 540 B, row-major M x 135)
  *   - corr   : lgr_corr (include/common.h:120-127 Correspondence), 16 B
  *   - T      : 16 floats COLUMN-major (Eigen::Matrix4f default)
  *   - host entry points (no suffix) borrow caller memory for the duration of the call, upload, run the device
@@ -267,6 +268,23 @@ int lgr_shot(lgr_ctx*, const float* kps, int m, const float* surf, int n, float 
              float* out_m_x_352, float* out_lrf_or_null);
 int lgr_shot_dev(lgr_ctx*, const float* d_kps, int m, const float* d_surf, int n, float radius, const float* d_lrf_or_null,
                  float* d_out_m_x_352, float* d_out_lrf_or_null);
+/* ---- gravity frames (src/common.cpp:693-755 estimateReferenceFrames with lrf_id "gravity", g = (0, 0, 1)) ----
+ * z = the key point's normal (floats 4..6 of its row).  acos(|clamp(z . g, -1, 1)|) > 0.04 (RF_MIN_ANGLE_RAD): y = g x z, x = y x z
+ * (not normalized); otherwise -- a near-vertical or NaN normal -- the SHOT frame of lgr_shot_lrf on the same surface and radius
+ * (NaN where that has none).  9 floats per key point as lgr_shot_lrf.  The dot and cross products follow DESIGN.md section 4. */
+int lgr_gravity_lrf(lgr_ctx*, const float* kps, int m, const float* surf, int n, float radius, float* out_m_x_9);
+int lgr_gravity_lrf_dev(lgr_ctx*, const float* d_kps, int m, const float* d_surf, int n, float radius, float* d_out_m_x_9);
+/* ---- RoPS135 on given frames (include/common.h estimateFeatures<RoPS135> after estimateReferenceFrames:
+ *      ROPSEstimationWithLocalReferenceFrames, include/pcl/impl/rops_custom_lrf.hpp:96-186 and :364-518; 5 bins, 3 rotations,
+ *      support radius = radius) ----
+ * The support is the surface points with squared distance < radius^2 (as lgr_shot), transformed by the frame (lrf: m x 9, required).
+ * Per axis x, y, z and angle 22.5, 45, 67.5 degrees: the rotated support's box, then for the projections XY, XZ, YZ the 5 x 5
+ * distribution matrix, its central moments (1,1), (2,1), (1,2), (2,2) and its entropy; the row divided by its L1 norm (unchanged
+ * below FLT_EPSILON).  An empty support (or a non-finite key point) gives the zero row; one support point or a NaN frame gives the
+ * zero row too (every point falls in cell (0, 0)).  logf, the bin index cast and Eigen's orders are those of DESIGN.md section 4
+ * (csrc/lgr_rops_math.h). */
+int lgr_rops(lgr_ctx*, const float* kps, int m, const float* surf, int n, float radius, const float* lrf, float* out_m_x_135);
+int lgr_rops_dev(lgr_ctx*, const float* d_kps, int m, const float* d_surf, int n, float radius, const float* d_lrf, float* d_out_m_x_135);
 /* Device self-check of the FPFH weighting kernel's reciprocal (v_rcp_f32 + one Newton step in place of the IEEE division sequence;
  * include/common.h:322-332 -> pcl::FPFHEstimation::weightPointSPFHSignature's 1.0f / dists[idx]): every float whose bit pattern lies in
  * [lo_bits, hi_bits] goes through both; out2[0] = values where they differ (must be 0 on [1e-36, 1e36], the range the kernel uses it on),
@@ -291,6 +309,12 @@ int lgr_match_shot(lgr_ctx*, const float* q352, int mq, const float* t352, int m
 int lgr_match_shot_dev(lgr_ctx*, const float* d_q352, int mq, const float* d_t352, int mt, int block, int32_t* d_idx, float* d_dist);
 /* both directions from one pass over the (a, b) distances */
 int lgr_match2_shot_dev(lgr_ctx*, const float* d_a352, int ma, const float* d_b352, int mb, int block,
+                        int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
+/* ---- include/matching.h:373-376 matchBF<RoPS135>(query, train, params): the contract of lgr_match_shot on M x 135 rows (OpenCV 4.5.1's
+ *      normL2Sqr for n = 135: 8 blocks of 16 in the lane order of lgr_match_shot, then d2 += t * t over elements 128..134 in order) ---- */
+int lgr_match_rops(lgr_ctx*, const float* q135, int mq, const float* t135, int mt, int block, int32_t* idx, float* dist);
+int lgr_match_rops_dev(lgr_ctx*, const float* d_q135, int mq, const float* d_t135, int mt, int block, int32_t* d_idx, float* d_dist);
+int lgr_match2_rops_dev(lgr_ctx*, const float* d_a135, int ma, const float* d_b135, int mb, int block,
                         int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
 /* ---- include/matching.h:373-376 matchFLANN<FPFH>(query_features, train_features, parameters), randomness 1 (:565-592):
  *      pcl::KdTreeFLANN is an exact search, so the nearest row is the one matchBF finds (the reference's own test asserts that,
@@ -361,14 +385,19 @@ int lgr_correspondences_dev(lgr_ctx*, const float* d_src, int ns, const float* d
  * lgr_align_ex*(..., NULL) are lgr_correspondences* and lgr_align*.  SHOT is built for the brute-force matcher only: SHOT with
  * use_bfmatcher = 0, with has_guess, or on a context whose arithmetic is LGR_ARITH_PCL returns LGR_ERR_UNSUPPORTED (the
  * arithmetic modes differ in the FPFH weighting only and mean nothing for SHOT; the SHOT stage has one arithmetic).  lrf_id
- * matters to SHOT only (FPFH never reads it, as in the reference): LGR_LRF_DEFAULT is built, the reference's 'gravity' and 'gt' frames
- * (src/common.cpp:693-755) return LGR_ERR_UNSUPPORTED, other values LGR_ERR_INVALID_ARG.
- * lgr_result.stage_ms[2] ("fpfh") carries the descriptor stage, whichever descriptor ran. */
-enum { LGR_DESCRIPTOR_FPFH = 0, LGR_DESCRIPTOR_SHOT = 1 };
-enum { LGR_LRF_DEFAULT = 0, LGR_LRF_GRAVITY = 1, LGR_LRF_GT = 2 };   /* gravity / gt: LGR_ERR_UNSUPPORTED */
+ * matters to SHOT and RoPS only (FPFH never reads it, as in the reference).  SHOT: LGR_LRF_DEFAULT is built, the reference's
+ * 'gravity' and 'gt' frames (src/common.cpp:693-755) return LGR_ERR_UNSUPPORTED, other values LGR_ERR_INVALID_ARG.
+ * RoPS (LGR_DESCRIPTOR_ROPS, include/common.h estimateFeatures<RoPS135>): LGR_LRF_GRAVITY is built (lgr_gravity_lrf, then lgr_rops,
+ * per call and per scale level, on key points whose normals are first re-estimated on the level's surface as include/matching.h:243-246
+ * does); LGR_LRF_DEFAULT returns LGR_ERR_UNSUPPORTED (the reference triangulates the cloud with
+ * GreedyProjectionTriangulation for it), LGR_LRF_GT too (this struct has no ground-truth channel), other values
+ * LGR_ERR_INVALID_ARG; use_bfmatcher = 0, has_guess and LGR_ARITH_PCL are refused as for SHOT.
+ * lgr_result.stage_ms[2] ("fpfh") carries the descriptor stage, whichever descriptor ran (for RoPS: frames and rows). */
+enum { LGR_DESCRIPTOR_FPFH = 0, LGR_DESCRIPTOR_SHOT = 1, LGR_DESCRIPTOR_ROPS = 2 };
+enum { LGR_LRF_DEFAULT = 0, LGR_LRF_GRAVITY = 1, LGR_LRF_GT = 2 };   /* SHOT: default only; RoPS: gravity only */
 typedef struct {
-    int32_t descriptor_id;   /* LGR_DESCRIPTOR_FPFH / LGR_DESCRIPTOR_SHOT */
-    int32_t lrf_id;          /* LGR_LRF_DEFAULT (SHOT only) */
+    int32_t descriptor_id;   /* LGR_DESCRIPTOR_FPFH / LGR_DESCRIPTOR_SHOT / LGR_DESCRIPTOR_ROPS */
+    int32_t lrf_id;          /* LGR_LRF_DEFAULT (SHOT) / LGR_LRF_GRAVITY (RoPS) */
     int32_t reserved[6];     /* 0 */
 } lgr_feature_params;
 void lgr_default_feature_params(lgr_feature_params* f);      /* FPFH, default frames */

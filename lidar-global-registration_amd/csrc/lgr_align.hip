@@ -171,9 +171,22 @@ static int filter_core(lgr_ctx* ctx, int matching_id, int ns, const int32_t* d_i
 static void tick(lgr_ctx* ctx, int i) { (void) hipEventRecord(ctx->ev[i], ctx->stream); }
 
 // the descriptor of the correspondence search (lgr_feature_params): its row length and its feature stage
-static int desc_len(int descriptor) { return descriptor == LGR_DESCRIPTOR_SHOT ? 352 : 33; }
-static int descriptor_dev(lgr_ctx* ctx, int descriptor, const float* kps, int m, const float* surf, int n, float radius, float* out) {
+static int desc_len(int descriptor) { return descriptor == LGR_DESCRIPTOR_SHOT ? 352 : (descriptor == LGR_DESCRIPTOR_ROPS ? 135 : 33); }
+static int descriptor_dev(lgr_ctx* ctx, int descriptor, const float* kps, int m, const float* surf, int n, float radius, float* out,
+                          const lgr_params* p, const float* vp) {
     if (descriptor == LGR_DESCRIPTOR_SHOT) return lgr_shot_dev(ctx, kps, m, surf, n, radius, nullptr, out, nullptr);
+    if (descriptor == LGR_DESCRIPTOR_ROPS) {
+        if (m == 0) return LGR_OK;
+        // include/matching.h:243-246 (reestimate_frames, true by default: lgr_params has no field for it): the key-point copy's normals
+        // are re-estimated on the level's surface, estimateNormalsPoints(normal_nr_points, kps, surface, viewpoint, true).  FPFH and SHOT
+        // never read them; the gravity frames do (z = the key point's normal).
+        float* kn;
+        LGR_TRY(lgr_ws_t(ctx, WS_ROPS_KPS, (size_t) m * 12, &kn));
+        LGR_HIP(ctx, hipMemcpyAsync(kn, kps, (size_t) m * 48, hipMemcpyDeviceToDevice, ctx->stream));
+        LGR_TRY(lgr_normals_knn_dev(ctx, kn, m, surf, n, p->normal_nr_points, vp, 1));
+        // estimateFeatures<RoPS135> estimates its frames on every call, so per scale level too (only gravity frames are built)
+        return lgr_rops_gravity_dev(ctx, kn, m, surf, n, radius, out);
+    }
     return lgr_fpfh_dev(ctx, kps, m, surf, n, radius, out);
 }
 
@@ -187,7 +200,7 @@ struct MsSide {
     int min_l2 = INT_MAX, max_l2 = INT_MIN;
     std::vector<std::vector<int>> lists;   // per scale: key-point indices
     std::vector<size_t> feat_off;          // per scale: row offset into the feature buffer
-    float* feat = nullptr;                 // device, sum(rows) x D (D = 33 FPFH, 352 SHOT)
+    float* feat = nullptr;                 // device, sum(rows) x D (D = 33 FPFH, 352 SHOT, 135 RoPS)
     int32_t* d_lists = nullptr;            // device copy of the lists, concatenated like feat_off
     std::vector<float> xyz;                // host copy of the key points (3 floats each) for the vote
 };
@@ -267,7 +280,7 @@ static int ms_initialize(lgr_ctx* ctx, MsSide& st, int side, const float* d_pcd,
         const int m = (int) st.lists[i].size();
         if (m) {
             gather_rows12_kernel<<<cdiv((long long) m * 12, 256), 256, 0, ctx->stream>>>(d_kps, st.d_lists + st.feat_off[i], m, sub);
-            LGR_TRY(descriptor_dev(ctx, descriptor, sub, m, out, nd, search_radius, st.feat + st.feat_off[i] * D));
+            LGR_TRY(descriptor_dev(ctx, descriptor, sub, m, out, nd, search_radius, st.feat + st.feat_off[i] * D, p, vp));
         }
         tick(ctx, 3);
         LGR_HIP(ctx, hipEventSynchronize(ctx->ev[3]));
@@ -330,6 +343,10 @@ static int match_dispatch(lgr_ctx* ctx, const lgr_params* p, int descriptor, con
     if (descriptor == LGR_DESCRIPTOR_SHOT) {   // (checked on entry: SHOT runs the brute-force matcher only)
         if (need_ba) return lgr_match2_shot_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d, ba_i, ba_d);
         return lgr_match_shot_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d);
+    }
+    if (descriptor == LGR_DESCRIPTOR_ROPS) {   // (likewise)
+        if (need_ba) return lgr_match2_rops_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d, ba_i, ba_d);
+        return lgr_match_rops_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d);
     }
     if (p->has_guess) {
         LGR_TRY(lgr_match_local_dev(ctx, a_pts, ma, b_pts, mb, fa, fb, p->guess, p->match_search_radius, ab_i, ab_d));
@@ -433,10 +450,19 @@ extern "C" void lgr_default_feature_params(lgr_feature_params* f) {
 static int feature_descriptor(lgr_ctx* ctx, const lgr_params* p, const lgr_feature_params* f, int* descriptor) {
     *descriptor = LGR_DESCRIPTOR_FPFH;
     if (!f) return LGR_OK;
-    LGR_CHECK(ctx, f->descriptor_id == LGR_DESCRIPTOR_FPFH || f->descriptor_id == LGR_DESCRIPTOR_SHOT, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, f->descriptor_id == LGR_DESCRIPTOR_FPFH || f->descriptor_id == LGR_DESCRIPTOR_SHOT || f->descriptor_id == LGR_DESCRIPTOR_ROPS,
+              LGR_ERR_UNSUPPORTED);
     if (f->descriptor_id == LGR_DESCRIPTOR_SHOT) {    // the frames matter to SHOT only (FPFH never reads lrf_id, include/common.h:366,407)
         LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT || f->lrf_id == LGR_LRF_GRAVITY || f->lrf_id == LGR_LRF_GT, LGR_ERR_INVALID_ARG);
         LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT, LGR_ERR_UNSUPPORTED);
+        LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);     // matchFLANN / matchLocal are built for FPFH only
+        LGR_CHECK(ctx, ctx->opt.arithmetic != LGR_ARITH_PCL, LGR_ERR_UNSUPPORTED);  // the arithmetic modes are FPFH weightings
+    }
+    if (f->descriptor_id == LGR_DESCRIPTOR_ROPS) {
+        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT || f->lrf_id == LGR_LRF_GRAVITY || f->lrf_id == LGR_LRF_GT, LGR_ERR_INVALID_ARG);
+        // default: estimateFeatures<RoPS135> triangulates the cloud (GreedyProjectionTriangulation) and takes RoPS's own frames;
+        // gt: the reference reads parameters.ground_truth, for which lgr_feature_params has no channel
+        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_GRAVITY, LGR_ERR_UNSUPPORTED);
         LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);     // matchFLANN / matchLocal are built for FPFH only
         LGR_CHECK(ctx, ctx->opt.arithmetic != LGR_ARITH_PCL, LGR_ERR_UNSUPPORTED);  // the arithmetic modes are FPFH weightings
     }
@@ -552,7 +578,7 @@ extern "C" int lgr_correspondences_ex_dev(lgr_ctx* ctx, const float* d_src, int 
         tick(cx, 2);
         // :243-246 re-estimates the normals of the key-point COPY; FPFH reads only the surface normals
         // (include/common.h:329), so that step has no observable effect and is not executed.
-        LGR_TRY(descriptor_dev(cx, descriptor, kclouds[c], ksizes[c], surf[c], nd, search_radius, feat[c]));   // :248
+        LGR_TRY(descriptor_dev(cx, descriptor, kclouds[c], ksizes[c], surf[c], nd, search_radius, feat[c], p, vp));   // :248
         tick(cx, 3);
         LGR_HIP(cx, hipEventSynchronize(cx->ev[3]));
         float t;

@@ -122,6 +122,7 @@ enum {
     WS_MS_KNN_I, WS_MS_KNN_D, WS_MS_LIST_S, WS_MS_LIST_T, WS_MS_SUB, WS_MS_FEAT_S, WS_MS_FEAT_T, WS_MS_SURF2, WS_MS_RES, WS_PLANE_VISITED, WS_PLANE_CLAIMED, WS_PLANE_OUT, WS_LOCAL_G, WS_SORT_TMP, WS_MATCH_BOX, WS_RANSAC_GHIST,
     WS_HOST_A, WS_HOST_B, WS_HOST_C, WS_HOST_D, WS_HOST_E, WS_HOST_F,
     WS_SHOT_PACK_A, WS_SHOT_PACK_B, WS_SHOT_KEYS,
+    WS_ROPS_MASKED, WS_ROPS_LRF, WS_ROPS_KPS,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 112, "grow lgr_ctx::ws");
@@ -152,6 +153,8 @@ struct GridDev {
 };
 // h <= 0: automatic cell (about `target` points per occupied cell, 2-D manifold heuristic)
 int lgr_grid_build(lgr_ctx* ctx, int slot_base, const float* d_pts, int n, float h, float target, GridDev* out);
+// the pipeline's RoPS stage (lgr_rops.hip): gravity frames (src/common.cpp:713-750), then RoPS135 rows on them
+int lgr_rops_gravity_dev(lgr_ctx* ctx, const float* d_kps, int m, const float* d_surf, int n, float radius, float* d_out135);
 // both bounding boxes of a cloud: out12 (host) = true min3, true max3 (finite points only; +-inf when empty),
 // reference-quirk min3, max3 (include/common.h:266-280)
 int lgr_bbox_host(lgr_ctx* ctx, const float* d_pts, int n, float* out12);

@@ -5,16 +5,17 @@
 //   include/correspondence_search.h:9-28  CorrespondenceSearch, FeatureBasedCorrespondenceSearch
 //   include/sac_prerejective_omp.h:21-56  SampleConsensusPrerejectiveOMP
 //   include/downsample.h:32               downsamplePointCloud
-//   include/common.h:322-332, 360-370     estimateFeatures<FPFH>, estimateFeatures<SHOT>
-//   include/matching.h:373-376            matchBF<FPFH>, matchBF<SHOT>
+//   include/common.h:322-332, 360-370     estimateFeatures<FPFH>, estimateFeatures<SHOT>, estimateFeatures<RoPS135> (gravity frames)
+//   include/matching.h:373-376            matchBF<FPFH>, matchBF<SHOT>, matchBF<RoPS135>
 //   include/transformation.h:6-7          estimateOptimalRigidTransformation
 //   include/hypotheses.h:10-12            updateHypotheses
 //   src/common.cpp:531-547, 644-655       calculateSmoothedDensities, estimateNormalsPoints
 //
 // The reference passes pcl::PointCloud<pcl::PointXYZINormal> / pcl::FPFHSignature33 / Eigen::Matrix4f.  Neither PCL
 // nor Eigen exists in this image, so the shim is written against three tiny layout-compatible types (lgr::PointN is
-// the 48-byte PointXYZINormal, lgr::FPFH the 132-byte signature, lgr::SHOT the 1444-byte pcl::SHOT352, lgr::Matrix4f a column-major
-// 4x4).  A maintainer of the reference defines LGR_COMPAT_POINT_T / LGR_COMPAT_FPFH_T / LGR_COMPAT_SHOT_T / LGR_COMPAT_MATRIX4F_T to the real types before
+// the 48-byte PointXYZINormal, lgr::FPFH the 132-byte signature, lgr::SHOT the 1444-byte pcl::SHOT352, lgr::RoPS135 the 540-byte
+// RoPS135, lgr::Matrix4f a column-major 4x4).  A maintainer of the reference defines LGR_COMPAT_POINT_T / LGR_COMPAT_FPFH_T /
+// LGR_COMPAT_SHOT_T / LGR_COMPAT_ROPS_T / LGR_COMPAT_MATRIX4F_T to the real types before
 // including this header: every access below is either `.points`, `.size()`, `.data()` or a
 // reinterpret of the contiguous storage, which the real types provide with the same layout.
 #pragma once
@@ -59,6 +60,13 @@ using SHOT = LGR_COMPAT_SHOT_T;
 #endif
 static_assert(sizeof(SHOT) == 1444, "SHOT must be the 1444-byte pcl::SHOT352 layout (352 + 9 floats)");
 
+#ifndef LGR_COMPAT_ROPS_T
+struct RoPS135 { float histogram[135]; };   // pcl::Histogram<135> (include/common.h)
+#else
+using RoPS135 = LGR_COMPAT_ROPS_T;
+#endif
+static_assert(sizeof(RoPS135) == 540, "RoPS135 must be the 540-byte pcl::Histogram<135> layout");
+
 #ifndef LGR_COMPAT_MATRIX4F_T
 struct Matrix4f {   // column-major like Eigen::Matrix4f
     float m[16];
@@ -84,6 +92,7 @@ template <class T> struct Cloud {   // the subset of pcl::PointCloud<T> the path
 using PointNCloud = Cloud<PointN>;
 using FPFHCloud = Cloud<FPFH>;
 using SHOTCloud = Cloud<SHOT>;
+using RoPS135Cloud = Cloud<RoPS135>;
 
 // include/common.h:120-127
 struct Correspondence {
@@ -237,17 +246,42 @@ inline void estimateFeatures<SHOT>(const PointNCloud::ConstPtr& pcd, const Point
     features->width = (unsigned) m;
 }
 
+// RoPS frames: "gravity" (compared in lower case) is built; the default frames need GreedyProjectionTriangulation and "gt" the ground
+// truth, neither of which the device path has
+inline bool lrf_is_gravity(std::string id) {
+    for (char& c : id) c = (char) std::tolower((unsigned char) c);
+    return id == "gravity";
+}
+// include/common.h estimateFeatures<RoPS135>: estimateReferenceFrames (gravity), then ROPSEstimationWithLocalReferenceFrames on them
+template <>
+inline void estimateFeatures<RoPS135>(const PointNCloud::ConstPtr& pcd, const PointNCloud::ConstPtr& surface, RoPS135Cloud::Ptr& features,
+                                      float radius_search, const AlignmentParameters& parameters) {
+    if (!lrf_is_gravity(parameters.lrf_id))
+        throw std::runtime_error("lgr: RoPS is built on gravity frames only (lrf '" + parameters.lrf_id + "' needs a triangulation or the ground truth)");
+    const int m = (int) pcd->size();
+    std::vector<float> frames((size_t) m * 9);
+    check(lgr_gravity_lrf(context(), raw(*pcd), m, raw(*surface), (int) surface->size(), radius_search, frames.data()), "estimateReferenceFrames");
+    features->points.resize(m);
+    check(lgr_rops(context(), raw(*pcd), m, raw(*surface), (int) surface->size(), radius_search, frames.data(),
+                   reinterpret_cast<float*>(features->points.data())), "estimateFeatures<RoPS135>");
+    features->width = (unsigned) m;
+}
+
 // ---- include/matching.h:373-376 (randomness = 1)
 template <class FeatureT>
 inline std::vector<MultivaluedCorrespondence> matchBF(const typename Cloud<FeatureT>::ConstPtr& query_features,
                                                       const typename Cloud<FeatureT>::ConstPtr& train_features,
                                                       const AlignmentParameters& parameters) {
-    static_assert(sizeof(FeatureT) == 132 || sizeof(FeatureT) == 1444, "only FPFH and SHOT are built on this path");
+    static_assert(sizeof(FeatureT) == 132 || sizeof(FeatureT) == 1444 || sizeof(FeatureT) == 540, "only FPFH, SHOT and RoPS135 are built on this path");
     if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness != 1 is not supported (data/test.yaml:14)");
     int mq = (int) query_features->size(), mt = (int) train_features->size();
     std::vector<int32_t> idx(mq);
     std::vector<float> dist(mq);
-    if constexpr (sizeof(FeatureT) == 1444) {   // SHOT352: the 352 descriptor floats of every row, without the frame
+    if constexpr (sizeof(FeatureT) == 540) {   // RoPS135: contiguous 135-float rows
+        check(lgr_match_rops(context(), reinterpret_cast<const float*>(query_features->points.data()), mq,
+                             reinterpret_cast<const float*>(train_features->points.data()), mt, parameters.bf_block_size, idx.data(), dist.data()),
+              "matchBF");
+    } else if constexpr (sizeof(FeatureT) == 1444) {   // SHOT352: the 352 descriptor floats of every row, without the frame
         auto rows = [](const Cloud<FeatureT>& c) {
             std::vector<float> r(c.size() * 352);
             for (std::size_t i = 0; i < c.size(); ++i) std::memcpy(r.data() + i * 352, &c.points[i], 352 * sizeof(float));
@@ -354,8 +388,13 @@ public:
         if (parameters_.descriptor_id == "shot") {
             f.descriptor_id = LGR_DESCRIPTOR_SHOT;
             if (!lrf_is_default(parameters_.lrf_id)) f.lrf_id = LGR_LRF_GRAVITY;
+        } else if (parameters_.descriptor_id == "rops") {   // gravity frames only (estimateFeatures<RoPS135> above)
+            if (!lrf_is_gravity(parameters_.lrf_id))
+                throw std::runtime_error("lgr: RoPS is built on gravity frames only (lrf '" + parameters_.lrf_id + "' needs a triangulation or the ground truth)");
+            f.descriptor_id = LGR_DESCRIPTOR_ROPS;
+            f.lrf_id = LGR_LRF_GRAVITY;
         } else if (parameters_.descriptor_id != "fpfh") {
-            throw std::runtime_error("lgr: only descriptors 'fpfh' and 'shot' are built on the device path");
+            throw std::runtime_error("lgr: only descriptors 'fpfh', 'shot' and 'rops' are built on the device path");
         }
         lgr_params a = to_abi(parameters_);
         auto out = std::make_shared<Correspondences>(src_->size());

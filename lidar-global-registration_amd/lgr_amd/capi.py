@@ -23,8 +23,8 @@ KEYPOINT_ANY, KEYPOINT_ISS = 0, 1
 SCORE_CONSTANT, SCORE_MAE, SCORE_MSE, SCORE_EXP = 0, 1, 2, 3
 ALIGN_RANSAC, ALIGN_GROR = 0, 1
 ORDER_REFERENCE, ORDER_CANONICAL = 0, 1
-DESCRIPTOR_FPFH, DESCRIPTOR_SHOT = 0, 1
-LRF_DEFAULT = 0
+DESCRIPTOR_FPFH, DESCRIPTOR_SHOT, DESCRIPTOR_ROPS = 0, 1, 2
+LRF_DEFAULT, LRF_GRAVITY, LRF_GT = 0, 1, 2
 ERR_UNSUPPORTED = -5
 
 CORR_DTYPE = np.dtype([("index_query", "<i4"), ("index_match", "<i4"), ("distance", "<f4"), ("threshold", "<f4")])
@@ -85,11 +85,14 @@ class FeatureParams(C.Structure):
     _fields_ = [("descriptor_id", C.c_int32), ("lrf_id", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
-def feature_params(descriptor="fpfh", lrf_id=LRF_DEFAULT):
-    """descriptor: 'fpfh' / 'shot' (or the LGR_DESCRIPTOR_* value)."""
+def feature_params(descriptor="fpfh", lrf_id=None):
+    """descriptor: 'fpfh' / 'shot' / 'rops' (or the LGR_DESCRIPTOR_* value).  lrf_id None: the frames built for the descriptor
+    (LRF_GRAVITY for RoPS, LRF_DEFAULT otherwise)."""
     f = FeatureParams()
     _lib.lgr_default_feature_params(C.byref(f))
-    f.descriptor_id = {"fpfh": DESCRIPTOR_FPFH, "shot": DESCRIPTOR_SHOT}.get(descriptor, descriptor)
+    f.descriptor_id = {"fpfh": DESCRIPTOR_FPFH, "shot": DESCRIPTOR_SHOT, "rops": DESCRIPTOR_ROPS}.get(descriptor, descriptor)
+    if lrf_id is None:
+        lrf_id = LRF_GRAVITY if f.descriptor_id == DESCRIPTOR_ROPS else LRF_DEFAULT
     f.lrf_id = int(lrf_id)
     return f
 
@@ -505,6 +508,56 @@ class Context:
         self.check(_lib.lgr_match_shot(self.h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), _ptr(idx), _ptr(dist)))
         return idx, dist
 
+    def gravity_lrf(self, kps, surf, radius):
+        """gravity-aligned frames: cuda float32 [m, 9]; SHOT frames where the normal is within 0.04 rad of the vertical (or NaN)."""
+        out = self.empty((kps.shape[0], 9), self.torch.float32)
+        self.check(_lib.lgr_gravity_lrf_dev(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius), _ptr(out)))
+        return out
+
+    def gravity_lrf_host(self, kps, surf, radius):
+        kps = np.ascontiguousarray(kps, np.float32); surf = np.ascontiguousarray(surf, np.float32)
+        out = np.zeros((kps.shape[0], 9), np.float32)
+        self.check(_lib.lgr_gravity_lrf(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius), _ptr(out)))
+        return out
+
+    def rops(self, kps, surf, radius, lrf):
+        """RoPS135 rows on the given frames (cuda [m, 9]): cuda float32 [m, 135]."""
+        out = self.empty((kps.shape[0], 135), self.torch.float32)
+        self.check(_lib.lgr_rops_dev(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius), _ptr(lrf.contiguous()),
+                                     _ptr(out)))
+        return out
+
+    def rops_host(self, kps, surf, radius, lrf):
+        kps = np.ascontiguousarray(kps, np.float32); surf = np.ascontiguousarray(surf, np.float32)
+        lrf = np.ascontiguousarray(lrf, np.float32)
+        out = np.zeros((kps.shape[0], 135), np.float32)
+        self.check(_lib.lgr_rops(self.h, _ptr(kps), kps.shape[0], _ptr(surf), surf.shape[0], C.c_float(radius), _ptr(lrf), _ptr(out)))
+        return out
+
+    def match_rops(self, q, t, block=10000):
+        """exact matchBF on [m, 135] rows: (idx int32 [mq], dist float32 [mq])."""
+        torch = self.torch
+        q = q.contiguous(); t = t.contiguous()
+        idx = self.empty((q.shape[0],), torch.int32)
+        dist = self.empty((q.shape[0],), torch.float32)
+        self.check(_lib.lgr_match_rops_dev(self.h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match2_rops(self, a, b, block=10000):
+        torch = self.torch
+        a = a.contiguous(); b = b.contiguous()
+        ab_i = self.empty((a.shape[0],), torch.int32); ab_d = self.empty((a.shape[0],), torch.float32)
+        ba_i = self.empty((b.shape[0],), torch.int32); ba_d = self.empty((b.shape[0],), torch.float32)
+        self.check(_lib.lgr_match2_rops_dev(self.h, _ptr(a), a.shape[0], _ptr(b), b.shape[0], int(block),
+                                            _ptr(ab_i), _ptr(ab_d), _ptr(ba_i), _ptr(ba_d)))
+        return ab_i, ab_d, ba_i, ba_d
+
+    def match_rops_host(self, q, t, block=10000):
+        q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
+        idx = np.zeros(q.shape[0], np.int32); dist = np.zeros(q.shape[0], np.float32)
+        self.check(_lib.lgr_match_rops(self.h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
     def fpfh_host(self, kps, surf, radius):
         kps = np.ascontiguousarray(kps, np.float32); surf = np.ascontiguousarray(surf, np.float32)
         out = np.zeros((kps.shape[0], 33), np.float32)
@@ -522,7 +575,7 @@ class Context:
         return out[: n.value].cpu().numpy().view(CORR_DTYPE).reshape(-1)
 
     def correspondences(self, src, tgt, params, descriptor="fpfh"):
-        """descriptor: 'fpfh' (lgr_correspondences_dev) or 'shot' / a FeatureParams (lgr_correspondences_ex_dev)."""
+        """descriptor: 'fpfh' (lgr_correspondences_dev) or 'shot' / 'rops' / a FeatureParams (lgr_correspondences_ex_dev)."""
         out = self.empty((src.shape[0], 4), self.torch.int32)
         n = C.c_int(0)
         if isinstance(descriptor, str) and descriptor == "fpfh":
@@ -630,7 +683,7 @@ class Context:
         return np.array(T, np.float32).reshape(4, 4).T.copy()
 
     def align(self, src, tgt, params, descriptor="fpfh"):
-        """descriptor: 'fpfh' (lgr_align_dev) or 'shot' / a FeatureParams (lgr_align_ex_dev)."""
+        """descriptor: 'fpfh' (lgr_align_dev) or 'shot' / 'rops' / a FeatureParams (lgr_align_ex_dev)."""
         res = Result()
         if isinstance(descriptor, str) and descriptor == "fpfh":
             self.check(_lib.lgr_align_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(res)))

@@ -70,12 +70,14 @@ def random_se3(rng, t_range=5.0):
     return T
 
 
-def make_pair(n_points=1_000_000, seed=SEED, noise=0.005, overlap=0.5, constant_density=True):
+def make_pair(n_points=1_000_000, seed=SEED, noise=0.005, overlap=0.5, constant_density=True, yaw_only=False):
     """Returns dict(src, tgt [n x 12 float32], T_gt [4x4: maps src frame -> tgt frame], vp_src, vp_tgt).
 
     src covers x in [0, 2/3] of the scene, tgt covers [1/3, 1] (50 % overlap), both in the scene frame; tgt is then
     moved by a random rigid T (so T_gt = T).  With constant_density the scene shrinks with sqrt(n / 1e6) so the
     point density (and therefore the FPFH neighbourhood size at r = 0.25 m) is that of the 1M-point configuration.
+    yaw_only: T's rotation is about the vertical (z) axis only, the motion of a levelled scanner (what gravity-aligned frames assume);
+    the default output does not change.
     """
     rng = np.random.default_rng(seed)
     scale = np.sqrt(n_points / 1.0e6) if constant_density else 1.0
@@ -86,6 +88,9 @@ def make_pair(n_points=1_000_000, seed=SEED, noise=0.005, overlap=0.5, constant_
     src += rng.normal(0, noise, src.shape)
     tgt += rng.normal(0, noise, tgt.shape)
     T = random_se3(rng)
+    if yaw_only:
+        a = rng.uniform(-np.pi, np.pi)
+        T[:3, :3] = [[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]]
     vp_scene = np.array([0.0, 0.0, 10.0])
     tgt_m = tgt @ T[:3, :3].T + T[:3, 3]
     vp_tgt = T[:3, :3] @ vp_scene + T[:3, 3]

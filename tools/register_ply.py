@@ -23,7 +23,9 @@ def main():
     ap.add_argument("--metric", default="uniformity", choices=["uniformity", "correspondences", "closest_plane", "combination"])
     ap.add_argument("--matching", default="cluster", choices=["lr", "one_sided", "cluster"])
     ap.add_argument("--alignment", default="ransac", choices=["ransac", "gror"])
-    ap.add_argument("--descriptor", default="fpfh", choices=["fpfh", "shot"])
+    ap.add_argument("--descriptor", default="fpfh", choices=["fpfh", "shot", "rops"])
+    ap.add_argument("--lrf", default="default", choices=["default", "gravity"],
+                    help="local reference frames (SHOT: default only; RoPS: gravity only; FPFH ignores them)")
     ap.add_argument("--feature-radius", type=float, default=0.0, help="<= 0: multi-scale (the reference's behaviour when unset)")
     ap.add_argument("--distance-thr", type=float, default=0.0, help="<= 0: automatic, 4 x the larger cloud density (src/common.cpp:267)")
     ap.add_argument("--iterations", type=int, default=1000000)
@@ -47,7 +49,8 @@ def main():
                                 distance_thr=a.distance_thr if a.distance_thr > 0 else None, iterations=a.iterations,
                                 normals_available=ld["normals_available"])
     t = time.perf_counter()
-    res = ctx.align(clouds[0], clouds[1], p, descriptor=a.descriptor)
+    lrf = {"default": capi.LRF_DEFAULT, "gravity": capi.LRF_GRAVITY}[a.lrf]
+    res = ctx.align(clouds[0], clouds[1], p, descriptor=a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf))
     dt = time.perf_counter() - t
     T = res.matrix()
     print(f"aligned in {1e3 * dt:.1f} ms: converged={res.converged} correspondences={res.n_correspondences} inliers={res.n_inliers} "
