@@ -205,3 +205,76 @@ def make_corner_scene(n=100, shift=5):
     vp_tgt = np.full(3, 2.0 * n, np.float32)
     vp_src = (CORNER_GT[:3, :3].T.astype(np.float64) @ (vp_tgt - CORNER_GT[:3, 3]).astype(np.float64)).astype(np.float32)
     return src, tgt, vp_src, vp_tgt
+
+
+# ---- fixtures of the multi-scale correspondence search (feature_radius unset; tests/test_multiscale_ref.py)
+def make_two_density_pair(n=6000, seed=31, keep=0.3, n_islands=8, island=6, lift=0.3):
+    """make_pair whose far half (x above the median) keeps only `keep` of its points: the key points fall on two radius levels.
+    Plus `n_islands` islands of `island` points within a centimetre, `lift` above the surface: their key points sit on the finest
+    level, where the down-sampled surface leaves them fewer than 5 neighbours (a NaN SHOT row), while the coarser radii reach the
+    surface."""
+    a = make_pair(n, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    out = dict(a)
+    for name in ("src", "tgt"):
+        pts = a[name]
+        x = pts[:, 0]
+        sel = (x <= np.median(x)) | (rng.random(len(pts)) < keep)
+        pts = pts[sel]
+        up = np.array([0.0, 0.0, lift]) if name == "src" else a["T_gt"][:3, :3] @ np.array([0.0, 0.0, lift])
+        c = pts[rng.choice(len(pts), n_islands, replace=False), :3].astype(np.float64) + up
+        isl = (c[:, None, :] + rng.uniform(-0.005, 0.005, (n_islands, island, 3))).reshape(-1, 3)
+        out[name] = np.ascontiguousarray(np.concatenate([pts, make_points(isl)]))
+    return out
+
+
+def make_pruned_pair(n=6000, seed=32, blob=120, blob_sigma=0.002, n_outliers=3, outlier_lift=5.0):
+    """make_pair plus, per cloud, a tight Gaussian blob of `blob` points on the surface (radius levels far below the bulk, fewer than
+    10 % of the largest level: pruned, clamped up) and `n_outliers` isolated points `outlier_lift` above it (levels far above, under
+    0.1 %: pruned, clamped down)"""
+    a = make_pair(n, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    out = dict(a)
+    for name in ("src", "tgt"):
+        pts = a[name]
+        c = pts[rng.integers(len(pts)), :3].astype(np.float64)
+        b = c + rng.normal(0, blob_sigma, (blob, 3))
+        lo, hi = pts[:, :3].min(0), pts[:, :3].max(0)
+        o = np.stack([rng.uniform(lo[0], hi[0], n_outliers), rng.uniform(lo[1], hi[1], n_outliers),
+                      np.full(n_outliers, hi[2] + outlier_lift)], 1) + rng.normal(0, 1.0, (n_outliers, 3))
+        out[name] = np.ascontiguousarray(np.concatenate([pts, make_points(b), make_points(o)]))
+    return out
+
+
+def make_disjoint_levels_pair(n=6000, seed=33):
+    """source at the 1M configuration's density, target spread over the full-size scene (about 80 times sparser): their radius levels
+    have no level in common"""
+    return dict(make_pair(n, seed=seed), tgt=make_pair(n, seed=seed, constant_density=False)["tgt"])
+
+
+def make_duplicates_pair(n=6000, seed=34, n_dup=400):
+    """make_pair with `n_dup` points of each cloud appended a second time (equal positions, so equal rows on every level): the
+    matcher's block tie rule and the vote's count ties.  Also returns the (original, copy) index pairs."""
+    a = make_pair(n, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    out = dict(a)
+    for name in ("src", "tgt"):
+        pts = a[name]
+        pick = np.sort(rng.choice(len(pts), n_dup, replace=False))
+        out[name] = np.ascontiguousarray(np.concatenate([pts, pts[pick]]))
+        out["dup_" + name] = np.stack([pick, len(pts) + np.arange(n_dup)], 1)
+    return out
+
+
+def make_lattice_pair(n_coarse=24, n_fine=48, spacing=1.0 / 16):
+    """two exact square lattices in the plane z = 0, an n_coarse^2 one of twice the spacing and an n_fine^2 one beside it, and the
+    target equal to the source.  Coordinates are small multiples of a power of two, so interior points of one lattice have
+    bit-identical rows: a query ties at distance 0 with several train key points on every level, the block rule picks a different one
+    per level (the level lists differ), and with a vote window below the spacing the vote meets equal counts at equal distances."""
+    coarse = np.stack(np.meshgrid(np.arange(n_coarse), np.arange(n_coarse), indexing="ij"), -1).reshape(-1, 2) * (2 * spacing)
+    fine = np.stack(np.meshgrid(np.arange(n_fine), np.arange(n_fine), indexing="ij"), -1).reshape(-1, 2) * spacing
+    fine = fine + np.array([2 * spacing * n_coarse + 1.0, 0.0])
+    xy = np.concatenate([coarse, fine])
+    pts = make_points(np.concatenate([xy, np.zeros((len(xy), 1))], 1))
+    vp = np.array([1.0, 1.0, 5.0], np.float32)
+    return dict(src=pts, tgt=pts.copy(), T_gt=np.eye(4), vp_src=vp, vp_tgt=vp.copy())

@@ -165,6 +165,14 @@ def test_normals(lgr, oracle, pair):
     tq = cuda(q)
     lgr.normals_knn(tq, 30, surf=cuda(ds), vp=pair["vp_src"])
     np.testing.assert_array_equal(bits(tq.cpu().numpy()), bits(want2))
+    # the same with normals_available = 1: the call descriptor_dev makes for RoPS key points (include/matching.h:243-246)
+    import ctypes as C
+    from lgr_amd import capi
+    want3 = oracle.normals_knn(q, 30, surf=ds, vp=pair["vp_src"], normals_available=True)
+    tq3, tds = cuda(q), cuda(ds)
+    v = (C.c_float * 3)(*[float(x) for x in pair["vp_src"]])
+    lgr.check(capi.lib().lgr_normals_knn_dev(lgr.h, capi._ptr(tq3), tq3.shape[0], capi._ptr(tds), tds.shape[0], 30, v, 1))
+    np.testing.assert_array_equal(bits(tq3.cpu().numpy()), bits(want3))
 
 
 @pytest.mark.parametrize("k", [16, 41, 57, 58, 64])
