@@ -53,7 +53,8 @@ enum {
 };
 
 enum { LGR_MATCH_LR = 0, LGR_MATCH_ONE_SIDED = 1, LGR_MATCH_CLUSTER = 2 };      /* src/matching.cpp:21-75 */
-enum { LGR_METRIC_CORRESPONDENCES = 0, LGR_METRIC_UNIFORMITY = 1, LGR_METRIC_CLOSEST_PLANE = 2, LGR_METRIC_COMBINATION = 3 };   /* src/metric.cpp:272-301 */
+enum { LGR_METRIC_CORRESPONDENCES = 0, LGR_METRIC_UNIFORMITY = 1, LGR_METRIC_CLOSEST_PLANE = 2, LGR_METRIC_COMBINATION = 3,
+       LGR_METRIC_WEIGHTED_CLOSEST_PLANE = 4 };   /* src/metric.cpp:272-301 */
 enum { LGR_SCORE_CONSTANT = 0, LGR_SCORE_MAE = 1, LGR_SCORE_MSE = 2, LGR_SCORE_EXP = 3 };
 enum { LGR_ALIGN_RANSAC = 0, LGR_ALIGN_GROR = 1 };                              /* src/alignment.cpp:92-101 */
 enum { LGR_KEYPOINT_ANY = 0, LGR_KEYPOINT_ISS = 1 };                            /* src/common.cpp:657-691 */
@@ -294,6 +295,8 @@ int lgr_selfcheck_rcp(lgr_ctx*, unsigned lo_bits, unsigned hi_bits, unsigned lon
  * for op), element-wise on host arrays: fn 0 acosf(a), 1 atanf(a), 2 atan2f(a, b), 3 sinf(a), 4 cosf(a) (sinf / cosf: |a| < 120).  A host
  * can compare them with its own libm (tests/test_gpu_pcl_arith.py compares with the oracle's restatement, which is pinned against glibc). */
 int lgr_selfcheck_libm(lgr_ctx*, int fn, const float* a, const float* b, long long n, float* out);
+/* fn 5: expf(a) (glibc 2.35's e_expf.c as its FMA build computes it, csrc/lgr_weights_math.h: every float, subnormal and zero results
+ * included), fn 6: logf(a) for finite a > 0 (e_logf.c, csrc/lgr_rops_math.h) -- the two the point weights of weighted_closest_plane use. */
 
 /* ---- include/matching.h:373-376 matchBF<FPFH>(query, train, params), randomness = 1 ----
  * idx[i] = matched train row or -1 (invalid / NaN query), dist[i] = L2 distance (sqrt) */
@@ -437,6 +440,41 @@ int lgr_evaluate_plane_dev(lgr_ctx*, const float* d_src, int ns, const float* d_
                            uint64_t seed, uint32_t counter, int* n_inliers, float* rmse, float* metric, float* threshold /* or NULL */,
                            int32_t* pairs /* host, or NULL */, int* n_pairs);
 
+/* ---- weighted_closest_plane (WeightedClosestPlaneMetricEstimator, src/metric.cpp:202-231) and its point weights (src/weights.cpp) ----
+ * The metric is closest_plane's (same sparse subset, inliers, rmse and final block) with the score of an inlier multiplied in f32 by the
+ * weight of its source point, and metric = score / (0.01 * weights_sum), in double, weights_sum = the sequential f32 sum of all source
+ * weights in index order.  The weights are computed once per source cloud, with k = 30 neighbours (the reference's NORMAL_NR_POINTS
+ * macro, not lgr_params.normal_nr_points).  weight_id in the order of src/common.cpp:49-55; harris and tomasi return
+ * LGR_ERR_UNSUPPORTED, other unknown ids LGR_ERR_INVALID_ARG.  nss counts into 251 bins.
+ * lgr_ransac* / lgr_align* with metric_id = LGR_METRIC_WEIGHTED_CLOSEST_PLANE use constant weights (the reference's default
+ * weight_id); the _ex / _ex2 entries take lgr_metric_params (NULL: the defaults).  Plane metrics always run on the launch chain. */
+enum { LGR_WEIGHT_CONSTANT = 0, LGR_WEIGHT_EXP_CURVATURE = 1, LGR_WEIGHT_CURVEDNESS = 2, LGR_WEIGHT_HARRIS = 3, LGR_WEIGHT_TOMASI = 4,
+       LGR_WEIGHT_CURVATURE = 5, LGR_WEIGHT_NSS = 6 };
+typedef struct {
+    int32_t weight_id;       /* LGR_WEIGHT_* (ignored when weights != NULL) */
+    int32_t reserved[5];     /* 0 */
+    const float* weights;    /* NULL, or ns caller-supplied finite per-source-point weights used instead of weight_id: a host pointer for the
+                              * host entries, a device pointer for the _dev entries */
+} lgr_metric_params;
+void lgr_default_metric_params(lgr_metric_params* m);   /* constant weights */
+int lgr_ransac_ex(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                  const lgr_params*, const lgr_metric_params*, lgr_result*, uint8_t* final_mask);
+int lgr_ransac_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                      const lgr_params*, const lgr_metric_params*, lgr_result* /* host */, uint8_t* d_final_mask);
+/* the weight map of weight_id (out: n floats) and, when weights_sum != NULL, its sequential f32 sum.  nr_points: the neighbours of the
+ * principal curvatures (exp_curvature, curvedness; 1..128, more returns LGR_ERR_UNSUPPORTED); the other maps ignore it. */
+int lgr_weights(lgr_ctx*, const float* pts, int n, int weight_id, int nr_points, float* out, float* weights_sum /* or NULL */);
+int lgr_weights_dev(lgr_ctx*, const float* d_pts, int n, int weight_id, int nr_points, float* d_out, float* weights_sum /* host, or NULL */);
+/* pcl::PrincipalCurvaturesEstimation over the k nearest neighbours of each point in the cloud itself ((distance, index) order, the
+ * point included; fewer when the cloud has fewer than k points): pc1 >= pc2, NaN for a non-finite point */
+int lgr_principal_curvatures(lgr_ctx*, const float* pts, int n, int k, float* pc1, float* pc2);
+int lgr_principal_curvatures_dev(lgr_ctx*, const float* d_pts, int n, int k, float* d_pc1, float* d_pc2);
+/* lgr_evaluate_plane_dev under weighted_closest_plane: d_weights = ns device floats, weights_sum = the metric's denominator */
+int lgr_evaluate_plane_weighted_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16] /* host */, int score_id,
+                                    uint64_t seed, uint32_t counter, const float* d_weights, float weights_sum,
+                                    int* n_inliers, float* rmse, float* metric, float* threshold /* or NULL */,
+                                    int32_t* pairs /* host, or NULL */, int* n_pairs);
+
 /* ---- include/transformation.h:6-7 estimateOptimalRigidTransformation(src, tgt, inliers, T) ---- */
 int lgr_refit_svd(lgr_ctx*, const float* src, const float* tgt, int ns, int nt, const lgr_corr* inliers, int n, float T16[16]);
 int lgr_refit_svd_dev(lgr_ctx*, const float* d_src, const float* d_tgt, const lgr_corr* d_corr, int c,
@@ -451,6 +489,12 @@ int lgr_align_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int 
 int lgr_align_ex(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, const lgr_feature_params*, lgr_result*);
 int lgr_align_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params*, const lgr_feature_params*,
                      lgr_result* /* host */);
+
+/* lgr_align_ex with the metric parameters of weighted_closest_plane (NULL: the defaults, i.e. lgr_align_ex) */
+int lgr_align_ex2(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, const lgr_feature_params*,
+                  const lgr_metric_params*, lgr_result*);
+int lgr_align_ex2_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params*, const lgr_feature_params*,
+                      const lgr_metric_params*, lgr_result* /* host */);
 
 /* ---- alignGror(src, tgt, correspondences, parameters) (src/alignment.cpp:21-35) =
  *      pcl::registration::GRORInitialAlignment::computeTransformation (include/gror/ia_gror.hpp:367-415) with

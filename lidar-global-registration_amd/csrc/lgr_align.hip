@@ -657,6 +657,11 @@ extern "C" int lgr_align_dev(lgr_ctx* ctx, const float* d_src, int ns, const flo
 
 extern "C" int lgr_align_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
                                 lgr_result* res) {
+    return lgr_align_ex2_dev(ctx, d_src, ns, d_tgt, nt, p, fp, nullptr, res);
+}
+
+extern "C" int lgr_align_ex2_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
+                                 const lgr_metric_params* mp, lgr_result* res) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (d_src || ns == 0) && (d_tgt || nt == 0) && p && res && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
@@ -686,7 +691,7 @@ extern "C" int lgr_align_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const 
     if (p->alignment_id == LGR_ALIGN_GROR) {   // src/alignment.cpp:21-35: resolution = distance_thr, K_optimal = 800
         rc_te = lgr_gror_dev(ctx, d_src, ns, d_tgt, nt, dc, c, p->distance_thr, 800, res, nullptr);
     } else {
-        rc_te = lgr_ransac_dev(ctx, d_src, ns, d_tgt, nt, dc, c, p, res, nullptr);
+        rc_te = lgr_ransac_ex_dev(ctx, d_src, ns, d_tgt, nt, dc, c, p, mp, res, nullptr);
     }
     ctx->corr_trusted = false;
     LGR_TRY(rc_te);
@@ -707,15 +712,27 @@ extern "C" int lgr_align(lgr_ctx* ctx, const float* src, int ns, const float* tg
 
 extern "C" int lgr_align_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
                             lgr_result* res) {
+    return lgr_align_ex2(ctx, src, ns, tgt, nt, p, fp, nullptr, res);
+}
+
+extern "C" int lgr_align_ex2(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
+                             const lgr_metric_params* mp, lgr_result* res) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (src || ns == 0) && (tgt || nt == 0) && p && res && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
-    if (ns < 2 || nt < 2) return lgr_align_ex_dev(ctx, nullptr, 0, nullptr, 0, p, fp, res);   // identity, not converged
+    if (ns < 2 || nt < 2) return lgr_align_ex2_dev(ctx, nullptr, 0, nullptr, 0, p, fp, mp, res);   // identity, not converged
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, &ds));
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, &dt));
     LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
     LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    return lgr_align_ex_dev(ctx, ds, ns, dt, nt, p, fp, res);
+    lgr_metric_params mpd;
+    if (mp && mp->weights) {   // host weights -> device
+        float* dw;
+        LGR_TRY(lgr_ws_t(ctx, WS_WEIGHTS_HOST, (size_t) ns + 1, &dw));
+        LGR_HIP(ctx, hipMemcpyAsync(dw, mp->weights, (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
+        mpd = *mp; mpd.weights = dw; mp = &mpd;
+    }
+    return lgr_align_ex2_dev(ctx, ds, ns, dt, nt, p, fp, mp, res);
 }

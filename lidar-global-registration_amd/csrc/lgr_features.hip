@@ -1151,7 +1151,7 @@ __global__ void libm_eval_kernel(int fn, const float* __restrict__ a, const floa
 extern "C" int lgr_selfcheck_libm(lgr_ctx* ctx, int fn, const float* a, const float* b, long long n, float* out) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_CHECK(ctx, fn >= 0 && fn <= 4 && a && out && n >= 0 && (fn != 2 || b), LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, fn >= 0 && fn <= 6 && a && out && n >= 0 && (fn != 2 || b), LGR_ERR_INVALID_ARG);
     if (n == 0) return LGR_OK;
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *da, *db, *dout;
@@ -1160,7 +1160,8 @@ extern "C" int lgr_selfcheck_libm(lgr_ctx* ctx, int fn, const float* a, const fl
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) n, &dout));
     LGR_HIP(ctx, hipMemcpyAsync(da, a, (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (fn == 2) LGR_HIP(ctx, hipMemcpyAsync(db, b, (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
-    libm_eval_kernel<<<8 * ctx->n_cu, 256, 0, ctx->stream>>>(fn, da, db, n, dout);
+    if (fn >= 5) LGR_TRY(lgr_weights_libm_launch(ctx, fn, da, n, dout));   // expf / logf of the point weights (lgr_weights.hip)
+    else libm_eval_kernel<<<8 * ctx->n_cu, 256, 0, ctx->stream>>>(fn, da, db, n, dout);
     LGR_HIP(ctx, hipGetLastError());
     LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));

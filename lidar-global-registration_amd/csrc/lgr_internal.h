@@ -123,6 +123,7 @@ enum {
     WS_HOST_A, WS_HOST_B, WS_HOST_C, WS_HOST_D, WS_HOST_E, WS_HOST_F,
     WS_SHOT_PACK_A, WS_SHOT_PACK_B, WS_SHOT_KEYS,
     WS_ROPS_MASKED, WS_ROPS_LRF, WS_ROPS_KPS,
+    WS_WEIGHTS, WS_WEIGHTS_KNN, WS_WEIGHTS_TMP, WS_WEIGHTS_VALS, WS_WEIGHTS_SUM, WS_WEIGHTS_HOST,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 112, "grow lgr_ctx::ws");
@@ -248,6 +249,10 @@ struct lgr_plane_dev {
     unsigned* visited;          // [n_wg][(ns + 31) / 32] claim bitmaps, all zero between hypotheses
     int* claimed;               // [n_wg][n_sp]
     int n_wg;
+    // weighted_closest_plane (lgr_weights.hip): per-source-point weights (NULL: the unweighted metric), their sequential f32 sum (the
+    // metric's denominator) and max(largest weight, 0) (the early-out gate's bound on one point's score)
+    const float* w = nullptr;
+    float w_sum = 0.f, w_gate = 0.f;
 };
 int lgr_plane_setup(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, uint64_t seed, lgr_plane_dev* out);
 // hypothesis h in [0, nh): transform d_Ts + 16 * off, Philox counter = counter_base + off, off = d_list ? d_list[h] : h.
@@ -257,6 +262,12 @@ int lgr_plane_setup(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt
 // a hypothesis whose upper bounds fall below both is abandoned -- it can be neither the best nor a record.  0 / INT_MAX / NULL: no gate.
 // dyn (the device-driven RANSAC schedule, round 5): the number of hypotheses, the counter base and the gate's two values are READ ON THE DEVICE from
 // these words when the launch runs (nh is then only an upper bound for the grid); a null member keeps the host's value.
+// lgr_weights.hip: the weight map of weight_id (on ctx->stream); weights_sum / largest weight / non-finite count (synchronises); the weights
+// of a weighted_closest_plane run (mp NULL: constant), w_gate = max(largest weight, 0)
+int lgr_weights_map(lgr_ctx* ctx, const float* d_pts, int n, int weight_id, int nr_points, float* d_w);
+int lgr_weights_sum(lgr_ctx* ctx, const float* d_w, int n, float* sum, float* w_max, int* n_bad);
+int lgr_weights_prepare(lgr_ctx* ctx, const float* d_src, int ns, const lgr_metric_params* mp, const float** d_w, float* w_sum, float* w_gate);
+int lgr_weights_libm_launch(lgr_ctx* ctx, int fn, const float* d_a, long long n, float* d_out);
 struct lgr_plane_dyn { const int* nh; const int* counter_base; const float* best_prev; const int* record_prev; };
 int lgr_plane_eval(lgr_ctx* ctx, const lgr_plane_dev& pd, const float* d_Ts, const int* d_list, int nh, unsigned counter_base, int score_id,
                    int* d_cnt, float* d_metric, float* d_rmse, int2* d_pairs, int* d_n_pairs, float best_prev = 0.f, int record_prev = 0x7fffffff,

@@ -145,18 +145,12 @@ __device__ __forceinline__ void lgr_pcl_roots2(float b, float c, float& r0, floa
     r2 = 0.5f * (b + sd);
     r1 = 0.5f * (b - sd);
 }
-__device__ __forceinline__ void lgr_pcl_eigen33(const float C[9], float& eigenvalue, float& vx, float& vy, float& vz) {
-    float scale = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) scale = fmaxf(scale, fabsf(C[i]));
-    if (scale <= 1.17549435e-38f) scale = 1.f;
-    float m[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) m[i] = C[i] / scale;
+// pcl::computeRoots of the SCALED symmetric matrix m (row-major): its three eigenvalues, r0 <= r1 <= r2.  Shared by the normals'
+// eigen33 below and the principal curvatures (lgr_weights.hip), which take all three.
+__device__ __forceinline__ void lgr_pcl_roots3(const float m[9], float& r0, float& r1, float& r2) {
     const float c0 = m[0] * m[4] * m[8] + 2.f * m[1] * m[2] * m[5] - m[0] * m[5] * m[5] - m[4] * m[2] * m[2] - m[8] * m[1] * m[1];
     const float c1 = m[0] * m[4] - m[1] * m[1] + m[0] * m[8] - m[2] * m[2] + m[4] * m[8] - m[5] * m[5];
     const float c2 = m[0] + m[4] + m[8];
-    float r0, r1, r2;
     if (fabsf(c0) < 1.1920929e-07f) {
         lgr_pcl_roots2(c2, c1, r0, r1, r2);
     } else {
@@ -182,6 +176,17 @@ __device__ __forceinline__ void lgr_pcl_eigen33(const float C[9], float& eigenva
         }
         if (r0 <= 0.f) lgr_pcl_roots2(c2, c1, r0, r1, r2);
     }
+}
+__device__ __forceinline__ void lgr_pcl_eigen33(const float C[9], float& eigenvalue, float& vx, float& vy, float& vz) {
+    float scale = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) scale = fmaxf(scale, fabsf(C[i]));
+    if (scale <= 1.17549435e-38f) scale = 1.f;
+    float m[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) m[i] = C[i] / scale;
+    float r0, r1, r2;
+    lgr_pcl_roots3(m, r0, r1, r2);
     eigenvalue = r0 * scale;
     m[0] -= r0; m[4] -= r0; m[8] -= r0;
     // rows 0 x 1, 0 x 2, 1 x 2; the longest (first maximum) normalised

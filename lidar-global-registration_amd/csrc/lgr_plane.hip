@@ -26,12 +26,16 @@ __device__ __forceinline__ void philox4(unsigned long long seed, unsigned c0, un
 
 constexpr int PB = 256;
 
+// W: weighted_closest_plane -- the score of an inlier is value * w[idx] in f32, the metric's denominator 0.01 * w_sum, and the gate's bound on
+// one point's score w_gate (= max(largest weight, 0)) in place of 1.  W = false is the closest_plane kernel.
+template <bool W>
 __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __restrict__ src, int ns, int n_sp, float thr, float r2,
                                                    unsigned long long seed, const float* __restrict__ Ts, const int* __restrict__ list, int nh,
                                                    unsigned counter_base, int score_id, unsigned* __restrict__ visited_all,
                                                    int* __restrict__ claimed_all, int* __restrict__ cnt_out, float* __restrict__ metric_out,
                                                    float* __restrict__ rmse_out, int2* __restrict__ pairs_out, int* __restrict__ n_pairs,
-                                                   float best_prev, int record_prev, const float* __restrict__ factor, lgr_plane_dyn dyn) {
+                                                   float best_prev, int record_prev, const float* __restrict__ factor, lgr_plane_dyn dyn,
+                                                   const float* __restrict__ w, float w_sum, float w_gate) {
     // (device-driven schedule: extents and gate values are the loop's state at the time this launch runs)
     if (dyn.nh) nh = min(nh, *dyn.nh);
     if (dyn.counter_base) counter_base = (unsigned) *dyn.counter_base;
@@ -139,6 +143,7 @@ __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __res
             if (score_id == LGR_SCORE_MAE) value = fabsf(dist - thr) / thr;
             else if (score_id == LGR_SCORE_MSE) value = (dist - thr) * (dist - thr) / (thr * thr);
             else if (score_id == LGR_SCORE_EXP) value = lgr_expf(-dist * dist / (2 * thr * thr));
+            if constexpr (W) value *= w[idx];   // calculateScore: value *= weights[inlier.index_query]
             sc += (long long) ((double) value * 4294967296.0);
             const float rel = dist / thr;
             sq += (long long) ((double) (rel * rel) * 4294967296.0);
@@ -157,7 +162,9 @@ __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __res
 #pragma unroll
             for (int w = 0; w < PB / 64; ++w) { tsc += g_sc[pp][w]; tcnt += g_cnt[pp][w]; }
             const int left = n_sp - done_pts;
-            const float m_max = (float) (((double) tsc / 4294967296.0 + (double) left) / (0.01 * (double) (float) ns)) * fac * 1.00001f;
+            float m_max;
+            if constexpr (W) m_max = (float) (((double) tsc / 4294967296.0 + (double) left * (double) w_gate) / (0.01 * (double) w_sum)) * fac * 1.00001f;
+            else m_max = (float) (((double) tsc / 4294967296.0 + (double) left) / (0.01 * (double) (float) ns)) * fac * 1.00001f;
             if (m_max < best_prev && tcnt + left < record_prev) { j_stop = done_pts; break; }
           }
         }
@@ -173,7 +180,8 @@ __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __res
             for (int w = 1; w < PB / 64; ++w) { sc += s_sc[w]; sq += s_sq[w]; cnt += s_cnt[w]; }
             const float score = (float) ((double) sc / 4294967296.0);
             cnt_out[h] = cnt;
-            metric_out[h] = (float) ((double) score / (0.01 * (double) (float) ns));   // score / (SPARSE_POINTS_FRACTION * src.size())
+            if constexpr (W) metric_out[h] = (float) ((double) score / (0.01 * (double) w_sum));   // score / (SPARSE_POINTS_FRACTION * weights_sum_)
+            else metric_out[h] = (float) ((double) score / (0.01 * (double) (float) ns));   // score / (SPARSE_POINTS_FRACTION * src.size())
             if (rmse_out) rmse_out[h] = cnt ? thr * (float) sqrt((double) sq / 4294967296.0 / (double) cnt) : 3.4028234663852886e38f;
         }
         __syncthreads();
@@ -208,8 +216,14 @@ int lgr_plane_eval(lgr_ctx* ctx, const lgr_plane_dev& pd, const float* d_Ts, con
     if (d_pairs) LGR_HIP(ctx, hipMemsetAsync(d_n_pairs, 0, 4, ctx->stream));
     int grid = std::min(nh, pd.n_wg);
     const lgr_plane_dyn none{nullptr, nullptr, nullptr, nullptr};
-    plane_kernel<<<grid, PB, 0, ctx->stream>>>(pd.g, pd.d_src, pd.ns, pd.n_sp, pd.thr, pd.r2, pd.seed, d_Ts, d_list, nh, counter_base, score_id,
-                                               pd.visited, pd.claimed, d_cnt, d_metric, d_rmse, d_pairs, d_n_pairs, best_prev, record_prev, d_factor, dyn ? *dyn : none);
+    if (pd.w)
+        plane_kernel<true><<<grid, PB, 0, ctx->stream>>>(pd.g, pd.d_src, pd.ns, pd.n_sp, pd.thr, pd.r2, pd.seed, d_Ts, d_list, nh, counter_base, score_id,
+                                                         pd.visited, pd.claimed, d_cnt, d_metric, d_rmse, d_pairs, d_n_pairs, best_prev, record_prev, d_factor,
+                                                         dyn ? *dyn : none, pd.w, pd.w_sum, pd.w_gate);
+    else
+        plane_kernel<false><<<grid, PB, 0, ctx->stream>>>(pd.g, pd.d_src, pd.ns, pd.n_sp, pd.thr, pd.r2, pd.seed, d_Ts, d_list, nh, counter_base, score_id,
+                                                          pd.visited, pd.claimed, d_cnt, d_metric, d_rmse, d_pairs, d_n_pairs, best_prev, record_prev, d_factor,
+                                                          dyn ? *dyn : none, nullptr, 0.f, 0.f);
     LGR_HIP(ctx, hipGetLastError());
     return LGR_OK;
 }

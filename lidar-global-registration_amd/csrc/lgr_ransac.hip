@@ -1410,7 +1410,7 @@ int evaluate_one_plane(lgr_ctx* ctx, const float* d_T, const Packed& pk, int c, 
             std::sort(pairs->begin(), pairs->end(), [](const int2& a, const int2& b) { return a.x < b.x; });   // source indices are distinct
         }
     }
-    if (metric_id == LGR_METRIC_CLOSEST_PLANE) {
+    if (metric_id == LGR_METRIC_CLOSEST_PLANE || metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE) {
         if (d_mask) LGR_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t) c, ctx->stream));
         out->n_inl = cnt; out->rmse = rm; out->metric = cp;
         return LGR_OK;
@@ -1438,6 +1438,33 @@ extern "C" int lgr_evaluate_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, 
     EvalOut e;
     std::vector<int2> pr;
     LGR_TRY(evaluate_one_plane(ctx, dT, none, 0, LGR_METRIC_CLOSEST_PLANE, score_id, nullptr, plane, counter, &e, pairs ? &pr : nullptr));
+    *n_inliers = e.n_inl; *rmse = e.rmse; *metric = e.metric;
+    if (threshold) *threshold = plane.thr;
+    if (pairs) {
+        for (size_t i = 0; i < pr.size(); ++i) { pairs[2 * i] = pr[i].x; pairs[2 * i + 1] = pr[i].y; }
+        if (n_pairs) *n_pairs = (int) pr.size();
+    }
+    return LGR_OK;
+}
+
+extern "C" int lgr_evaluate_plane_weighted_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16], int score_id,
+                                               uint64_t seed, uint32_t counter, const float* d_weights, float weights_sum, int* n_inliers, float* rmse,
+                                               float* metric, float* threshold, int32_t* pairs, int* n_pairs) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, d_src && d_tgt && d_weights && T16 && n_inliers && rmse && metric && ns > 0 && nt > 1 && score_id >= 0 && score_id <= 3, LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    lgr_plane_dev plane;
+    LGR_TRY(lgr_plane_setup(ctx, d_src, ns, d_tgt, nt, seed, &plane));
+    plane.w = d_weights; plane.w_sum = weights_sum; plane.w_gate = 0.f;   // (one transform: no gate)
+    float* dT;
+    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 64, &dT));
+    LGR_HIP(ctx, hipMemcpyAsync(dT, T16, 64, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    Packed none{nullptr, nullptr, nullptr};
+    EvalOut e;
+    std::vector<int2> pr;
+    LGR_TRY(evaluate_one_plane(ctx, dT, none, 0, LGR_METRIC_WEIGHTED_CLOSEST_PLANE, score_id, nullptr, plane, counter, &e, pairs ? &pr : nullptr));
     *n_inliers = e.n_inl; *rmse = e.rmse; *metric = e.metric;
     if (threshold) *threshold = plane.thr;
     if (pairs) {
@@ -1555,7 +1582,8 @@ static int run_batch(lgr_ctx* ctx, const float* d_src, const float* d_tgt, const
         LGR_TRY(lgr_ws_t(ctx, WS_PLANE_OUT, (size_t) 2 * nb + 16, &pl_cnt));
         pl_cp = (float*) (pl_cnt + nb);
     }
-    if (plane && p->metric_id == LGR_METRIC_CLOSEST_PLANE) {
+    const bool closest = plane && (p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE);
+    if (closest) {
         // every hypothesis that passed the prerejection is evaluated on its sparse subset; its plane inliers are "the inliers"
         // (gate: a hypothesis that can reach neither the best metric nor the record inlier count of the earlier batches is abandoned)
         LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list, nh, (unsigned) first, p->score_id, pl_cnt, pl_cp, nullptr, nullptr, nullptr,
@@ -1572,7 +1600,7 @@ static int run_batch(lgr_ctx* ctx, const float* d_src, const float* d_tgt, const
     int nh2 = h[0] + h[1];
     *n_cand = nh2;
     if (nh2 == 0) return LGR_OK;
-    if (plane && p->metric_id == LGR_METRIC_CLOSEST_PLANE) {
+    if (closest) {
         plane_pick_kernel<<<cdiv(nh, 256), 256, 0, ctx->stream>>>(b.flags2, b.pos2, nh, pl_cnt, pl_cp, b.metric, b.ninl);
     } else if (plane) {   // combination: correspondences metric with the constant score (include/metric.h:191-192) x plane metric
         LGR_TRY(metric_launch(ctx, b.Ts, b.list2, nh2, pk, c, LGR_METRIC_CORRESPONDENCES, LGR_SCORE_CONSTANT, b.metric, b.ninl, nullptr, nullptr));
@@ -1674,7 +1702,7 @@ static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float*
         LGR_TRY(lgr_ws_t(ctx, WS_PLANE_OUT, (size_t) 2 * nb_max + 16, &pl_cnt));
         pl_cp = (float*) (pl_cnt + nb_max);
     }
-    const bool closest = plane && p->metric_id == LGR_METRIC_CLOSEST_PLANE;
+    const bool closest = plane && (p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE);
     const bool need_list = p->metric_id != LGR_METRIC_UNIFORMITY;
     const int g_metric = std::max(1, ctx->n_cu), g_count = 128 * std::max(1, ctx->n_cu);   // one 120 KB workgroup per CU; four times the resident single-wave workgroups (the tail evens out)
     float2* scratch = nullptr;
@@ -1783,8 +1811,9 @@ static int check_params(lgr_ctx* ctx, const lgr_params* p) {
     LGR_CHECK(ctx, p != nullptr, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, p->n_samples >= LGR_MIN_SAMPLES && p->n_samples <= LGR_MAX_SAMPLES, LGR_ERR_UNSUPPORTED);   // (fewer than 3 pairs leave Umeyama's rotation open)
     LGR_CHECK(ctx, p->metric_id == LGR_METRIC_UNIFORMITY || p->metric_id == LGR_METRIC_CORRESPONDENCES ||
-                       p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_COMBINATION,
-              LGR_ERR_UNSUPPORTED);   // weighted_closest_plane (src/weights.cpp) is not built
+                       p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_COMBINATION ||
+                       p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE,
+              LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, p->score_id >= 0 && p->score_id <= 3, LGR_ERR_INVALID_ARG);
     return LGR_OK;
 }
@@ -1847,9 +1876,19 @@ extern "C" int lgr_ransac_replay_dev(lgr_ctx* ctx, const float* d_src, int ns, c
 
 extern "C" int lgr_ransac_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
                               const lgr_params* p, lgr_result* res, uint8_t* d_final_mask) {
+    return lgr_ransac_ex_dev(ctx, d_src, ns, d_tgt, nt, d_corr, c, p, nullptr, res, d_final_mask);
+}
+
+extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                                 const lgr_params* p, const lgr_metric_params* mp, lgr_result* res, uint8_t* d_final_mask) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_TRY(check_params(ctx, p));
+    const bool weighted = p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE;
+    if (weighted && mp && !mp->weights) {   // refused before any work (lgr_weights.hip repeats the check)
+        LGR_CHECK(ctx, mp->weight_id >= LGR_WEIGHT_CONSTANT && mp->weight_id <= LGR_WEIGHT_NSS, LGR_ERR_INVALID_ARG);
+        LGR_CHECK(ctx, mp->weight_id != LGR_WEIGHT_HARRIS && mp->weight_id != LGR_WEIGHT_TOMASI, LGR_ERR_UNSUPPORTED);
+    }
     LGR_CHECK(ctx, d_src && d_tgt && (d_corr || c == 0) && res && c >= 0 && ns > 0 && nt > 0, LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     auto t_start = std::chrono::steady_clock::now();
@@ -1874,7 +1913,8 @@ extern "C" int lgr_ransac_dev(lgr_ctx* ctx, const float* d_src, int ns, const fl
         LGR_HIP(ctx, hipMemcpyAsync(d_best, I, 64, hipMemcpyHostToDevice, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    const bool plane_metric = p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_COMBINATION;
+    const bool plane_metric = p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_COMBINATION || weighted;
+    const bool closest = p->metric_id == LGR_METRIC_CLOSEST_PLANE || weighted;   // (the plane pairs feed the refit)
     if (!plane_metric) {
         // the loop, the final evaluation and the refit driven from the device: one host synchronisation (ransac_device_schedule)
         uint8_t* d_mask = d_final_mask;
@@ -1885,6 +1925,14 @@ extern "C" int lgr_ransac_dev(lgr_ctx* ctx, const float* d_src, int ns, const fl
     }
     lgr_plane_dev plane;
     LGR_TRY(lgr_plane_setup(ctx, d_src, ns, d_tgt, nt, seed, &plane));
+    if (weighted) {
+        // WeightedClosestPlaneMetricEstimator::setSourceCloud: the weights and their sum, once per run
+        auto t_w = std::chrono::steady_clock::now();
+        LGR_TRY(lgr_weights_prepare(ctx, d_src, ns, mp, &plane.w, &plane.w_sum, &plane.w_gate));
+        if (getenv("LGR_RANSAC_DEBUG"))
+            fprintf(stderr, "[lgr] weights: %.3f ms, sum %.9g, gate %.9g\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_w).count(),
+                    (double) plane.w_sum, (double) plane.w_gate);
+    }
     if (p->has_guess) {
         // src/sac_prerejective_omp.cpp:134-147: the guess is the hypothesis to beat (final_tn / final_metric).  Its inliers only seed
         // the global largest_inlier_set, which the loop never reads (thread-local sets start empty, :177): the bound is unaffected.
@@ -1916,13 +1964,13 @@ extern "C" int lgr_ransac_dev(lgr_ctx* ctx, const float* d_src, int ns, const fl
     std::vector<int2> plane_pairs;
     if (plane_metric)
         LGR_TRY(evaluate_one_plane(ctx, d_best, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFEu, &e,
-                                   p->metric_id == LGR_METRIC_CLOSEST_PLANE ? &plane_pairs : nullptr));
+                                   closest ? &plane_pairs : nullptr));
     else LGR_TRY(evaluate_one(ctx, d_best, pk, c, p->metric_id, p->score_id, d_mask, &e, false));   // the final block uses inliers and metric only
     bool enough = e.n_inl > MIN_NR_FINAL_INLIERS || (float) e.n_inl > MIN_INLIER_RATE * (float) c;
     float min_tol = p->metric_id == LGR_METRIC_UNIFORMITY ? 0.3f : 0.0f;   // include/metric.h:97-99 / 73-75 / 124-126 / 198-200
     bool converged = enough && e.metric > min_tol;
     float* d_Tn = d_best + 16;
-    if (p->metric_id == LGR_METRIC_CLOSEST_PLANE) {
+    if (closest) {
         // estimateOptimalRigidTransformation over the plane pairs (source point, nearest target point), ascending source index
         const int np = (int) plane_pairs.size();
         Packed pp;
@@ -1961,6 +2009,11 @@ extern "C" int lgr_ransac_dev(lgr_ctx* ctx, const float* d_src, int ns, const fl
 
 extern "C" int lgr_ransac(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
                           const lgr_params* p, lgr_result* res, uint8_t* final_mask) {
+    return lgr_ransac_ex(ctx, src, ns, tgt, nt, corr, c, p, nullptr, res, final_mask);
+}
+
+extern "C" int lgr_ransac_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                             const lgr_params* p, const lgr_metric_params* mp, lgr_result* res, uint8_t* final_mask) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, src && tgt && (corr || c == 0) && res && ns > 0 && nt > 0 && c >= 0, LGR_ERR_INVALID_ARG);
@@ -1975,7 +2028,14 @@ extern "C" int lgr_ransac(lgr_ctx* ctx, const float* src, int ns, const float* t
     LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
     LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
     if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * 16, hipMemcpyHostToDevice, ctx->stream));
-    LGR_TRY(lgr_ransac_dev(ctx, ds, ns, dt, nt, dc, c, p, res, dm));
+    lgr_metric_params mpd;
+    if (mp && mp->weights) {   // host weights -> device
+        float* dw;
+        LGR_TRY(lgr_ws_t(ctx, WS_WEIGHTS_HOST, (size_t) ns + 1, &dw));
+        LGR_HIP(ctx, hipMemcpyAsync(dw, mp->weights, (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
+        mpd = *mp; mpd.weights = dw; mp = &mpd;
+    }
+    LGR_TRY(lgr_ransac_ex_dev(ctx, ds, ns, dt, nt, dc, c, p, mp, res, dm));
     if (final_mask && c >= p->n_samples) {
         LGR_HIP(ctx, hipMemcpyAsync(final_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));

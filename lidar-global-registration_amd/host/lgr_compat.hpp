@@ -178,7 +178,8 @@ inline lgr_params to_abi(const AlignmentParameters& p) {
     a.iss_radius_src = p.iss_radius_src; a.iss_radius_tgt = p.iss_radius_tgt;
     a.matching_id = p.matching_id == "cluster" ? LGR_MATCH_CLUSTER : (p.matching_id == "one_sided" ? LGR_MATCH_ONE_SIDED : LGR_MATCH_LR);
     a.metric_id = p.metric_id == "uniformity" ? LGR_METRIC_UNIFORMITY : p.metric_id == "closest_plane" ? LGR_METRIC_CLOSEST_PLANE
-                  : p.metric_id == "combination" ? LGR_METRIC_COMBINATION : LGR_METRIC_CORRESPONDENCES;   // weighted_closest_plane: not built
+                  : p.metric_id == "combination" ? LGR_METRIC_COMBINATION
+                  : p.metric_id == "weighted_closest_plane" ? LGR_METRIC_WEIGHTED_CLOSEST_PLANE : LGR_METRIC_CORRESPONDENCES;
     a.score_id = p.score_id == "mae" ? LGR_SCORE_MAE : (p.score_id == "mse" ? LGR_SCORE_MSE : (p.score_id == "exp" ? LGR_SCORE_EXP : LGR_SCORE_CONSTANT));
     a.max_iterations = p.max_iterations; a.normals_available = p.normals_available; a.fix_seed = p.fix_seed;
     if (p.vp_src) { a.has_vp_src = 1; std::memcpy(a.vp_src, p.vp_src->data(), 12); }
@@ -187,6 +188,16 @@ inline lgr_params to_abi(const AlignmentParameters& p) {
     a.match_search_radius = p.match_search_radius;
     if (p.guess) { a.has_guess = 1; std::memcpy(a.guess, p.guess->data(), 64); }
     return a;
+}
+// weight_id -> the weights of weighted_closest_plane; unknown names fall back to constant, as getWeightFunction does (src/weights.cpp:27-44,
+// with a warning there).  harris / tomasi are passed on and refused by the library (LGR_ERR_UNSUPPORTED).
+inline lgr_metric_params to_metric_abi(const AlignmentParameters& p) {
+    lgr_metric_params m;
+    lgr_default_metric_params(&m);
+    const std::string& w = p.weight_id;
+    m.weight_id = w == "exp_curvature" ? LGR_WEIGHT_EXP_CURVATURE : w == "curvedness" ? LGR_WEIGHT_CURVEDNESS : w == "harris" ? LGR_WEIGHT_HARRIS
+                  : w == "tomasi" ? LGR_WEIGHT_TOMASI : w == "curvature" ? LGR_WEIGHT_CURVATURE : w == "nss" ? LGR_WEIGHT_NSS : LGR_WEIGHT_CONSTANT;
+    return m;
 }
 inline const float* raw(const PointNCloud& c) { return reinterpret_cast<const float*>(c.points.data()); }
 
@@ -418,9 +429,10 @@ public:
         : src_(std::move(src)), tgt_(std::move(tgt)), correspondences_(std::move(correspondences)), parameters_(std::move(parameters)) {}
     AlignmentResult align() {
         lgr_params a = to_abi(parameters_);
+        lgr_metric_params m = to_metric_abi(parameters_);
         lgr_result r;
-        check(lgr_ransac(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(),
-                         reinterpret_cast<const lgr_corr*>(correspondences_->data()), (int) correspondences_->size(), &a, &r, nullptr),
+        check(lgr_ransac_ex(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(),
+                            reinterpret_cast<const lgr_corr*>(correspondences_->data()), (int) correspondences_->size(), &a, &m, &r, nullptr),
               "SampleConsensusPrerejectiveOMP::align");
         AlignmentResult out;
         out.src = src_; out.tgt = tgt_; out.correspondences = correspondences_;

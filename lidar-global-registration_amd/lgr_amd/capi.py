@@ -18,7 +18,9 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("LGR_HIP_LIB") or os.path.join(_CSRC, "liblgr_hip.so")
 
 MATCH_LR, MATCH_ONE_SIDED, MATCH_CLUSTER = 0, 1, 2
-METRIC_CORRESPONDENCES, METRIC_UNIFORMITY, METRIC_CLOSEST_PLANE, METRIC_COMBINATION = 0, 1, 2, 3
+METRIC_CORRESPONDENCES, METRIC_UNIFORMITY, METRIC_CLOSEST_PLANE, METRIC_COMBINATION, METRIC_WEIGHTED_CLOSEST_PLANE = 0, 1, 2, 3, 4
+WEIGHT_CONSTANT, WEIGHT_EXP_CURVATURE, WEIGHT_CURVEDNESS, WEIGHT_HARRIS, WEIGHT_TOMASI, WEIGHT_CURVATURE, WEIGHT_NSS = 0, 1, 2, 3, 4, 5, 6
+WEIGHT_IDS = {"constant": 0, "exp_curvature": 1, "curvedness": 2, "harris": 3, "tomasi": 4, "curvature": 5, "nss": 6}
 KEYPOINT_ANY, KEYPOINT_ISS = 0, 1
 SCORE_CONSTANT, SCORE_MAE, SCORE_MSE, SCORE_EXP = 0, 1, 2, 3
 ALIGN_RANSAC, ALIGN_GROR = 0, 1
@@ -26,6 +28,7 @@ ORDER_REFERENCE, ORDER_CANONICAL = 0, 1
 DESCRIPTOR_FPFH, DESCRIPTOR_SHOT, DESCRIPTOR_ROPS = 0, 1, 2
 LRF_DEFAULT, LRF_GRAVITY, LRF_GT = 0, 1, 2
 ERR_UNSUPPORTED = -5
+ERR_INVALID_ARG = -1
 
 CORR_DTYPE = np.dtype([("index_query", "<i4"), ("index_match", "<i4"), ("distance", "<f4"), ("threshold", "<f4")])
 
@@ -95,6 +98,22 @@ def feature_params(descriptor="fpfh", lrf_id=None):
         lrf_id = LRF_GRAVITY if f.descriptor_id == DESCRIPTOR_ROPS else LRF_DEFAULT
     f.lrf_id = int(lrf_id)
     return f
+
+
+class MetricParams(C.Structure):
+    _fields_ = [("weight_id", C.c_int32), ("reserved", C.c_int32 * 5), ("weights", C.c_void_p)]
+
+
+def metric_params(weight="constant", weights=None):
+    """weighted_closest_plane's point weights: weight = 'constant' / 'exp_curvature' / 'curvedness' / 'curvature' / 'nss' (or the
+    LGR_WEIGHT_* value); weights = caller-supplied per-source-point weights (numpy for the host entries, a cuda tensor for the _dev
+    entries: keep it alive for the call) used instead."""
+    m = MetricParams()
+    _lib.lgr_default_metric_params(C.byref(m))
+    m.weight_id = WEIGHT_IDS.get(weight, weight) if isinstance(weight, str) else int(weight)
+    if weights is not None:
+        m.weights = _ptr(weights).value
+    return m
 
 
 class LgrError(RuntimeError):
@@ -636,6 +655,53 @@ class Context:
             out["pairs"] = pairs[: npairs.value].copy()
         return out
 
+    def evaluate_plane_weighted(self, src, tgt, T, weights, weights_sum, score_id=SCORE_CONSTANT, seed=566, counter=0, with_pairs=False):
+        """lgr_evaluate_plane_weighted_dev: weights = cuda float32 [ns], weights_sum = the metric's denominator."""
+        T16 = (C.c_float * 16)(*np.asarray(T, np.float32).T.reshape(16).tolist())
+        n, rm, me, th, npairs = C.c_int(0), C.c_float(0), C.c_float(0), C.c_float(0), C.c_int(0)
+        pairs = np.zeros((max(int(0.01 * src.shape[0]), 1), 2), np.int32) if with_pairs else None
+        self.check(_lib.lgr_evaluate_plane_weighted_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], T16, int(score_id), C.c_uint64(seed),
+                                                        C.c_uint32(counter), _ptr(weights.contiguous()), C.c_float(weights_sum), C.byref(n), C.byref(rm),
+                                                        C.byref(me), C.byref(th), _ptr(pairs), C.byref(npairs)))
+        out = dict(n_inl=n.value, rmse=rm.value, metric=me.value, thr=th.value)
+        if with_pairs:
+            out["pairs"] = pairs[: npairs.value].copy()
+        return out
+
+    def weights(self, pts, weight="constant", nr_points=30, with_sum=True):
+        """the weight map of weight (name or LGR_WEIGHT_*) on cuda points [n, 12]: (cuda float32 [n], weights_sum or None)."""
+        wid = WEIGHT_IDS.get(weight, weight) if isinstance(weight, str) else int(weight)
+        out = self.empty((max(pts.shape[0], 1),), self.torch.float32)
+        s = C.c_float(0)
+        self.check(_lib.lgr_weights_dev(self.h, _ptr(pts), pts.shape[0], int(wid), int(nr_points), _ptr(out), C.byref(s) if with_sum else None))
+        return out[: pts.shape[0]], (s.value if with_sum else None)
+
+    def weights_host(self, pts, weight="constant", nr_points=30):
+        pts = np.ascontiguousarray(pts, np.float32)
+        wid = WEIGHT_IDS.get(weight, weight) if isinstance(weight, str) else int(weight)
+        out = np.zeros(max(pts.shape[0], 1), np.float32)
+        s = C.c_float(0)
+        self.check(_lib.lgr_weights(self.h, _ptr(pts), pts.shape[0], int(wid), int(nr_points), _ptr(out), C.byref(s)))
+        return out[: pts.shape[0]], s.value
+
+    def principal_curvatures(self, pts, k=30):
+        """pcl::PrincipalCurvaturesEstimation over k neighbours in the cloud itself: (pc1, pc2), cuda float32 [n] each."""
+        n = pts.shape[0]
+        pc1 = self.empty((max(n, 1),), self.torch.float32); pc2 = self.empty((max(n, 1),), self.torch.float32)
+        self.check(_lib.lgr_principal_curvatures_dev(self.h, _ptr(pts), n, int(k), _ptr(pc1), _ptr(pc2)))
+        return pc1[:n], pc2[:n]
+
+    def ransac_ex(self, src, tgt, corr, params, mparams=None):
+        """lgr_ransac_ex_dev (mparams: a MetricParams, None = the defaults)."""
+        corr = self._corr_dev(corr)
+        c = corr.shape[0]
+        res = Result()
+        mask = self.empty((max(c, 1),), self.torch.uint8)
+        self.check(_lib.lgr_ransac_ex_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), c,
+                                          C.byref(params), C.byref(mparams) if mparams is not None else None, C.byref(res), _ptr(mask)))
+        self._join()
+        return res, mask[:c].cpu().numpy()
+
     def ransac_replay(self, src, tgt, corr, params, triples):
         torch = self.torch
         corr = self._corr_dev(corr)
@@ -691,6 +757,22 @@ class Context:
             f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
             self.check(_lib.lgr_align_ex_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
                                              C.byref(res)))
+        return res
+
+    def align_ex2(self, src, tgt, params, descriptor="fpfh", mparams=None):
+        """lgr_align_ex2_dev: descriptor as in align, mparams a MetricParams (None = the defaults)."""
+        res = Result()
+        f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+        self.check(_lib.lgr_align_ex2_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
+                                          C.byref(mparams) if mparams is not None else None, C.byref(res)))
+        return res
+
+    def align_ex2_host(self, src, tgt, params, descriptor="fpfh", mparams=None):
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        res = Result()
+        f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+        self.check(_lib.lgr_align_ex2(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
+                                      C.byref(mparams) if mparams is not None else None, C.byref(res)))
         return res
 
     def align_host(self, src, tgt, params, descriptor="fpfh"):

@@ -20,7 +20,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("source"); ap.add_argument("target")
     ap.add_argument("--keypoint", default="iss", choices=["iss", "any"])           # the reference's default (src/common.cpp:247)
-    ap.add_argument("--metric", default="uniformity", choices=["uniformity", "correspondences", "closest_plane", "combination"])
+    ap.add_argument("--metric", default="uniformity", choices=["uniformity", "correspondences", "closest_plane", "combination",
+                                                                    "weighted_closest_plane"])
+    ap.add_argument("--weight", default="constant", choices=["constant", "exp_curvature", "curvedness", "curvature", "nss"],
+                    help="point weights of weighted_closest_plane (src/weights.cpp)")
     ap.add_argument("--matching", default="cluster", choices=["lr", "one_sided", "cluster"])
     ap.add_argument("--alignment", default="ransac", choices=["ransac", "gror"])
     ap.add_argument("--descriptor", default="fpfh", choices=["fpfh", "shot", "rops"])
@@ -50,7 +53,10 @@ def main():
                                 normals_available=ld["normals_available"])
     t = time.perf_counter()
     lrf = {"default": capi.LRF_DEFAULT, "gravity": capi.LRF_GRAVITY}[a.lrf]
-    res = ctx.align(clouds[0], clouds[1], p, descriptor=a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf))
+    if a.metric == "weighted_closest_plane":
+        res = ctx.align_ex2(clouds[0], clouds[1], p, descriptor=capi.feature_params(a.descriptor, lrf_id=lrf), mparams=capi.metric_params(a.weight))
+    else:
+        res = ctx.align(clouds[0], clouds[1], p, descriptor=a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf))
     dt = time.perf_counter() - t
     T = res.matrix()
     print(f"aligned in {1e3 * dt:.1f} ms: converged={res.converged} correspondences={res.n_correspondences} inliers={res.n_inliers} "
