@@ -165,7 +165,8 @@ typedef struct {
     int32_t rerank_refilter;  /* MFMA re-filter of the rerank's candidate groups: 1 (default) / 0 (whole-group exact scan) */
     int32_t pair_cap;         /* pairs per rerank item the re-filter may emit before falling back to the group scan: -1 default (8) */
     int32_t poison_tables;    /* diagnostics: fill never-computed minimum-table entries with 0 (nothing may read them) */
-    int32_t self_check;       /* diagnostics: device check of the proven filter bound on sampled queries (lgr_match_last_check) */
+    int32_t self_check;       /* diagnostics: device check of the proven filter bound (lgr_match_last_check, lgr_match_last_check_cover):
+                               * 1 every 37th query, 2 every query (test sizes), 0 off */
     int32_t shell_bound;      /* radial shell bound per (row block, column stage) in the passes that have upper bounds: 1 (default) / 0 */
     int32_t split_sweep;      /* final pass of the rotated format as two kernels -- the coarse sweep appends the tiles it keeps to a list, a second
                                * kernel finishes them: 1 (default) / 0 (one fused kernel, round 3) */
@@ -366,9 +367,13 @@ int lgr_match_last_lbstats(lgr_ctx*, double* out2);
  * exact side scan instead of the MFMA filter (0 when the lane was off, found no consensus among the block sums, or gave up); [2] = 1 when it
  * gave up (more than 1024 such rows on a side: the call was rebuilt with every finite row in the filter). */
 int lgr_match_last_irregular(lgr_ctx*, unsigned* out3);
-/* self-check of the matcher's filter bound (lgr_match_options.self_check = 1, test sizes): worst |filtered - exact| / eps over
+/* self-check of the matcher's filter bound (lgr_match_options.self_check = 1 or 2, test sizes): worst |filtered - exact| / eps over
  * sampled table entries of the last match call, rows then columns; -1 = not run.  Must be <= 1. */
 int lgr_match_last_check(lgr_ctx*, double* out2);
+/* what that check covered, rows [0..3] then columns [4..7]: entries checked, entries whose upper side was tested, entries whose upper
+ * side was waived (the exact minimum lies above the coarse rejection's U^2), entries with a row that counts as computed only through the
+ * per-stage column criterion (columns; 0 for rows).  ~0 (-1) = not run: all eight, or a direction's four when it was not matched. */
+int lgr_match_last_check_cover(lgr_ctx*, unsigned long long* out8);
 /* ---- src/common.cpp:531-547 calculateSmoothedDensities(pcd, k) / :202-208 calculatePointCloudDensity ---- */
 int lgr_smoothed_densities(lgr_ctx*, const float* pts, int n, int k, float* out);
 int lgr_smoothed_densities_dev(lgr_ctx*, const float* d_pts, int n, int k, float* d_out);

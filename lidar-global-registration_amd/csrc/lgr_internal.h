@@ -66,6 +66,7 @@ struct lgr_ctx {
     lgr_helper* helper = nullptr;               // of an internal context: the host thread that drives it (opt.helper_contexts)
     lgr_match_stats mstats{};                   // lgr_match_last_*: the last match call of THIS context
     double mcheck[2] = {-1, -1};
+    unsigned long long mcover[8] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // lgr_match_last_check_cover
     bool internal = false;                      // an aux / aux2 context: works inside its owner's turn (lgr_turn)
     int turn_depth = 0;                         // public entry points call each other: only the outermost one takes the device's turn
     unsigned long long turn_id = 0;             // identity for the turn hand-over (never reused, unlike the address)

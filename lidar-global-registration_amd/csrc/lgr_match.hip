@@ -108,6 +108,15 @@ extern "C" int lgr_match_last_check(lgr_ctx* ctx, double* out2) {
     return LGR_OK;
 }
 
+// ... and what it covered, rows [0..3] then columns [4..7]: entries checked, entries whose upper side was tested, entries whose upper side
+// was waived (coarse rejection), entries with a row guaranteed only through the per-stage column criterion (columns; 0 for rows);
+// all ~0 when the check did not run, a direction's four when that direction was not matched.
+extern "C" int lgr_match_last_check_cover(lgr_ctx* ctx, unsigned long long* out8) {
+    if (!ctx || !out8) return LGR_ERR_INVALID_ARG;
+    for (int k = 0; k < 8; ++k) out8[k] = ctx->mcover[k];
+    return LGR_OK;
+}
+
 // environment: debug dumps only (LGR_MATCH_DEBUG); everything that selects a path is an lgr_match_options field
 static int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -330,6 +339,7 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
     double* const g_last_check = ctx->mcheck;
     memset(&g_last_stats, 0, sizeof g_last_stats);
     g_last_check[0] = g_last_check[1] = -1;
+    for (unsigned long long& c : ctx->mcover) c = ~0ull;
     ctx->mfma_timed = 0;
     // default result: unmatched
     if (ma) { LGR_HIP(ctx, hipMemsetAsync(d_ab_idx, 0xff, (size_t) ma * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(d_ab_dist, 0, (size_t) ma * 4, ctx->stream)); }
@@ -850,7 +860,9 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
             comp_rows_kernel<<<cdiv((long long) n_rb * n_groups, 256), 256, 0, ctx->stream>>>(done, sched_final, group_leaf, n_rb, n_leaves, n_groups, comp_r);
             if (both) comp_cols_kernel<<<cdiv((long long) n_leaves * n_rg, 256), 256, 0, ctx->stream>>>(done, sched_final, n_rb, n_leaves, n_rg, rg_rows / BLOCK_ROWS, comp_c);
         };
-        chk_done = done; chk_sched = sched;   // (chk_sched: re-pointed to the touched pairs below when the final pass defers its initialisation) chk_lb = LBsq; chk_ustage = colstage ? u_stage : nullptr;
+        // (chk_sched: re-pointed to the touched pairs below when the final pass defers its initialisation)
+        chk_done = done; chk_sched = sched;
+        chk_lb = LBsq; chk_ustage = colstage ? u_stage : nullptr;
         comp_rows = CompView{comp_r, n_groups, nullptr};
         comp_cols = CompView{comp_c, n_rg, tile_leaf};
         // do the bounds separate anything?  (zero / finite lower bounds: counted by box_lb_kernel where it writes the final bounds, by lb_stats_kernel
@@ -1130,22 +1142,27 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
     }
     if (mo.self_check && sortedA) {
         unsigned* d_worst = (unsigned*) (misc + 192);
+        unsigned long long* d_cover = (unsigned long long*) (misc + 3840);   // [2][CHECK_N] (behind the level-1 centres, inside the first 4 KB)
+        static_assert(2 * CHECK_N == 8, "lgr_match_last_check_cover reports four counters per direction");
         LGR_HIP(ctx, hipMemsetAsync(d_worst, 0, 8, ctx->stream));
-        const int stride = 37;
+        LGR_HIP(ctx, hipMemsetAsync(d_cover, 0, 2 * CHECK_N * 8, ctx->stream));
+        const int stride = mo.self_check >= 2 ? 1 : 37;   // 2: every query (test sizes); 1: every 37th
         check_kernel<true><<<cdiv(ma_pad, stride), 256, (size_t) (n_groups + 8) * 4, ctx->stream>>>(
             (const float*) rowmin, n_groups, ma_pad, 0, group_start, sortedA, A.perm, sortedB, B.perm, mb_pad, nAp, A.blkcl, nullptr, gmaxB, nullptr,
-            ex, comp_rows, stride, nullptr, nullptr, 0, nullptr, nullptr, chk_uq_rows, chk_uq_cols, d_worst);
+            ex, comp_rows, stride, nullptr, nullptr, 0, nullptr, nullptr, chk_uq_rows, chk_uq_cols, d_worst, d_cover);
         if (both)
             check_kernel<false><<<cdiv(mb_pad, stride), 256, (size_t) (n_rg + 8) * 4, ctx->stream>>>(
                 (const float*) colmin, n_rg, mb_pad, rg_rows, nullptr, sortedB, B.perm, sortedA, A.perm, ma_pad, nullptr, nullptr, nBp, gmaxA, cl_of_rg,
-                ex, comp_cols, stride, chk_done, chk_sched, n_leaves, chk_lb, chk_ustage, chk_uq_rows, chk_uq_cols, d_worst + 1);
+                ex, comp_cols, stride, chk_done, chk_sched, n_leaves, chk_lb, chk_ustage, chk_uq_rows, chk_uq_cols, d_worst + 1, d_cover + CHECK_N);
         unsigned* hw;
-        LGR_TRY(lgr_pinned(ctx, 64, (void**) &hw));
+        LGR_TRY(lgr_pinned(ctx, 128, (void**) &hw));
         LGR_HIP(ctx, hipMemcpyAsync(hw, d_worst, 8, hipMemcpyDeviceToHost, ctx->stream));
+        LGR_HIP(ctx, hipMemcpyAsync(hw + 16, d_cover, 2 * CHECK_N * 8, hipMemcpyDeviceToHost, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
         float r0, r1;
         memcpy(&r0, hw, 4); memcpy(&r1, hw + 1, 4);
         g_last_check[0] = r0; g_last_check[1] = r1;
+        memcpy(ctx->mcover, hw + 16, (both ? 2 : 1) * CHECK_N * 8);
     }
 
     // ---- 5. exact rerank

@@ -450,7 +450,13 @@ __global__ __launch_bounds__(256) void mask_stats_kernel(int pass, const unsigne
 
 // Self-check of the filter bound (lgr_match_options.self_check; tests, up to 1M x 1M): for sampled queries and every computed group,
 // |filtered minimum - exact minimum of the squared distance (double)| / eps, maximised through atomicMax on the float
-// bits.  eps is a proven bound, so the ratio must stay <= 1; tests assert it on both operand formats.
+// bits.  eps is a proven bound, so the ratio must stay <= 1; tests assert it on both operand formats.  What was checked is counted
+// too (a direction that checks nothing reports ratio 0): cover[CHECK_*] of the direction, one atomic add per workgroup.
+enum { CHECK_ENTRIES = 0,   // entries checked (some row reached them: best_all finite)
+       CHECK_UPPER,         // ... whose upper side was tested
+       CHECK_WAIVED,        // ... whose upper side was waived: the guaranteed minimum lies above the coarse rejection's U^2
+       CHECK_COLSTAGE,      // columns: entries with a row that is guaranteed only through the per-stage column criterion
+       CHECK_N };
 template <bool ROWDIR>
 __global__ void check_kernel(const float* __restrict__ table, int n_groups, int q_pad, int group_size, const int* __restrict__ starts,
                              const float* __restrict__ Qsorted, const int* __restrict__ permQ, const float* __restrict__ Tsorted,
@@ -459,7 +465,8 @@ __global__ void check_kernel(const float* __restrict__ table, int n_groups, int 
                              EpsExtra ex, CompView comp, int stride, const uint8_t* __restrict__ done, const uint8_t* __restrict__ sched,
                              int n_leaves, const float* __restrict__ LBsq, const unsigned* __restrict__ u_stage,
                              const float* __restrict__ uq_rows /* coarse rejection: u_row (per row), or nullptr */,
-                             const float* __restrict__ uq_cols /* coarse rejection: u_colv (per column), or nullptr */, unsigned* __restrict__ worst) {
+                             const float* __restrict__ uq_cols /* coarse rejection: u_colv (per column), or nullptr */, unsigned* __restrict__ worst,
+                             unsigned long long* __restrict__ cover /* [CHECK_N] */) {
     extern __shared__ int list_s[];
     const int i = blockIdx.x * stride;   // sampled padded query position
     // the computed groups of the row block (rows) / of the leaf (columns) this query lives in
@@ -471,6 +478,7 @@ __global__ void check_kernel(const float* __restrict__ table, int n_groups, int 
     const float xq = ROWDIR ? sqrtf(nQ[i]) * 1.0000002f : 0.f;
     float q[33];
     for (int k = 0; k < 33; ++k) q[k] = Qsorted[(size_t) i * 33 + k];
+    unsigned n_entries = 0, n_upper = 0, n_waived = 0, n_colstage = 0;   // (thread 0)
     for (int kk = 0; kk < (n_list < 0 ? n_groups : n_list); ++kk) {
         const int g = n_list < 0 ? kk : list_s[kk];
         const float v = table[(size_t) g * q_pad + i];
@@ -481,6 +489,7 @@ __global__ void check_kernel(const float* __restrict__ table, int n_groups, int 
         // reach the column too -- their minima land in the entry when it is already initialised and are lost otherwise
         // (extra information either way: the rerank only needs the guaranteed rows).
         double best = 1e300, best_all = 1e300;
+        int cs = 0;   // a row guaranteed through the column-stage rule alone ((sv & 2) without (sv & 1) on the column's own leaf)
         for (int j = j0 + (int) threadIdx.x; j < j1; j += blockDim.x) {
             if (permT[j] < 0) continue;
             bool sure = true;
@@ -497,7 +506,7 @@ __global__ void check_kernel(const float* __restrict__ table, int n_groups, int 
                     const uint8_t sv = done[t] | sched[t];
                     const bool c = (sv & 1) || ((sv & 2) && u_stage && col_stage_needed(LBsq[t], u_stage[gst]));   // mask_kernel's rule
                     on = on || c || (sv & DONE_SHELL);   // (pass 0's shell selection may have reached the column: not guaranteed)
-                    if (gl == my_leaf) sure = c;
+                    if (gl == my_leaf) { sure = c; cs |= (c && !(sv & 1)) ? 1 : 0; }
                 }
                 if (!on) continue;
             }
@@ -509,13 +518,17 @@ __global__ void check_kernel(const float* __restrict__ table, int n_groups, int 
         for (int o = 32; o > 0; o >>= 1) {
             double other = __shfl_xor(best, o); best = other < best ? other : best;
             other = __shfl_xor(best_all, o); best_all = other < best_all ? other : best_all;
+            cs |= __shfl_xor(cs, o);
         }
         __shared__ double sh[4], sh_all[4];
+        __shared__ int sh_cs[4];
         __syncthreads();
-        if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = best; sh_all[threadIdx.x >> 6] = best_all; }
+        if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = best; sh_all[threadIdx.x >> 6] = best_all; sh_cs[threadIdx.x >> 6] = cs; }
         __syncthreads();
         if (threadIdx.x == 0) {
-            for (int w = 1; w < (int) (blockDim.x >> 6); ++w) { best = sh[w] < best ? sh[w] : best; best_all = sh_all[w] < best_all ? sh_all[w] : best_all; }
+            for (int w = 1; w < (int) (blockDim.x >> 6); ++w) {
+                best = sh[w] < best ? sh[w] : best; best_all = sh_all[w] < best_all ? sh_all[w] : best_all; cs |= sh_cs[w];
+            }
             if (best_all < 1e299) {   // rows reached the entry
                 float e = group_eps<ROWDIR>(i, g, xq, nQ_sets, gmax, n_groups, p, cl_of_group, q_pad, ex);
                 // upper side (entry <= guaranteed minimum + eps, and finite): required unless the coarse rejection may have
@@ -531,8 +544,18 @@ __global__ void check_kernel(const float* __restrict__ table, int n_groups, int 
                     if (upper) ratio = fmaxf(ratio, (float) (fmax((double) v - best, 0.0) / (double) e));
                 } else if (upper) ratio = 1e30f;
                 atomicMax(worst, __float_as_uint(ratio));
+                n_entries += 1;
+                n_upper += upper ? 1 : 0;
+                n_waived += (best < 1e299 && !upper) ? 1 : 0;
+                n_colstage += cs ? 1 : 0;
             }
         }
+    }
+    if (threadIdx.x == 0) {
+        if (n_entries) atomicAdd(&cover[CHECK_ENTRIES], (unsigned long long) n_entries);
+        if (n_upper) atomicAdd(&cover[CHECK_UPPER], (unsigned long long) n_upper);
+        if (n_waived) atomicAdd(&cover[CHECK_WAIVED], (unsigned long long) n_waived);
+        if (n_colstage) atomicAdd(&cover[CHECK_COLSTAGE], (unsigned long long) n_colstage);
     }
 }
 

@@ -399,6 +399,16 @@ class Context:
         self.check(_lib.lgr_match_last_check(self.h, out))
         return out[0], out[1]
 
+    def match_check_cover(self):
+        """what the self-check of the last match call covered, per direction: {"rows": {...}, "cols": {...}} with the counts of
+        "entries" checked, "upper" (upper side tested), "waived" (upper side waived by the coarse rejection) and "colstage" (a row
+        guaranteed only through the per-stage column criterion); -1 when that direction was not checked"""
+        out = (C.c_ulonglong * 8)()
+        self.check(_lib.lgr_match_last_check_cover(self.h, out))
+        keys = ("entries", "upper", "waived", "colstage")
+        return {d: {k: (-1 if out[4 * j + n] == 0xFFFFFFFFFFFFFFFF else int(out[4 * j + n])) for n, k in enumerate(keys)}
+                for j, d in enumerate(("rows", "cols"))}
+
     def match_kernel_ms(self):
         ms = C.c_float(0)
         self.check(_lib.lgr_match_last_kernel_ms(self.h, C.byref(ms)))

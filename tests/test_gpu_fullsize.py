@@ -4,6 +4,8 @@ grid, rigid-motion equivariance of the pipeline stages, and ground-truth recover
 import numpy as np
 import pytest
 
+from test_gpu_match import checked
+
 pytestmark = pytest.mark.gpu
 
 
@@ -60,13 +62,14 @@ def test_matcher_1m_coarse_rejection_is_invisible(lgr, opts):
     lgr.sync()
     assert lgr.match_format() == "f16r"
     tested, abandoned = lgr.match_coarse()
-    r_rows, r_cols = lgr.match_check()
-    assert 0.0 <= r_rows <= 1.0 and 0.0 <= r_cols <= 1.0, (r_rows, r_cols)
+    # (the production schedule at this size takes (row block, leaf) pairs for the columns' per-stage criterion: the check must see them)
+    r_rows, r_cols, _ = checked(lgr, "1M coarse rejection", colstage=True)
     assert lgr.match_work() < 0.5 and abandoned > 0.5 * tested > 0, (lgr.match_work(), tested, abandoned)
     opts(poison_tables=1, self_check=1, coarse_rejection=0)
     off = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 200000)]
     lgr.sync()
     assert lgr.match_coarse() == (0.0, 0.0)
+    checked(lgr, "1M coarse rejection off", coarse=False, colstage=True)
     for x, y in zip(on, off):
         np.testing.assert_array_equal(x.view(np.uint32), y.view(np.uint32))
     print(f"1M coarse rejection: {abandoned:.0f} of {tested:.0f} final-pass tiles abandoned, work {lgr.match_work():.3f}, "
@@ -76,8 +79,7 @@ def test_matcher_1m_coarse_rejection_is_invisible(lgr, opts):
     noshell = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 200000)]
     lgr.sync()
     assert lgr.match_shell() == 0.0
-    r_rows, r_cols = lgr.match_check()
-    assert 0.0 <= r_rows <= 1.0 and 0.0 <= r_cols <= 1.0, (r_rows, r_cols)
+    checked(lgr, "1M shell bound off")
     for x, y in zip(on, noshell):
         np.testing.assert_array_equal(x.view(np.uint32), y.view(np.uint32))
 

@@ -47,6 +47,30 @@ def opts(lgr, **extra):
 FMT = {"f32": 0, "f16": 1, "f16r": 2}
 
 
+def checked(lgr, label, coarse=True, colstage=None, cols_upper=True):
+    """The device self-check of the last match call (lgr_match_options.self_check): the worst |filtered - exact| / eps of both
+    directions within [0, 1], and both directions really checked entries and tested their upper side -- a direction that checks
+    nothing would report ratio 0.  cols_upper=False: the column entries may all lack a guaranteed row (pass 0's shell selection
+    reaches columns without covering them; on a few dozen distinct rows that can be all there is).  coarse=False: no coarse
+    rejection ran, so no upper side is waived and every row entry (all of its rows are guaranteed) has its upper side tested.
+    colstage: True / False = some / no column entry holds a row that is guaranteed only through the per-stage column criterion.
+    Prints the ratios and counts; returns (r_rows, r_cols, cover)."""
+    r_rows, r_cols = lgr.match_check()
+    cov = lgr.match_check_cover()
+    rows, cols = cov["rows"], cov["cols"]
+    print(f"self-check [{label}]: ratio rows {r_rows:.3g} cols {r_cols:.3g} | rows {rows} | cols {cols}")
+    assert 0.0 <= r_rows <= 1.0 and 0.0 <= r_cols <= 1.0, (r_rows, r_cols, cov)
+    for c in (rows, cols):
+        assert c["entries"] > 0 and c["upper"] + c["waived"] <= c["entries"] and c["colstage"] <= c["entries"], cov
+    assert rows["upper"] > 0 and (cols["upper"] > 0 or not cols_upper), cov
+    assert rows["colstage"] == 0, cov
+    if not coarse:
+        assert rows["upper"] == rows["entries"] and rows["waived"] == 0 and cols["waived"] == 0, cov
+    if colstage is not None:
+        assert (cols["colstage"] > 0) == colstage, cov
+    return r_rows, r_cols, cov
+
+
 def fpfh_like(rng, m, spread=1.0):
     """rows shaped like FPFH: three 11-bin blocks, each summing to 100."""
     x = rng.gamma(0.6 * spread, 1.0, (m, 3, 11)).astype(np.float64) + 1e-3
@@ -176,7 +200,7 @@ def test_filter_bound_self_check(lgr, oracle, matcher_mode, fmt, kind):
         pytest.skip("same filter code path as prune_sub4 / auto")
     # f16r: the rotated 30-coordinate format forced on ANY data (rows whose blocks do not sum to a constant make its
     # dropped-coordinate term large: the bound must still hold and the result stay exact); f16: forced off
-    opts(lgr, self_check=1, operand_format=FMT[fmt])
+    opts(lgr, self_check=2, operand_format=FMT[fmt])
     rng = np.random.default_rng(77)
     ma, mb = 6000, 9000
     if kind == "fpfh":
@@ -198,9 +222,9 @@ def test_filter_bound_self_check(lgr, oracle, matcher_mode, fmt, kind):
     lgr.match_bf2(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), 2500)
     lgr.sync()
     assert lgr.match_format() == fmt
-    r_rows, r_cols = lgr.match_check()
-    assert 0.0 <= r_rows <= 1.0 and 0.0 <= r_cols <= 1.0, (r_rows, r_cols)
-    print(f"filter bound ratio [{fmt} {kind} {matcher_mode}]: rows {r_rows:.3g} cols {r_cols:.3g}")
+    # (auto: the skipping path is not taken at this size -- no coarse rejection, no column-stage rows)
+    auto = matcher_mode == "auto"
+    checked(lgr, f"{fmt} {kind} {matcher_mode}", coarse=not auto, colstage=False if auto else None, cols_upper=auto or fmt != "f16r")
 
 
 def test_coarse_rejection(lgr, oracle, matcher_mode):
@@ -219,20 +243,20 @@ def test_coarse_rejection(lgr, oracle, matcher_mode):
         return (100.0 * x / x.sum(2, keepdims=True)).reshape(m, 33).astype(np.float32)
     # half tight clusters, half one broad distribution (there the bounds exclude little: the final pass has tiles to test)
     a = np.concatenate([cloud(6000), fpfh_like(rng, 6000)]); b = np.concatenate([fpfh_like(rng, 8000), cloud(7000)])
-    opts(lgr, self_check=1, coarse_rejection=2)   # (2: the sweep also when the pass schedules most of the tiles, as it does at this size)
+    opts(lgr, self_check=2, coarse_rejection=2)   # (2: the sweep also when the pass schedules most of the tiles, as it does at this size)
     oi, ri = run_both(lgr, oracle, a, b, 4000)
     ta, tb = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     on = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 4000)]
     lgr.sync()
     assert lgr.match_format() == "f16r"
     tested, abandoned = lgr.match_coarse()
-    r_rows, r_cols = lgr.match_check()
-    assert 0.0 <= r_rows <= 1.0 and 0.0 <= r_cols <= 1.0, (r_rows, r_cols)
+    checked(lgr, f"coarse rejection {matcher_mode}")
     assert tested > 0 and 0 < abandoned <= tested, (tested, abandoned)
-    opts(lgr, self_check=1, coarse_rejection=0)
+    opts(lgr, self_check=2, coarse_rejection=0)
     off = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 4000)]
     lgr.sync()
     assert lgr.match_coarse() == (0.0, 0.0)
+    checked(lgr, f"coarse rejection off {matcher_mode}", coarse=False)
     for x, y in zip(on, off):
         np.testing.assert_array_equal(x.view(np.uint32), y.view(np.uint32))
     print(f"coarse rejection [{matcher_mode}]: {abandoned:.0f} of {tested:.0f} tiles abandoned")
@@ -257,11 +281,12 @@ def test_final_pass_implementations_agree(lgr, oracle, matcher_mode):
     ta, tb = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     results = {}
     for name, extra in (("split", dict(split_sweep=1)), ("fused", dict(split_sweep=0)), ("overflow", dict(split_sweep=1, kept_cap=64))):
-        opts(lgr, self_check=1, coarse_rejection=2, **extra)
+        opts(lgr, self_check=2, coarse_rejection=2, **extra)
         run_both(lgr, oracle, a, b, 4000)                          # both directions against the oracle
         results[name] = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 4000)]
         lgr.sync()
         assert lgr.match_format() == "f16r"
+        checked(lgr, f"final pass {name} {matcher_mode}")
         tested, abandoned = lgr.match_coarse()
         assert tested > 0 and 0 < abandoned < tested, (name, tested, abandoned)   # (some tiles are kept: more than the 64 the small list holds)
         assert tested - abandoned > 64 or name != "overflow", (tested, abandoned)
@@ -289,28 +314,59 @@ def test_shell_bound(lgr, oracle, matcher_mode):
         return (100.0 * x / x.sum(2, keepdims=True)).reshape(m, 33).astype(np.float32)
     a = np.concatenate([cloud(9000), fpfh_like(rng, 3000)]); b = np.concatenate([fpfh_like(rng, 4000), cloud(11000)])
     a[17] = b[40]; a[18] = b[40]                                   # exact ties across the two sets
-    opts(lgr, self_check=1, coarse_rejection=2)   # (2: the sweep also when the pass schedules most of the tiles)
+    opts(lgr, self_check=2, coarse_rejection=2)   # (2: the sweep also when the pass schedules most of the tiles)
     run_both(lgr, oracle, a, b, 4000)
     ta, tb = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     on = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 4000)]
     lgr.sync()
     assert lgr.match_format() == "f16r"
     skipped, work_on = lgr.match_shell(), lgr.match_work()
-    r_rows, r_cols = lgr.match_check()
-    assert 0.0 <= r_rows <= 1.0 and 0.0 <= r_cols <= 1.0, (r_rows, r_cols)
+    checked(lgr, f"shell bound {matcher_mode}")
     one = [t.cpu().numpy() for t in lgr.match_bf(ta, tb, 4000)]
-    opts(lgr, self_check=1, shell_bound=0, coarse_rejection=2)
+    opts(lgr, self_check=2, shell_bound=0, coarse_rejection=2)
     off = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 4000)]
     lgr.sync()
     assert lgr.match_shell() == 0.0
     work_off = lgr.match_work()
-    r_rows, r_cols = lgr.match_check()
-    assert 0.0 <= r_rows <= 1.0 and 0.0 <= r_cols <= 1.0, (r_rows, r_cols)
+    checked(lgr, f"shell bound off {matcher_mode}")
     for x, y in zip(on, off):
         np.testing.assert_array_equal(x.view(np.uint32), y.view(np.uint32))
     np.testing.assert_array_equal(one[0], on[0]); np.testing.assert_array_equal(one[1].view(np.uint32), on[1].view(np.uint32))
     assert skipped > 0 and work_on <= work_off, (skipped, work_on, work_off)
     print(f"shell bound [{matcher_mode}]: {skipped:.0f} tiles left out inside the sweep, stages computed {work_on:.4f} (off: {work_off:.4f})")
+
+
+def test_self_check_coverage(lgr, oracle, matcher_mode):
+    """The self-check must look at what the schedule computed, and its counts must show it.  The final pass schedules (row block, leaf)
+    pairs for the columns' per-stage criterion alone (lgr_match_options.column_stage).  With the fused final-pass kernel (which computes
+    every scheduled pair; the split sweep reports only the pairs that keep a tile) the column check counts rows it guarantees only
+    through that rule and holds the bound on them; with the criterion off it counts none; without the coarse rejection every row entry
+    has its upper side tested and nothing is waived.  Every query is checked (self_check = 2); matches stay oracle-exact."""
+    import torch
+    if matcher_mode not in ("prune_sub4", "prune_sub64"):
+        pytest.skip("needs the skipping passes (upper bounds) and the default schedule")
+    rng = np.random.default_rng(31337)   # test_final_pass_implementations_agree's scene
+    centres = fpfh_like(rng, 32)
+    def cloud(m):
+        x = centres[rng.integers(0, 32, m)].astype(np.float64).reshape(m, 3, 11)
+        x = np.abs(x + rng.normal(0, 1.5, x.shape)) + 1e-3
+        return (100.0 * x / x.sum(2, keepdims=True)).reshape(m, 33).astype(np.float32)
+    a = np.concatenate([cloud(5000), fpfh_like(rng, 7000)]); b = np.concatenate([fpfh_like(rng, 6000), cloud(8000)])
+    ta, tb = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    runs = {}
+    for name, extra, kw in (("column_stage fused", dict(coarse_rejection=2, split_sweep=0), dict(colstage=True)),
+                            ("column_stage plain", dict(coarse_rejection=0), dict(coarse=False)),
+                            ("leaf columns fused", dict(coarse_rejection=2, split_sweep=0, column_stage=0), dict(colstage=False))):
+        opts(lgr, self_check=2, **extra)
+        if name == "column_stage fused":
+            run_both(lgr, oracle, a, b, 4000)
+        runs[name] = [t.cpu().numpy() for t in lgr.match_bf2(ta, tb, 4000)]
+        lgr.sync()
+        assert lgr.match_format() == "f16r"
+        checked(lgr, f"{name} {matcher_mode}", **kw)
+    for name in ("column_stage plain", "leaf columns fused"):
+        for x, y in zip(runs["column_stage fused"], runs[name]):
+            np.testing.assert_array_equal(x.view(np.uint32), y.view(np.uint32))
 
 
 def test_rerank_refilter(lgr, oracle, matcher_mode):
