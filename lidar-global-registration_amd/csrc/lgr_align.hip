@@ -89,14 +89,6 @@ __global__ void filter_emit(int ns, const int32_t* __restrict__ ij, const int* _
     out[pos[i]] = c;
 }
 
-__global__ void invalidate_nan_rows(const float* __restrict__ feat, int m, int32_t* __restrict__ idx) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    bool ok = true;
-    for (int k = 0; k < 33; ++k) ok = ok && (fabsf(feat[(size_t) i * 33 + k]) <= 3.4028234663852886e38f);
-    if (!ok) idx[i] = -1;
-}
-
 }  // namespace
 
 // the filter's per-cloud tables: smoothed densities (thresholds) of both key-point clouds and, for the cluster filter, their

@@ -10,9 +10,9 @@
 //   the record inlier set (largest count, ties -> lowest i) tightens the bound through estimateMaxIterations and the
 //   best hypothesis is the maximum metric (strict '>', ties -> lowest i).
 // Float sequences restate the oracle op for op (oracle/src/orc_ransac.cpp); compiled with -ffp-contract=off.
-// Round 4: for the uniformity / correspondences metrics the loop itself runs from the device (RState, ransac_device_schedule below):
-// the host enqueues two rounds and the final block blind and reads one record -- one synchronisation per alignment; the closest-plane
-// metrics keep the host-driven rounds (their sparse subsets are keyed by batch).
+// The loop itself runs from the device for all five metrics (RState, ransac_device_schedule below; rounds 4-5).  Uniformity / correspondences:
+// the host enqueues two rounds and the final block blind and reads one record -- one synchronisation per alignment.  The plane metrics: the
+// same rounds with the plane evaluation in them (a hypothesis's sparse subset is keyed by its iteration), then a host-driven final block.
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
@@ -31,8 +31,6 @@ constexpr int MIN_NR_FINAL_INLIERS = 20;   // :9
 constexpr double MIN_INLIER_RATE = 0.15;   // :10
 
 // ---------------------------------------------------------------------------------------------------- sampling
-__device__ __forceinline__ void philox4x32(unsigned long long seed, unsigned iter, unsigned out[4]) { lgr_philox4(seed, iter, 0u, 0u, 0u, out); }
-
 // src/sac_prerejective_omp.cpp:33-77 selectCorrespondences (control flow kept literally), NS = AlignmentParameters::n_samples
 // The reference's loops (for i < NS: draw, for j < i: bump / wrap / insert-and-break) unrolled at compile time so that sample[] stays in
 // registers (with run-time indices it lived in scratch memory).  `step` is one pass of the j loop's body at position j for the value x
@@ -205,7 +203,7 @@ constexpr int LGR_MIN_SAMPLES = 3, LGR_MAX_SAMPLES = 8;
 __device__ __forceinline__ float next_up(float x) { return __uint_as_float(__float_as_uint(x) + 1u); }
 __device__ __forceinline__ float next_down(float x) { return __uint_as_float(__float_as_uint(x) - 1u); }
 
-// PP (count_kernel's operand): one 64-byte record per TWO correspondences, {sx sy sz | qx qy qz | s* | band slope} as 2-vectors, padded
+// PP (count_item's operand): one 64-byte record per TWO correspondences, {sx sy sz | qx qy qz | s* | band slope} as 2-vectors, padded
 // with never-inlier fillers to a multiple of 64 correspondences; pstats = bit patterns of max |source coordinate|, max |target
 // coordinate|, max finite s* (float max through integer atomics: all values >= 0).
 constexpr int CP_FLOATS = 16;
@@ -251,7 +249,7 @@ __global__ void pack_kernel(const float* __restrict__ src, const float* __restri
     if (PP) {
         float* r = PP + (size_t) (i >> 1) * CP_FLOATS + (i & 1);
         r[0] = s.x; r[2] = s.y; r[4] = s.z; r[6] = t.x; r[8] = t.y; r[10] = t.z; r[12] = ss;
-        // slope of the decision band of count_kernel's fused evaluation: 28 sqrt(s*), rounded up (inf for an infinite threshold)
+        // slope of the decision band of count_item's fused evaluation: 28 sqrt(s*), rounded up (inf for an infinite threshold)
         r[14] = (ss < 3.4028234663852886e38f) ? next_up(28.f * __builtin_sqrtf(ss)) * 1.000001f : __uint_as_float(0x7f800000u);
         const float sm = fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fabsf(s.z)), qm = fmaxf(fmaxf(fabsf(t.x), fabsf(t.y)), fabsf(t.z));
         // NaN coordinates: the integer max of the bit pattern keeps them (a NaN pattern is above every finite one) -> the band becomes NaN
@@ -285,7 +283,7 @@ __global__ void pack_kernel(const float* __restrict__ src, const float* __restri
 // lane = hypothesis (T in registers), loop over a chunk of correspondences broadcast from LDS.
 // counts[h] = {inliers (4-norm rule, src/metric.cpp:141), support (3-norm rule, src/metric.cpp:111)}
 constexpr int CB = 64;        // hypotheses per workgroup (one wave)
-constexpr int CCH = 2048;     // correspondences per workgroup (fewer when there are few hypotheses: cch of count_kernel)
+constexpr int CCH = 2048;     // correspondences per workgroup (fewer when there are few hypotheses: count_chunk)
 // The O(H x C) verification.  Round 3: per (hypothesis, correspondence) pair the reference's expressions (LGR_APPLY, the Eigen
 // 4-vector and 3-vector norms: ~25 unfused multiply / add instructions per pair) are evaluated only where they can decide something.
 // A FUSED evaluation -- e_k = fma(c_k0, x, fma(c_k1, y, fma(c_k2, z, c_k3 - q_k))), d2~ = fma(e_z, e_z, fma(e_y, e_y, e_x e_x)): 15 packed
@@ -390,12 +388,7 @@ __host__ __device__ inline int count_chunk(int nh, int c) {
     const long long hb = (nh + CB - 1) / CB;
     return (hb * ((c + CCH - 1) / CCH) >= 4096) ? CCH : ((hb * ((c + 511) / 512) >= 4096) ? 512 : 128);
 }
-__global__ __launch_bounds__(CB) void count_kernel(const float* __restrict__ Ts, const int* __restrict__ list, int nh,
-                                                    const CPair* __restrict__ PP, const unsigned* __restrict__ pstats, int c, int2* __restrict__ counts,
-                                                    unsigned* __restrict__ maskT, int cch) {
-    count_item(blockIdx.x, blockIdx.y, Ts, list, nh, PP, pstats, c, counts, maskT, cch, threadIdx.x);
-}
-// the same over a work list whose size only the device knows (device-driven schedule, lgr_ransac_dev): nh = *nh_dev hypotheses, a fixed
+// the work list's size is known to the device only (device-driven schedule, lgr_ransac_dev): nh = *nh_dev hypotheses, a fixed
 // grid of single-wave workgroups strides over the (hypothesis block, chunk) items, hypothesis blocks fastest (neighbouring workgroups
 // read the same correspondences)
 __global__ __launch_bounds__(CB) void count_list_kernel(const float* __restrict__ Ts, const int* __restrict__ list, const int* __restrict__ nh_dev,
@@ -671,7 +664,7 @@ __global__ __launch_bounds__(MB) void metric_kernel(const float* __restrict__ Ts
                                                      float* __restrict__ metric_out, int* __restrict__ ninl_out,
                                                      float* __restrict__ rmse_out, uint8_t* __restrict__ mask,
                                                      float2* __restrict__ scratch /* [gridDim.x][c] inlier (dist, thr) lists */,
-                                                     const unsigned* __restrict__ maskT /* count_kernel's inlier bits [mask_nh][mask_pitch(c)], or nullptr */,
+                                                     const unsigned* __restrict__ maskT /* count_item's inlier bits [mask_nh][mask_pitch(c)], or nullptr */,
                                                      const int* __restrict__ hpos /* candidate -> row of maskT */, int mask_nh,
                                                      const int* __restrict__ ghist = nullptr /* [30000 + 1]: the uniformity histogram and the inlier count of the ONE
                                                         hypothesis, already counted by inlier_hist_kernel (single-transform evaluations) */,
@@ -682,33 +675,9 @@ __global__ __launch_bounds__(MB) void metric_kernel(const float* __restrict__ Ts
                 ghist, nh2_dev, mask_nh_dev);
 }
 
-// ---------------------------------------------------------------------------------------------------- batch reduce
+// ---------------------------------------------------------------------------------------------------- plumbing
 constexpr int MAX_ROUND_BATCHES = 16;   // batches of the schedule evaluated per round of launches
-struct BatchStats {
-    unsigned long long best_key;   // (metric bits << 32) | (0xffffffff - batch offset); 0 = none
-    unsigned long long rec_key;    // (n_inl << 32) | (0xffffffff - batch offset); 0 = none
-    int n_ok, n_cand, rec_support, pad;
-};
 
-__global__ void flag_ge_kernel(const int2* __restrict__ counts, int nh, int min_inliers, int* __restrict__ flags) {
-    int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h < nh) flags[h] = counts[h].x >= min_inliers ? 1 : 0;
-}
-// closest-plane metric plumbing: inlier counts of the plane test replace the correspondence counts (the estimator's
-// `inliers` are the plane pairs, src/metric.cpp:187-199); candidates pick up their plane metric; combination multiplies
-__global__ void plane_counts_kernel(const int* __restrict__ cnt, int nh, int2* __restrict__ counts) {
-    int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h < nh) counts[h].x = cnt[h];
-}
-__global__ void plane_pick_kernel(const int* __restrict__ flags, const int* __restrict__ pos, int nh, const int* __restrict__ cnt,
-                                  const float* __restrict__ cp, float* __restrict__ metric, int* __restrict__ ninl) {
-    int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h < nh && flags[h]) { metric[pos[h]] = cp[h]; ninl[pos[h]] = cnt[h]; }
-}
-__global__ void plane_mul_kernel(float* __restrict__ metric, const float* __restrict__ cp, int n) {
-    int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) metric[j] = metric[j] * cp[j];   // metric_cs * metric_cp (src/metric.cpp:248)
-}
 __global__ void plane_pack_kernel(const float* __restrict__ src, const float* __restrict__ tgt, const int2* __restrict__ pairs, int n,
                                   float4* __restrict__ P0, float4* __restrict__ P1) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -722,28 +691,6 @@ __global__ void compact_kernel(const int* __restrict__ flags, const int* __restr
                                int* __restrict__ out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && flags[i]) out[pos[i]] = map ? map[i] : i;
-}
-// Batch statistics, one BatchStats per sub-batch of `sub` iterations (several batches of the reference schedule are
-// evaluated by one round of launches; the host replays them in order, see lgr_ransac_dev).
-__global__ void reduce_kernel(const int* __restrict__ list2, int nh2, const float* __restrict__ metric, const int* __restrict__ ninl,
-                              int sub, BatchStats* __restrict__ st) {
-    // list2[j] = offset of candidate j in the round; metric[j], ninl[j] its phase-2 results
-    int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nh2) return;
-    unsigned off = (unsigned) list2[j];
-    BatchStats* t = st + off / (unsigned) sub;
-    atomicMax(&t->best_key, ((unsigned long long) __float_as_uint(metric[j]) << 32) | (0xffffffffu - off));
-    atomicMax(&t->rec_key, ((unsigned long long) (unsigned) ninl[j] << 32) | (0xffffffffu - off));
-}
-__global__ void support_kernel(const int* __restrict__ list, const int2* __restrict__ counts, int nh, int sub, BatchStats* __restrict__ st) {
-    // per sub-batch: number of prerejection survivors, and the support count of the record holder
-    int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= nh) return;
-    int off = list[h];
-    BatchStats* t = st + off / sub;
-    atomicAdd(&t->n_ok, 1);
-    unsigned long long rk = t->rec_key;
-    if (rk != 0 && (int) (0xffffffffu - (unsigned) (rk & 0xffffffffu)) == off) t->rec_support = counts[h].y;
 }
 
 // ordered compaction of the inlier pairs (mask -> flags -> exclusive scan -> scatter) ahead of the sequential refit
@@ -761,9 +708,11 @@ __global__ void compact_pairs_kernel(const float4* __restrict__ P0, const float4
 // src/transformation.cpp:4-38: sequential float sums over the inliers in correspondence order.  Lanes 0..5 own the
 // six centroid accumulators, then lanes 0..8 the nine entries of H; the SVD and R, t follow on lane 0.
 constexpr int RCH = 2048;   // pairs staged per chunk
-__global__ __launch_bounds__(256) void refit_kernel(const float4* __restrict__ P0, const float4* __restrict__ P1, const uint8_t* __restrict__ mask, int c,
-                                                    float* __restrict__ Tout, const int* __restrict__ n_a = nullptr, const int* __restrict__ n_b = nullptr) {
-    if (n_a) c = n_a[0] + n_b[0];   // device-driven schedule: the number of compacted pairs = last exclusive-scan entry + last flag
+__global__ __launch_bounds__(256) void refit_kernel(const float4* __restrict__ P0, const float4* __restrict__ P1, int c, float* __restrict__ Tout,
+                                                    const int* __restrict__ n_a = nullptr, const int* __restrict__ n_b = nullptr) {
+    // every pair of P0 / P1 counts: the callers compact the inliers first (refit_launch), so there is no per-element branch and the LDS
+    // reads run ahead of the dependent adds
+    if (n_a) c = n_a[0] + n_b[0];   // the number of compacted pairs stayed on the device: last exclusive-scan entry + last flag
     // the sums are sequential by definition; the pairs are staged through LDS by the whole block (coalesced loads), so the
     // summing lanes walk LDS instead of waiting on one global load per term
     // (round 5: the staged chunk is COMPONENT-major, so a summing lane reads consecutive words; in the second pass the whole block also forms the
@@ -771,7 +720,6 @@ __global__ __launch_bounds__(256) void refit_kernel(const float4* __restrict__ P
     //  read and the one dependent addition per term: 80 000 inliers 2.0 -> ~1 ms, the lanes were bound by instruction issue, not by the chain)
     constexpr int RCH2 = 1024;        // pairs per chunk of the second pass (nine products per pair in the same array)
     __shared__ float sp[RCH * 8];     // pass 1: [6 components][RCH]; pass 2: [9 products][RCH2]
-    __shared__ uint8_t sm[RCH];
     __shared__ float cen[6];
     __shared__ float Hs[9];
     __shared__ int sn;
@@ -785,23 +733,14 @@ __global__ __launch_bounds__(256) void refit_kernel(const float4* __restrict__ P
                 const float4 p = P0[i0 + i], q = P1[i0 + i];
                 sp[0 * RCH + i] = p.x; sp[1 * RCH + i] = p.y; sp[2 * RCH + i] = p.z;
                 sp[3 * RCH + i] = q.x; sp[4 * RCH + i] = q.y; sp[5 * RCH + i] = q.z;
-                sm[i] = mask ? mask[i0 + i] : (uint8_t) 1;
             }
             __syncthreads();
             if (l < 6) {
                 const int m = min(RCH, c - i0);
                 const float* col = sp + l * RCH;
-                if (!mask) {   // (every caller compacts first: no per-element branch, so the LDS reads run ahead of the dependent adds)
 #pragma unroll 16
-                    for (int i = 0; i < m; ++i) acc += col[i];
-                    n += m;
-                } else {
-                    for (int i = 0; i < m; ++i) {
-                        if (!sm[i]) continue;
-                        acc += col[i];
-                        ++n;
-                    }
-                }
+                for (int i = 0; i < m; ++i) acc += col[i];
+                n += m;
             }
         }
         if (l < 6) cen[l] = acc / (float) n;
@@ -821,21 +760,13 @@ __global__ __launch_bounds__(256) void refit_kernel(const float4* __restrict__ P
                 for (int a = 0; a < 3; ++a)
 #pragma unroll
                     for (int b = 0; b < 3; ++b) sp[(3 * a + b) * RCH2 + i] = da[a] * db[b];
-                sm[i] = mask ? mask[i0 + i] : (uint8_t) 1;
             }
             __syncthreads();
             if (l < 9) {
                 const int m = min(RCH2, c - i0);
                 const float* col = sp + l * RCH2;
-                if (!mask) {
 #pragma unroll 16
-                    for (int i = 0; i < m; ++i) acc += col[i];
-                } else {
-                    for (int i = 0; i < m; ++i) {
-                        if (!sm[i]) continue;
-                        acc += col[i];
-                    }
-                }
+                for (int i = 0; i < m; ++i) acc += col[i];
             }
         }
         if (l < 9) Hs[l] = acc;
@@ -874,22 +805,24 @@ _Pragma("unroll")
 }
 
 // ---------------------------------------------------------------------------------------------------- device-driven schedule
-// The whole loop of SampleConsensusPrerejectiveOMP::align (src/sac_prerejective_omp.cpp:156-257) without the host in it (round 4; the
-// closest-plane metrics keep the host-driven rounds).  The schedule's state -- iterations done, the adaptive bound, the record inlier set,
+// The whole loop of SampleConsensusPrerejectiveOMP::align (src/sac_prerejective_omp.cpp:156-257) without the host in it, for all five
+// metrics (round 4; the plane metrics since round 5).  The schedule's state -- iterations done, the adaptive bound, the record inlier set,
 // the best metric and transform -- lives in an RState on the device.  A ROUND (the first: one batch; then up to MAX_ROUND_BATCHES) is six
 // launches whose sizes are upper bounds and whose real extents are read from the RState:
-//   rs_begin    the round's iteration range, the candidate gate, counters and BatchStats cleared
+//   rs_begin    the round's iteration range, the candidate gate, counters cleared
 //   rs_hyp      sample -> prerejection -> 3-point transform; survivors appended to a list (one atomic per wave; ANY list order gives the
 //               same results: every later reduction carries the iteration number as its tie-break)
 //   count_list  the O(H x C) verification over (hypothesis block, chunk) items, a fixed grid striding over them
 //   rs_cand     hypotheses with enough inliers for the gate -> candidate list
 //   metric      the metric of every candidate, a fixed grid striding over them
-//   rs_replay   per-batch statistics, then ONE lane replays the round's batches in schedule order exactly as the host did: best hypothesis
+//   rs_replay   per-batch statistics, then ONE lane replays the round's batches in schedule order exactly as the reference's loop: best hypothesis
 //               (strict >, ties -> lowest iteration), record inlier set -> estimateMaxIterations (src/metric.cpp:103-123, in double) ->
 //               bound, batches behind the end of the loop discarded
-// and every kernel returns at once when the loop has ended.  The host enqueues two rounds and the final block (evaluation of the best
-// transform, refit over its inliers, evaluation of the refit: also sized on the device) blind and then reads ONE record; when the loop
-// has not ended by then (max_iterations far above two rounds and no record yet) it repeats.  The adaptive bound is evaluated with the
+// (the plane metrics add the plane evaluation and the rs_plane_* kernels below) and every kernel returns at once when the loop has ended.
+// The host enqueues two rounds and, for uniformity / correspondences, the final block (evaluation of the best transform, refit over its
+// inliers, evaluation of the refit: also sized on the device) blind and then reads ONE record; when the loop has not ended by then
+// (max_iterations far above two rounds and no record yet) it repeats.  The plane metrics' final block is the caller's (lgr_ransac_ex_dev):
+// its refit needs the plane pairs sorted by source index on the host.  The adaptive bound is evaluated with the
 // device's double-precision log / pow, the oracle with libm's: both are accurate to an ulp, the bound is the integer part of a quotient of
 // the two, so a difference needs a quotient within ~1e-15 of an integer.
 struct RState {
@@ -913,7 +846,7 @@ struct RState {
     unsigned long long busy_max[8], busy_sum[8];               // ... and the workgroups' own work per phase (without the barrier): maximum and sum over the workgroups
 };
 
-__device__ __noinline__ int est_from_support_dev(int count, int c, float confidence, int nr_samples) {   // = est_from_support below
+__device__ __noinline__ int est_from_support_dev(int count, int c, float confidence, int nr_samples) {   // src/metric.cpp:116-122 given the support count
     // (a real call: inlined, its double-precision log / pow bring ~100 registers of constants that the resident kernel's loop would carry)
     float frac = (float) count / (float) c;
     frac /= 4.f;
@@ -928,8 +861,7 @@ __device__ __noinline__ int rs_gate_dev(float final_metric, int metric_id, int c
     else if (final_metric > 0.f && metric_id == LGR_METRIC_CORRESPONDENCES) mi = max(mi, (int) floor((double) final_metric * (double) c / 1.001) - 1);
     return mi;
 }
-__device__ __forceinline__ void rs_begin_body(RState* S, BatchStats* st, int first_round) {
-    if (threadIdx.x < MAX_ROUND_BATCHES) { BatchStats z{}; st[threadIdx.x] = z; }
+__device__ __forceinline__ void rs_begin_body(RState* S, int first_round) {
     if (threadIdx.x != 0) return;
     S->n_ok = 0; S->n_cand = 0; S->round_nb = 0; S->round_batches = 0;
     if (S->stop) return;
@@ -948,7 +880,7 @@ __device__ __forceinline__ void rs_begin_body(RState* S, BatchStats* st, int fir
     S->round_first = S->done; S->round_nb = nb; S->round_batches = n_batches;
     S->rounds += 1;
 }
-__global__ void rs_begin_kernel(RState* __restrict__ S, BatchStats* __restrict__ st, int first_round) { rs_begin_body(S, st, first_round); }
+__global__ void rs_begin_kernel(RState* __restrict__ S, int first_round) { rs_begin_body(S, first_round); }
 
 // iteration `b` of the round (b - lane is wave-uniform; a wave wholly behind the round's end does nothing)
 // (round 5: the sampled pairs come from the packed correspondences -- P0[i].xyz / P1[i].xyz ARE the source / target point of correspondence i, 32
@@ -1039,7 +971,7 @@ __global__ __launch_bounds__(1024) void rs_cand_kernel(RState* __restrict__ S, c
 }
 
 __device__ __forceinline__ void rs_replay_body(const int tid, RState* S, const int* list, const int* list2, const float* metric, const int* ninl, const int2* counts,
-                                               const int* posmap, const float* Ts, BatchStats* st_out) {
+                                               const int* posmap, const float* Ts) {
     __shared__ unsigned long long best_key[MAX_ROUND_BATCHES], rec_key[MAX_ROUND_BATCHES];
     __shared__ int n_ok_b[MAX_ROUND_BATCHES];
     if (S->stop || S->round_nb == 0) return;
@@ -1063,7 +995,6 @@ __device__ __forceinline__ void rs_replay_body(const int tid, RState* S, const i
     for (int j = 0; j < S->round_batches && done < bound; ++j) {
         const int nbj = min(batch, max_it - done);
         num_rej += nbj - n_ok_b[j];
-        st_out[j].n_ok = n_ok_b[j]; st_out[j].best_key = best_key[j]; st_out[j].rec_key = rec_key[j];
         if (best_key[j]) {
             const float m = __uint_as_float((unsigned) (best_key[j] >> 32));
             const int off = (int) (0xffffffffu - (unsigned) (best_key[j] & 0xffffffffull));
@@ -1087,8 +1018,8 @@ __device__ __forceinline__ void rs_replay_body(const int tid, RState* S, const i
 }
 __global__ __launch_bounds__(1024) void rs_replay_kernel(RState* __restrict__ S, const int* __restrict__ list, const int* __restrict__ list2,
                                                           const float* __restrict__ metric, const int* __restrict__ ninl, const int2* __restrict__ counts,
-                                                          const int* __restrict__ posmap, const float* __restrict__ Ts, BatchStats* __restrict__ st_out) {
-    rs_replay_body(threadIdx.x, S, list, list2, metric, ninl, counts, posmap, Ts, st_out);
+                                                          const int* __restrict__ posmap, const float* __restrict__ Ts) {
+    rs_replay_body(threadIdx.x, S, list, list2, metric, ninl, counts, posmap, Ts);
 }
 
 // ---------------------------------------------------------------------------------------------------- the resident loop
@@ -1133,7 +1064,7 @@ __device__ __forceinline__ bool rs_grid_barrier(RState* S, const unsigned n_wg) 
 struct ResidentArgs {
     int c; int n_samples;
     unsigned long long seed; float edge_thr;
-    RState* S; BatchStats* st;
+    RState* S;
     float* Ts; int* list; int* posmap; int2* counts; int* list2; int* hpos; float* metric; int* ninl;
     unsigned* maskT; int mask_cap; float2* scratch;
     int metric_id, score_id, max_rounds;
@@ -1145,7 +1076,7 @@ __global__ __launch_bounds__(MB) void rs_resident_kernel(const ResidentArgs a, c
                                                          const float4* __restrict__ in_P1, const float* __restrict__ in_sstar) {
     const int wg = blockIdx.x, n_wg = gridDim.x, tid = threadIdx.x;
     RState* const S = a.S;
-    if (wg == 0) rs_begin_body(S, a.st, 1);
+    if (wg == 0) rs_begin_body(S, 1);
     unsigned long long t_prev = wall_clock64();
     auto stamp = [&](int phase) {   // (workgroup 0's view of where the loop's time goes: LGR_RANSAC_DEBUG prints it)
         if (wg == 0 && tid == 0) { const unsigned long long t = wall_clock64(); S->phase_ticks[phase] += t - t_prev; t_prev = t; }
@@ -1209,14 +1140,15 @@ __global__ __launch_bounds__(MB) void rs_resident_kernel(const ResidentArgs a, c
         stamp(4);
         if (wg == 0) {
             asm volatile("" : "+v"(tid_m));
-            rs_replay_body(tid_m, S, a.list, a.list2, a.metric, a.ninl, a.counts, a.posmap, a.Ts, a.st);
+            rs_replay_body(tid_m, S, a.list, a.list2, a.metric, a.ninl, a.counts, a.posmap, a.Ts);
             __syncthreads();
-            rs_begin_body(S, a.st, 0);   // the next round's range (or `stop`)
+            rs_begin_body(S, 0);   // the next round's range (or `stop`)
         }
     }
 }
-// closest-plane / combination metrics inside the device-driven schedule (round 5): run_batch's plumbing kernels with their extents read from the
-// RState (fixed grids striding over them)
+// closest-plane / combination metrics inside the device-driven schedule (round 5), extents read from the RState (fixed grids striding over
+// them): the plane test's inlier counts replace the correspondence counts (the estimator's `inliers` are the plane pairs,
+// src/metric.cpp:187-199); candidates pick up their plane metric; combination multiplies
 __global__ void rs_plane_counts_kernel(const RState* __restrict__ S, const int* __restrict__ cnt, int2* __restrict__ counts) {
     const int n = S->n_ok;
     for (int h = blockIdx.x * blockDim.x + threadIdx.x; h < n; h += gridDim.x * blockDim.x) counts[h].x = cnt[h];
@@ -1244,16 +1176,17 @@ int comb_or_max(int n, int k) {
     return result > mx ? mx : (int) result;
 }
 
-// src/metric.cpp:116-122 given the support count
-int est_from_support(int count, int c, float confidence, int nr_samples) {
-    float frac = (float) count / (float) c;
-    frac /= 4.f;
-    if (frac <= 0.0 || std::log(1.0 - std::pow(frac, nr_samples)) >= 0.0) return INT_MAX;
-    double iterations = std::log(1.0 - confidence) / std::log(1.0 - std::pow(frac, nr_samples));
-    return static_cast<int>(std::min((double) INT_MAX, iterations));
-}
-
 struct Packed { float4* P0; float4* P1; float* sstar; const CPair* PP; const unsigned* pstats; };
+
+// WS_RANSAC_MISC as every entry point of this file sees it (lgr_gror.hip keeps a list of its own in the slot during its own call).  One
+// size for all of them, so the slot is never re-allocated under a pointer taken earlier in the same call.
+struct RansacMisc {
+    RState S;          // the device-driven schedule's state; S.best_T and S.Tn are the best and the refit transform of an alignment, plane metrics included
+    float ev[8];       // evaluate_one_dev: [0..2] the evaluation in flight, [4..6] the guess's (rs_guess_kernel reads it)
+    float out[4];      // a small result the host reads back: evaluate_one's (metric, n_inl bits, rmse), lgr_selfcheck_philox's block
+    float T[16];       // a single transform the host uploaded (lgr_evaluate*_dev), lgr_refit_svd_dev's result
+};
+int ransac_misc(lgr_ctx* ctx, RansacMisc** out) { return lgr_ws_t(ctx, WS_RANSAC_MISC, 1, out); }
 
 __global__ void corr_range_kernel(const lgr_corr* __restrict__ corr, int c, int ns, int nt, int* __restrict__ bad) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1300,18 +1233,18 @@ int pack(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, c
     return LGR_OK;
 }
 
-// refit over the inliers flagged in d_mask (NULL: all pairs): compaction in correspondence order, then refit_kernel
+// refit over the inliers flagged in d_mask (NULL: all pairs): compaction in correspondence order, then refit_kernel; the number of inliers
+// stays on the device
 int refit_launch(lgr_ctx* ctx, const Packed& pk, int c, const uint8_t* d_mask, float* d_Tout) {
     if (!d_mask || c == 0) {
-        refit_kernel<<<1, 256, 0, ctx->stream>>>(pk.P0, pk.P1, nullptr, c, d_Tout);
+        refit_kernel<<<1, 256, 0, ctx->stream>>>(pk.P0, pk.P1, c, d_Tout);
         LGR_HIP(ctx, hipGetLastError());
         return LGR_OK;
     }
     int* flags;
     LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_HIST, (size_t) 2 * c + 16 + 8 * ((size_t) c + 4), &flags));
     int* pos = flags + c;
-    float4* Q0 = (float4*) (flags + 2 * (size_t) c + 16 - ((2 * (size_t) c) & 3));
-    Q0 = (float4*) (((uintptr_t) (flags + 2 * (size_t) c) + 15) & ~(uintptr_t) 15);
+    float4* Q0 = (float4*) (((uintptr_t) (flags + 2 * (size_t) c) + 15) & ~(uintptr_t) 15);
     float4* Q1 = Q0 + c;
     mask_flags_kernel<<<cdiv(c, 256), 256, 0, ctx->stream>>>(d_mask, c, flags);
     size_t tb = 0;
@@ -1320,13 +1253,7 @@ int refit_launch(lgr_ctx* ctx, const Packed& pk, int c, const uint8_t* d_mask, f
     LGR_TRY(lgr_ws(ctx, WS_GRID_TMP, tb, &tmp));
     LGR_HIP(ctx, rocprim::exclusive_scan(tmp, tb, flags, pos, 0, (size_t) c, rocprim::plus<int>(), ctx->stream));
     compact_pairs_kernel<<<cdiv(c, 256), 256, 0, ctx->stream>>>(pk.P0, pk.P1, flags, pos, c, Q0, Q1);
-    int* h;
-    LGR_TRY(lgr_pinned(ctx, 64, (void**) &h));
-    LGR_HIP(ctx, hipMemcpyAsync(h, pos + (c - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(h + 1, flags + (c - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int n = h[0] + h[1];
-    refit_kernel<<<1, 256, 0, ctx->stream>>>(Q0, Q1, nullptr, n, d_Tout);
+    refit_kernel<<<1, 256, 0, ctx->stream>>>(Q0, Q1, 0, d_Tout, pos + (c - 1), flags + (c - 1));
     LGR_HIP(ctx, hipGetLastError());
     return LGR_OK;
 }
@@ -1354,26 +1281,12 @@ int metric_launch(lgr_ctx* ctx, const float* Ts, const int* list2, int nh2, cons
 }
 
 struct EvalOut { int n_inl; float rmse; float metric; };
-// single transform (device pointer d_T to 16 floats): mask + stats
-int evaluate_one(lgr_ctx* ctx, const float* d_T, const Packed& pk, int c, int metric_id, int score_id, uint8_t* d_mask, EvalOut* out,
-                 bool want_rmse = true /* false: no ordered inlier list when the metric itself does not need one (rmse = 0) */) {
-    float* res;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 64, &res));
-    float* d_metric = res + 32; int* d_ninl = (int*) (res + 33); float* d_rmse = res + 34;
-    if (!want_rmse) LGR_HIP(ctx, hipMemsetAsync(d_rmse, 0, 4, ctx->stream));
-    if (metric_id == LGR_METRIC_UNIFORMITY && !want_rmse && c > 0) {
-        // the counting half on the whole device, the entropy half in one workgroup
-        int* ghist;
-        LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_GHIST, (size_t) 30000 + 64, &ghist));
-        LGR_HIP(ctx, hipMemsetAsync(ghist, 0, (30000 + 1) * 4, ctx->stream));
-        inlier_hist_kernel<<<cdiv(c, 256), 256, 0, ctx->stream>>>(d_T, pk.P0, pk.P1, pk.sstar, c, d_mask, ghist);
-        LGR_HIP(ctx, hipFuncSetAttribute((const void*) metric_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) metric_smem()));
-        metric_kernel<<<1, MB, metric_smem(), ctx->stream>>>(d_T, nullptr, 1, pk.P0, pk.P1, pk.sstar, c, metric_id, score_id, d_metric, d_ninl, nullptr, nullptr,
-                                                             nullptr, nullptr, nullptr, 0, ghist);
-        LGR_HIP(ctx, hipGetLastError());
-    } else {
-        LGR_TRY(metric_launch(ctx, d_T, nullptr, 1, pk, c, metric_id, score_id, d_metric, d_ninl, want_rmse ? d_rmse : nullptr, d_mask));
-    }
+// single transform (device pointer d_T to 16 floats): mask + stats, read back
+int evaluate_one(lgr_ctx* ctx, const float* d_T, const Packed& pk, int c, int metric_id, int score_id, uint8_t* d_mask, EvalOut* out) {
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    float* d_metric = M->out; int* d_ninl = (int*) (M->out + 1); float* d_rmse = M->out + 2;
+    LGR_TRY(metric_launch(ctx, d_T, nullptr, 1, pk, c, metric_id, score_id, d_metric, d_ninl, d_rmse, d_mask));
     float* h;
     LGR_TRY(lgr_pinned(ctx, 64, (void**) &h));
     LGR_HIP(ctx, hipMemcpyAsync(h, d_metric, 12, hipMemcpyDeviceToHost, ctx->stream));
@@ -1421,23 +1334,27 @@ int evaluate_one_plane(lgr_ctx* ctx, const float* d_T, const Packed& pk, int c, 
     return LGR_OK;
 }
 
-extern "C" int lgr_evaluate_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16], int score_id,
-                                      uint64_t seed, uint32_t counter, int* n_inliers, float* rmse, float* metric, float* threshold,
-                                      int32_t* pairs, int* n_pairs) {
+// one transform under the closest-plane metric, or (d_weights) the weighted one
+static int evaluate_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16], int score_id, uint64_t seed,
+                              uint32_t counter, int metric_id, const float* d_weights, float weights_sum, int* n_inliers, float* rmse, float* metric,
+                              float* threshold, int32_t* pairs, int* n_pairs) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_CHECK(ctx, d_src && d_tgt && T16 && n_inliers && rmse && metric && ns > 0 && nt > 1 && score_id >= 0 && score_id <= 3, LGR_ERR_INVALID_ARG);
+    const bool weighted = metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE;
+    LGR_CHECK(ctx, d_src && d_tgt && (d_weights || !weighted) && T16 && n_inliers && rmse && metric && ns > 0 && nt > 1 && score_id >= 0 && score_id <= 3,
+              LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     lgr_plane_dev plane;
     LGR_TRY(lgr_plane_setup(ctx, d_src, ns, d_tgt, nt, seed, &plane));
-    float* dT;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 64, &dT));
-    LGR_HIP(ctx, hipMemcpyAsync(dT, T16, 64, hipMemcpyHostToDevice, ctx->stream));
+    if (weighted) { plane.w = d_weights; plane.w_sum = weights_sum; plane.w_gate = 0.f; }   // (one transform: no gate)
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    LGR_HIP(ctx, hipMemcpyAsync(M->T, T16, 64, hipMemcpyHostToDevice, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     Packed none{nullptr, nullptr, nullptr};
     EvalOut e;
     std::vector<int2> pr;
-    LGR_TRY(evaluate_one_plane(ctx, dT, none, 0, LGR_METRIC_CLOSEST_PLANE, score_id, nullptr, plane, counter, &e, pairs ? &pr : nullptr));
+    LGR_TRY(evaluate_one_plane(ctx, M->T, none, 0, metric_id, score_id, nullptr, plane, counter, &e, pairs ? &pr : nullptr));
     *n_inliers = e.n_inl; *rmse = e.rmse; *metric = e.metric;
     if (threshold) *threshold = plane.thr;
     if (pairs) {
@@ -1446,32 +1363,17 @@ extern "C" int lgr_evaluate_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, 
     }
     return LGR_OK;
 }
-
+extern "C" int lgr_evaluate_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16], int score_id,
+                                      uint64_t seed, uint32_t counter, int* n_inliers, float* rmse, float* metric, float* threshold,
+                                      int32_t* pairs, int* n_pairs) {
+    return evaluate_plane_dev(ctx, d_src, ns, d_tgt, nt, T16, score_id, seed, counter, LGR_METRIC_CLOSEST_PLANE, nullptr, 0.f, n_inliers, rmse, metric,
+                              threshold, pairs, n_pairs);
+}
 extern "C" int lgr_evaluate_plane_weighted_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16], int score_id,
                                                uint64_t seed, uint32_t counter, const float* d_weights, float weights_sum, int* n_inliers, float* rmse,
                                                float* metric, float* threshold, int32_t* pairs, int* n_pairs) {
-    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
-    if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_CHECK(ctx, d_src && d_tgt && d_weights && T16 && n_inliers && rmse && metric && ns > 0 && nt > 1 && score_id >= 0 && score_id <= 3, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
-    lgr_plane_dev plane;
-    LGR_TRY(lgr_plane_setup(ctx, d_src, ns, d_tgt, nt, seed, &plane));
-    plane.w = d_weights; plane.w_sum = weights_sum; plane.w_gate = 0.f;   // (one transform: no gate)
-    float* dT;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 64, &dT));
-    LGR_HIP(ctx, hipMemcpyAsync(dT, T16, 64, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    Packed none{nullptr, nullptr, nullptr};
-    EvalOut e;
-    std::vector<int2> pr;
-    LGR_TRY(evaluate_one_plane(ctx, dT, none, 0, LGR_METRIC_WEIGHTED_CLOSEST_PLANE, score_id, nullptr, plane, counter, &e, pairs ? &pr : nullptr));
-    *n_inliers = e.n_inl; *rmse = e.rmse; *metric = e.metric;
-    if (threshold) *threshold = plane.thr;
-    if (pairs) {
-        for (size_t i = 0; i < pr.size(); ++i) { pairs[2 * i] = pr[i].x; pairs[2 * i + 1] = pr[i].y; }
-        if (n_pairs) *n_pairs = (int) pr.size();
-    }
-    return LGR_OK;
+    return evaluate_plane_dev(ctx, d_src, ns, d_tgt, nt, T16, score_id, seed, counter, LGR_METRIC_WEIGHTED_CLOSEST_PLANE, d_weights, weights_sum, n_inliers,
+                              rmse, metric, threshold, pairs, n_pairs);
 }
 
 extern "C" int lgr_ransac_samples_n_dev(lgr_ctx* ctx, uint64_t seed, int first, int n, int n_corr, int n_samples, int32_t* d_tuples) {
@@ -1500,8 +1402,9 @@ extern "C" int lgr_selfcheck_philox(lgr_ctx* ctx, uint64_t key, const uint32_t c
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, counter4 && out4, LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned* d;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 64, &d));
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    unsigned* d = reinterpret_cast<unsigned*>(M->out);
     philox_kernel<<<1, 1, 0, ctx->stream>>>(key, counter4[0], counter4[1], counter4[2], counter4[3], d);
     LGR_HIP(ctx, hipGetLastError());
     LGR_HIP(ctx, hipMemcpyAsync(out4, d, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -1519,98 +1422,29 @@ extern "C" int lgr_evaluate_dev(lgr_ctx* ctx, const float* d_src, int ns, const 
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     Packed pk;
     LGR_TRY(pack(ctx, d_src, ns, d_tgt, nt, d_corr, c, &pk));
-    float* dT;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 64, &dT));
-    LGR_HIP(ctx, hipMemcpyAsync(dT, T16, 64, hipMemcpyHostToDevice, ctx->stream));
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    LGR_HIP(ctx, hipMemcpyAsync(M->T, T16, 64, hipMemcpyHostToDevice, ctx->stream));
     EvalOut e;
-    LGR_TRY(evaluate_one(ctx, dT, pk, c, metric_id, score_id, d_mask, &e));
+    LGR_TRY(evaluate_one(ctx, M->T, pk, c, metric_id, score_id, d_mask, &e));
     if (n_inliers) *n_inliers = e.n_inl;
     if (rmse) *rmse = e.rmse;
     if (metric) *metric = e.metric;
     return LGR_OK;
 }
 
-// one batch: hypotheses -> ok-list -> counts -> candidate list -> metrics.  Returns device arrays + host counts.
+// The per-iteration arrays of a round of the device-driven schedule (and of lgr_ransac_replay_dev), nb iterations each.  `ok` (the
+// prerejection flags hypotheses_kernel writes and compact_kernel scans) is used by lgr_ransac_replay_dev alone; the schedule appends its
+// survivors to `list` itself and reuses `pos` as its posmap (iteration offset -> position in `list`).
 struct BatchBuffers {
-    float* Ts; int* ok; int* pos; int* list; int2* counts; int* flags2; int* pos2; int* list2; float* metric; int* ninl; int* hpos; BatchStats* st;
+    float* Ts; int* ok; int* pos; int* list; int2* counts; int* list2; float* metric; int* ninl; int* hpos;
 };
 static int batch_buffers(lgr_ctx* ctx, int nb, BatchBuffers* b) {
     LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_T, (size_t) nb * 16, &b->Ts));
     int* s;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_STATS, (size_t) nb * 13 + 64 + MAX_ROUND_BATCHES * (sizeof(BatchStats) / 4), &s));
+    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_STATS, (size_t) nb * 9 + 64, &s));
     b->ok = s; b->pos = s + nb; b->list = s + 2 * (size_t) nb; b->counts = (int2*) (s + 3 * (size_t) nb);
-    b->flags2 = s + 5 * (size_t) nb; b->pos2 = s + 6 * (size_t) nb; b->list2 = s + 7 * (size_t) nb;
-    b->metric = (float*) (s + 8 * (size_t) nb); b->ninl = s + 9 * (size_t) nb; b->hpos = s + 10 * (size_t) nb;
-    b->st = (BatchStats*) (s + 11 * (size_t) nb + ((11 * (size_t) nb) & 1));
-    return LGR_OK;
-}
-
-// runs one batch.  h_counts: [0] n_ok, [1] n_cand (hypotheses with >= MIN_NR_INLIERS inliers)
-static int run_batch(lgr_ctx* ctx, const float* d_src, const float* d_tgt, const lgr_corr* d_corr, int c, const Packed& pk,
-                     const lgr_params* p, uint64_t seed, int first, int nb, const int32_t* d_triples, BatchBuffers& b,
-                     int* n_ok, int* n_cand, const lgr_plane_dev* plane = nullptr, int min_inliers = MIN_NR_INLIERS,
-                     float best_prev = 0.f, int record_prev = 0) {
-    LGR_NS_DISPATCH(p->n_samples, (hypotheses_kernel<NS><<<cdiv(nb, 128), 128, 0, ctx->stream>>>(d_src, d_tgt, d_corr, c, seed, first, nb, d_triples,
-                                                                                                  p->edge_thr_coef, b.Ts, b.ok)));
-    size_t tb = 0;
-    LGR_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, b.ok, b.pos, 0, (size_t) nb, rocprim::plus<int>(), ctx->stream));
-    void* tmp;
-    LGR_TRY(lgr_ws(ctx, WS_GRID_TMP, tb, &tmp));
-    LGR_HIP(ctx, rocprim::exclusive_scan(tmp, tb, b.ok, b.pos, 0, (size_t) nb, rocprim::plus<int>(), ctx->stream));
-    compact_kernel<<<cdiv(nb, 256), 256, 0, ctx->stream>>>(b.ok, b.pos, nb, nullptr, b.list);
-    int* h;
-    LGR_TRY(lgr_pinned(ctx, 64, (void**) &h));
-    LGR_HIP(ctx, hipMemcpyAsync(h, b.pos + (nb - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(h + 1, b.ok + (nb - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int nh = h[0] + h[1];
-    *n_ok = nh; *n_cand = 0;
-    if (nh == 0) return LGR_OK;
-    LGR_HIP(ctx, hipMemsetAsync(b.counts, 0, (size_t) nh * 8, ctx->stream));
-    // few hypotheses (the first round, the lr filter): shorter correspondence chunks, so that the launch still has a few thousand waves
-    const int cch = count_chunk(nh, c);
-    dim3 g(cdiv(nh, CB), cdiv(c, cch));
-    // inlier bit masks for phase 2 (uniformity / correspondence-count metrics need the inlier set only); skipped when they
-    // would not fit 2 GB (then phase 2 tests every correspondence again)
-    unsigned* maskT = nullptr;
-    const size_t mask_words = mask_pitch(c) * nh;
-    if (!plane && p->metric_id == LGR_METRIC_UNIFORMITY && mask_words * 4 <= ((size_t) 2 << 30)) LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASKT, mask_words, &maskT));
-    count_kernel<<<g, CB, 0, ctx->stream>>>(b.Ts, b.list, nh, pk.PP, pk.pstats, c, b.counts, maskT, cch);
-    int* pl_cnt = nullptr;
-    float* pl_cp = nullptr;
-    if (plane) {
-        LGR_TRY(lgr_ws_t(ctx, WS_PLANE_OUT, (size_t) 2 * nb + 16, &pl_cnt));
-        pl_cp = (float*) (pl_cnt + nb);
-    }
-    const bool closest = plane && (p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE);
-    if (closest) {
-        // every hypothesis that passed the prerejection is evaluated on its sparse subset; its plane inliers are "the inliers"
-        // (gate: a hypothesis that can reach neither the best metric nor the record inlier count of the earlier batches is abandoned)
-        LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list, nh, (unsigned) first, p->score_id, pl_cnt, pl_cp, nullptr, nullptr, nullptr,
-                               best_prev, record_prev, nullptr));   // (record_prev == 0: no record yet, nothing is abandoned)
-        plane_counts_kernel<<<cdiv(nh, 256), 256, 0, ctx->stream>>>(pl_cnt, nh, b.counts);
-    }
-    flag_ge_kernel<<<cdiv(nh, 256), 256, 0, ctx->stream>>>(b.counts, nh, min_inliers, b.flags2);
-    LGR_HIP(ctx, rocprim::exclusive_scan(tmp, tb, b.flags2, b.pos2, 0, (size_t) nh, rocprim::plus<int>(), ctx->stream));
-    compact_kernel<<<cdiv(nh, 256), 256, 0, ctx->stream>>>(b.flags2, b.pos2, nh, b.list, b.list2);
-    if (maskT) compact_kernel<<<cdiv(nh, 256), 256, 0, ctx->stream>>>(b.flags2, b.pos2, nh, nullptr, b.hpos);   // candidate -> ok-list position
-    LGR_HIP(ctx, hipMemcpyAsync(h, b.pos2 + (nh - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(h + 1, b.flags2 + (nh - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int nh2 = h[0] + h[1];
-    *n_cand = nh2;
-    if (nh2 == 0) return LGR_OK;
-    if (closest) {
-        plane_pick_kernel<<<cdiv(nh, 256), 256, 0, ctx->stream>>>(b.flags2, b.pos2, nh, pl_cnt, pl_cp, b.metric, b.ninl);
-    } else if (plane) {   // combination: correspondences metric with the constant score (include/metric.h:191-192) x plane metric
-        LGR_TRY(metric_launch(ctx, b.Ts, b.list2, nh2, pk, c, LGR_METRIC_CORRESPONDENCES, LGR_SCORE_CONSTANT, b.metric, b.ninl, nullptr, nullptr));
-        LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list2, nh2, (unsigned) first, p->score_id, pl_cnt, pl_cp, nullptr, nullptr, nullptr,
-                               best_prev, 0x7fffffff, b.metric));   // (records are correspondence counts here: only the metric gates)
-        plane_mul_kernel<<<cdiv(nh2, 256), 256, 0, ctx->stream>>>(b.metric, pl_cp, nh2);
-    } else {
-        LGR_TRY(metric_launch(ctx, b.Ts, b.list2, nh2, pk, c, p->metric_id, p->score_id, b.metric, b.ninl, nullptr, nullptr, maskT, b.hpos, nh));
-    }
-    LGR_HIP(ctx, hipGetLastError());
+    b->list2 = s + 5 * (size_t) nb; b->metric = (float*) (s + 6 * (size_t) nb); b->ninl = s + 7 * (size_t) nb; b->hpos = s + 8 * (size_t) nb;
     return LGR_OK;
 }
 
@@ -1633,43 +1467,25 @@ static int evaluate_one_dev(lgr_ctx* ctx, const float* d_T, const Packed& pk, in
     LGR_HIP(ctx, hipGetLastError());
     return LGR_OK;
 }
-// refit over the inliers flagged in d_mask, the number of inliers staying on the device
-static int refit_launch_dev(lgr_ctx* ctx, const Packed& pk, int c, const uint8_t* d_mask, float* d_Tout) {
-    int* flags;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_HIST, (size_t) 2 * c + 16 + 8 * ((size_t) c + 4), &flags));
-    int* pos = flags + c;
-    float4* Q0 = (float4*) (((uintptr_t) (flags + 2 * (size_t) c) + 15) & ~(uintptr_t) 15);
-    float4* Q1 = Q0 + c;
-    mask_flags_kernel<<<cdiv(c, 256), 256, 0, ctx->stream>>>(d_mask, c, flags);
-    size_t tb = 0;
-    LGR_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, flags, pos, 0, (size_t) c, rocprim::plus<int>(), ctx->stream));
-    void* tmp;
-    LGR_TRY(lgr_ws(ctx, WS_GRID_TMP, tb, &tmp));
-    LGR_HIP(ctx, rocprim::exclusive_scan(tmp, tb, flags, pos, 0, (size_t) c, rocprim::plus<int>(), ctx->stream));
-    compact_pairs_kernel<<<cdiv(c, 256), 256, 0, ctx->stream>>>(pk.P0, pk.P1, flags, pos, c, Q0, Q1);
-    refit_kernel<<<1, 256, 0, ctx->stream>>>(Q0, Q1, nullptr, 0, d_Tout, pos + (c - 1), flags + (c - 1));
-    LGR_HIP(ctx, hipGetLastError());
-    return LGR_OK;
-}
 
-// The device-driven schedule (uniformity / correspondences metrics): see RState.  ONE host synchronisation per pair of rounds -- one per
-// alignment whenever the loop ends within two rounds, i.e. for every max_iterations up to 17 batches and whenever a record inlier set
-// brings the bound below that.
-// plane != nullptr (closest_plane / combination, round 5): the same rounds with the plane evaluation in them; the loop only -- the final block
-// (plane pairs sorted by source index for the refit) stays with the caller, which finds the loop's state in *state_out and the best transform
-// on the device at *d_best_out.  initial_metric: the guess's metric (the caller evaluated it), or 0.
+// The device-driven schedule: see RState.  ONE host synchronisation per pair of rounds -- one per alignment (uniformity / correspondences)
+// whenever the loop ends within two rounds, i.e. for every max_iterations up to 17 batches and whenever a record inlier set brings the
+// bound below that.
+// plane != nullptr (the plane metrics, round 5): the same rounds with the plane evaluation in them; the loop only -- the final block (plane
+// pairs sorted by source index for the refit) stays with the caller, which finds the loop's state in *state_out and the best transform on
+// the device in RansacMisc::S.best_T.  initial_metric: the guess's metric (the caller evaluated it), or 0.
 static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float* d_tgt, const lgr_corr* d_corr, int c, const Packed& pk, const lgr_params* p,
                                   uint64_t seed, int max_iterations, int batch, uint8_t* d_mask, lgr_result* res, const lgr_plane_dev* plane = nullptr,
-                                  float initial_metric = 0.f, RState* state_out = nullptr, float** d_best_out = nullptr) {
+                                  float initial_metric = 0.f, RState* state_out = nullptr) {
     LGR_HIP(ctx, hipFuncSetAttribute((const void*) metric_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) metric_smem()));
     const int nb_max = (int) std::min<long long>((long long) batch * MAX_ROUND_BATCHES, std::max(max_iterations, 1));
     BatchBuffers b;
     LGR_TRY(batch_buffers(ctx, nb_max, &b));
     int* posmap = b.pos;   // [nb_max]: iteration offset in the round -> position in the survivors' list
-    char* misc;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, sizeof(RState) + 256, &misc));
-    RState* dS = (RState*) misc;
-    float* d_ev = (float*) (misc + sizeof(RState));   // scratch of the single-transform evaluations
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    RState* dS = &M->S;
+    float* d_ev = M->ev;   // scratch of the single-transform evaluations
     RState* hS;
     LGR_TRY(lgr_pinned(ctx, sizeof(RState), (void**) &hS));
     memset(hS, 0, sizeof(RState));
@@ -1710,7 +1526,7 @@ static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float*
     const bool ransac_debug = getenv("LGR_RANSAC_DEBUG") != nullptr;
     auto enqueue_round = [&](bool first) -> int {
         const int nb_up = first ? std::min(batch, nb_max) : nb_max;
-        rs_begin_kernel<<<1, 64, 0, ctx->stream>>>(dS, b.st, first ? 1 : 0);
+        rs_begin_kernel<<<1, 64, 0, ctx->stream>>>(dS, first ? 1 : 0);
         LGR_NS_DISPATCH(p->n_samples, (rs_hyp_kernel<NS><<<cdiv(nb_up, 128), 128, 0, ctx->stream>>>(pk.P0, pk.P1, c, seed, dS, p->edge_thr_coef, b.Ts, b.list,
                                                                                                      posmap, b.counts)));
         count_list_kernel<<<g_count, CB, 0, ctx->stream>>>(b.Ts, b.list, &dS->n_ok, pk.PP, pk.pstats, c, b.counts, maskT, mask_cap);
@@ -1732,7 +1548,7 @@ static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float*
         } else
         metric_kernel<<<g_metric, MB, metric_smem(), ctx->stream>>>(b.Ts, b.list2, 0, pk.P0, pk.P1, pk.sstar, c, p->metric_id, p->score_id, b.metric, b.ninl,
                                                                     nullptr, nullptr, scratch, maskT, b.hpos, mask_cap, nullptr, &dS->n_cand, &dS->n_ok);
-        rs_replay_kernel<<<1, 1024, 0, ctx->stream>>>(dS, b.list, b.list2, b.metric, b.ninl, b.counts, posmap, b.Ts, b.st);
+        rs_replay_kernel<<<1, 1024, 0, ctx->stream>>>(dS, b.list, b.list2, b.metric, b.ninl, b.counts, posmap, b.Ts);
         LGR_HIP(ctx, hipGetLastError());
         return LGR_OK;
     };
@@ -1745,14 +1561,14 @@ static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float*
         LGR_CHECK(ctx, per_cu >= 1 && g_metric >= 1, LGR_ERR_HIP);   // (the grid must fit the device at once: one workgroup per CU)
         ResidentArgs ra{};
         ra.c = c; ra.n_samples = p->n_samples; ra.seed = seed; ra.edge_thr = p->edge_thr_coef;
-        ra.S = dS; ra.st = b.st; ra.Ts = b.Ts; ra.list = b.list; ra.posmap = posmap; ra.counts = b.counts; ra.list2 = b.list2; ra.hpos = b.hpos;
+        ra.S = dS; ra.Ts = b.Ts; ra.list = b.list; ra.posmap = posmap; ra.counts = b.counts; ra.list2 = b.list2; ra.hpos = b.hpos;
         ra.metric = b.metric; ra.ninl = b.ninl;
         ra.maskT = maskT; ra.mask_cap = mask_cap; ra.scratch = scratch; ra.metric_id = p->metric_id; ra.score_id = p->score_id;
         ra.max_rounds = (int) std::min<long long>(((long long) max_iterations + batch - 1) / batch + 2, INT_MAX);
         rs_resident_kernel<<<g_metric, MB, metric_smem(), ctx->stream>>>(ra, d_src, d_tgt, d_corr, pk.PP, pk.pstats, pk.P0, pk.P1, pk.sstar);
         LGR_HIP(ctx, hipGetLastError());
         LGR_TRY(evaluate_one_dev(ctx, dS->best_T, pk, c, p->metric_id, p->score_id, d_mask, d_ev, &dS->e_metric));
-        LGR_TRY(refit_launch_dev(ctx, pk, c, d_mask, dS->Tn));
+        LGR_TRY(refit_launch(ctx, pk, c, d_mask, dS->Tn));
         LGR_TRY(evaluate_one_dev(ctx, dS->Tn, pk, c, p->metric_id, p->score_id, d_mask, d_ev, &dS->e2_metric));
         LGR_HIP(ctx, hipMemcpyAsync(hS, dS, sizeof(RState), hipMemcpyDeviceToHost, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1777,7 +1593,7 @@ static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float*
         if (!plane) {
             // :265-296 final re-estimation (enqueued blind: redone when the loop turns out not to have ended)
             LGR_TRY(evaluate_one_dev(ctx, dS->best_T, pk, c, p->metric_id, p->score_id, d_mask, d_ev, &dS->e_metric));
-            LGR_TRY(refit_launch_dev(ctx, pk, c, d_mask, dS->Tn));
+            LGR_TRY(refit_launch(ctx, pk, c, d_mask, dS->Tn));
             LGR_TRY(evaluate_one_dev(ctx, dS->Tn, pk, c, p->metric_id, p->score_id, d_mask, d_ev, &dS->e2_metric));
         }
         LGR_HIP(ctx, hipMemcpyAsync(hS, dS, sizeof(RState), hipMemcpyDeviceToHost, ctx->stream));
@@ -1788,7 +1604,6 @@ static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float*
     }
     if (plane) {   // the caller's final block takes over
         *state_out = *hS;
-        *d_best_out = dS->best_T;
         return LGR_OK;
     }
     int e_ninl, e2_ninl;
@@ -1901,21 +1716,8 @@ extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const
     LGR_TRY(pack(ctx, d_src, ns, d_tgt, nt, d_corr, c, &pk));
     int max_iterations = std::min(comb_or_max(c, p->n_samples), p->max_iterations);
     int batch = std::max(1, p->ransac_batch);
-    int bound = max_iterations, done = 0, largest = 0, num_rejections = 0, best_iter = -1;
-    (void) largest;
-    float final_metric = 0.f;
-    float* d_best;   // device copy of the best transform so far
-    static_assert(sizeof(RState) + 256 <= 256 * sizeof(float), "the device schedule's state fits the slot as requested here (no re-allocation under d_best)");
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 256, &d_best));
-    {
-        float I[16];
-        for (int i = 0; i < 16; ++i) I[i] = (i % 5 == 0) ? 1.f : 0.f;
-        LGR_HIP(ctx, hipMemcpyAsync(d_best, I, 64, hipMemcpyHostToDevice, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    const bool plane_metric = p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_COMBINATION || weighted;
     const bool closest = p->metric_id == LGR_METRIC_CLOSEST_PLANE || weighted;   // (the plane pairs feed the refit)
-    if (!plane_metric) {
+    if (!closest && p->metric_id != LGR_METRIC_COMBINATION) {
         // the loop, the final evaluation and the refit driven from the device: one host synchronisation (ransac_device_schedule)
         uint8_t* d_mask = d_final_mask;
         if (!d_mask) LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASK, (size_t) c + 16, &d_mask));
@@ -1923,6 +1725,11 @@ extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const
         res->time_te = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         return LGR_OK;
     }
+    // the plane metrics: the guess's evaluation, the loop on the device-driven schedule, then a host-driven final block
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    float* const d_best = M->S.best_T;   // where the schedule keeps the best transform so far
+    float* const d_Tn = M->S.Tn;
     lgr_plane_dev plane;
     LGR_TRY(lgr_plane_setup(ctx, d_src, ns, d_tgt, nt, seed, &plane));
     if (weighted) {
@@ -1933,43 +1740,31 @@ extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const
             fprintf(stderr, "[lgr] weights: %.3f ms, sum %.9g, gate %.9g\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_w).count(),
                     (double) plane.w_sum, (double) plane.w_gate);
     }
+    float guess_metric = 0.f;
     if (p->has_guess) {
         // src/sac_prerejective_omp.cpp:134-147: the guess is the hypothesis to beat (final_tn / final_metric).  Its inliers only seed
         // the global largest_inlier_set, which the loop never reads (thread-local sets start empty, :177): the bound is unaffected.
+        // (the schedule starts from the same transform: it uploads its RState with best_T = the guess)
         LGR_HIP(ctx, hipMemcpyAsync(d_best, p->guess, 64, hipMemcpyHostToDevice, ctx->stream));
         uint8_t* d_gm;
         LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASK, (size_t) c + 16, &d_gm));
         EvalOut eg;
-        if (plane_metric) LGR_TRY(evaluate_one_plane(ctx, d_best, pk, c, p->metric_id, p->score_id, d_gm, plane, 0xFFFFFFFDu, &eg, nullptr));
-        else LGR_TRY(evaluate_one(ctx, d_best, pk, c, p->metric_id, p->score_id, d_gm, &eg, false));
-        final_metric = eg.metric;
+        LGR_TRY(evaluate_one_plane(ctx, d_best, pk, c, p->metric_id, p->score_id, d_gm, plane, 0xFFFFFFFDu, &eg, nullptr));
+        guess_metric = eg.metric;
     }
-    // The loop itself runs on the device-driven schedule (round 5; rounds 3-4 drove the plane metrics' batches from the host, one batch and three
-    // synchronisations at a time): a round evaluates up to MAX_ROUND_BATCHES batches -- the sparse subset of a hypothesis is keyed by its ITERATION
-    // (Philox counter = round_first + offset), so it does not matter which round or batch evaluates it; the gate uses the loop's state at the
-    // start of the round (a looser gate than batch by batch: it still only abandons what can be neither the best nor a record).
-    {
-        RState hs_end;
-        float* d_best_loop = nullptr;
-        LGR_TRY(ransac_device_schedule(ctx, d_src, d_tgt, d_corr, c, pk, p, seed, max_iterations, batch, nullptr, res, &plane, final_metric, &hs_end, &d_best_loop));
-        done = hs_end.done; bound = hs_end.bound; largest = hs_end.largest; num_rejections = hs_end.num_rejections; best_iter = hs_end.best_iter;
-        final_metric = hs_end.final_metric;
-        // (the schedule's RState shares WS_RANSAC_MISC with d_best: the best transform moves to the front, where the final block expects it)
-        LGR_HIP(ctx, hipMemcpyAsync(d_best, d_best_loop, 64, hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    // A round evaluates up to MAX_ROUND_BATCHES batches -- the sparse subset of a hypothesis is keyed by its ITERATION (Philox counter =
+    // round_first + offset), so it does not matter which round or batch evaluates it; the gate uses the loop's state at the start of the
+    // round (a looser gate than batch by batch: it still only abandons what can be neither the best nor a record).
+    RState loop;
+    LGR_TRY(ransac_device_schedule(ctx, d_src, d_tgt, d_corr, c, pk, p, seed, max_iterations, batch, nullptr, res, &plane, guess_metric, &loop));
     // :265-296 final re-estimation
     uint8_t* d_mask = d_final_mask;
     if (!d_mask) LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASK, (size_t) c + 16, &d_mask));
     EvalOut e;
     std::vector<int2> plane_pairs;
-    if (plane_metric)
-        LGR_TRY(evaluate_one_plane(ctx, d_best, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFEu, &e,
-                                   closest ? &plane_pairs : nullptr));
-    else LGR_TRY(evaluate_one(ctx, d_best, pk, c, p->metric_id, p->score_id, d_mask, &e, false));   // the final block uses inliers and metric only
-    bool enough = e.n_inl > MIN_NR_FINAL_INLIERS || (float) e.n_inl > MIN_INLIER_RATE * (float) c;
-    float min_tol = p->metric_id == LGR_METRIC_UNIFORMITY ? 0.3f : 0.0f;   // include/metric.h:97-99 / 73-75 / 124-126 / 198-200
-    bool converged = enough && e.metric > min_tol;
-    float* d_Tn = d_best + 16;
+    LGR_TRY(evaluate_one_plane(ctx, d_best, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFEu, &e, closest ? &plane_pairs : nullptr));
+    const bool enough = e.n_inl > MIN_NR_FINAL_INLIERS || (float) e.n_inl > MIN_INLIER_RATE * (float) c;
+    const bool converged = enough && e.metric > 0.0f;   // min tolerable metric of the plane estimators: include/metric.h:124-126 / 198-200
     if (closest) {
         // estimateOptimalRigidTransformation over the plane pairs (source point, nearest target point), ascending source index
         const int np = (int) plane_pairs.size();
@@ -1988,21 +1783,20 @@ extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const
         LGR_TRY(refit_launch(ctx, pk, c, d_mask, d_Tn));
     }
     EvalOut e2;
-    if (plane_metric) LGR_TRY(evaluate_one_plane(ctx, d_Tn, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFFu, &e2, nullptr));
-    else LGR_TRY(evaluate_one(ctx, d_Tn, pk, c, p->metric_id, p->score_id, d_mask, &e2, false));
+    LGR_TRY(evaluate_one_plane(ctx, d_Tn, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFFu, &e2, nullptr));
     float* hT;
     LGR_TRY(lgr_pinned(ctx, 64, (void**) &hT));
     LGR_HIP(ctx, hipMemcpyAsync(hT, d_Tn, 64, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(res->transformation, hT, 64);
-    res->iterations = done;
+    res->iterations = loop.done;
     res->converged = converged ? 1 : 0;
     res->n_inliers = e2.n_inl;
     res->metric = e2.metric;
-    res->best_metric_before_refit = final_metric;
-    res->best_iteration = best_iter;
-    res->num_rejections = num_rejections;
-    res->estimated_iters = bound;
+    res->best_metric_before_refit = loop.final_metric;
+    res->best_iteration = loop.best_iter;
+    res->num_rejections = loop.num_rejections;
+    res->estimated_iters = loop.bound;
     res->time_te = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     return LGR_OK;
 }
@@ -2053,8 +1847,9 @@ extern "C" int lgr_refit_svd_dev(lgr_ctx* ctx, const float* d_src, const float* 
     LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_PACK, (size_t) c * 2 + (size_t) (c + 3) / 4 + 4, &P));
     Packed pk{P, P + c, (float*) (P + 2 * (size_t) c), nullptr, nullptr};
     if (c > 0) pack_kernel<<<cdiv(c, 256), 256, 0, ctx->stream>>>(d_src, d_tgt, d_corr, c, nullptr, pk.P0, pk.P1, pk.sstar, nullptr, nullptr, c);
-    float* dT;
-    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MISC, 64, &dT));
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    float* dT = M->T;
     LGR_TRY(refit_launch(ctx, pk, c, d_mask, dT));
     float* hT;
     LGR_TRY(lgr_pinned(ctx, 64, (void**) &hT));

@@ -361,7 +361,7 @@ def resources(co):
 # here.  SGPR spills (v_writelane into a spare VGPR, no memory) are listed, not gated.  The fused match_mfma variants are NOT in the list:
 # at their 128-VGPR launch bound hipcc parks three or four per-work-item values in scratch outside the K loop.
 GATED = ["normals_kernel", "normals_wave_kernel", "refit_kernel", "hypotheses_kernel", "gror_umeyama_kernel", "spfh_tile_kernel", "fpfh_mfma_kernel",
-         "count_kernel", "count_list_kernel", "match_sweep", "match_tiles", "rs_hyp_kernel", "rs_store_eval_kernel", "rops_kernel",
+         "count_list_kernel", "match_sweep", "match_tiles", "rs_hyp_kernel", "rs_store_eval_kernel", "rops_kernel",
          "pc_kernel", "seq_sum_kernel", "weights_map_kernel", "nss_hist_kernel", "plane_kernel"]
 
 
