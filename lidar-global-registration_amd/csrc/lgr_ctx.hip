@@ -35,7 +35,7 @@ lgr_turn::~lgr_turn() {
     c->turn_depth--;
     if (!held) return;
     DevTurn& t = g_turn[c->device];
-    // (helper streams have been drained or joined into c->stream by the time a public entry point returns: lgr_aux_job, join_b)
+    // (helper streams have been drained or joined into c->stream by the time a public entry point returns: lgr_aux_job, the matcher's Fork::join)
     (void) hipSetDevice(c->device);
     if (!t.done && hipEventCreateWithFlags(&t.done, hipEventDisableTiming) != hipSuccess) t.done = nullptr;
     t.recorded = t.done && hipEventRecord(t.done, c->stream) == hipSuccess;

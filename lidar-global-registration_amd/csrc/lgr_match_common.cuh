@@ -49,7 +49,7 @@ constexpr int NEAR_T = LGR_NEAR_T;          // pass 0 visits the NEAR_T nearest 
 #ifndef LGR_PRUNE_BETAS
 #define LGR_PRUNE_BETAS 1.0f   // ONE final pass.  Intermediate thresholds (0.5f, 1.0f / 0.7f, 1.0f: a sweeping pass between pass 0 and the final one) were measured
                                // again in round 4 with the sweep kernel: 26.6-27.4 ms per pair against 25.4 at pass-0 widths 24-40 (a pass boundary costs 1.2 ms).  More than one
-                               // entry is NOT supported any more: the repair of an overflowing tile list (match_impl) covers the last pass only (static_assert there).
+                               // entry is NOT supported any more: the repair of an overflowing tile list (MatchCall::read_back_stats) covers the last pass only (static_assert there).
 #endif
 #ifndef LGR_GROUP_COLS
 #define LGR_GROUP_COLS 1024
@@ -74,7 +74,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 //          steps 4-5: A45 = h2(-2 x') | 0, a2     x  B01 (again)              a2.b1 + the rows' second norm term
 //      (norms as two-term expansions against one constant c0, pack16_kernel): 2/3 of the operand bytes of six stored fragments.
 //      Used only when the dropped coordinates are (numerically) constant over both sets; their largest measured energy
-//      enters the error bound, so any input stays exact (match_impl, "rot").
+//      enters the error bound, so any input stays exact (operand_scale, "rot").
 // KS = MFMA steps of a tile, NF = fragments stored per 32-row tile and side; step kk multiplies A fragment fa(kk) by B fragment fb(kk).
 enum { FMT_F32 = 0, FMT_F16 = 1, FMT_F16R = 2 };
 template <int FMT> struct OpFmt;

@@ -47,7 +47,7 @@ __global__ void pack_kernel(const float* __restrict__ X, const int* __restrict__
 // (N = A1 B1 + A2 B2 + A3 B3 up to 2^-33 N or the f16 flush limit).
 // Rotated format (NF = 4 stored fragments, KS = 6 steps: OpFmt<FMT_F16R>): stored K index c of a row / column:
 // [0,30) h1, 30..31 norm slots, [32,62) h2, 62..63 norm slots; a norm is the two-term expansion N ~ c0 (n1 + n2) against
-// the one constant c0 = a_norm[0] (error bound: match_impl, "rot").
+// the one constant c0 = a_norm[0] (error bound: operand_scale, "rot").
 // rows: h = split(-2 x' 2^s);  cols: h = split(x' 2^s).
 // Helmert coordinates of one 11-bin block: y_k = (x_0 + .. + x_{k-1} - k x_k) / sqrt(k (k + 1)), k = 1..10 (orthonormal, all
 // orthogonal to (1,..,1)); *u = (x_0 + .. + x_10) / sqrt(11) is the dropped coordinate.

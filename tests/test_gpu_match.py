@@ -95,6 +95,8 @@ def run_both(lgr, oracle, a, b, block):
     i1, d1 = lgr.match_bf(ta, tb, block)
     lgr.sync()
     np.testing.assert_array_equal(i1.cpu().numpy(), oi)
+    ok = oi >= 0
+    np.testing.assert_array_equal(d1.cpu().numpy()[ok].view(np.uint32), od[ok].view(np.uint32))
     return oi, ri
 
 
