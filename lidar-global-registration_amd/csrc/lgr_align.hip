@@ -7,7 +7,6 @@
 
 #include <chrono>
 #include <cmath>
-#include <thread>
 
 #include <climits>
 
@@ -162,51 +161,158 @@ static int filter_core(lgr_ctx* ctx, int matching_id, int ns, const int32_t* d_i
 
 static void tick(lgr_ctx* ctx, int i) { (void) hipEventRecord(ctx->ev[i], ctx->stream); }
 
-// the descriptor of the correspondence search (lgr_feature_params): its row length and its feature stage
-static int desc_len(int descriptor) { return descriptor == LGR_DESCRIPTOR_SHOT ? 352 : (descriptor == LGR_DESCRIPTOR_ROPS ? 135 : 33); }
-static int descriptor_dev(lgr_ctx* ctx, int descriptor, const float* kps, int m, const float* surf, int n, float radius, float* out,
-                          const lgr_params* p, const float* vp) {
-    if (descriptor == LGR_DESCRIPTOR_SHOT) return lgr_shot_dev(ctx, kps, m, surf, n, radius, nullptr, out, nullptr);
-    if (descriptor == LGR_DESCRIPTOR_ROPS) {
-        if (m == 0) return LGR_OK;
-        // include/matching.h:243-246 (reestimate_frames, true by default: lgr_params has no field for it): the key-point copy's normals
-        // are re-estimated on the level's surface, estimateNormalsPoints(normal_nr_points, kps, surface, viewpoint, true).  FPFH and SHOT
-        // never read them; the gravity frames do (z = the key point's normal).
-        float* kn;
-        LGR_TRY(lgr_ws_t(ctx, WS_ROPS_KPS, (size_t) m * 12, &kn));
-        LGR_HIP(ctx, hipMemcpyAsync(kn, kps, (size_t) m * 48, hipMemcpyDeviceToDevice, ctx->stream));
-        LGR_TRY(lgr_normals_knn_dev(ctx, kn, m, surf, n, p->normal_nr_points, vp, 1));
-        // estimateFeatures<RoPS135> estimates its frames on every call, so per scale level too (only gravity frames are built)
-        return lgr_rops_gravity_dev(ctx, kn, m, surf, n, radius, out);
-    }
-    return lgr_fpfh_dev(ctx, kps, m, surf, n, radius, out);
-}
-
-// ---- multi-scale matching (feature_radius unset): include/matching.h:176-262 (initialize) and :264-352
-// (match_multiscale).  The heavy stages (5-NN, down-sampling chain, normals, FPFH, brute-force matching per level) run on
-// the device; the per-key-point level assignment (log2f/sqrtf of the reference's host arithmetic, level pruning) and
-// the proximity vote over the <= nr_scales matches of a key point run on the host between them.
-struct MsSide {
-    int n_kps = 0;
-    float iss_radius = 0.f;
-    int min_l2 = INT_MAX, max_l2 = INT_MIN;
-    std::vector<std::vector<int>> lists;   // per scale: key-point indices
-    std::vector<size_t> feat_off;          // per scale: row offset into the feature buffer
-    float* feat = nullptr;                 // device, sum(rows) x D (D = 33 FPFH, 352 SHOT, 135 RoPS)
-    int32_t* d_lists = nullptr;            // device copy of the lists, concatenated like feat_off
-    std::vector<float> xyz;                // host copy of the key points (3 floats each) for the vote
-};
-
+// rows of 12 floats picked by index: the key-point cloud pcd[kps_indices] (pcl::copyPointCloud, include/matching.h:167) and the
+// per-level key-point sub-clouds of the multi-scale path
 __global__ void gather_rows12_kernel(const float* __restrict__ pts, const int32_t* __restrict__ idx, int m, float* __restrict__ out) {
     size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (size_t) m * 12) return;
     out[e] = pts[(size_t) idx[e / 12] * 12 + e % 12];
 }
+static void gather_rows12(lgr_ctx* ctx, const float* pts, const int32_t* idx, int m, float* out) {
+    gather_rows12_kernel<<<cdiv((long long) m * 12, 256), 256, 0, ctx->stream>>>(pts, idx, m, out);
+}
+// finalize (include/matching.h:150-160): local key-point indices -> indices of the clouds
+__global__ void finalize_kernel(lgr_corr* __restrict__ corr, int n, const int32_t* __restrict__ ks, const int32_t* __restrict__ kt) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    corr[i].index_query = ks[corr[i].index_query];
+    corr[i].index_match = kt[corr[i].index_match];
+}
 
-static int ms_initialize(lgr_ctx* ctx, MsSide& st, int side, const float* d_pcd, int n, const float* d_kps, int n_kps, float iss_radius,
-                         const lgr_params* p, int descriptor, const float* vp, float* ms) {
-    const int D = desc_len(descriptor);
-    st.n_kps = n_kps; st.iss_radius = iss_radius;
+// ---- the descriptors of the correspondence search (lgr_feature_params), one table entry each
+typedef int (*FeatureStage)(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, float* out, const lgr_params* p, const float* vp);
+struct Descriptor {
+    int len;              // floats per row
+    FeatureStage stage;   // rows of m > 0 key points on a level's surface
+    bool dense;           // matched by lgr_match_dense (brute force only); FPFH has the guess / FLANN / brute-force dispatch and lgr_match_prepare
+    int lrf;              // the one lrf_id that is built (FPFH never reads lrf_id, include/common.h:366,407)
+};
+static int fpfh_stage(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, float* out, const lgr_params*, const float*) { return lgr_fpfh_dev(ctx, kps, m, surf, n, radius, out); }
+static int shot_stage(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, float* out, const lgr_params*, const float*) { return lgr_shot_dev(ctx, kps, m, surf, n, radius, nullptr, out, nullptr); }
+static int rops_stage(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, float* out, const lgr_params* p, const float* vp) {
+    // include/matching.h:243-246 (reestimate_frames, true by default: lgr_params has no field for it): the key-point copy's normals
+    // are re-estimated on the level's surface, estimateNormalsPoints(normal_nr_points, kps, surface, viewpoint, true).  FPFH and SHOT
+    // never read them (so their stages skip the step); the gravity frames do (z = the key point's normal).
+    float* kn;
+    LGR_TRY(lgr_ws_t(ctx, WS_ROPS_KPS, (size_t) m * 12, &kn));
+    LGR_HIP(ctx, hipMemcpyAsync(kn, kps, (size_t) m * 48, hipMemcpyDeviceToDevice, ctx->stream));
+    LGR_TRY(lgr_normals_knn_dev(ctx, kn, m, surf, n, p->normal_nr_points, vp, 1));
+    // estimateFeatures<RoPS135> estimates its frames on every call, so per scale level too
+    return lgr_rops_gravity_dev(ctx, kn, m, surf, n, radius, out);
+}
+static const Descriptor DESCRIPTORS[] = {
+    /* LGR_DESCRIPTOR_FPFH */ {33, fpfh_stage, false, LGR_LRF_DEFAULT},
+    // the reference's other SHOT frames (gravity, gt) replace getLocalRF and are not built
+    /* LGR_DESCRIPTOR_SHOT */ {352, shot_stage, true, LGR_LRF_DEFAULT},
+    // default: estimateFeatures<RoPS135> triangulates the cloud (GreedyProjectionTriangulation) and takes RoPS's own frames;
+    // gt: the reference reads parameters.ground_truth, for which lgr_feature_params has no channel
+    /* LGR_DESCRIPTOR_ROPS */ {135, rops_stage, true, LGR_LRF_GRAVITY},
+};
+static_assert(LGR_DESCRIPTOR_FPFH == 0 && LGR_DESCRIPTOR_SHOT == 1 && LGR_DESCRIPTOR_ROPS == 2, "DESCRIPTORS is indexed by descriptor_id");
+
+extern "C" void lgr_default_feature_params(lgr_feature_params* f) {
+    if (!f) return;
+    memset(f, 0, sizeof(*f));
+    f->descriptor_id = LGR_DESCRIPTOR_FPFH;
+    f->lrf_id = LGR_LRF_DEFAULT;
+}
+
+// the descriptor a feature-parameter struct selects, checked against the rest of the configuration (NULL: FPFH)
+static int feature_descriptor(lgr_ctx* ctx, const lgr_params* p, const lgr_feature_params* f, const Descriptor** out) {
+    *out = &DESCRIPTORS[LGR_DESCRIPTOR_FPFH];
+    if (!f) return LGR_OK;
+    LGR_CHECK(ctx, f->descriptor_id >= 0 && f->descriptor_id < (int) (sizeof DESCRIPTORS / sizeof *DESCRIPTORS), LGR_ERR_UNSUPPORTED);
+    const Descriptor& d = DESCRIPTORS[f->descriptor_id];
+    if (d.dense) {
+        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT || f->lrf_id == LGR_LRF_GRAVITY || f->lrf_id == LGR_LRF_GT, LGR_ERR_INVALID_ARG);
+        LGR_CHECK(ctx, f->lrf_id == d.lrf, LGR_ERR_UNSUPPORTED);
+        LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);     // matchFLANN / matchLocal are built for FPFH only
+        LGR_CHECK(ctx, ctx->opt.arithmetic != LGR_ARITH_PCL, LGR_ERR_UNSUPPORTED);  // the arithmetic modes are FPFH weightings
+    }
+    *out = &d;
+    return LGR_OK;
+}
+
+// ---- One correspondence search (lgr_correspondences_ex_dev, at the end of this section, is the list of its stages): what the stages
+// share.  Streams: the filter tables run on aux2 (start_tables), posted before the feature stages; the source cloud's features run on
+// the caller's context with lgr_match_prepare right behind them, the target cloud's on aux (lgr_run_pair); finish joins aux2.
+struct CorrCall {
+    lgr_ctx* ctx;
+    const lgr_params* p;
+    const Descriptor* d = nullptr;
+    const float *clouds[2], *kclouds[2];     // the clouds; the key-point clouds (the clouds themselves, or the ISS detections
+    int sizes[2], ksizes[2];                 // with their index lists)
+    int32_t* kidx[2] = {nullptr, nullptr};
+    lgr_corr* d_out;
+    int* n_out;
+    bool empty = false;                      // a cloud without two points: nothing to match
+    float *feat[2], *surf[2], *dij, *dji;    // workspace: rows and down-sampled surfaces per cloud, the matches of both directions
+    int32_t *ij, *ji;
+    FilterTables ftab;
+    float ms[3] = {0, 0, 0};
+    // lgr_aux_job keeps a REFERENCE to its callable, so `tables` has to outlive the posted job: it is declared in front of the guard
+    // that waits for the job, members are destroyed in reverse order, and so every exit of the entry point waits first.  The
+    // prepare-cancel guard comes last: it runs first, as it did when all three were locals of one function.
+    struct Tables {
+        CorrCall* c;
+        int operator()(lgr_ctx* cx) const {
+            LGR_TRY(filter_cloud_tables(cx, c->kclouds[0], c->ksizes[0], c->p->cluster_k, c->ftab.thr_s, c->ftab.knn_s));
+            return filter_cloud_tables(cx, c->kclouds[1], c->ksizes[1], c->p->cluster_k, c->ftab.thr_t, c->ftab.knn_t);
+        }
+    } tables{this};
+    lgr_helper_guard tables_guard;   // every exit path waits for the helper (which always drains its stream)
+    struct PrepGuard { lgr_ctx* c; ~PrepGuard() { lgr_match_prepare_cancel(c); } } prep_guard;
+
+    CorrCall(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, lgr_corr* d_out, int* n_out)
+        : ctx(ctx), p(p), clouds{d_src, d_tgt}, kclouds{d_src, d_tgt}, sizes{ns, nt}, ksizes{ns, nt}, d_out(d_out), n_out(n_out), prep_guard{ctx} {}
+    CorrCall(const CorrCall&) = delete;
+    const float* vp(int side) const { return side == 0 ? (p->has_vp_src ? p->vp_src : nullptr) : (p->has_vp_tgt ? p->vp_tgt : nullptr); }
+    float iss_radius(int side) const { return side == 0 ? p->iss_radius_src : p->iss_radius_tgt; }
+    bool both_dirs() const { return p->matching_id != LGR_MATCH_ONE_SIDED; }
+};
+
+// One level of one cloud (include/matching.h:234-248; the single-scale search has one level): down-sample `in` into `surf`, normals,
+// descriptors of m key points -- kps[d_list[0..m)] gathered into `sub`, or kps[0..m) when d_list is NULL -- into `out`.  The three
+// stage times are added to ms; *nd is the down-sampled size.
+static int level_features(lgr_ctx* cx, const CorrCall& c, int side, const float* in, int n_in, float voxel, float radius, float* surf,
+                          const float* kps, int m, const int32_t* d_list, float* sub, float* out, float* ms, int* nd) {
+    const lgr_params* p = c.p;
+    tick(cx, 0);
+    LGR_TRY(lgr_downsample_dev(cx, in, n_in, voxel, surf, nd));
+    tick(cx, 1);
+    LGR_TRY(lgr_normals_knn_dev(cx, surf, *nd, nullptr, 0, p->normal_nr_points, c.vp(side), p->normals_available));
+    tick(cx, 2);
+    if (m) {
+        if (d_list) { gather_rows12(cx, kps, d_list, m, sub); kps = sub; }
+        LGR_TRY(c.d->stage(cx, kps, m, surf, *nd, radius, out, p, c.vp(side)));
+    }
+    tick(cx, 3);
+    LGR_HIP(cx, hipEventSynchronize(cx->ev[3]));
+    float t;
+    for (int s = 0; s < 3; ++s) { (void) hipEventElapsedTime(&t, cx->ev[s], cx->ev[s + 1]); ms[s] += t; }
+    return LGR_OK;
+}
+
+// ---- multi-scale matching (feature_radius unset): include/matching.h:176-262 (initialize) and :264-352
+// (match_multiscale).  The heavy stages (5-NN, down-sampling chain, normals, descriptors, brute-force matching per level) run on
+// the device; the per-key-point level assignment (log2f/sqrtf of the reference's host arithmetic, level pruning) and
+// the proximity vote over the <= nr_scales matches of a key point run on the host between them.
+struct MsSide {
+    float iss_radius = 0.f;
+    int min_l2 = INT_MAX, max_l2 = INT_MIN;
+    std::vector<std::vector<int>> lists;   // per scale: key-point indices
+    std::vector<size_t> feat_off;          // per scale: row offset into the feature buffer
+    float* feat = nullptr;                 // device, sum(rows) x D (D = the descriptor's row length)
+    int32_t* d_lists = nullptr;            // device copy of the lists, concatenated like feat_off
+    std::vector<float> xyz;                // host copy of the key points (3 floats each) for the vote
+};
+
+static int ms_initialize(CorrCall& c, int side, MsSide& st) {
+    lgr_ctx* ctx = c.ctx;
+    const lgr_params* p = c.p;
+    const int D = c.d->len, n = c.sizes[side], n_kps = c.ksizes[side];
+    const float *d_pcd = c.clouds[side], *d_kps = c.kclouds[side];
+    st.iss_radius = c.iss_radius(side);
     const int k = 5;
     LGR_CHECK(ctx, n >= k, LGR_ERR_INVALID_ARG);
     // :180-188 density of every key point = distance to its 4th neighbour in the full cloud
@@ -263,21 +369,9 @@ static int ms_initialize(lgr_ctx* ctx, MsSide& st, int side, const float* d_pcd,
         float search_radius = powf(p->scale_factor, (float) (st.min_l2 + i));
         float voxel = sqrtf(M_PI * search_radius * search_radius / (float) p->feature_nr_points);
         float* out = (i & 1) ? bufB : bufA;
-        int nd = 0;
-        tick(ctx, 0);
-        LGR_TRY(lgr_downsample_dev(ctx, in, n_in, voxel, out, &nd));
-        tick(ctx, 1);
-        LGR_TRY(lgr_normals_knn_dev(ctx, out, nd, nullptr, 0, p->normal_nr_points, vp, p->normals_available));
-        tick(ctx, 2);
-        const int m = (int) st.lists[i].size();
-        if (m) {
-            gather_rows12_kernel<<<cdiv((long long) m * 12, 256), 256, 0, ctx->stream>>>(d_kps, st.d_lists + st.feat_off[i], m, sub);
-            LGR_TRY(descriptor_dev(ctx, descriptor, sub, m, out, nd, search_radius, st.feat + st.feat_off[i] * D, p, vp));
-        }
-        tick(ctx, 3);
-        LGR_HIP(ctx, hipEventSynchronize(ctx->ev[3]));
-        float t;
-        for (int s = 0; s < 3; ++s) { (void) hipEventElapsedTime(&t, ctx->ev[s], ctx->ev[s + 1]); ms[s] += t; }
+        int nd;
+        LGR_TRY(level_features(ctx, c, side, in, n_in, voxel, search_radius, out, d_kps, (int) st.lists[i].size(), st.d_lists + st.feat_off[i], sub,
+                               st.feat + st.feat_off[i] * D, c.ms, &nd));
         in = out; n_in = nd;
     }
     return LGR_OK;
@@ -329,17 +423,14 @@ static void inverse4(const float* m16, float* out16) {
 }
 
 // the matcher dispatch of match_multiscale (include/matching.h:294-312): guess -> matchLocal in both directions (the inverse guess
-// for train -> query, :296), else bf -> matchBF (one MFMA pass serves both directions), else matchFLANN
-static int match_dispatch(lgr_ctx* ctx, const lgr_params* p, int descriptor, const float* a_pts, const float* fa, int ma, const float* b_pts, const float* fb, int mb,
-                          bool need_ba, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
-    if (descriptor == LGR_DESCRIPTOR_SHOT) {   // (checked on entry: SHOT runs the brute-force matcher only)
-        if (need_ba) return lgr_match2_shot_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d, ba_i, ba_d);
-        return lgr_match_shot_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d);
-    }
-    if (descriptor == LGR_DESCRIPTOR_ROPS) {   // (likewise)
-        if (need_ba) return lgr_match2_rops_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d, ba_i, ba_d);
-        return lgr_match_rops_dev(ctx, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d);
-    }
+// for train -> query, :296), else bf -> matchBF (one MFMA pass serves both directions), else matchFLANN.  The long descriptors
+// run the exact dense matcher (checked on entry: brute force only).
+static int match_dispatch(const CorrCall& c, const float* a_pts, const float* fa, int ma, const float* b_pts, const float* fb, int mb,
+                          int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
+    lgr_ctx* ctx = c.ctx;
+    const lgr_params* p = c.p;
+    const bool need_ba = c.both_dirs();
+    if (c.d->dense) return lgr_match_dense(ctx, c.d->len, fa, ma, fb, mb, p->bf_block_size, ab_i, ab_d, need_ba ? ba_i : nullptr, need_ba ? ba_d : nullptr);
     if (p->has_guess) {
         LGR_TRY(lgr_match_local_dev(ctx, a_pts, ma, b_pts, mb, fa, fb, p->guess, p->match_search_radius, ab_i, ab_d));
         if (need_ba) {
@@ -357,17 +448,14 @@ static int match_dispatch(lgr_ctx* ctx, const lgr_params* p, int descriptor, con
     return LGR_OK;
 }
 
-static int ms_match_tables(lgr_ctx* ctx, const float* const* clouds, const int* sizes, const float* const* kclouds, const int* ksizes,
-                           const lgr_params* p, int descriptor, int32_t* d_ij, float* d_dij, int32_t* d_ji, float* d_dji, float* ms) {
-    const int D = desc_len(descriptor);
+static int ms_match_tables(CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    const int D = c.d->len;
     MsSide st[2];
-    for (int c = 0; c < 2; ++c) {
-        const float* vp = c == 0 ? (p->has_vp_src ? p->vp_src : nullptr) : (p->has_vp_tgt ? p->vp_tgt : nullptr);
-        LGR_TRY(ms_initialize(ctx, st[c], c, clouds[c], sizes[c], kclouds[c], ksizes[c], c == 0 ? p->iss_radius_src : p->iss_radius_tgt, p, descriptor, vp, ms));
-    }
+    for (int s = 0; s < 2; ++s) LGR_TRY(ms_initialize(c, s, st[s]));
     tick(ctx, 4);
-    const bool need_ji = p->matching_id != LGR_MATCH_ONE_SIDED;
-    const int ns = ksizes[0], nt = ksizes[1];
+    const bool need_ji = c.both_dirs();
+    const int ns = c.ksizes[0], nt = c.ksizes[1];
     std::vector<std::vector<int>> mi_ij(ns), mi_ji(need_ji ? nt : 0);
     std::vector<std::vector<float>> md_ij(ns), md_ji(need_ji ? nt : 0);
     const int lo = std::max(st[0].min_l2, st[1].min_l2), hi = std::min(st[0].max_l2, st[1].max_l2);
@@ -384,14 +472,14 @@ static int ms_match_tables(lgr_ctx* ctx, const float* const* clouds, const int* 
         const float* fa = st[0].feat + st[0].feat_off[ia] * D;
         const float* fb = st[1].feat + st[1].feat_off[ib] * D;
         const float *pa = nullptr, *pb = nullptr;
-        if (p->has_guess) {   // matchLocal works on the level's key-point sub-clouds (kps_multiscale, include/matching.h:243)
+        if (c.p->has_guess) {   // matchLocal works on the level's key-point sub-clouds (kps_multiscale, include/matching.h:243)
             float* sub;
             LGR_TRY(lgr_ws_t(ctx, WS_MS_SUB, (size_t) (ma + mb) * 12 + 4, &sub));
-            gather_rows12_kernel<<<cdiv((long long) ma * 12, 256), 256, 0, ctx->stream>>>(kclouds[0], st[0].d_lists + st[0].feat_off[ia], ma, sub);
-            gather_rows12_kernel<<<cdiv((long long) mb * 12, 256), 256, 0, ctx->stream>>>(kclouds[1], st[1].d_lists + st[1].feat_off[ib], mb, sub + (size_t) ma * 12);
+            gather_rows12(ctx, c.kclouds[0], st[0].d_lists + st[0].feat_off[ia], ma, sub);
+            gather_rows12(ctx, c.kclouds[1], st[1].d_lists + st[1].feat_off[ib], mb, sub + (size_t) ma * 12);
             pa = sub; pb = sub + (size_t) ma * 12;
         }
-        LGR_TRY(match_dispatch(ctx, p, descriptor, pa, fa, ma, pb, fb, mb, need_ji, ab_i, ab_d, ba_i, ba_d));
+        LGR_TRY(match_dispatch(c, pa, fa, ma, pb, fb, mb, ab_i, ab_d, ba_i, ba_d));
         std::vector<int32_t> h((size_t) 2 * (ma + mb));
         LGR_HIP(ctx, hipMemcpyAsync(h.data(), r, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -407,58 +495,142 @@ static int ms_match_tables(lgr_ctx* ctx, const float* const* clouds, const int* 
     std::vector<float> dij(ns), dji(need_ji ? nt : 0);
     ms_vote(st[1], mi_ij, md_ij, ij, dij);
     if (need_ji) ms_vote(st[0], mi_ji, md_ji, ji, dji);
-    LGR_HIP(ctx, hipMemcpyAsync(d_ij, ij.data(), (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(d_dij, dij.data(), (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(c.ij, ij.data(), (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(c.dij, dij.data(), (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
     if (need_ji) {
-        LGR_HIP(ctx, hipMemcpyAsync(d_ji, ji.data(), (size_t) nt * 4, hipMemcpyHostToDevice, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(d_dji, dji.data(), (size_t) nt * 4, hipMemcpyHostToDevice, ctx->stream));
+        LGR_HIP(ctx, hipMemcpyAsync(c.ji, ji.data(), (size_t) nt * 4, hipMemcpyHostToDevice, ctx->stream));
+        LGR_HIP(ctx, hipMemcpyAsync(c.dji, dji.data(), (size_t) nt * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host staging vectors go out of scope
     return LGR_OK;
 }
 
-// key-point cloud = pcd[kps_indices] (pcl::copyPointCloud, include/matching.h:167); 12 floats per point
-__global__ void gather_points_kernel(const float* __restrict__ pts, const int32_t* __restrict__ idx, int m, float* __restrict__ out) {
-    size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t) m * 12) return;
-    out[e] = pts[(size_t) idx[e / 12] * 12 + e % 12];
-}
-// finalize (include/matching.h:150-160): local key-point indices -> indices of the clouds
-__global__ void finalize_kernel(lgr_corr* __restrict__ corr, int n, const int32_t* __restrict__ ks, const int32_t* __restrict__ kt) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    corr[i].index_query = ks[corr[i].index_query];
-    corr[i].index_match = kt[corr[i].index_match];
+// ---- the stages of lgr_correspondences_ex_dev, in the order they run
+static int check(CorrCall& c, const lgr_feature_params* fp) {
+    lgr_ctx* ctx = c.ctx;
+    const lgr_params* p = c.p;
+    LGR_CHECK(ctx, (c.clouds[0] || c.sizes[0] == 0) && (c.clouds[1] || c.sizes[1] == 0) && p && c.n_out && c.sizes[0] >= 0 && c.sizes[1] >= 0, LGR_ERR_INVALID_ARG);
+    LGR_TRY(feature_descriptor(ctx, p, fp, &c.d));
+    if (c.sizes[0] < 2 || c.sizes[1] < 2) { *c.n_out = 0; c.empty = true; return LGR_OK; }   // the reference ends with an empty correspondence list
+    LGR_CHECK(ctx, c.d_out != nullptr, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, p->randomness == 1, LGR_ERR_UNSUPPORTED);        // data/test.yaml:14 "currently only 1 is supported"
+    LGR_CHECK(ctx, p->feature_nr_points > 0 && p->normal_nr_points >= 1 && p->normal_nr_points <= 64 && p->bf_block_size > 0 && p->scale_factor > 1.f,
+              LGR_ERR_INVALID_ARG);
+    // checked before any stage runs (this entry point builds the filter tables itself, so lgr_filter_dev's checks do not cover it):
+    // the cluster filter keeps at most 64 spatial neighbours per point (filter_flags<64>)
+    LGR_CHECK(ctx, p->matching_id == LGR_MATCH_LR || p->matching_id == LGR_MATCH_ONE_SIDED || p->matching_id == LGR_MATCH_CLUSTER, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, p->matching_id != LGR_MATCH_CLUSTER || (p->cluster_k >= 1 && p->cluster_k <= 64), LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    *c.n_out = 0;
+    LGR_CHECK(ctx, p->keypoint_id == LGR_KEYPOINT_ANY || p->keypoint_id == LGR_KEYPOINT_ISS, LGR_ERR_UNSUPPORTED);
+    return LGR_OK;
 }
 
-extern "C" void lgr_default_feature_params(lgr_feature_params* f) {
-    if (!f) return;
-    memset(f, 0, sizeof(*f));
-    f->descriptor_id = LGR_DESCRIPTOR_FPFH;
-    f->lrf_id = LGR_LRF_DEFAULT;
+// key points (src/correspondence_search.cpp:8-11): every point, or the ISS detections.  kps = pcd[kps_indices]
+// (include/matching.h:167); every later stage works on the key-point clouds and the indices are mapped back at the
+// end (finalize, include/matching.h:150-160).
+static int keypoints(CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    if (c.p->keypoint_id != LGR_KEYPOINT_ISS) return LGR_OK;
+    for (int s = 0; s < 2; ++s) {
+        float* kp;
+        LGR_TRY(lgr_ws_t(ctx, s == 0 ? WS_PIPE_KIDX_S : WS_PIPE_KIDX_T, (size_t) c.sizes[s] + 1, &c.kidx[s]));
+        int m = 0;
+        LGR_TRY(lgr_iss_keypoints_dev(ctx, c.clouds[s], c.sizes[s], c.iss_radius(s), 0.975f, 0.975f, 4, c.kidx[s], &m));
+        LGR_TRY(lgr_ws_t(ctx, s == 0 ? WS_PIPE_KPS_S : WS_PIPE_KPS_T, (size_t) std::max(m, 1) * 12, &kp));
+        if (m) gather_rows12(ctx, c.clouds[s], c.kidx[s], m, kp);
+        c.kclouds[s] = kp; c.ksizes[s] = m;
+    }
+    return LGR_OK;
 }
 
-// the descriptor a feature-parameter struct selects, checked against the rest of the configuration (NULL: FPFH)
-static int feature_descriptor(lgr_ctx* ctx, const lgr_params* p, const lgr_feature_params* f, int* descriptor) {
-    *descriptor = LGR_DESCRIPTOR_FPFH;
-    if (!f) return LGR_OK;
-    LGR_CHECK(ctx, f->descriptor_id == LGR_DESCRIPTOR_FPFH || f->descriptor_id == LGR_DESCRIPTOR_SHOT || f->descriptor_id == LGR_DESCRIPTOR_ROPS,
-              LGR_ERR_UNSUPPORTED);
-    if (f->descriptor_id == LGR_DESCRIPTOR_SHOT) {    // the frames matter to SHOT only (FPFH never reads lrf_id, include/common.h:366,407)
-        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT || f->lrf_id == LGR_LRF_GRAVITY || f->lrf_id == LGR_LRF_GT, LGR_ERR_INVALID_ARG);
-        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT, LGR_ERR_UNSUPPORTED);
-        LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);     // matchFLANN / matchLocal are built for FPFH only
-        LGR_CHECK(ctx, ctx->opt.arithmetic != LGR_ARITH_PCL, LGR_ERR_UNSUPPORTED);  // the arithmetic modes are FPFH weightings
+static int alloc(CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    const int ns = c.ksizes[0], nt = c.ksizes[1];
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_S, (size_t) ns * c.d->len, &c.feat[0]));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_T, (size_t) nt * c.d->len, &c.feat[1]));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_S, (size_t) c.sizes[0] * 12, &c.surf[0]));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_T, (size_t) c.sizes[1] * 12, &c.surf[1]));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_IJ, (size_t) ns, &c.ij));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_JI, (size_t) nt, &c.ji));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_DIJ, (size_t) ns, &c.dij));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_DJI, (size_t) nt, &c.dji));
+    LGR_TRY(filter_tables_alloc(ctx, c.p->matching_id, ns, nt, c.p->cluster_k, &c.ftab));
+    return lgr_ctx_aux2(ctx);
+}
+
+// The filter's per-cloud tables do not depend on the matches: a third context computes them from a host thread of its own
+// while the feature stages and the matcher run (their sorts and k-NN kernels fill the matcher's low-occupancy phases).
+static int start_tables(CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    c.tables_guard.aux = ctx->aux2;
+    if (ctx->opt.helper_contexts) {
+        LGR_HIP(ctx, hipEventRecord(ctx->aux2_ev, ctx->stream));
+        LGR_HIP(ctx, hipStreamWaitEvent(ctx->aux2->stream, ctx->aux2_ev, 0));
+        LGR_TRY(lgr_helper_post(ctx, ctx->aux2, lgr_aux_job(ctx->aux2, c.tables)));
+        c.tables_guard.armed = true;
+    } else {
+        const int rc = c.tables(ctx->aux2);            // same stream, this thread
+        if (rc != LGR_OK) { ctx->err = ctx->aux2->err; return rc; }
     }
-    if (f->descriptor_id == LGR_DESCRIPTOR_ROPS) {
-        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_DEFAULT || f->lrf_id == LGR_LRF_GRAVITY || f->lrf_id == LGR_LRF_GT, LGR_ERR_INVALID_ARG);
-        // default: estimateFeatures<RoPS135> triangulates the cloud (GreedyProjectionTriangulation) and takes RoPS's own frames;
-        // gt: the reference reads parameters.ground_truth, for which lgr_feature_params has no channel
-        LGR_CHECK(ctx, f->lrf_id == LGR_LRF_GRAVITY, LGR_ERR_UNSUPPORTED);
-        LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);     // matchFLANN / matchLocal are built for FPFH only
-        LGR_CHECK(ctx, ctx->opt.arithmetic != LGR_ARITH_PCL, LGR_ERR_UNSUPPORTED);  // the arithmetic modes are FPFH weightings
+    return LGR_OK;
+}
+
+// The two clouds' feature stages are independent until the matcher: the source cloud runs on this context, the target cloud
+// on a second context (own stream and workspace) driven by a second host thread, so that the ~20 host read-backs per cloud
+// (voxel counts, grid extents) and the short sort / scan launches of one cloud hide behind the other cloud's kernels.
+// Results cannot depend on it (disjoint outputs; every kernel is deterministic).
+static int features_and_match_single(CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    const lgr_params* p = c.p;
+    // include/matching.h:172,230-231: radius quantised to a power of scale_factor; voxel from feature_nr_points
+    const int log2_radius = (int) std::floor(std::log2(p->feature_radius) / std::log2(p->scale_factor));
+    const float search_radius = powf(p->scale_factor, (float) log2_radius);
+    const float voxel = sqrtf(M_PI * search_radius * search_radius / (float) p->feature_nr_points);
+    auto cloud_features = [&](lgr_ctx* cx, int s, float* ms) -> int {
+        LGR_HIP(cx, hipSetDevice(cx->device));
+        int nd;
+        return level_features(cx, c, s, c.clouds[s], c.sizes[s], voxel, search_radius, c.surf[s], c.kclouds[s], c.ksizes[s], nullptr, nullptr, c.feat[s], ms, &nd);
+    };
+    float ms_t[3] = {0, 0, 0};
+    const auto t_feat0 = std::chrono::steady_clock::now();
+    // The source cloud is done first (this thread): the matcher's query-side half (clustering, assignment, sort) runs right behind
+    // its features, under the target cloud's feature kernels on the second context.
+    const bool prepare_query = p->use_bfmatcher && !p->has_guess && !c.d->dense;   // match_dispatch: the FPFH brute-force matcher will be called
+    LGR_TRY(lgr_run_pair(ctx,
+        [&](lgr_ctx* cx) {
+            LGR_TRY(cloud_features(cx, 0, c.ms));
+            return prepare_query ? lgr_match_prepare(cx, c.feat[0], c.ksizes[0], c.ksizes[1], c.both_dirs()) : (int) LGR_OK;
+        },
+        [&](lgr_ctx* cx) { return cloud_features(cx, 1, ms_t); }));
+    // the two clouds overlap in wall time: report the wall time of the feature stages, split in proportion to the stage times
+    // the two streams measured (each of which includes the other stream's interleaved kernels)
+    const float wall = 1e3f * std::chrono::duration<float>(std::chrono::steady_clock::now() - t_feat0).count();
+    float sum = 0.f;
+    for (int s = 0; s < 3; ++s) { c.ms[s] += ms_t[s]; sum += c.ms[s]; }
+    if (sum > 0.f) for (int s = 0; s < 3; ++s) c.ms[s] *= wall / sum;
+    tick(ctx, 4);
+    return match_dispatch(c, c.kclouds[0], c.feat[0], c.ksizes[0], c.kclouds[1], c.feat[1], c.ksizes[1], c.ij, c.dij, c.ji, c.dji);
+}
+
+// wait for the tables, filter, map key-point indices back (finalize), stage times
+static int finish(CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    const lgr_params* p = c.p;
+    tick(ctx, 5);
+    if (c.tables_guard.armed) {
+        const int rc_tab = c.tables_guard.wait();
+        (void) hipSetDevice(ctx->device);
+        if (rc_tab != LGR_OK) { ctx->err = ctx->aux2->err; return rc_tab; }
     }
-    *descriptor = f->descriptor_id;
+    LGR_TRY(filter_core(ctx, p->matching_id, c.ksizes[0], c.ij, c.dij, c.ji, c.dji, p->distance_thr, p->cluster_k, c.ftab, c.d_out, c.n_out));
+    if (c.kidx[0] && *c.n_out) finalize_kernel<<<cdiv(*c.n_out, 256), 256, 0, ctx->stream>>>(c.d_out, *c.n_out, c.kidx[0], c.kidx[1]);
+    tick(ctx, 6);
+    LGR_HIP(ctx, hipEventSynchronize(ctx->ev[6]));
+    float t;
+    ctx->stage_ms[0] = c.ms[0]; ctx->stage_ms[1] = c.ms[1]; ctx->stage_ms[2] = c.ms[2];
+    (void) hipEventElapsedTime(&t, ctx->ev[4], ctx->ev[5]); ctx->stage_ms[3] = t;
+    (void) hipEventElapsedTime(&t, ctx->ev[5], ctx->ev[6]); ctx->stage_ms[4] = t;
     return LGR_OK;
 }
 
@@ -471,155 +643,29 @@ extern "C" int lgr_correspondences_ex_dev(lgr_ctx* ctx, const float* d_src, int 
                                           const lgr_feature_params* fp, lgr_corr* d_out, int* n_out) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_CHECK(ctx, (d_src || ns == 0) && (d_tgt || nt == 0) && p && n_out && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
-    int descriptor;
-    LGR_TRY(feature_descriptor(ctx, p, fp, &descriptor));
-    const int D = desc_len(descriptor);
-    if (ns < 2 || nt < 2) { *n_out = 0; return LGR_OK; }   // nothing to match (the reference ends with an empty correspondence list)
-    LGR_CHECK(ctx, d_out != nullptr, LGR_ERR_INVALID_ARG);
-    LGR_CHECK(ctx, p->randomness == 1, LGR_ERR_UNSUPPORTED);        // data/test.yaml:14 "currently only 1 is supported"
-    LGR_CHECK(ctx, p->feature_nr_points > 0 && p->normal_nr_points >= 1 && p->normal_nr_points <= 64 && p->bf_block_size > 0 && p->scale_factor > 1.f,
-              LGR_ERR_INVALID_ARG);
-    // checked before any stage runs (this entry point builds the filter tables itself, so lgr_filter_dev's checks do not cover it):
-    // the cluster filter keeps at most 64 spatial neighbours per point (filter_flags<64>)
-    LGR_CHECK(ctx, p->matching_id == LGR_MATCH_LR || p->matching_id == LGR_MATCH_ONE_SIDED || p->matching_id == LGR_MATCH_CLUSTER, LGR_ERR_INVALID_ARG);
-    LGR_CHECK(ctx, p->matching_id != LGR_MATCH_CLUSTER || (p->cluster_k >= 1 && p->cluster_k <= 64), LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
-    *n_out = 0;
-    // include/matching.h:172,230-231: radius quantised to a power of scale_factor; voxel from feature_nr_points
-    // (feature_radius unset, i.e. <= 0 here: the multi-scale path below, include/matching.h:176-208)
-    const bool multiscale = !(p->feature_radius > 0.f);
-    float search_radius = 0.f, voxel = 0.f;
-    if (!multiscale) {
-        int log2_radius = (int) std::floor(std::log2(p->feature_radius) / std::log2(p->scale_factor));
-        search_radius = powf(p->scale_factor, (float) log2_radius);
-        voxel = sqrtf(M_PI * search_radius * search_radius / (float) p->feature_nr_points);
-    }
-    const float* clouds[2] = {d_src, d_tgt};
-    int sizes[2] = {ns, nt};
-    // key points (src/correspondence_search.cpp:8-11): every point, or the ISS detections.  kps = pcd[kps_indices]
-    // (include/matching.h:167); every later stage works on the key-point clouds and the indices are mapped back at the
-    // end (finalize, include/matching.h:150-160).
-    const bool iss = p->keypoint_id == LGR_KEYPOINT_ISS;
-    LGR_CHECK(ctx, p->keypoint_id == LGR_KEYPOINT_ANY || iss, LGR_ERR_UNSUPPORTED);
-    const float* kclouds[2] = {d_src, d_tgt};
-    int ksizes[2] = {ns, nt};
-    int32_t* kidx[2] = {nullptr, nullptr};
-    if (iss) {
-        for (int c = 0; c < 2; ++c) {
-            float* kp;
-            LGR_TRY(lgr_ws_t(ctx, c == 0 ? WS_PIPE_KIDX_S : WS_PIPE_KIDX_T, (size_t) sizes[c] + 1, &kidx[c]));
-            int m = 0;
-            LGR_TRY(lgr_iss_keypoints_dev(ctx, clouds[c], sizes[c], c == 0 ? p->iss_radius_src : p->iss_radius_tgt, 0.975f, 0.975f, 4, kidx[c], &m));
-            LGR_TRY(lgr_ws_t(ctx, c == 0 ? WS_PIPE_KPS_S : WS_PIPE_KPS_T, (size_t) std::max(m, 1) * 12, &kp));
-            if (m) gather_points_kernel<<<cdiv((long long) m * 12, 256), 256, 0, ctx->stream>>>(clouds[c], kidx[c], m, kp);
-            kclouds[c] = kp; ksizes[c] = m;
-        }
-        if (ksizes[0] == 0 || ksizes[1] == 0) return LGR_OK;
-    }
-    const int ns_all = ns, nt_all = nt;
-    (void) ns_all; (void) nt_all;
-    ns = ksizes[0]; nt = ksizes[1];
-    float* feat[2];
-    float* surf[2];
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_S, (size_t) ns * D, &feat[0]));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_T, (size_t) nt * D, &feat[1]));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_S, (size_t) sizes[0] * 12, &surf[0]));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_T, (size_t) sizes[1] * 12, &surf[1]));
-    float ms[3] = {0, 0, 0};
-    int32_t *ij, *ji;
-    float *dij, *dji;
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_IJ, (size_t) ns, &ij));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_JI, (size_t) nt, &ji));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_DIJ, (size_t) ns, &dij));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_DJI, (size_t) nt, &dji));
-    // The filter's per-cloud tables do not depend on the matches: a third context computes them from a host thread of its own
-    // while the feature stages and the matcher run (their sorts and k-NN kernels fill the matcher's low-occupancy phases).
-    FilterTables ftab;
-    LGR_TRY(filter_tables_alloc(ctx, p->matching_id, ns, nt, p->cluster_k, &ftab));
-    LGR_TRY(lgr_ctx_aux2(ctx));
-    auto cloud_tables = [&](lgr_ctx* cx) -> int {
-        LGR_TRY(filter_cloud_tables(cx, kclouds[0], ns, p->cluster_k, ftab.thr_s, ftab.knn_s));
-        return filter_cloud_tables(cx, kclouds[1], nt, p->cluster_k, ftab.thr_t, ftab.knn_t);
-    };
-    lgr_helper_guard tables_guard{ctx->aux2, false};   // every exit path waits for the helper (which always drains its stream)
-    if (ctx->opt.helper_contexts) {
-        LGR_HIP(ctx, hipEventRecord(ctx->aux2_ev, ctx->stream));
-        LGR_HIP(ctx, hipStreamWaitEvent(ctx->aux2->stream, ctx->aux2_ev, 0));
-        LGR_TRY(lgr_helper_post(ctx, ctx->aux2, lgr_aux_job(ctx->aux2, cloud_tables)));
-        tables_guard.armed = true;
-    } else {
-        const int rc = cloud_tables(ctx->aux2);        // same stream, this thread
-        if (rc != LGR_OK) { ctx->err = ctx->aux2->err; return rc; }
-    }
-    if (multiscale) {
-        LGR_TRY(ms_match_tables(ctx, clouds, sizes, kclouds, ksizes, p, descriptor, ij, dij, ji, dji, ms));
-    } else {
-    // The two clouds' feature stages are independent until the matcher: the source cloud runs on this context, the target cloud
-    // on a second context (own stream and workspace) driven by a second host thread, so that the ~20 host read-backs per cloud
-    // (voxel counts, grid extents) and the short sort / scan launches of one cloud hide behind the other cloud's kernels.
-    // Results cannot depend on it (disjoint outputs; every kernel is deterministic).
-    auto cloud_features = [&](lgr_ctx* cx, int c, float* out_ms) -> int {
-        LGR_HIP(cx, hipSetDevice(cx->device));
-        int nd = 0;
-        tick(cx, 0);
-        LGR_TRY(lgr_downsample_dev(cx, clouds[c], sizes[c], voxel, surf[c], &nd));                       // :234
-        tick(cx, 1);
-        const float* vp = c == 0 ? (p->has_vp_src ? p->vp_src : nullptr) : (p->has_vp_tgt ? p->vp_tgt : nullptr);
-        LGR_TRY(lgr_normals_knn_dev(cx, surf[c], nd, nullptr, 0, p->normal_nr_points, vp, p->normals_available));   // :235
-        tick(cx, 2);
-        // :243-246 re-estimates the normals of the key-point COPY; FPFH reads only the surface normals
-        // (include/common.h:329), so that step has no observable effect and is not executed.
-        LGR_TRY(descriptor_dev(cx, descriptor, kclouds[c], ksizes[c], surf[c], nd, search_radius, feat[c], p, vp));   // :248
-        tick(cx, 3);
-        LGR_HIP(cx, hipEventSynchronize(cx->ev[3]));
-        float t;
-        for (int s = 0; s < 3; ++s) { (void) hipEventElapsedTime(&t, cx->ev[s], cx->ev[s + 1]); out_ms[s] += t; }
-        return LGR_OK;
-    };
-    float ms_t[3] = {0, 0, 0};
-    const auto t_feat0 = std::chrono::steady_clock::now();
-    // The source cloud is done first (this thread): the matcher's query-side half (clustering, assignment, sort) runs right behind
-    // its features, under the target cloud's feature kernels on the second context.
-    const bool both_dirs = p->matching_id != LGR_MATCH_ONE_SIDED;
-    const bool prepare_query = p->use_bfmatcher && !p->has_guess && descriptor == LGR_DESCRIPTOR_FPFH;   // match_dispatch: the FPFH brute-force matcher will be called
-    struct PrepGuard { lgr_ctx* c; ~PrepGuard() { lgr_match_prepare_cancel(c); } } prep_guard{ctx};
-    LGR_TRY(lgr_run_pair(ctx,
-        [&](lgr_ctx* cx) {
-            LGR_TRY(cloud_features(cx, 0, ms));
-            return prepare_query ? lgr_match_prepare(cx, feat[0], ns, nt, both_dirs) : (int) LGR_OK;
-        },
-        [&](lgr_ctx* cx) { return cloud_features(cx, 1, ms_t); }));
-    {
-        // the two clouds overlap in wall time: report the wall time of the feature stages, split in proportion to the stage times
-        // the two streams measured (each of which includes the other stream's interleaved kernels)
-        const float wall = 1e3f * std::chrono::duration<float>(std::chrono::steady_clock::now() - t_feat0).count();
-        float sum = 0.f;
-        for (int s = 0; s < 3; ++s) { ms[s] += ms_t[s]; sum += ms[s]; }
-        if (sum > 0.f) for (int s = 0; s < 3; ++s) ms[s] *= wall / sum;
-    }
-    tick(ctx, 4);
-    LGR_TRY(match_dispatch(ctx, p, descriptor, kclouds[0], feat[0], ns, kclouds[1], feat[1], nt, p->matching_id != LGR_MATCH_ONE_SIDED, ij, dij, ji, dji));
-    }
-    tick(ctx, 5);
-    if (tables_guard.armed) {
-        const int rc_tab = tables_guard.wait();
-        (void) hipSetDevice(ctx->device);
-        if (rc_tab != LGR_OK) { ctx->err = ctx->aux2->err; return rc_tab; }
-    }
-    LGR_TRY(filter_core(ctx, p->matching_id, ns, ij, dij, ji, dji, p->distance_thr, p->cluster_k, ftab, d_out, n_out));
-    if (iss && *n_out) finalize_kernel<<<cdiv(*n_out, 256), 256, 0, ctx->stream>>>(d_out, *n_out, kidx[0], kidx[1]);
-    tick(ctx, 6);
-    LGR_HIP(ctx, hipEventSynchronize(ctx->ev[6]));
-    float t;
-    ctx->stage_ms[0] = ms[0]; ctx->stage_ms[1] = ms[1]; ctx->stage_ms[2] = ms[2];
-    (void) hipEventElapsedTime(&t, ctx->ev[4], ctx->ev[5]); ctx->stage_ms[3] = t;
-    (void) hipEventElapsedTime(&t, ctx->ev[5], ctx->ev[6]); ctx->stage_ms[4] = t;
-    return LGR_OK;
+    CorrCall c(ctx, d_src, ns, d_tgt, nt, p, d_out, n_out);   // its guards act on every return below
+    LGR_TRY(check(c, fp));
+    if (c.empty) return LGR_OK;
+    LGR_TRY(keypoints(c));
+    if (c.ksizes[0] == 0 || c.ksizes[1] == 0) return LGR_OK;   // ISS found nothing on a side: no job has been posted yet
+    LGR_TRY(alloc(c));
+    LGR_TRY(start_tables(c));                                  // aux2, under everything up to finish
+    // (feature_radius unset, i.e. <= 0 here: the multi-scale path, include/matching.h:176-208)
+    LGR_TRY(p->feature_radius > 0.f ? features_and_match_single(c) : ms_match_tables(c));
+    return finish(c);
 }
 
 extern "C" int lgr_correspondences(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, lgr_corr* out, int* n_out) {
     return lgr_correspondences_ex(ctx, src, ns, tgt, nt, p, nullptr, out, n_out);
+}
+
+// host entry points: both clouds to the device (WS_HOST_A / WS_HOST_B) on ctx->stream
+static int upload_clouds(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, float** ds, float** dt) {
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, ds));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, dt));
+    LGR_HIP(ctx, hipMemcpyAsync(*ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(*dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
+    return LGR_OK;
 }
 
 extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
@@ -632,16 +678,14 @@ extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, co
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
     lgr_corr* dc;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, &ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, &dt));
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));
-    LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
+    LGR_TRY(upload_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     LGR_TRY(lgr_correspondences_ex_dev(ctx, ds, ns, dt, nt, p, fp, dc, n_out));
     if (*n_out) LGR_HIP(ctx, hipMemcpyAsync(out, dc, (size_t) *n_out * 16, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LGR_OK;
 }
+
 
 extern "C" int lgr_align_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, lgr_result* res) {
     return lgr_align_ex_dev(ctx, d_src, ns, d_tgt, nt, p, nullptr, res);
@@ -660,7 +704,7 @@ extern "C" int lgr_align_ex2_dev(lgr_ctx* ctx, const float* d_src, int ns, const
     // alignTeaser throws in the reference (src/alignment.cpp:40)
     LGR_CHECK(ctx, p->alignment_id == LGR_ALIGN_RANSAC || p->alignment_id == LGR_ALIGN_GROR, LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, p->n_samples >= 3 && p->n_samples <= 8, LGR_ERR_UNSUPPORTED);   // (lgr_ransac.hip instantiates its kernels for 3..8)
-    int descriptor;
+    const Descriptor* descriptor;
     LGR_TRY(feature_descriptor(ctx, p, fp, &descriptor));
     if (ns < 2 || nt < 2) {
         // a cloud without two points gives no correspondences; the reference then leaves the identity, not converged
@@ -715,16 +759,8 @@ extern "C" int lgr_align_ex2(lgr_ctx* ctx, const float* src, int ns, const float
     if (ns < 2 || nt < 2) return lgr_align_ex2_dev(ctx, nullptr, 0, nullptr, 0, p, fp, mp, res);   // identity, not converged
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, &ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, &dt));
-    LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
+    LGR_TRY(upload_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     lgr_metric_params mpd;
-    if (mp && mp->weights) {   // host weights -> device
-        float* dw;
-        LGR_TRY(lgr_ws_t(ctx, WS_WEIGHTS_HOST, (size_t) ns + 1, &dw));
-        LGR_HIP(ctx, hipMemcpyAsync(dw, mp->weights, (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
-        mpd = *mp; mpd.weights = dw; mp = &mpd;
-    }
+    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
     return lgr_align_ex2_dev(ctx, ds, ns, dt, nt, p, fp, mp, res);
 }

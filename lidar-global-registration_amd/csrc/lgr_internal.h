@@ -122,7 +122,7 @@ enum {
     WS_PIPE_CORR, WS_PIPE_KNN_S, WS_PIPE_KNN_T, WS_PIPE_FLAGS, WS_PIPE_MISC, WS_PIPE_KIDX_S, WS_PIPE_KIDX_T, WS_PIPE_KPS_S, WS_PIPE_KPS_T,
     WS_MS_KNN_I, WS_MS_KNN_D, WS_MS_LIST_S, WS_MS_LIST_T, WS_MS_SUB, WS_MS_FEAT_S, WS_MS_FEAT_T, WS_MS_SURF2, WS_MS_RES, WS_PLANE_VISITED, WS_PLANE_CLAIMED, WS_PLANE_OUT, WS_LOCAL_G, WS_SORT_TMP, WS_MATCH_BOX, WS_RANSAC_GHIST,
     WS_HOST_A, WS_HOST_B, WS_HOST_C, WS_HOST_D, WS_HOST_E, WS_HOST_F,
-    WS_SHOT_PACK_A, WS_SHOT_PACK_B, WS_SHOT_KEYS,
+    WS_DENSE_PACK_A, WS_DENSE_PACK_B, WS_DENSE_KEYS,
     WS_ROPS_MASKED, WS_ROPS_LRF, WS_ROPS_KPS,
     WS_WEIGHTS, WS_WEIGHTS_KNN, WS_WEIGHTS_TMP, WS_WEIGHTS_VALS, WS_WEIGHTS_SUM, WS_WEIGHTS_HOST,
     WS_COUNT
@@ -239,6 +239,18 @@ int lgr_sort_pairs_u64(lgr_ctx* ctx, const unsigned long long* kin, unsigned lon
 // (d_a33, ma, mb, both directions) or dropped by lgr_match_prepare_cancel.
 int lgr_match_prepare(lgr_ctx* ctx, const float* d_a33, int ma, int mb, bool both);
 void lgr_match_prepare_cancel(lgr_ctx* ctx);
+// lgr_match_dense.hip: the exact dense matcher of the long descriptors, row_len 352 (SHOT) or 135 (RoPS), else LGR_ERR_UNSUPPORTED
+int lgr_match_dense(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block,
+                    int32_t* ab_i, float* ab_d, int32_t* ba_i /* NULL: one direction */, float* ba_d);
+// host weights of a metric (lgr_align_ex2, lgr_ransac_ex) -> device copy on ctx->stream; *mp then points at the patched copy `staged`
+static inline int lgr_stage_host_weights(lgr_ctx* ctx, int ns, const lgr_metric_params** mp, lgr_metric_params* staged) {
+    if (!*mp || !(*mp)->weights) return LGR_OK;
+    float* dw;
+    LGR_TRY(lgr_ws_t(ctx, WS_WEIGHTS_HOST, (size_t) ns + 1, &dw));
+    LGR_HIP(ctx, hipMemcpyAsync(dw, (*mp)->weights, (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    *staged = **mp; staged->weights = dw; *mp = staged;
+    return LGR_OK;
+}
 
 // ---- closest-plane metric on the device (lgr_plane.hip) ----
 struct lgr_plane_dev {

@@ -1823,12 +1823,7 @@ extern "C" int lgr_ransac_ex(lgr_ctx* ctx, const float* src, int ns, const float
     LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
     if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * 16, hipMemcpyHostToDevice, ctx->stream));
     lgr_metric_params mpd;
-    if (mp && mp->weights) {   // host weights -> device
-        float* dw;
-        LGR_TRY(lgr_ws_t(ctx, WS_WEIGHTS_HOST, (size_t) ns + 1, &dw));
-        LGR_HIP(ctx, hipMemcpyAsync(dw, mp->weights, (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
-        mpd = *mp; mpd.weights = dw; mp = &mpd;
-    }
+    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
     LGR_TRY(lgr_ransac_ex_dev(ctx, ds, ns, dt, nt, dc, c, p, mp, res, dm));
     if (final_mask && c >= p->n_samples) {
         LGR_HIP(ctx, hipMemcpyAsync(final_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));

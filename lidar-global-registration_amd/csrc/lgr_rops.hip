@@ -3,7 +3,6 @@
 //   src/common.cpp:693-755 estimateReferenceFrames, lrf_id "gravity"                 -> lgr_gravity_lrf*
 //   include/common.h estimateFeatures<RoPS135> with given frames = ROPSEstimationWithLocalReferenceFrames
 //     (include/pcl/impl/rops_custom_lrf.hpp:96-186, :364-518; 5 bins, 3 rotations, support radius = radius)  -> lgr_rops*
-// (the 135-d matcher lives next to the 352-d one in lgr_shot.hip)
 // Canonical choices: Eigen's 3-term reductions and cross product of lgr_rops_math.h, glibc's logf restated
 // there, and its rule for static_cast<unsigned>; tests/cpp/rops_ref.cpp states the stage on the CPU with the host's own libm and the
 // -m gpu tests compare bit for bit.

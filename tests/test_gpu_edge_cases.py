@@ -163,3 +163,40 @@ def test_out_of_range_correspondence_indices_are_an_error_not_a_fault(lgr, pair)
     edge = good.copy()
     edge["index_query"][0] = 4999; edge["index_match"][0] = 4999
     lgr.ransac(src, tgt, edge, p)
+
+
+@pytest.mark.parametrize("helper_contexts", [1, 0])
+def test_error_exit_while_the_filter_tables_job_is_in_flight(pair, helper_contexts):
+    """Multi-scale search on two 4-point clouds: the filter-tables job is posted (helper_contexts=1: to the third context's host
+    thread), then the multi-scale set-up refuses a cloud of fewer than 5 points with LGR_ERR_INVALID_ARG -- an ordinary error return
+    that has to wait for the job before the call's state goes away.  After each refused call the same context gives the
+    registration of a fresh context, bit for bit."""
+    from lgr_amd import capi, synthetic
+    lib = capi.lib()
+    tiny = synthetic.make_pair(4000, seed=21)
+    s4, t4 = tiny["src"][:4].copy(), tiny["tgt"][:4].copy()
+    for a in (s4, t4):
+        assert np.isfinite(a[:, :3]).all() and len(np.unique(a[:, :3], axis=0)) == 4
+    s4, t4 = cuda(s4), cuda(t4)
+    bad = base_params(capi, tiny, feature_radius=0.0)
+    bad.matching_id = capi.MATCH_LR
+    src, tgt, p = cuda(pair["src"]), cuda(pair["tgt"]), base_params(capi, pair)
+
+    def key(r):
+        return r.matrix().view(np.uint32), (r.iterations, r.n_inliers, r.n_correspondences, r.converged)
+
+    fresh, ctx = capi.Context(0), capi.Context(0)
+    try:
+        fresh.set_options(helper_contexts=helper_contexts)
+        ctx.set_options(helper_contexts=helper_contexts)
+        want = key(fresh.align(src, tgt, p))
+        ps, pt = C.c_void_p(s4.data_ptr()), C.c_void_p(t4.data_ptr())
+        out, n, res = ctx.empty((4, 4), s4.dtype), C.c_int(-1), capi.Result()
+        for call in (lambda: lib.lgr_correspondences_dev(ctx.h, ps, 4, pt, 4, C.byref(bad), C.c_void_p(out.data_ptr()), C.byref(n)),
+                     lambda: lib.lgr_align_dev(ctx.h, ps, 4, pt, 4, C.byref(bad), C.byref(res))):
+            assert call() == ERR_INVALID_ARG
+            got = key(ctx.align(src, tgt, p))
+            np.testing.assert_array_equal(got[0], want[0])
+            np.testing.assert_array_equal(got[1], want[1])
+    finally:
+        fresh.close(); ctx.close()
