@@ -522,6 +522,69 @@ int lgr_choose_best_hypothesis_dev(lgr_ctx*, const float* d_src, int ns, const f
                                    const float* tns16 /* host, n x 16 */, int n, float T_out16[16], int* best_index, float* uniformities /* host, n, or NULL */);
 int lgr_update_hypotheses(float* tns16, float* metrics, int n, int cap, const float* new_T16, float new_metric, float distance_thr);
 
+/* ---- include/analysis.h:36-98 AlignmentAnalysis::start(transformation_gt, testname) (src/analysis.cpp:218-246): a transformation judged
+ *      against a known ground truth.  What the reference leaves unordered (OpenMP reductions, kd-tree ties) has the declared orders of
+ *      points move in PCL's se3 order, "nearest within r" is the closest-plane metric's rule (strict d2 < r * r,
+ *      smallest squared distance, then the lowest index; non-finite points never match), every float sum over points is the sequential
+ *      f32 sum in ascending index over per-point terms.  No file side effects (AlignmentAnalysis::save is the caller's business:
+ *      tools/register_ply.py --ground-truth).  Point rows must be 16-byte aligned.  0 < distance_thr <= 1e18, so that the squared search
+ *      radius (2 distance_thr)^2 and the grid cell stay finite in f32; anything else is LGR_ERR_INVALID_ARG. ---- */
+typedef struct {
+    float   r_err, t_err;                /* src/analysis.cpp:19-24 calculateRotationAndTranslationDifferences (radians, length) */
+    float   pcd_err;                     /* :30-43 calculatePointCloudRmse; NaN for an empty source */
+    float   overlap_rmse;                /* :45-88 calculateOverlapRmse; quiet NaN when overlap_size == 0 */
+    int32_t overlap_size;
+    float   normal_diff;                 /* :141-185 calculateNormalDifference (radians; pi when nothing counts) */
+    int32_t n_normal_overlap;
+    int32_t n_overlap_src, n_overlap_tgt, n_overlap;   /* src/common.cpp:558-591 mergeOverlaps at the ground truth; n_overlap = the sum */
+    float   overlap;                     /* src/analysis.cpp:229 n_overlap / (float) (ns + nt) */
+    float   overlap_area;                /* :230-234; NaN when either cloud of the ratio has fewer than 2 points */
+    int32_t n_correspondences;           /* c */
+    int32_t n_correct_correspondences;   /* :187-206 buildCorrectCorrespondences */
+    int32_t n_inliers;                   /* set bytes of the inlier mask (0 without one) */
+    int32_t n_correct_inliers;           /* mask && correct: buildCorrectInliers' test for the correspondence metrics (src/metric.cpp) */
+    float   corr_uniformity;             /* :90-130 over the correct correspondences; 0 when there is none (the reference divides 0 by 0) */
+    int32_t converged;                   /* as passed in */
+    int32_t converged_and_overlap_ok;    /* converged && overlap_rmse < distance_thr (src/main.cpp:356; NaN compares false) */
+    int32_t reserved[5];                 /* 0 */
+} lgr_gt_eval;
+/* inlier_mask (optional): c bytes, e.g. final_mask of lgr_ransac*.  correct_mask (optional): receives c bytes, 1 = correct correspondence.
+ * ns == 0 or nt == 0 is not an error: counts 0, overlap_rmse NaN, normal_diff pi. */
+int lgr_evaluate_gt(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float T16[16],
+                    const float Tgt16[16], float distance_thr, int converged, const uint8_t* inlier_mask_or_null, lgr_gt_eval* out,
+                    uint8_t* correct_mask_or_null);
+int lgr_evaluate_gt_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c, const float T16[16] /* host */,
+                        const float Tgt16[16] /* host */, float distance_thr, int converged, const uint8_t* d_inlier_mask_or_null,
+                        lgr_gt_eval* out /* host */, uint8_t* d_correct_mask_or_null);
+/* src/analysis.cpp:45-88 calculateOverlapRmse (and :30-43 calculatePointCloudRmse, computed by the same pass; pcd_err may be NULL).
+ * d_idx (optional, ns ints): the target point whose tangent plane source point i was measured against, -1 where the point was skipped. */
+int lgr_overlap_rmse_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16] /* host */, const float Tgt16[16] /* host */,
+                         float distance_thr, float* overlap_rmse, int* overlap_size, float* pcd_err /* host outs */, int32_t* d_idx_or_null);
+int lgr_overlap_rmse(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T16[16], const float Tgt16[16], float distance_thr,
+                     float* overlap_rmse, int* overlap_size, float* pcd_err_or_null, int32_t* idx_or_null);   /* host twin */
+/* src/common.cpp:558-591 mergeOverlaps(Tgt * src, tgt, dst, distance_thr) as two byte masks (optional: ns and nt bytes) + src/analysis.cpp:229-234:
+ * n_overlap2 = {source points, target points} in the overlap, overlap, overlap_area (calculateSmoothedDensities with its default k = 2).
+ * overlap_area may be NULL: the two density passes it costs are then not run.  dst of the reference = the source rows whose mask byte is
+ * set (moved by Tgt), then the target rows whose byte is set, each in index order. */
+int lgr_merge_overlaps_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float Tgt16[16] /* host */, float distance_thr,
+                           uint8_t* d_mask_src_or_null, uint8_t* d_mask_tgt_or_null, int n_overlap2[2], float* overlap,
+                           float* overlap_area_or_null /* host outs */);
+int lgr_merge_overlaps(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float Tgt16[16], float distance_thr,
+                       uint8_t* mask_src_or_null, uint8_t* mask_tgt_or_null, int n_overlap2[2], float* overlap,
+                       float* overlap_area_or_null);   /* host twin */
+/* src/analysis.cpp:187-206 buildCorrectCorrespondences alone: correct_mask (optional, c bytes), n3 = {correct correspondences, correct
+ * inliers, inliers} (the last two 0 without an inlier mask).  Correspondence indices are checked against ns and nt. */
+int lgr_correct_correspondences_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                                    const float Tgt16[16] /* host */, const uint8_t* d_inlier_mask_or_null, uint8_t* d_correct_mask_or_null,
+                                    int n3[3] /* host */);
+int lgr_correct_correspondences(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float Tgt16[16],
+                                const uint8_t* inlier_mask_or_null, uint8_t* correct_mask_or_null, int n3[3]);   /* host twin */
+/* src/analysis.cpp:141-185 calculateNormalDifference (without checkNormals' assert): the element of rank n / 2 of the ascending differences */
+int lgr_normal_difference_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float Tgt16[16] /* host */, float distance_thr,
+                              float* normal_diff, int* n_normal_overlap /* host outs */);
+int lgr_normal_difference(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float Tgt16[16], float distance_thr,
+                          float* normal_diff, int* n_normal_overlap);   /* host twin */
+
 #ifdef __cplusplus
 }
 #endif

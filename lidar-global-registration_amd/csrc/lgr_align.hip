@@ -404,7 +404,7 @@ static void ms_vote(const MsSide& tr, const std::vector<std::vector<int>>& mi, c
 
 // inverse of a column-major 4x4 by Gauss-Jordan with partial pivoting in double, rounded to float: the canonical stand-in for
 // Eigen's Matrix4f::inverse() (include/matching.h:296), same as the oracle's orc_inverse4
-static void inverse4(const float* m16, float* out16) {
+void lgr_inverse4(const float* m16, float* out16) {
     double a[4][8];
     for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { a[r][c] = m16[4 * c + r]; a[r][4 + c] = r == c ? 1.0 : 0.0; }
     for (int col = 0; col < 4; ++col) {
@@ -435,7 +435,7 @@ static int match_dispatch(const CorrCall& c, const float* a_pts, const float* fa
         LGR_TRY(lgr_match_local_dev(ctx, a_pts, ma, b_pts, mb, fa, fb, p->guess, p->match_search_radius, ab_i, ab_d));
         if (need_ba) {
             float inv[16];
-            inverse4(p->guess, inv);
+            lgr_inverse4(p->guess, inv);
             LGR_TRY(lgr_match_local_dev(ctx, b_pts, mb, a_pts, ma, fb, fa, inv, p->match_search_radius, ba_i, ba_d));
         }
     } else if (p->use_bfmatcher) {

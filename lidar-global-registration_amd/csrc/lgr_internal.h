@@ -43,7 +43,7 @@ struct lgr_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
-    lgr_buf ws[112];
+    lgr_buf ws[128];
     void* pinned = nullptr;  // small pinned host scratch for read-backs
     size_t pinned_cap = 0;
     hipEvent_t ev[32];       // 0..8 stage timers (lgr_align), 9.. pairs around the match_mfma passes
@@ -125,9 +125,10 @@ enum {
     WS_DENSE_PACK_A, WS_DENSE_PACK_B, WS_DENSE_KEYS,
     WS_ROPS_MASKED, WS_ROPS_LRF, WS_ROPS_KPS,
     WS_WEIGHTS, WS_WEIGHTS_KNN, WS_WEIGHTS_TMP, WS_WEIGHTS_VALS, WS_WEIGHTS_SUM, WS_WEIGHTS_HOST,
+    WS_GT_MISC, WS_GT_TERMS, WS_GT_ALIGNED, WS_GT_OVERLAP, WS_GT_FLAGS, WS_GT_KNN, WS_GT_DENS, WS_GT_CORR,   // lgr_analysis.hip
     WS_COUNT
 };
-static_assert(WS_COUNT <= 112, "grow lgr_ctx::ws");
+static_assert(WS_COUNT <= 128, "grow lgr_ctx::ws");
 
 // returns device pointer of at least `bytes` (contents undefined unless kept); grows with 25% slack
 int lgr_ws(lgr_ctx* ctx, int slot, size_t bytes, void** out);
@@ -168,6 +169,8 @@ __host__ __device__ inline float lgr_bbox_key_inv(unsigned k) {
     memcpy(&f, &b, 4);
     return f;
 }
+// inverse of a column-major 4x4 (lgr_align.hip: Gauss-Jordan in double, the canonical stand-in for Eigen's Matrix4f::inverse())
+void lgr_inverse4(const float* m16, float* out16);
 // lgr_knn_dev with an optional distance table (d_d2 == nullptr: index lists only)
 int lgr_knn_lists(lgr_ctx* ctx, const float* d_q, int nq, const float* d_pts, int n, int k, int32_t* d_idx, float* d_d2);
 

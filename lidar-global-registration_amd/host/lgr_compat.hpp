@@ -10,6 +10,9 @@
 //   include/transformation.h:6-7          estimateOptimalRigidTransformation
 //   include/hypotheses.h:10-12            updateHypotheses
 //   src/common.cpp:531-547, 644-655       calculateSmoothedDensities, estimateNormalsPoints
+//   include/analysis.h:14-34, 36-98       calculatePointCloudRmse, calculateOverlapRmse, calculateNormalDifference,
+//                                         buildCorrectCorrespondences, AlignmentAnalysis (start without its file side effects)
+//   include/common.h:294                  mergeOverlaps
 //
 // The reference passes pcl::PointCloud<pcl::PointXYZINormal> / pcl::FPFHSignature33 / Eigen::Matrix4f.  Neither PCL
 // nor Eigen exists in this image, so the shim is written against three tiny layout-compatible types (lgr::PointN is
@@ -22,6 +25,7 @@
 #include <array>
 #include <cctype>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -479,5 +483,106 @@ inline AlignmentResult alignPointClouds(const PointNCloud::ConstPtr& src, const 
     else result = alignRansac(src, tgt, correspondences, params);   // unknown ids fall back to RANSAC (:96-100)
     return result;
 }
+
+
+// ---- include/analysis.h, include/common.h:294: the ground-truth analysis on the device (declared orders: DESIGN.md section 4).  Each free
+//      function runs its own pass only (the host building blocks of lgr.h); AlignmentAnalysis runs the whole evaluation once.
+inline lgr_gt_eval evaluateGroundTruth(const PointNCloud& src, const PointNCloud& tgt, const Correspondences& correspondences,
+                                       const Matrix4f& transformation, const Matrix4f& transformation_gt, float distance_thr, bool converged,
+                                       std::vector<uint8_t>* correct = nullptr) {
+    lgr_gt_eval e;
+    if (correct) correct->assign(correspondences.size(), 0);
+    check(lgr_evaluate_gt(context(), raw(src), (int) src.size(), raw(tgt), (int) tgt.size(), reinterpret_cast<const lgr_corr*>(correspondences.data()),
+                          (int) correspondences.size(), transformation.data(), transformation_gt.data(), distance_thr, converged ? 1 : 0, nullptr, &e,
+                          correct && !correct->empty() ? correct->data() : nullptr), "evaluateGroundTruth");
+    return e;
+}
+// src/analysis.cpp:30-43 (the point pass against an empty target: no neighbour is found; the threshold only has to be valid)
+inline float calculatePointCloudRmse(const PointNCloud::ConstPtr& pcd, const Matrix4f& transformation, const Matrix4f& transformation_gt) {
+    float rmse = 0.f, pcd_err = 0.f;
+    int n = 0;
+    check(lgr_overlap_rmse(context(), raw(*pcd), (int) pcd->size(), nullptr, 0, transformation.data(), transformation_gt.data(), 1.f, &rmse, &n,
+                           &pcd_err, nullptr), "calculatePointCloudRmse");
+    return pcd_err;
+}
+// src/analysis.cpp:45-88
+inline float calculateOverlapRmse(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& transformation,
+                                  const Matrix4f& transformation_gt, float inlier_threshold) {
+    float rmse = 0.f;
+    int n = 0;
+    check(lgr_overlap_rmse(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), transformation.data(), transformation_gt.data(),
+                           inlier_threshold, &rmse, &n, nullptr, nullptr), "calculateOverlapRmse");
+    return rmse;
+}
+// src/analysis.cpp:141-185 (without checkNormals' assert)
+inline float calculateNormalDifference(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, float distance_thr,
+                                       const Matrix4f& transformation_gt) {
+    float diff = 0.f;
+    int n = 0;
+    check(lgr_normal_difference(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), transformation_gt.data(), distance_thr, &diff, &n),
+          "calculateNormalDifference");
+    return diff;
+}
+// src/analysis.cpp:187-206
+inline void buildCorrectCorrespondences(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Correspondences& correspondences,
+                                        Correspondences& correct_correspondences, const Matrix4f& transformation_gt) {
+    std::vector<uint8_t> correct(correspondences.size(), 0);
+    int n3[3];
+    check(lgr_correct_correspondences(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(),
+                                      reinterpret_cast<const lgr_corr*>(correspondences.data()), (int) correspondences.size(), transformation_gt.data(),
+                                      nullptr, correct.empty() ? nullptr : correct.data(), n3), "buildCorrectCorrespondences");
+    correct_correspondences.clear();
+    correct_correspondences.reserve((size_t) n3[0]);
+    for (size_t i = 0; i < correspondences.size(); ++i)
+        if (correct[i]) correct_correspondences.push_back(correspondences[i]);
+}
+// src/common.cpp:558-591 (include/common.h:294): pcd1 is compared as it is (the caller has moved it already), so the ABI's ground truth is
+// the identity, which moves no finite point; dst = the kept rows of pcd1, then of pcd2, each in index order
+inline void mergeOverlaps(const PointNCloud::ConstPtr& pcd1, const PointNCloud::ConstPtr& pcd2, PointNCloud::Ptr& dst, float distance_thr) {
+    std::vector<uint8_t> m1(pcd1->size() + 1, 0), m2(pcd2->size() + 1, 0);
+    int n2[2];
+    float overlap = 0.f;
+    const Matrix4f I = Matrix4f::Identity();
+    check(lgr_merge_overlaps(context(), raw(*pcd1), (int) pcd1->size(), raw(*pcd2), (int) pcd2->size(), I.data(), distance_thr, m1.data(), m2.data(), n2,
+                             &overlap, nullptr), "mergeOverlaps");
+    dst->points.clear();
+    dst->points.reserve((size_t) n2[0] + (size_t) n2[1]);
+    for (size_t i = 0; i < pcd1->size(); ++i)
+        if (m1[i]) dst->points.push_back(pcd1->points[i]);
+    for (size_t i = 0; i < pcd2->size(); ++i)
+        if (m2[i]) dst->points.push_back(pcd2->points[i]);
+    dst->width = (unsigned) dst->points.size(); dst->height = 1;
+}
+
+// include/analysis.h:36-98.  start() prints nothing and writes no results.csv (the reference's print() / save()): the figures are read
+// through the getters and evaluation().
+class AlignmentAnalysis {
+public:
+    AlignmentAnalysis() {}
+    AlignmentAnalysis(AlignmentResult result, AlignmentParameters parameters) : parameters_(std::move(parameters)), result_(std::move(result)) {}
+    void start(const std::optional<Matrix4f>& transformation_gt, const std::string& testname) {
+        testname_ = testname;
+        has_gt_ = transformation_gt.has_value();
+        if (!has_gt_) return;
+        static const Correspondences none;
+        eval_ = evaluateGroundTruth(*result_.src, *result_.tgt, result_.correspondences ? *result_.correspondences : none, result_.transformation,
+                                    transformation_gt.value(), parameters_.distance_thr, result_.converged);
+    }
+    inline bool alignmentHasConverged() const { return result_.converged; }
+    inline Matrix4f getTransformation() const { return result_.transformation; }
+    inline float getRotationError() const { return has_gt_ ? eval_.r_err : nan_(); }
+    inline float getTranslationError() const { return has_gt_ ? eval_.t_err : nan_(); }
+    inline float getOverlapError() const { return has_gt_ ? eval_.overlap_rmse : nan_(); }
+    inline float getPointCloudError() const { return has_gt_ ? eval_.pcd_err : nan_(); }
+    inline float getRunningTime() const { return (float) (result_.time_cs + result_.time_te); }
+    inline const lgr_gt_eval& evaluation() const { return eval_; }   // every figure of start(), src/main.cpp:356's verdict included
+private:
+    static float nan_() { return std::numeric_limits<float>::quiet_NaN(); }
+    AlignmentParameters parameters_;
+    AlignmentResult result_;
+    lgr_gt_eval eval_{};
+    bool has_gt_ = false;
+    std::string testname_;
+};
 
 }  // namespace lgr

@@ -116,6 +116,19 @@ def metric_params(weight="constant", weights=None):
     return m
 
 
+class GtEval(C.Structure):
+    """lgr_gt_eval (include/lgr.h): an alignment judged against its ground truth.  Angles in radians."""
+    _fields_ = [("r_err", C.c_float), ("t_err", C.c_float), ("pcd_err", C.c_float), ("overlap_rmse", C.c_float), ("overlap_size", C.c_int32),
+                ("normal_diff", C.c_float), ("n_normal_overlap", C.c_int32), ("n_overlap_src", C.c_int32), ("n_overlap_tgt", C.c_int32),
+                ("n_overlap", C.c_int32), ("overlap", C.c_float), ("overlap_area", C.c_float), ("n_correspondences", C.c_int32),
+                ("n_correct_correspondences", C.c_int32), ("n_inliers", C.c_int32), ("n_correct_inliers", C.c_int32),
+                ("corr_uniformity", C.c_float), ("converged", C.c_int32), ("converged_and_overlap_ok", C.c_int32), ("reserved", C.c_int32 * 5)]
+    correct_mask = None   # numpy uint8 [c], set by Context.evaluate_gt*
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class LgrError(RuntimeError):
     pass
 
@@ -795,3 +808,65 @@ class Context:
             self.check(_lib.lgr_align_ex(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
                                          C.byref(res)))
         return res
+
+    # ---- ground-truth evaluation (src/analysis.cpp:218-246) --------------------------------------------------
+    @staticmethod
+    def _T16(T):
+        return (C.c_float * 16)(*np.asarray(T, np.float32).T.reshape(16).tolist())
+
+    def evaluate_gt(self, src, tgt, corr, T, T_gt, distance_thr, converged=True, inlier_mask=None):
+        """lgr_evaluate_gt_dev: src / tgt cuda float32 [n,12], corr a cuda int32 [c,4] tensor or a numpy CORR_DTYPE array, T / T_gt 4x4,
+        inlier_mask (optional) c bytes (numpy or cuda uint8).  Returns a GtEval with .correct_mask (numpy uint8 [c])."""
+        torch = self.torch
+        corr = self._corr_dev(corr)
+        c = corr.shape[0]
+        if isinstance(inlier_mask, np.ndarray):
+            inlier_mask = torch.from_numpy(np.ascontiguousarray(inlier_mask, np.uint8)).to(self._dev())
+        cm = self.empty((max(c, 1),), torch.uint8)
+        out = GtEval()
+        self.check(_lib.lgr_evaluate_gt_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), c, self._T16(T), self._T16(T_gt),
+                                            C.c_float(distance_thr), int(bool(converged)), _ptr(inlier_mask), C.byref(out), _ptr(cm)))
+        self._join()
+        out.correct_mask = cm[:c].cpu().numpy()
+        return out
+
+    def evaluate_gt_host(self, src, tgt, corr, T, T_gt, distance_thr, converged=True, inlier_mask=None):
+        """lgr_evaluate_gt: numpy in, GtEval out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        corr = np.ascontiguousarray(corr)
+        c = corr.shape[0]
+        im = None if inlier_mask is None else np.ascontiguousarray(inlier_mask, np.uint8)
+        cm = np.zeros(max(c, 1), np.uint8)
+        out = GtEval()
+        self.check(_lib.lgr_evaluate_gt(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), c, self._T16(T), self._T16(T_gt),
+                                        C.c_float(distance_thr), int(bool(converged)), _ptr(im), C.byref(out), _ptr(cm)))
+        out.correct_mask = cm[:c]
+        return out
+
+    def overlap_rmse(self, src, tgt, T, T_gt, distance_thr):
+        """lgr_overlap_rmse_dev -> (overlap_rmse, overlap_size, pcd_err, idx numpy int32 [ns]: the target point a source point was measured
+        against, -1 where it was skipped)"""
+        idx = self.empty((max(src.shape[0], 1),), self.torch.int32)
+        rm, n, pe = C.c_float(0), C.c_int(0), C.c_float(0)
+        self.check(_lib.lgr_overlap_rmse_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T), self._T16(T_gt),
+                                             C.c_float(distance_thr), C.byref(rm), C.byref(n), C.byref(pe), _ptr(idx)))
+        self._join()
+        return rm.value, n.value, pe.value, idx[: src.shape[0]].cpu().numpy()
+
+    def merge_overlaps(self, src, tgt, T_gt, distance_thr):
+        """lgr_merge_overlaps_dev -> dict(mask_src, mask_tgt (numpy uint8), n_overlap_src, n_overlap_tgt, overlap, overlap_area)"""
+        ms = self.empty((max(src.shape[0], 1),), self.torch.uint8); mt = self.empty((max(tgt.shape[0], 1),), self.torch.uint8)
+        n2 = (C.c_int * 2)()
+        ov, oa = C.c_float(0), C.c_float(0)
+        self.check(_lib.lgr_merge_overlaps_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T_gt), C.c_float(distance_thr),
+                                               _ptr(ms), _ptr(mt), n2, C.byref(ov), C.byref(oa)))
+        self._join()
+        return dict(mask_src=ms[: src.shape[0]].cpu().numpy(), mask_tgt=mt[: tgt.shape[0]].cpu().numpy(), n_overlap_src=n2[0], n_overlap_tgt=n2[1],
+                    overlap=ov.value, overlap_area=oa.value)
+
+    def normal_difference(self, src, tgt, T_gt, distance_thr):
+        """lgr_normal_difference_dev -> (median normal difference in radians, points it was taken over)"""
+        nd, n = C.c_float(0), C.c_int(0)
+        self.check(_lib.lgr_normal_difference_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T_gt), C.c_float(distance_thr),
+                                                  C.byref(nd), C.byref(n)))
+        return nd.value, n.value

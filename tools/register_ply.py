@@ -3,9 +3,12 @@
 
     python tools/register_ply.py source.ply target.ply [--keypoint iss|any] [--metric uniformity|combination|...]
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
+                                 [--ground-truth transformations_gt.csv NAME [--results results.csv]]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
+With --ground-truth: formats.get_transformation -> lgr_evaluate_gt (AlignmentAnalysis::start, src/analysis.cpp:218-246), printed in the
+order of AlignmentAnalysis::print (:248-272) and appended to results.csv as AlignmentAnalysis::save does (:274-328).
 """
 import argparse
 import os
@@ -33,6 +36,9 @@ def main():
     ap.add_argument("--distance-thr", type=float, default=0.0, help="<= 0: automatic, 4 x the larger cloud density (src/common.cpp:267)")
     ap.add_argument("--iterations", type=int, default=1000000)
     ap.add_argument("--out", default=None, help="transformations.csv to append to")
+    ap.add_argument("--ground-truth", nargs=2, metavar=("CSV", "NAME"), default=None,
+                    help="transformation CSV and the row that holds the ground truth: analyse the result against it")
+    ap.add_argument("--results", default="results.csv", help="results.csv the analysis row is appended to (with --ground-truth)")
     a = ap.parse_args()
 
     import numpy as np
@@ -62,9 +68,63 @@ def main():
     print(f"aligned in {1e3 * dt:.1f} ms: converged={res.converged} correspondences={res.n_correspondences} inliers={res.n_inliers} "
           f"metric={res.metric:.4f} iterations={res.iterations}")
     print(np.array2string(T, precision=6, suppress_small=True))
+    name = os.path.splitext(os.path.basename(a.source))[0] + "_" + os.path.splitext(os.path.basename(a.target))[0]
     if a.out:
-        name = os.path.splitext(os.path.basename(a.source))[0] + "_" + os.path.splitext(os.path.basename(a.target))[0]
         formats.save_transformation(a.out, name, T)
+    if a.ground_truth:
+        analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
+
+
+def analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
+    """AlignmentAnalysis::start / print / save for the alignment just made"""
+    import numpy as np
+    from lgr_amd import profile
+    T_gt = formats.get_transformation(a.ground_truth[0], a.ground_truth[1])
+    score = {v: k for k, v in profile.SCORE.items()}[p.score_id]
+    desc = a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf)
+    # the alignment's own correspondences: lgr_align hands none back, so the search (deterministic) runs once more here
+    corr = ctx.correspondences(clouds[0], clouds[1], p, descriptor=desc)
+    # metric, rmse and inliers of the final transformation (start: buildInliersAndEstimateMetric); the plane metrics have no
+    # correspondence inliers: their figures are the alignment's
+    inl, n_inl, rmse, metric = None, res.n_inliers, None, res.metric
+    if a.metric in ("uniformity", "correspondences"):
+        inl, n_inl, rmse, metric = ctx.evaluate(clouds[0], clouds[1], corr, T, metric_id=p.metric_id, score_id=p.score_id)
+    t = time.perf_counter()
+    e = ctx.evaluate_gt(clouds[0], clouds[1], corr, T, T_gt, p.distance_thr, bool(res.converged), inl)
+    dt = time.perf_counter() - t
+    deg = 180.0 / np.pi
+    print("\n Ground truth transformation:")
+    print(np.array2string(T_gt, precision=6, suppress_small=True))
+    print(f"converged: {'true' if res.converged else 'false'}")
+    print(f"metric: {metric:.7f}")
+    print("inliers_rmse: " + ("n/a (plane metric)" if rmse is None else f"{rmse:.7f}"))
+    print(f"correct inliers: {e.n_correct_inliers}/{n_inl}")
+    print(f"correct correspondences: {e.n_correct_correspondences}/{e.n_correspondences}")
+    print(f"rotation error (deg): {deg * e.r_err:.7f}")
+    print(f"translation error: {e.t_err:.7f}")
+    print(f"point cloud error: {e.pcd_err:.7f}")
+    print(f"median of normal differences (deg): {deg * e.normal_diff:.7f}")
+    print(f"uniformity of correct correspondences' distribution: {e.corr_uniformity:.7f}")
+    print(f"overlap error: {e.overlap_rmse:.7f} over {e.overlap_size} points; overlap: {e.overlap:.7f}, overlap area: {e.overlap_area:.7f}")
+    print(f"success (converged and overlap error < {p.distance_thr:.6g}): {'true' if e.converged_and_overlap_ok else 'false'}")
+    print(f"analysed in {1e3 * dt:.1f} ms")
+    row = formats.results_row(
+        version="lgr_amd", descriptor=a.descriptor, testname=name, metric=metric, rmse="" if rmse is None else rmse, correspondences=e.n_correspondences,
+        correct_correspondences=e.n_correct_correspondences, inliers=n_inl, correct_inliers=e.n_correct_inliers,
+        nr_points=p.feature_nr_points, distance_thr=p.distance_thr, edge_thr=p.edge_thr_coef, iteration=res.iterations,
+        matching_type=a.matching, randomness=p.randomness, r_err=e.r_err, t_err=e.t_err, pcd_err=e.pcd_err, normal_diff=e.normal_diff,
+        corr_uniformity=e.corr_uniformity, lrf_type=a.lrf, metric_type=a.metric, overlap_rmse=e.overlap_rmse, alignment_type=a.alignment,
+        keypoint_type=a.keypoint, time_cs=res.time_cs, time_te=res.time_te, score_type=score, iss_radius_src=p.iss_radius_src,
+        iss_radius_tgt=p.iss_radius_tgt, normal_nr_points=p.normal_nr_points, reestimate=0,   # (the device path has no frame re-estimation)
+        scale=p.scale_factor, cluster_k=p.cluster_k,
+        feature_radius=p.feature_radius if p.feature_radius > 0 else "", overlap=e.overlap, overlap_area=e.overlap_area,
+        converged=int(res.converged))
+    new = not os.path.exists(a.results)
+    with open(a.results, "a") as f:
+        if new:
+            f.write(formats.RESULTS_HEADER + "\n")
+        f.write(row + "\n")
+    print(f"appended the analysis row to {a.results}" + (" (new file)" if new else ""))
 
 
 if __name__ == "__main__":
