@@ -585,6 +585,59 @@ int lgr_normal_difference_dev(lgr_ctx*, const float* d_src, int ns, const float*
 int lgr_normal_difference(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float Tgt16[16], float distance_thr,
                           float* normal_diff, int* n_normal_overlap);   /* host twin */
 
+/* ---- ClosestPlaneMetricEstimator / WeightedClosestPlaneMetricEstimator::buildInliersAndEstimateMetric in their DENSE form, sparse = false
+ *      (src/metric.cpp:10-53,181-231 with calculateScore :55-81): every source point, in index order -- what AlignmentAnalysis::start
+ *      evaluates a finished alignment with (src/analysis.cpp:211,223) and estimateTestMetric writes to metrics.csv (src/main.cpp:41-116).
+ *      Per point the expressions are those of lgr_evaluate_plane_dev (the same point gets the same nearest target, distance and value
+ *      from either); score and the squared-error sum are the reference's serial f32 loops in ascending source index.
+ *      mp == NULL: closest_plane.  mp != NULL: weighted_closest_plane with the weights of mp (weight_id, or mp->weights: ns finite floats,
+ *      a device pointer for the _dev entry, a host pointer for the host twin); harris / tomasi return LGR_ERR_UNSUPPORTED.
+ *      inlier_threshold <= 0: calculatePointCloudDensity(tgt), as setTargetCloud does; > 0: used as given, so that a caller that evaluates
+ *      several transforms against one target pays for the density once (out->threshold of the first call).  NaN or > 1e18: LGR_ERR_INVALID_ARG.
+ *      ns == 0 or nt < 2: LGR_ERR_INVALID_ARG.  Point rows must be 16-byte aligned.
+ *      d_inliers (optional, room for ns): the reference's `inliers` vector, {source index, nearest target index, dist, threshold} in
+ *      ascending source index; out->n_inliers entries are written.  d_nn (optional, ns ints): the nearest target within 2 x threshold of
+ *      every moved source point, -1 where there is none (or the moved point is not finite) -- whether or not the point is an inlier. ---- */
+typedef struct {
+    int32_t n_inliers;
+    float   rmse;          /* sqrtf(sum dist^2 / n_inliers); FLT_MAX when there is no inlier (src/metric.cpp:49-52) */
+    float   metric;        /* score / ns, or score / weights_sum with weights (src/metric.cpp:199,214): the division in double */
+    float   threshold;     /* the inlier threshold used */
+    float   score;         /* calculateScore's sum, before the division */
+    int32_t reserved[3];   /* 0 */
+} lgr_plane_dense_eval;
+int lgr_evaluate_plane_dense_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16] /* host */, int score_id,
+                                 const lgr_metric_params* mp_or_null, float inlier_threshold, lgr_plane_dense_eval* out /* host */,
+                                 lgr_corr* d_inliers_or_null, int32_t* d_nn_or_null);
+int lgr_evaluate_plane_dense(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T16[16], int score_id,
+                             const lgr_metric_params* mp_or_null, float inlier_threshold, lgr_plane_dense_eval* out,
+                             lgr_corr* inliers_or_null, int32_t* nn_or_null);   /* host twin */
+
+/* ---- the first statement of AlignmentAnalysis::start plus buildCorrectInliers (src/analysis.cpp:211,223-224, src/metric.cpp:83-101) for
+ *      any metric_id: metric_estimator_->buildInliersAndEstimateMetric(T, inliers, rmse, metric, rand) with the DENSE estimator of
+ *      getMetricEstimatorFromParameters(parameters, false), then the inliers that are correct under the ground truth.
+ *        correspondences, uniformity       lgr_evaluate_dev; correct inliers = inlier mask && buildCorrectCorrespondences
+ *        closest_plane, weighted_...       lgr_evaluate_plane_dense_dev (mp: the weights, NULL = constant); correct inliers =
+ *                                          lgr_correct_correspondences_dev over the dense inlier list (each carries the plane threshold)
+ *        combination                       inliers and rmse of the correspondence estimator (constant score: CombinationMetricEstimator
+ *                                          default-constructs it); metric = metric_cs * metric_cp in f32, metric_cp the dense closest-plane
+ *                                          metric under score_id (src/metric.cpp:239-250); correct inliers as for correspondences
+ *      Tgt16 == NULL: no ground truth, n_correct_inliers = 0.
+ *      inlier_mask (optional, c bytes): the inlier mask of the correspondence estimator (correspondences, uniformity, combination; not written
+ *      under the plane metrics).  inliers (optional, room for ns): the dense inlier list of the plane metrics, n_inliers entries (not written
+ *      under the other metrics). ---- */
+typedef struct {
+    float   metric, rmse;
+    int32_t n_inliers, n_correct_inliers;
+    int32_t reserved[4];   /* 0 */
+} lgr_metric_eval;
+int lgr_analysis_metric_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c, const float T16[16] /* host */,
+                            const float* Tgt16_or_null /* host */, int metric_id, int score_id, const lgr_metric_params* mp_or_null,
+                            lgr_metric_eval* out /* host */, uint8_t* d_inlier_mask_or_null, lgr_corr* d_inliers_or_null);
+int lgr_analysis_metric(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float T16[16],
+                        const float* Tgt16_or_null, int metric_id, int score_id, const lgr_metric_params* mp_or_null, lgr_metric_eval* out,
+                        uint8_t* inlier_mask_or_null, lgr_corr* inliers_or_null);   /* host twin */
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,8 +13,6 @@
 //     (a skipped point's term is +0, which leaves a sum of non-negative terms unchanged); counts are integers (order free);
 //   * the median of the normal differences is the element of rank n / 2 of the ascending values (a radix sort of their bit patterns:
 //     all of them are >= 0); a NaN difference does not count (the reference's `diff >= 0.f` filter drops it too).
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -22,10 +20,11 @@
 #include "lgr_grid.cuh"
 #include "lgr_internal.h"
 #include "lgr_libm.cuh"
+#include "lgr_pointpass.cuh"
 
 namespace {
 
-constexpr int AB = 256;
+constexpr int AB = PP_BLOCK;
 constexpr float GT_PI = 3.14159274101257324f;   // (float) M_PI
 
 struct GtMats { float T[16], G[16], D[16]; };   // estimate, ground truth, D = T^-1 * G (column-major)
@@ -44,30 +43,6 @@ __device__ __forceinline__ void so3(const float* __restrict__ M, float x, float 
 __device__ __forceinline__ float sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 __device__ __forceinline__ bool fin(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
-
-// nearest grid point within r2 of p: sorted position or -1.  The candidate loop has no branch on the candidate: every lane offers every
-// candidate of its cells and keeps the better one by selects, so a wave never serialises on which lanes found something.
-__device__ __forceinline__ int nearest_within(const GridDev& g, float px, float py, float pz, float r2, float& best_d2, int& best_idx) {
-    int nn = -1, nn_t = -1;
-    float best = 0.f;
-    if (g.n > 0 && lgr_finite3(px, py, pz))
-        lgr_visit27(g, px, py, pz, [&](int t, const float4& Q) {
-            const float d2 = lgr_dist2(px, py, pz, Q.x, Q.y, Q.z);
-            const int qi = __float_as_int(Q.w);
-            const bool take = (d2 < r2) && (nn < 0 || d2 < best || (d2 == best && qi < nn));
-            nn = take ? qi : nn;
-            nn_t = take ? t : nn_t;
-            best = take ? d2 : best;
-        });
-    best_d2 = best;
-    best_idx = nn;
-    return nn_t;
-}
-
-__device__ __forceinline__ void wave_count(bool f, int* counter) {
-    const unsigned long long m = __ballot(f);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(counter, __popcll(m));
-}
 
 // Quantities 2, 3 and 6 in one launch: thread i handles source point i (its point-cloud term, its overlap term after ONE grid walk) and
 // correspondence i.  counters: [0] overlap_size, [1] correct correspondences, [2] correct inliers, [3] inliers.
@@ -185,44 +160,7 @@ __global__ __launch_bounds__(AB) void gt_normal_diff_kernel(const float4* __rest
     wave_count(counted, counter);
 }
 
-// Sequential f32 sums in index order, one workgroup per job: lane 0 adds tile k (one dependent chain, float4 reads from LDS) while waves
-// 1-3 stage tile k + 1.  sq: the term is v * v (the squared smoothed densities of src/analysis.cpp:232).
-constexpr int GT_SUM_TILE = 4096, GT_SUM_JOBS = 4;
-struct GtSumJobs { const float* p[GT_SUM_JOBS]; int n[GT_SUM_JOBS]; int sq[GT_SUM_JOBS]; };
-__global__ __launch_bounds__(AB) void gt_seqsum_kernel(GtSumJobs jobs, float* __restrict__ out) {
-    __shared__ float4 tile[2][GT_SUM_TILE / 4];
-    const float* __restrict__ w = jobs.p[blockIdx.x];
-    const int n = jobs.n[blockIdx.x];
-    const bool sq = jobs.sq[blockIdx.x] != 0;
-    float sum = 0.f;
-    auto stage = [&](int b, int k, int t0, int stride) {
-        float* dst = (float*) tile[k];
-        const int len = min(GT_SUM_TILE, n - b);
-        for (int t = t0; t < len; t += stride) {
-            const float v = w[b + t];
-            dst[t] = sq ? v * v : v;
-        }
-    };
-    stage(0, 0, threadIdx.x, AB);
-    __syncthreads();
-    int k = 0;
-    for (int b = 0; b < n; b += GT_SUM_TILE, k ^= 1) {
-        if (threadIdx.x >= 64) {
-            if (b + GT_SUM_TILE < n) stage(b + GT_SUM_TILE, k ^ 1, threadIdx.x - 64, AB - 64);
-        } else if (threadIdx.x == 0) {
-            const int len = min(GT_SUM_TILE, n - b), n4 = len >> 2;
-            const float4* t = tile[k];
-#pragma unroll 8
-            for (int q = 0; q < n4; ++q) {
-                const float4 v = t[q];
-                sum += v.x; sum += v.y; sum += v.z; sum += v.w;
-            }
-            for (int r = 4 * n4; r < len; ++r) sum += ((const float*) t)[r];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sum;
-}
+// (the sequential f32 sum jobs -- GtSumJobs, gt_seqsum_kernel -- are in lgr_pointpass.cuh)
 
 // compaction of the overlap cloud: flags of [aligned source | target] in index order, then the kept rows
 __global__ __launch_bounds__(AB) void gt_flags_kernel(const uint8_t* __restrict__ ma, int na, const uint8_t* __restrict__ mb, int nb, int* __restrict__ flags) {
@@ -396,11 +334,7 @@ int run_merge(lgr_ctx* ctx, const GtState& st, const GridDev& gt, const float* d
     *overlap = (float) no / (float) (ns + nt);
     if (!overlap_area || no < 2 || ns < 2) return LGR_OK;   // calculateSmoothedDensities would rassert (src/common.cpp:532)
     gt_flags_kernel<<<cdiv((long long) n, AB), AB, 0, ctx->stream>>>(d_mask_src, ns, d_mask_tgt, nt, flags);
-    size_t tb = 0;
-    LGR_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, flags, pos, 0, n, rocprim::plus<int>(), ctx->stream));
-    void* tmp;
-    LGR_TRY(lgr_ws(ctx, WS_GRID_TMP, tb, &tmp));
-    LGR_HIP(ctx, rocprim::exclusive_scan(tmp, tb, flags, pos, 0, n, rocprim::plus<int>(), ctx->stream));
+    LGR_TRY(pp_scan_flags(ctx, flags, pos, n));
     float *d_ov, *d_dens;
     LGR_TRY(lgr_ws_t(ctx, WS_GT_OVERLAP, (size_t) 12 * no + 16, &d_ov));
     LGR_TRY(lgr_ws_t(ctx, WS_GT_DENS, (size_t) std::max(no, ns) + 16, &d_dens));

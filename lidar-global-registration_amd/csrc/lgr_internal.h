@@ -126,6 +126,7 @@ enum {
     WS_ROPS_MASKED, WS_ROPS_LRF, WS_ROPS_KPS,
     WS_WEIGHTS, WS_WEIGHTS_KNN, WS_WEIGHTS_TMP, WS_WEIGHTS_VALS, WS_WEIGHTS_SUM, WS_WEIGHTS_HOST,
     WS_GT_MISC, WS_GT_TERMS, WS_GT_ALIGNED, WS_GT_OVERLAP, WS_GT_FLAGS, WS_GT_KNN, WS_GT_DENS, WS_GT_CORR,   // lgr_analysis.hip
+    WS_PD_TERMS, WS_PD_MISC, WS_PD_INLIERS, WS_PD_MASK,   // lgr_plane_dense.hip
     WS_COUNT
 };
 static_assert(WS_COUNT <= 128, "grow lgr_ctx::ws");

@@ -24,10 +24,12 @@
 #pragma once
 #include <array>
 #include <cctype>
+#include <cmath>
 #include <cstring>
 #include <limits>
 #include <memory>
 #include <optional>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -554,15 +556,192 @@ inline void mergeOverlaps(const PointNCloud::ConstPtr& pcd1, const PointNCloud::
     dst->width = (unsigned) dst->points.size(); dst->height = 1;
 }
 
+// ---- include/utils.h:13-25, include/metric.h: the metric estimators in their DENSE form (sparse = false), the form AlignmentAnalysis and
+//      estimateTestMetric use.  The dense evaluations draw no random numbers: `rand` is accepted and never called.
+class UniformRandIntGenerator {
+public:
+    UniformRandIntGenerator(const int min, const int max, std::mt19937::result_type seed = std::random_device{}()) : dist_(min, max), gen_(seed) {}
+    int operator()() { return dist_(gen_); }
+private:
+    std::uniform_int_distribution<int> dist_;
+    std::mt19937 gen_;
+};
+
+enum ScoreFunction { Constant, MAE, MSE, EXP };
+
+inline int weight_abi(const std::string& w) {   // unknown names fall back to constant, as getWeightFunction does (src/weights.cpp:27-44)
+    return w == "exp_curvature" ? LGR_WEIGHT_EXP_CURVATURE : w == "curvedness" ? LGR_WEIGHT_CURVEDNESS : w == "harris" ? LGR_WEIGHT_HARRIS
+           : w == "tomasi" ? LGR_WEIGHT_TOMASI : w == "curvature" ? LGR_WEIGHT_CURVATURE : w == "nss" ? LGR_WEIGHT_NSS : LGR_WEIGHT_CONSTANT;
+}
+
+class MetricEstimator {
+public:
+    using Ptr = std::shared_ptr<MetricEstimator>;
+    using ConstPtr = std::shared_ptr<const MetricEstimator>;
+    explicit MetricEstimator(ScoreFunction score_function = ScoreFunction::Constant) : score_function_(score_function) {}
+    virtual ~MetricEstimator() = default;
+    virtual float getInitialMetric() const { return 0.0f; }
+    virtual float getMinTolerableMetric() const { return 0.0f; }
+    virtual void buildInliersAndEstimateMetric(const Matrix4f& transformation, Correspondences& inliers, float& rmse, float& metric,
+                                               UniformRandIntGenerator& rand) const = 0;
+    // src/metric.cpp:83-101: the same test as buildCorrectCorrespondences (src/analysis.cpp:187-206), over the inliers
+    virtual void buildCorrectInliers(const Correspondences& inliers, Correspondences& correct_inliers, const Matrix4f& transformation_gt) const {
+        buildCorrectCorrespondences(src_, tgt_, inliers, correct_inliers, transformation_gt);
+    }
+    virtual inline void setCorrespondences(const CorrespondencesConstPtr& correspondences) { correspondences_ = correspondences; }
+    virtual inline void setSourceCloud(const PointNCloud::ConstPtr& src) { src_ = src; }
+    virtual inline void setTargetCloud(const PointNCloud::ConstPtr& tgt) { tgt_ = tgt; }
+    virtual std::string getClassName() const = 0;
+
+protected:
+    // lgr_analysis_metric under metric_id for this estimator's clouds, correspondences and score.  The inliers of the plane metrics are the
+    // device's list; those of the correspondence estimator are the correspondences the device's mask marks, their distance recomputed here
+    // in f32 as |T p - q| (the device reports the mask, the count and the sums, not the distances)
+    void evaluate(int metric_id, int score_id, const lgr_metric_params* mp, const Matrix4f& transformation, Correspondences& inliers, float& rmse,
+                  float& metric) const {
+        if (!src_ || !tgt_) throw std::runtime_error("lgr: MetricEstimator: setSourceCloud / setTargetCloud first");
+        static const Correspondences none;
+        const Correspondences& corr = correspondences_ ? *correspondences_ : none;
+        const bool plane = metric_id == LGR_METRIC_CLOSEST_PLANE || metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE;
+        std::vector<uint8_t> mask(corr.size() + 1, 0);
+        std::vector<lgr_corr> list(plane ? src_->size() + 1 : 1);
+        lgr_metric_eval e;
+        check(lgr_analysis_metric(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(), reinterpret_cast<const lgr_corr*>(corr.data()),
+                                  (int) corr.size(), transformation.data(), nullptr, metric_id, score_id, mp, &e, plane ? nullptr : mask.data(),
+                                  plane ? list.data() : nullptr), getClassName().c_str());
+        rmse = e.rmse;
+        metric = e.metric;
+        inliers.clear();
+        inliers.reserve((size_t) e.n_inliers);
+        if (plane) {
+            for (int i = 0; i < e.n_inliers; ++i) inliers.emplace_back(list[i].index_query, list[i].index_match, list[i].distance, list[i].threshold);
+            return;
+        }
+        const float* T = transformation.data();
+        for (size_t i = 0; i < corr.size(); ++i) {
+            if (!mask[i]) continue;
+            const float* p = raw(*src_) + 12 * (size_t) corr[i].index_query;
+            const float* q = raw(*tgt_) + 12 * (size_t) corr[i].index_match;
+            float d[3];
+            for (int r = 0; r < 3; ++r) d[r] = (((T[r] * p[0] + T[4 + r] * p[1]) + T[8 + r] * p[2]) + T[12 + r]) - q[r];
+            inliers.emplace_back(corr[i].index_query, corr[i].index_match, std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]), corr[i].threshold);
+        }
+    }
+    int score_abi() const {
+        return score_function_ == MAE ? LGR_SCORE_MAE : score_function_ == MSE ? LGR_SCORE_MSE : score_function_ == EXP ? LGR_SCORE_EXP : LGR_SCORE_CONSTANT;
+    }
+    static void refuse_sparse(bool sparse) {
+        // the sparse 1 % subset of this path is defined by Philox and a per-hypothesis counter, which this signature cannot carry
+        if (sparse) throw std::invalid_argument("lgr: the sparse closest-plane estimator takes a Philox counter: call lgr_evaluate_plane_dev "
+                                                "(lgr_evaluate_plane_weighted_dev) instead");
+    }
+    CorrespondencesConstPtr correspondences_;
+    PointNCloud::ConstPtr src_, tgt_;
+    ScoreFunction score_function_;
+};
+
+class CorrespondencesMetricEstimator : public MetricEstimator {
+public:
+    explicit CorrespondencesMetricEstimator(ScoreFunction score_function = ScoreFunction::Constant) : MetricEstimator(score_function) {}
+    void buildInliersAndEstimateMetric(const Matrix4f& transformation, Correspondences& inliers, float& rmse, float& metric,
+                                       UniformRandIntGenerator&) const override {
+        evaluate(LGR_METRIC_CORRESPONDENCES, score_abi(), nullptr, transformation, inliers, rmse, metric);
+    }
+    inline std::string getClassName() const override { return "CorrespondencesMetricEstimator"; }
+};
+
+class UniformityMetricEstimator : public CorrespondencesMetricEstimator {
+public:
+    UniformityMetricEstimator() : CorrespondencesMetricEstimator(ScoreFunction::Constant) {}
+    inline float getMinTolerableMetric() const override { return 0.3f; }
+    void buildInliersAndEstimateMetric(const Matrix4f& transformation, Correspondences& inliers, float& rmse, float& metric,
+                                       UniformRandIntGenerator&) const override {
+        evaluate(LGR_METRIC_UNIFORMITY, score_abi(), nullptr, transformation, inliers, rmse, metric);
+    }
+};
+
+class ClosestPlaneMetricEstimator : public MetricEstimator {
+public:
+    explicit ClosestPlaneMetricEstimator(bool sparse = false, ScoreFunction score_function = ScoreFunction::Constant) : MetricEstimator(score_function) {
+        refuse_sparse(sparse);
+    }
+    void buildInliersAndEstimateMetric(const Matrix4f& transformation, Correspondences& inliers, float& rmse, float& metric,
+                                       UniformRandIntGenerator&) const override {
+        evaluate(LGR_METRIC_CLOSEST_PLANE, score_abi(), nullptr, transformation, inliers, rmse, metric);
+    }
+    inline std::string getClassName() const override { return "ClosestPlaneMetricEstimator"; }
+};
+
+class WeightedClosestPlaneMetricEstimator : public MetricEstimator {
+public:
+    WeightedClosestPlaneMetricEstimator() = delete;
+    // nr_points: the library computes the weights with k = 30 neighbours, the reference's NORMAL_NR_POINTS -- the only value it is ever called with
+    WeightedClosestPlaneMetricEstimator(std::string weight_id, int nr_points, bool sparse = false, ScoreFunction score_function = ScoreFunction::Constant)
+        : MetricEstimator(score_function), weight_id_(std::move(weight_id)) {
+        refuse_sparse(sparse);
+        if (nr_points != 30) throw std::invalid_argument("lgr: WeightedClosestPlaneMetricEstimator: nr_points must be 30 (NORMAL_NR_POINTS)");
+    }
+    void buildInliersAndEstimateMetric(const Matrix4f& transformation, Correspondences& inliers, float& rmse, float& metric,
+                                       UniformRandIntGenerator&) const override {
+        lgr_metric_params m;
+        lgr_default_metric_params(&m);
+        m.weight_id = weight_abi(weight_id_);
+        evaluate(LGR_METRIC_WEIGHTED_CLOSEST_PLANE, score_abi(), &m, transformation, inliers, rmse, metric);
+    }
+    inline std::string getClassName() const override { return "WeightedClosestPlaneMetricEstimator"; }
+protected:
+    std::string weight_id_;
+};
+
+class CombinationMetricEstimator : public MetricEstimator {
+public:
+    explicit CombinationMetricEstimator(bool sparse = false, ScoreFunction score_function = ScoreFunction::Constant) : MetricEstimator(score_function) {
+        refuse_sparse(sparse);
+    }
+    // inliers and rmse of the correspondence estimator (constant score), metric = metric_cs * metric_cp (src/metric.cpp:239-250)
+    void buildInliersAndEstimateMetric(const Matrix4f& transformation, Correspondences& inliers, float& rmse, float& metric,
+                                       UniformRandIntGenerator&) const override {
+        evaluate(LGR_METRIC_COMBINATION, score_abi(), nullptr, transformation, inliers, rmse, metric);
+    }
+    inline std::string getClassName() const override { return "CombinationMetricEstimator"; }
+};
+
+// src/metric.cpp:270-301.  sparse = true throws (std::invalid_argument, naming lgr_evaluate_plane_dev) for the plane-based estimators
+inline MetricEstimator::Ptr getMetricEstimatorFromParameters(const AlignmentParameters& parameters, bool sparse = false) {
+    const std::string& s = parameters.score_id;
+    const ScoreFunction score_function = s == "mae" ? ScoreFunction::MAE : s == "mse" ? ScoreFunction::MSE : s == "exp" ? ScoreFunction::EXP : ScoreFunction::Constant;
+    if (parameters.metric_id == "uniformity") return std::make_shared<UniformityMetricEstimator>();
+    if (parameters.metric_id == "closest_plane") return std::make_shared<ClosestPlaneMetricEstimator>(sparse, score_function);
+    if (parameters.metric_id == "weighted_closest_plane")
+        return std::make_shared<WeightedClosestPlaneMetricEstimator>(parameters.weight_id, 30 /* NORMAL_NR_POINTS */, sparse, score_function);
+    if (parameters.metric_id == "combination") return std::make_shared<CombinationMetricEstimator>(sparse, score_function);
+    return std::make_shared<CorrespondencesMetricEstimator>(score_function);   // unknown ids too (with a warning in the reference)
+}
+
 // include/analysis.h:36-98.  start() prints nothing and writes no results.csv (the reference's print() / save()): the figures are read
-// through the getters and evaluation().
+// through the getters, evaluation() and its neighbours metric(), rmse(), inliers(), correctInliers().
 class AlignmentAnalysis {
 public:
     AlignmentAnalysis() {}
-    AlignmentAnalysis(AlignmentResult result, AlignmentParameters parameters) : parameters_(std::move(parameters)), result_(std::move(result)) {}
+    // src/analysis.cpp:208-216: the estimator is the dense one of the parameters' metric
+    AlignmentAnalysis(AlignmentResult result, AlignmentParameters parameters) : parameters_(std::move(parameters)), result_(std::move(result)) {
+        metric_estimator_ = getMetricEstimatorFromParameters(parameters_);
+        metric_estimator_->setSourceCloud(result_.src);
+        metric_estimator_->setTargetCloud(result_.tgt);
+        metric_estimator_->setCorrespondences(result_.correspondences);
+    }
     void start(const std::optional<Matrix4f>& transformation_gt, const std::string& testname) {
         testname_ = testname;
         has_gt_ = transformation_gt.has_value();
+        // :222-223, with or without a ground truth (clouds the dense plane evaluation cannot take -- none, an empty source, fewer than two
+        // target points -- leave metric 0, rmse FLT_MAX and no inliers)
+        inliers_.clear(); correct_inliers_.clear();
+        metric_ = 0.f; rmse_ = std::numeric_limits<float>::max();
+        if (metric_estimator_ && result_.src && result_.tgt && result_.src->size() > 0 && result_.tgt->size() > 1) {
+            UniformRandIntGenerator rand(0, std::numeric_limits<int>::max(), 566 /* SEED */);
+            metric_estimator_->buildInliersAndEstimateMetric(result_.transformation, inliers_, rmse_, metric_, rand);
+            if (has_gt_) metric_estimator_->buildCorrectInliers(inliers_, correct_inliers_, transformation_gt.value());   // :236
+        }
         if (!has_gt_) return;
         static const Correspondences none;
         eval_ = evaluateGroundTruth(*result_.src, *result_.tgt, result_.correspondences ? *result_.correspondences : none, result_.transformation,
@@ -575,12 +754,21 @@ public:
     inline float getOverlapError() const { return has_gt_ ? eval_.overlap_rmse : nan_(); }
     inline float getPointCloudError() const { return has_gt_ ? eval_.pcd_err : nan_(); }
     inline float getRunningTime() const { return (float) (result_.time_cs + result_.time_te); }
+    inline MetricEstimator::Ptr getMetricEstimator() { return metric_estimator_; }
     inline const lgr_gt_eval& evaluation() const { return eval_; }   // every figure of start(), src/main.cpp:356's verdict included
+    // start()'s first statement and buildCorrectInliers.  The reference keeps these four private and only streams them (print, results.csv)
+    inline float metric() const { return metric_; }
+    inline float rmse() const { return rmse_; }
+    inline const Correspondences& inliers() const { return inliers_; }
+    inline const Correspondences& correctInliers() const { return correct_inliers_; }
 private:
     static float nan_() { return std::numeric_limits<float>::quiet_NaN(); }
     AlignmentParameters parameters_;
     AlignmentResult result_;
     lgr_gt_eval eval_{};
+    MetricEstimator::Ptr metric_estimator_;
+    Correspondences inliers_, correct_inliers_;
+    float metric_ = 0.f, rmse_ = std::numeric_limits<float>::max();
     bool has_gt_ = false;
     std::string testname_;
 };

@@ -129,6 +129,19 @@ class GtEval(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class PlaneDenseEval(C.Structure):
+    """lgr_plane_dense_eval (include/lgr.h): the dense closest-plane evaluation of one transform."""
+    _fields_ = [("n_inliers", C.c_int32), ("rmse", C.c_float), ("metric", C.c_float), ("threshold", C.c_float), ("score", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+    inliers = None   # numpy CORR_DTYPE [n_inliers] (with_inliers), set by Context.evaluate_plane_dense*
+    nn = None        # numpy int32 [ns] (with_nn)
+
+
+class MetricEval(C.Structure):
+    """lgr_metric_eval (include/lgr.h): metric, rmse, inliers and correct inliers of an alignment under any metric_id."""
+    _fields_ = [("metric", C.c_float), ("rmse", C.c_float), ("n_inliers", C.c_int32), ("n_correct_inliers", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class LgrError(RuntimeError):
     pass
 
@@ -870,3 +883,104 @@ class Context:
         self.check(_lib.lgr_normal_difference_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T_gt), C.c_float(distance_thr),
                                                   C.byref(nd), C.byref(n)))
         return nd.value, n.value
+
+    def correct_correspondences(self, src, tgt, corr, T_gt, inlier_mask=None):
+        """lgr_correct_correspondences_dev -> (correct mask numpy uint8 [c], n_correct, n_correct_inliers, n_inliers)"""
+        torch = self.torch
+        corr = self._corr_dev(corr)
+        c = corr.shape[0]
+        if isinstance(inlier_mask, np.ndarray):
+            inlier_mask = torch.from_numpy(np.ascontiguousarray(inlier_mask, np.uint8)).to(self._dev())
+        cm = self.empty((max(c, 1),), torch.uint8)
+        n3 = (C.c_int * 3)()
+        self.check(_lib.lgr_correct_correspondences_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), c, self._T16(T_gt),
+                                                        _ptr(inlier_mask), _ptr(cm), n3))
+        self._join()
+        return cm[:c].cpu().numpy(), n3[0], n3[1], n3[2]
+
+    # ---- the dense closest-plane evaluation (src/metric.cpp:10-53,181-231, sparse = false) and the analysis layer's metric figures ----
+    @staticmethod
+    def _mparams(weights, weight):
+        """None (closest_plane) or a MetricParams: caller weights (numpy for host entries, cuda for _dev) or the map named by weight"""
+        if weights is None and weight is None:
+            return None
+        return metric_params("constant" if weight is None else weight, weights)
+
+    def evaluate_plane_dense(self, src, tgt, T, score_id=SCORE_CONSTANT, weights=None, weights_sum=None, weight=None, threshold=0.0, with_inliers=False,
+                             with_nn=False):
+        """lgr_evaluate_plane_dense_dev on cuda clouds [n, 12].  weights: cuda float32 [ns] (weighted_closest_plane with a caller's map), or
+        weight: the name / id of a built map ('curvature', ...); neither: closest_plane.  The library takes the metric's denominator from the
+        weights itself (their sequential f32 sum); weights_sum is accepted for symmetry with evaluate_plane_weighted and must equal that sum
+        when given.  threshold <= 0: the target's density; > 0: used as given.  Returns a PlaneDenseEval with .inliers (numpy CORR_DTYPE
+        [n_inliers]) and .nn (numpy int32 [ns], -1 = no target in range) when asked for."""
+        torch = self.torch
+        ns = src.shape[0]
+        if weights is not None:
+            weights = weights.contiguous()
+            if weights_sum is not None:
+                s = self._weights_sum(weights)
+                if np.float32(s).view(np.uint32) != np.float32(weights_sum).view(np.uint32):
+                    raise ValueError(f"weights_sum {weights_sum!r} is not the sequential f32 sum of the weights ({s!r})")
+        mp = self._mparams(weights, weight)
+        inl = self.empty((max(ns, 1), 4), torch.int32) if with_inliers else None
+        nn = self.empty((max(ns, 1),), torch.int32) if with_nn else None
+        out = PlaneDenseEval()
+        self.check(_lib.lgr_evaluate_plane_dense_dev(self.h, _ptr(src), ns, _ptr(tgt), tgt.shape[0], self._T16(T), int(score_id),
+                                                     C.byref(mp) if mp is not None else None, C.c_float(threshold), C.byref(out), _ptr(inl), _ptr(nn)))
+        self._join()
+        if with_inliers:
+            out.inliers = inl[: out.n_inliers].cpu().numpy().view(CORR_DTYPE).reshape(-1)
+        if with_nn:
+            out.nn = nn[:ns].cpu().numpy()
+        return out
+
+    @staticmethod
+    def _weights_sum(weights):
+        """the sequential f32 sum of cuda weights in index order (numpy's accumulate adds one element after the other)"""
+        w = weights.cpu().numpy().astype(np.float32)
+        return np.add.accumulate(w, dtype=np.float32)[-1] if len(w) else np.float32(0)
+
+    def evaluate_plane_dense_host(self, src, tgt, T, score_id=SCORE_CONSTANT, weights=None, weights_sum=None, weight=None, threshold=0.0,
+                                  with_inliers=False, with_nn=False):
+        """lgr_evaluate_plane_dense: numpy in (weights a numpy float32 [ns]), PlaneDenseEval out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        ns = src.shape[0]
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.float32)
+        mp = self._mparams(weights, weight)
+        inl = np.zeros(max(ns, 1), CORR_DTYPE) if with_inliers else None
+        nn = np.zeros(max(ns, 1), np.int32) if with_nn else None
+        out = PlaneDenseEval()
+        self.check(_lib.lgr_evaluate_plane_dense(self.h, _ptr(src), ns, _ptr(tgt), tgt.shape[0], self._T16(T), int(score_id),
+                                                 C.byref(mp) if mp is not None else None, C.c_float(threshold), C.byref(out), _ptr(inl), _ptr(nn)))
+        if with_inliers:
+            out.inliers = inl[: out.n_inliers].copy()
+        if with_nn:
+            out.nn = nn[:ns].copy()
+        return out
+
+    def analysis_metric(self, src, tgt, corr, T, T_gt=None, metric_id=METRIC_UNIFORMITY, score_id=SCORE_MSE, weights=None, weight=None):
+        """lgr_analysis_metric_dev: what AlignmentAnalysis::start's first statement and buildCorrectInliers yield under metric_id -> MetricEval
+        (T_gt None: n_correct_inliers = 0).  weights / weight: the point weights of weighted_closest_plane (neither: constant)."""
+        corr = self._corr_dev(corr)
+        if weights is not None:
+            weights = weights.contiguous()
+        mp = self._mparams(weights, weight)
+        out = MetricEval()
+        self.check(_lib.lgr_analysis_metric_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), corr.shape[0], self._T16(T),
+                                                self._T16(T_gt) if T_gt is not None else None, int(metric_id), int(score_id),
+                                                C.byref(mp) if mp is not None else None, C.byref(out), None, None))
+        return out
+
+    def analysis_metric_host(self, src, tgt, corr, T, T_gt=None, metric_id=METRIC_UNIFORMITY, score_id=SCORE_MSE, weights=None, weight=None):
+        """lgr_analysis_metric: numpy in, MetricEval out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        corr = np.ascontiguousarray(corr)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.float32)
+        mp = self._mparams(weights, weight)
+        out = MetricEval()
+        self.check(_lib.lgr_analysis_metric(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), corr.shape[0], self._T16(T),
+                                            self._T16(T_gt) if T_gt is not None else None, int(metric_id), int(score_id),
+                                            C.byref(mp) if mp is not None else None, C.byref(out), None, None))
+        return out

@@ -29,6 +29,7 @@ RESULTS_HEADER = ("version,descriptor,testname,metric,rmse,correspondences,corre
                   "corr_uniformity,lrf_type,metric_type,overlap_rmse,alignment_type,keypoint_type,time_cs,time_te,score_type,"
                   "iss_radius_src,iss_radius_tgt,normal_nr_points,reestimate,scale,cluster_k,feature_radius,"
                   "overlap,overlap_area,converged")
+METRICS_HEADER = "testname,metric_corr,metric_icp,inliers_corr,inliers_icp,metric_corr_gt,metric_icp_gt,inliers_corr_gt,inliers_icp_gt"
 
 
 def _g(v):
@@ -204,3 +205,13 @@ def results_row(**kw):
     if unknown:
         raise KeyError(sorted(unknown))
     return ",".join(_g(kw[c]) if c in kw and not isinstance(kw[c], str) else (kw.get(c, "")) for c in cols)
+
+
+def metrics_row(testname, found, gt):
+    """One row of metrics.csv as estimateTestMetric streams it (src/main.cpp:105-114): the test name, then for the found transformation and for
+    the ground truth `metric_corr, metric_icp, inliers_corr, inliers_icp` (floats as ostream << float prints them).  found / gt: tuples in
+    that order."""
+    out = [testname]
+    for m_corr, m_icp, n_corr, n_icp in (found, gt):
+        out += [_g(float(m_corr)), _g(float(m_icp)), _g(int(n_corr)), _g(int(n_icp))]
+    return ",".join(out)

@@ -3,12 +3,14 @@
 
     python tools/register_ply.py source.ply target.ply [--keypoint iss|any] [--metric uniformity|combination|...]
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
-                                 [--ground-truth transformations_gt.csv NAME [--results results.csv]]
+                                 [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
-With --ground-truth: formats.get_transformation -> lgr_evaluate_gt (AlignmentAnalysis::start, src/analysis.cpp:218-246), printed in the
-order of AlignmentAnalysis::print (:248-272) and appended to results.csv as AlignmentAnalysis::save does (:274-328).
+With --ground-truth: formats.get_transformation -> lgr_analysis_metric (the dense metric estimator of start's first statement, every
+metric) + lgr_evaluate_gt (AlignmentAnalysis::start, src/analysis.cpp:218-246), printed in the order of AlignmentAnalysis::print (:248-272)
+and appended to results.csv as AlignmentAnalysis::save does (:274-328).  With --metrics-csv as well: estimateTestMetric's row
+(src/main.cpp:41-116) -- the correspondence metric and the dense closest-plane metric of the found transformation and of the ground truth.
 """
 import argparse
 import os
@@ -39,7 +41,10 @@ def main():
     ap.add_argument("--ground-truth", nargs=2, metavar=("CSV", "NAME"), default=None,
                     help="transformation CSV and the row that holds the ground truth: analyse the result against it")
     ap.add_argument("--results", default="results.csv", help="results.csv the analysis row is appended to (with --ground-truth)")
+    ap.add_argument("--metrics-csv", default=None, help="metrics.csv estimateTestMetric's row is appended to (needs --ground-truth)")
     a = ap.parse_args()
+    if a.metrics_csv and not a.ground_truth:
+        ap.error("--metrics-csv needs --ground-truth")
 
     import numpy as np
     from lgr_amd import capi, formats, profile
@@ -84,21 +89,21 @@ def analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
     desc = a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf)
     # the alignment's own correspondences: lgr_align hands none back, so the search (deterministic) runs once more here
     corr = ctx.correspondences(clouds[0], clouds[1], p, descriptor=desc)
-    # metric, rmse and inliers of the final transformation (start: buildInliersAndEstimateMetric); the plane metrics have no
-    # correspondence inliers: their figures are the alignment's
-    inl, n_inl, rmse, metric = None, res.n_inliers, None, res.metric
-    if a.metric in ("uniformity", "correspondences"):
-        inl, n_inl, rmse, metric = ctx.evaluate(clouds[0], clouds[1], corr, T, metric_id=p.metric_id, score_id=p.score_id)
+    # metric, rmse, inliers and correct inliers of the final transformation under the run's metric, in the estimator's dense form (start:
+    # buildInliersAndEstimateMetric + buildCorrectInliers)
+    mkw = dict(weight=a.weight) if a.metric == "weighted_closest_plane" else {}
+    m = ctx.analysis_metric(clouds[0], clouds[1], corr, T, T_gt, metric_id=p.metric_id, score_id=p.score_id, **mkw)
+    n_inl, rmse, metric = m.n_inliers, m.rmse, m.metric
     t = time.perf_counter()
-    e = ctx.evaluate_gt(clouds[0], clouds[1], corr, T, T_gt, p.distance_thr, bool(res.converged), inl)
+    e = ctx.evaluate_gt(clouds[0], clouds[1], corr, T, T_gt, p.distance_thr, bool(res.converged))
     dt = time.perf_counter() - t
     deg = 180.0 / np.pi
     print("\n Ground truth transformation:")
     print(np.array2string(T_gt, precision=6, suppress_small=True))
     print(f"converged: {'true' if res.converged else 'false'}")
     print(f"metric: {metric:.7f}")
-    print("inliers_rmse: " + ("n/a (plane metric)" if rmse is None else f"{rmse:.7f}"))
-    print(f"correct inliers: {e.n_correct_inliers}/{n_inl}")
+    print(f"inliers_rmse: {rmse:.7f}")
+    print(f"correct inliers: {m.n_correct_inliers}/{n_inl}")
     print(f"correct correspondences: {e.n_correct_correspondences}/{e.n_correspondences}")
     print(f"rotation error (deg): {deg * e.r_err:.7f}")
     print(f"translation error: {e.t_err:.7f}")
@@ -109,8 +114,8 @@ def analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
     print(f"success (converged and overlap error < {p.distance_thr:.6g}): {'true' if e.converged_and_overlap_ok else 'false'}")
     print(f"analysed in {1e3 * dt:.1f} ms")
     row = formats.results_row(
-        version="lgr_amd", descriptor=a.descriptor, testname=name, metric=metric, rmse="" if rmse is None else rmse, correspondences=e.n_correspondences,
-        correct_correspondences=e.n_correct_correspondences, inliers=n_inl, correct_inliers=e.n_correct_inliers,
+        version="lgr_amd", descriptor=a.descriptor, testname=name, metric=metric, rmse=rmse, correspondences=e.n_correspondences,
+        correct_correspondences=e.n_correct_correspondences, inliers=n_inl, correct_inliers=m.n_correct_inliers,
         nr_points=p.feature_nr_points, distance_thr=p.distance_thr, edge_thr=p.edge_thr_coef, iteration=res.iterations,
         matching_type=a.matching, randomness=p.randomness, r_err=e.r_err, t_err=e.t_err, pcd_err=e.pcd_err, normal_diff=e.normal_diff,
         corr_uniformity=e.corr_uniformity, lrf_type=a.lrf, metric_type=a.metric, overlap_rmse=e.overlap_rmse, alignment_type=a.alignment,
@@ -125,6 +130,21 @@ def analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
             f.write(formats.RESULTS_HEADER + "\n")
         f.write(row + "\n")
     print(f"appended the analysis row to {a.results}" + (" (new file)" if new else ""))
+    if a.metrics_csv:
+        # estimateTestMetric: CorrespondencesMetricEstimator and the dense ClosestPlaneMetricEstimator, both under the run's score, for the found
+        # transformation and for the ground truth; the target's density is computed by the first dense evaluation and handed to the second
+        found, thr = [], 0.0
+        for tn in (T, T_gt):
+            _, n_corr, _, m_corr = ctx.evaluate(clouds[0], clouds[1], corr, tn, metric_id=capi.METRIC_CORRESPONDENCES, score_id=p.score_id)
+            d = ctx.evaluate_plane_dense(clouds[0], clouds[1], tn, p.score_id, threshold=thr)
+            thr = d.threshold
+            found.append((m_corr, d.metric, n_corr, d.n_inliers))
+        new = not os.path.exists(a.metrics_csv)
+        with open(a.metrics_csv, "a") as f:
+            if new:
+                f.write(formats.METRICS_HEADER + "\n")
+            f.write(formats.metrics_row(name, found[0], found[1]) + "\n")
+        print(f"appended the metric row to {a.metrics_csv}" + (" (new file)" if new else ""))
 
 
 if __name__ == "__main__":
