@@ -638,6 +638,73 @@ int lgr_analysis_metric(lgr_ctx*, const float* src, int ns, const float* tgt, in
                         const float* Tgt16_or_null, int metric_id, int score_id, const lgr_metric_params* mp_or_null, lgr_metric_eval* out,
                         uint8_t* inlier_mask_or_null, lgr_corr* inliers_or_null);   /* host twin */
 
+/* ---- the `debug` command and the `compare` test type: generateDebugFiles, compareHypotheses and compareOverlaps (src/main.cpp:152-284)
+ *      without their files.  Colours are 0x00RRGGBB in an int32, as setPointColor takes them (src/common.cpp:1149-1153).  Declared orders:
+ *      DESIGN.md section 4.  Point rows must be 16-byte aligned; 0 < distance <= 1e18, anything else is LGR_ERR_INVALID_ARG; an empty
+ *      cloud is not an error: counts are 0 and nothing is written. ---- */
+#define LGR_COLOR_BEIGE    0xf8c471   /* include/common.h:26-34 */
+#define LGR_COLOR_RED      0xff0000
+#define LGR_COLOR_PARAKEET 0x03c04a
+#define LGR_COLOR_BLUE     0x0000ff
+#define LGR_COLOR_WHITE    0xffffff
+/* per-point outputs of one temperature map, each NULL or an array of one entry per compared point (device memory for the _dev entries,
+ * host memory for the host twins) */
+typedef struct {
+    float*   temp_distance;   /* TemperatureType::Distance: the plane distance, distance_max where there is no neighbour or it is not below */
+    float*   temp_normal;     /* TemperatureType::NormalDifference: radians, (float) M_PI / 2 at most and where the distance one is at its maximum */
+    int32_t* color_distance;  /* getColor(temp_distance, 0, distance_max) */
+    int32_t* color_normal;    /* getColor(temp_normal, 0, (float) M_PI / 2) */
+    int32_t* nn;              /* the reference point the temperatures were taken against, -1 when there is none within 2 distance_max */
+} lgr_temperature_out;
+/* src/common.cpp:859-906 calculateTemperatureMap(compared, reference, type, ...) for both types after ONE search (the reference searches
+ * once per type and finds the same neighbour): nearest reference point within DIST_TO_PLANE_COEFFICIENT * distance_max under the rule of
+ * lgr_merge_overlaps; dist_to_plane = |n_q . (q - p)|, the squared distance where that is not finite.  *n_below = temperatures < distance_max,
+ * the rows the reference keeps for its *_distances_*.csv (src/common.cpp:932-937). */
+int lgr_temperature_map_dev(lgr_ctx*, const float* d_compared, int n, const float* d_reference, int nr, float distance_max,
+                            const lgr_temperature_out* out_or_null, int* n_below /* host */);
+int lgr_temperature_map(lgr_ctx*, const float* compared, int n, const float* reference, int nr, float distance_max,
+                        const lgr_temperature_out* out_or_null, int* n_below);   /* host twin */
+/* src/common.cpp:908-963 saveTemperatureMaps(src, tgt, name, params, distance_thr, transformation) with normals available: the source moved
+ * by T (pcl::transformPointCloudWithNormals), then one map per direction, source against target and target against the moved source.
+ * moved_or_null: room for ns rows, receives the moved source (what the reference writes to its PLY files).  n_below2 = {source, target}. */
+int lgr_temperature_maps_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16] /* host */, float distance_thr,
+                             const lgr_temperature_out* src_out_or_null, const lgr_temperature_out* tgt_out_or_null, float* d_moved_or_null,
+                             int n_below2[2] /* host */);
+int lgr_temperature_maps(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T16[16], float distance_thr,
+                         const lgr_temperature_out* src_out_or_null, const lgr_temperature_out* tgt_out_or_null, float* moved_or_null,
+                         int n_below2[2]);   /* host twin */
+/* src/main.cpp:152-205 compareOverlaps for n transformations (the reference passes two: the found one and the ground truth): per
+ * transformation the source moved by it, the moved source points whose NEAREST target (no radius) lies closer than distance_thr along that
+ * target's normal, the target points likewise against the moved source; counts[k] = size of that overlap, weighted_counts[k] = sequential
+ * f32 sum of the squared smoothed densities (k = 2) of the overlap cloud {moved source rows, then target rows, each in index order}; 0
+ * where the overlap has fewer than 2 points (declared: calculateSmoothedDensities would rassert).  counts2 (optional, 2 n): {source,
+ * target} points per transformation.  Masks (optional): n x ns and n x nt bytes.  A non-finite point is in no overlap. */
+int lgr_compare_overlaps_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float* tns16 /* host, n x 16 */, int n,
+                             float distance_thr, int32_t* counts /* host, n */, float* weighted_counts /* host, n */,
+                             int32_t* counts2_or_null /* host */, uint8_t* d_mask_src_or_null, uint8_t* d_mask_tgt_or_null);
+int lgr_compare_overlaps(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float* tns16, int n, float distance_thr,
+                         int32_t* counts, float* weighted_counts, int32_t* counts2_or_null, uint8_t* mask_src_or_null,
+                         uint8_t* mask_tgt_or_null);   /* host twin */
+/* the search behind lgr_compare_overlaps: nearest point of d_pts for every query (rows of 12 floats both), under the order of lgr_knn_dev
+ * with k = 1 (squared distance, then index), at a cost that does not depend on how far a query lies from the cloud.  -1 / +inf where the
+ * query is not finite or the cloud has no finite point. */
+int lgr_nearest_dev(lgr_ctx*, const float* d_q, int nq, const float* d_pts, int n, int32_t* d_idx, float* d_d2_or_null);
+/* src/common.cpp:818-835 getColor(v, vmin, vmax) per value */
+int lgr_color_map_dev(lgr_ctx*, const float* d_values, int n, float vmin, float vmax, int32_t* d_colors);
+int lgr_color_map(lgr_ctx*, const float* values, int n, float vmin, float vmax, int32_t* colors);   /* host twin */
+/* src/common.cpp:837-850 saveColorizedWeights: getColor between quantile(0.01, weights) and quantile(0.99, weights) (include/utils.h:45-66);
+ * range2 (optional) receives the two quantiles */
+int lgr_color_weights_dev(lgr_ctx*, const float* d_weights, int n, int32_t* d_colors, float range2_or_null[2] /* host */);
+int lgr_color_weights(lgr_ctx*, const float* weights, int n, int32_t* colors, float range2_or_null[2]);   /* host twin */
+/* src/common.cpp:771-816 savePointCloudWithCorrespondences, the colours of its n points: parakeet with key points (beige without), key
+ * points beige, the points of `corr` red, of `inliers` blue, then mixPointColor with white once per entry of `correct` that touches the
+ * point (is_source: index_query, else index_match).  An index outside [0, n) is LGR_ERR_INVALID_ARG. */
+int lgr_color_correspondences_dev(lgr_ctx*, int n, const int32_t* d_kp_idx_or_null, int n_kp, const lgr_corr* d_corr, int c,
+                                  const lgr_corr* d_correct, int n_correct, const lgr_corr* d_inliers, int n_inliers, int is_source,
+                                  int32_t* d_colors);
+int lgr_color_correspondences(lgr_ctx*, int n, const int32_t* kp_idx_or_null, int n_kp, const lgr_corr* corr, int c, const lgr_corr* correct,
+                              int n_correct, const lgr_corr* inliers, int n_inliers, int is_source, int32_t* colors);   /* host twin */
+
 #ifdef __cplusplus
 }
 #endif

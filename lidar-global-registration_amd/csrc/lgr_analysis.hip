@@ -29,21 +29,6 @@ constexpr float GT_PI = 3.14159274101257324f;   // (float) M_PI
 
 struct GtMats { float T[16], G[16], D[16]; };   // estimate, ground truth, D = T^-1 * G (column-major)
 
-// pcl::detail::Transformer::se3 / so3
-__device__ __forceinline__ void se3(const float* __restrict__ M, float x, float y, float z, float& ox, float& oy, float& oz) {
-    ox = M[0] * x + (M[4] * y + (M[8] * z + M[12]));
-    oy = M[1] * x + (M[5] * y + (M[9] * z + M[13]));
-    oz = M[2] * x + (M[6] * y + (M[10] * z + M[14]));
-}
-__device__ __forceinline__ void so3(const float* __restrict__ M, float x, float y, float z, float& ox, float& oy, float& oz) {
-    ox = M[0] * x + (M[4] * y + M[8] * z);
-    oy = M[1] * x + (M[5] * y + M[9] * z);
-    oz = M[2] * x + (M[6] * y + M[10] * z);
-}
-__device__ __forceinline__ float sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-__device__ __forceinline__ bool fin(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
-
 // Quantities 2, 3 and 6 in one launch: thread i handles source point i (its point-cloud term, its overlap term after ONE grid walk) and
 // correspondence i.  counters: [0] overlap_size, [1] correct correspondences, [2] correct inliers, [3] inliers.
 __global__ __launch_bounds__(AB) void gt_point_kernel(GridDev g, const float4* __restrict__ src, int ns, const float4* __restrict__ tgt,
@@ -98,23 +83,6 @@ __global__ __launch_bounds__(AB) void gt_point_kernel(GridDev g, const float4* _
     wave_count(inl, counters + 3);
 }
 
-// the ground-truth-aligned source: rows {G p, 1 | G n, 0 | third quad copied} (pcl::transformPointCloudWithNormals)
-__global__ __launch_bounds__(AB) void gt_align_kernel(const float4* __restrict__ src, int ns, const GtMats* __restrict__ mats, float4* __restrict__ out) {
-    __shared__ float G[16];
-    if (threadIdx.x < 16) G[threadIdx.x] = mats->G[threadIdx.x];
-    __syncthreads();
-    const int i = blockIdx.x * AB + threadIdx.x;
-    if (i >= ns) return;
-    const float4 P = src[(size_t) i * 3], N = src[(size_t) i * 3 + 1];
-    float4 p, n;
-    se3(G, P.x, P.y, P.z, p.x, p.y, p.z);
-    so3(G, N.x, N.y, N.z, n.x, n.y, n.z);
-    p.w = 1.f; n.w = 0.f;
-    out[(size_t) i * 3] = p;
-    out[(size_t) i * 3 + 1] = n;
-    out[(size_t) i * 3 + 2] = src[(size_t) i * 3 + 2];
-}
-
 // one pass of mergeOverlaps (src/common.cpp:563-584): compared point i is in the overlap when its nearest reference point within the
 // radius lies closer than thr to it along that point's normal (the squared distance stands in for a non-finite plane distance)
 __global__ __launch_bounds__(AB) void gt_overlap_mask_kernel(GridDev ref, const float4* __restrict__ cmp, int n, float thr, float r2,
@@ -160,21 +128,8 @@ __global__ __launch_bounds__(AB) void gt_normal_diff_kernel(const float4* __rest
     wave_count(counted, counter);
 }
 
-// (the sequential f32 sum jobs -- GtSumJobs, gt_seqsum_kernel -- are in lgr_pointpass.cuh)
+// (se3 / so3, the cloud move, the sequential f32 sum jobs and the overlap compaction are in lgr_pointpass.cuh)
 
-// compaction of the overlap cloud: flags of [aligned source | target] in index order, then the kept rows
-__global__ __launch_bounds__(AB) void gt_flags_kernel(const uint8_t* __restrict__ ma, int na, const uint8_t* __restrict__ mb, int nb, int* __restrict__ flags) {
-    const int i = blockIdx.x * AB + threadIdx.x;
-    if (i < na + nb) flags[i] = (i < na ? ma[i] : mb[i - na]) ? 1 : 0;
-}
-__global__ __launch_bounds__(AB) void gt_compact_rows_kernel(const float4* __restrict__ a, int na, const float4* __restrict__ b, int nb,
-                                                             const int* __restrict__ flags, const int* __restrict__ pos, float4* __restrict__ out) {
-    const int i = blockIdx.x * AB + threadIdx.x;
-    if (i >= na + nb || !flags[i]) return;
-    const float4* r = i < na ? a + (size_t) i * 3 : b + (size_t) (i - na) * 3;
-    float4* o = out + (size_t) pos[i] * 3;
-    o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
-}
 // the correct correspondences with an infinite threshold (order free: the uniformity histogram counts a set)
 __global__ __launch_bounds__(AB) void gt_compact_corr_kernel(const lgr_corr* __restrict__ corr, const uint8_t* __restrict__ correct, int c,
                                                              lgr_corr* __restrict__ out, int* __restrict__ n_out) {
@@ -186,8 +141,6 @@ __global__ __launch_bounds__(AB) void gt_compact_corr_kernel(const lgr_corr* __r
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-bool aligned16(const void* p) { return ((uintptr_t) p & 15) == 0; }
-
 // src/analysis.cpp:19-24 as the oracle states it (orc_rot_trans_diff): the angle of R1^T R2 from its unit quaternion, in double
 void rot_trans_diff(const float* T1, const float* T2, float* angle, float* tdist) {
     double R[9];
@@ -223,16 +176,6 @@ int upload_mats(lgr_ctx* ctx, const float* T16, const float* G16, const GtMats**
     *d_mats = (const GtMats*) d;
     *d_counters = (int*) (d + 192);    // 16 ints
     *d_sums = (float*) (d + 256);      // 8 floats
-    return LGR_OK;
-}
-
-// words [first, first + n) of a device array -> host (through the pinned scratch; synchronises)
-int read_words(lgr_ctx* ctx, const void* d, int n, void* out) {
-    void* h;
-    LGR_TRY(lgr_pinned(ctx, 64, &h));
-    LGR_HIP(ctx, hipMemcpyAsync(h, d, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(out, h, (size_t) n * 4);
     return LGR_OK;
 }
 
@@ -289,7 +232,7 @@ int run_correct(lgr_ctx* ctx, const GtState& st, const float* d_src, const float
 
 int align_source(lgr_ctx* ctx, const GtState& st, const float* d_src, int ns, float** d_aligned) {
     LGR_TRY(lgr_ws_t(ctx, WS_GT_ALIGNED, (size_t) 12 * ns + 16, d_aligned));
-    if (ns > 0) gt_align_kernel<<<cdiv(ns, AB), AB, 0, ctx->stream>>>((const float4*) d_src, ns, st.mats, (float4*) *d_aligned);
+    if (ns > 0) pp_move_kernel<<<cdiv(ns, AB), AB, 0, ctx->stream>>>((const float4*) d_src, ns, st.mats->G, (float4*) *d_aligned);
     LGR_HIP(ctx, hipGetLastError());
     return LGR_OK;
 }
@@ -333,12 +276,12 @@ int run_merge(lgr_ctx* ctx, const GtState& st, const GridDev& gt, const float* d
     const int no = n2[0] + n2[1];
     *overlap = (float) no / (float) (ns + nt);
     if (!overlap_area || no < 2 || ns < 2) return LGR_OK;   // calculateSmoothedDensities would rassert (src/common.cpp:532)
-    gt_flags_kernel<<<cdiv((long long) n, AB), AB, 0, ctx->stream>>>(d_mask_src, ns, d_mask_tgt, nt, flags);
+    pp_flags_kernel<<<cdiv((long long) n, AB), AB, 0, ctx->stream>>>(d_mask_src, ns, d_mask_tgt, nt, flags);
     LGR_TRY(pp_scan_flags(ctx, flags, pos, n));
     float *d_ov, *d_dens;
     LGR_TRY(lgr_ws_t(ctx, WS_GT_OVERLAP, (size_t) 12 * no + 16, &d_ov));
     LGR_TRY(lgr_ws_t(ctx, WS_GT_DENS, (size_t) std::max(no, ns) + 16, &d_dens));
-    gt_compact_rows_kernel<<<cdiv((long long) n, AB), AB, 0, ctx->stream>>>((const float4*) d_aligned, ns, (const float4*) d_tgt, nt, flags, pos, (float4*) d_ov);
+    pp_compact_rows_kernel<<<cdiv((long long) n, AB), AB, 0, ctx->stream>>>((const float4*) d_aligned, ns, (const float4*) d_tgt, nt, flags, pos, (float4*) d_ov);
     LGR_HIP(ctx, hipGetLastError());
     LGR_TRY(density_sq_sum(ctx, st, d_ov, no, d_dens, 2));
     LGR_TRY(density_sq_sum(ctx, st, d_src, ns, d_dens, 3));
@@ -508,17 +451,7 @@ extern "C" int lgr_evaluate_gt_dev(lgr_ctx* ctx, const float* d_src, int ns, con
 }
 
 namespace {
-// host clouds -> the WS_HOST_A / WS_HOST_B slots (nullptr for an empty cloud); the copies are ordered on the context's stream
-int stage_clouds(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, float** ds, float** dt) {
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12 + 4, ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12 + 4, dt));
-    if (ns) LGR_HIP(ctx, hipMemcpyAsync(*ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (nt) LGR_HIP(ctx, hipMemcpyAsync(*dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (!ns) *ds = nullptr;
-    if (!nt) *dt = nullptr;
-    return LGR_OK;
-}
+// (stage_clouds, host clouds -> the WS_HOST_A / WS_HOST_B slots, is in lgr_pointpass.cuh)
 #define GT_CHECK_HOST_CLOUDS(ctx) LGR_CHECK(ctx, ns >= 0 && nt >= 0 && (src || ns == 0) && (tgt || nt == 0), LGR_ERR_INVALID_ARG)
 }  // namespace
 

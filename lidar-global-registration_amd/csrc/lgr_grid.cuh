@@ -165,3 +165,113 @@ __device__ __forceinline__ void lgr_visit27(const GridDev& g, float qx, float qy
             }
         }
 }
+
+// ---- exact nearest neighbour whose cost does not depend on where the query lies (lgr_debug.hip) ----
+// lgr_knn_query centres its rings on the query's own cell: right for a query inside the cloud, cubic in the separation (and an
+// out-of-range cell index) for one far outside it.  Here the search descends the grid itself.  cell_start is an exclusive prefix sum over
+// the cells in (z, y, x) order, so the points of ANY contiguous cell range [lo, hi) are the contiguous sorted positions
+// [cell_start[lo], cell_start[hi]): two loads say how many points a node holds.  Nodes are such ranges of three kinds -- whole z-slabs
+// [z0, z1), rows [y0, y1) of one slab, cells [x0, x1) of one row -- each an axis-aligned box of cells.  A node is halved along its axis
+// (a single slab turns into its rows, a single row into its cells), the nearer half is followed, the other pushed; a node with no point,
+// or whose box lies farther than the best candidate, is dropped; a node of at most LGR_FAR_LEAF points is scanned.
+//   * Order: candidates compete under (d2, original index) with d2 = lgr_dist2, the order of lgr_knn_query's list with k = 1.  The order is
+//     total, so the result does not depend on the visiting order: it is the brute-force minimum, provided no node that could hold it is dropped.
+//   * Bound: a point of cell a along one axis has u_p = fl(fl(p - o) / h) in [a, a + 1) (lgr_cellc, the expression that built the grid);
+//     the query's u_q is the same expression.  Along that axis |q - p| >= (gap - m) h with gap = max(a0 - u_q, u_q - a1, 0) over the
+//     node's cells [a0, a1) and m = 4e-7 (|u_q| + d) covering the rounding of both u (two roundings of relative size 2^-24 each, |u_p| <= d).
+//     The squared bound is taken times 0.9999, which covers the roundings of lgr_dist2 and of the bound's own arithmetic.  A node is dropped
+//     only when bound > best d2 (strictly): a dropped node holds no point of equal computed distance, so no lower index is lost.
+//   * Work: every push halves a node, so the stack holds at most ceil(log2 dz) + ceil(log2 dy) + ceil(log2 dx) <= 31 entries (the grid has
+//     at most 256e6 cells); should it be full the node at hand is scanned instead of split (still exact).  No ring is walked at all: the
+//     number of nodes visited depends on the points near the answer, not on the separation -- an empty region costs two loads however
+//     many cells it spans.  Queries farther than about 1.8e19 from the cloud make every squared distance +inf: all points tie, nothing
+//     can be dropped, and the lowest index of all wins after a visit of every occupied node.
+// Stack: three words per entry, slot-major [LGR_FAR_STACK][BLOCK] in LDS (lane i on bank i % 32).
+constexpr int LGR_FAR_STACK = 32, LGR_FAR_LEAF = 8;
+
+struct FarQuery { float ux, uy, uz, mx, my, mz; };
+
+__device__ __forceinline__ float lgr_far_gap(int a0, int a1, float u, float m) {
+    const float g = fmaxf(fmaxf((float) a0 - u, u - (float) a1), 0.f) - m;
+    return fmaxf(g, 0.f);
+}
+// squared lower bound of the distance from the query to the box of node (kind, [lo, hi)); kind 0: slabs, 1: rows of a slab, 2: cells of a row
+__device__ __forceinline__ float lgr_far_bound(const GridDev& g, const FarQuery& Q, int kind, int lo, int hi) {
+    int x0 = 0, x1 = g.dx, y0 = 0, y1 = g.dy, z0, z1;
+    if (kind == 0) {
+        const int slab = g.dy * g.dx;
+        z0 = lo / slab; z1 = hi / slab;
+    } else if (kind == 1) {
+        const int r0 = lo / g.dx, r1 = hi / g.dx;
+        z0 = r0 / g.dy; z1 = z0 + 1;
+        y0 = r0 - z0 * g.dy; y1 = r1 - z0 * g.dy;
+    } else {
+        const int row = lo / g.dx;
+        x0 = lo - row * g.dx; x1 = hi - row * g.dx;
+        z0 = row / g.dy; z1 = z0 + 1;
+        y0 = row - z0 * g.dy; y1 = y0 + 1;
+    }
+    const float gx = lgr_far_gap(x0, x1, Q.ux, Q.mx) * g.h, gy = lgr_far_gap(y0, y1, Q.uy, Q.my) * g.h, gz = lgr_far_gap(z0, z1, Q.uz, Q.mz) * g.h;
+    return ((gx * gx + gy * gy) + gz * gz) * 0.9999f;
+}
+
+// nearest grid point of the finite query (qx, qy, qz): its sorted position (-1: the grid is empty), squared distance and original index.
+// st_lo / st_hi / st_b: this thread's stack columns (element e at [e * BLOCK]); hi carries the node kind in its top two bits.
+template <int BLOCK>
+__device__ __forceinline__ int lgr_nearest_far(const GridDev& g, float qx, float qy, float qz, int* st_lo, int* st_hi, float* st_b,
+                                               float& best_d2, int& best_idx) {
+    int nn = -1, nn_t = -1;
+    float best = 0.f;
+    best_d2 = 0.f; best_idx = -1;
+    if (g.n <= 0) return -1;
+    FarQuery Q;
+    Q.ux = (qx - g.ox) / g.h; Q.uy = (qy - g.oy) / g.h; Q.uz = (qz - g.oz) / g.h;
+    Q.mx = 4e-7f * (fabsf(Q.ux) + (float) g.dx); Q.my = 4e-7f * (fabsf(Q.uy) + (float) g.dy); Q.mz = 4e-7f * (fabsf(Q.uz) + (float) g.dz);
+    auto scan = [&](int b, int e) {
+        for (int t = b; t < e; ++t) {
+            const float4 P = g.pxyz[t];
+            const float d2 = lgr_dist2(qx, qy, qz, P.x, P.y, P.z);
+            const int pi = __float_as_int(P.w);
+            const bool take = nn < 0 || d2 < best || (d2 == best && pi < nn);
+            nn = take ? pi : nn; nn_t = take ? t : nn_t; best = take ? d2 : best;
+        }
+    };
+    int sp = 0, kind = 0, lo = 0, hi = g.dz * g.dy * g.dx;
+    float bnd = 0.f;
+    for (;;) {
+        bool pop = true;
+        if (!(nn >= 0 && bnd > best)) {
+            const int b = g.cell_start[lo], e = g.cell_start[hi];
+            if (e > b) {
+                const int unit = kind == 0 ? g.dy * g.dx : (kind == 1 ? g.dx : 1);
+                const int len = (hi - lo) / unit;
+                if (e - b <= LGR_FAR_LEAF || (len == 1 && kind == 2) || (len > 1 && sp == LGR_FAR_STACK)) {
+                    scan(b, e);
+                } else if (len == 1) {
+                    ++kind;   // one slab: its rows; one row: its cells (same range, same bound)
+                    pop = false;
+                } else {
+                    const int mid = lo + (len >> 1) * unit;
+                    const float ba = lgr_far_bound(g, Q, kind, lo, mid), bb = lgr_far_bound(g, Q, kind, mid, hi);
+                    const bool a_first = !(bb < ba);
+                    st_lo[sp * BLOCK] = a_first ? mid : lo;
+                    st_hi[sp * BLOCK] = (a_first ? hi : mid) | (kind << 30);
+                    st_b[sp * BLOCK] = a_first ? bb : ba;
+                    ++sp;
+                    if (a_first) { hi = mid; bnd = ba; } else { lo = mid; bnd = bb; }
+                    pop = false;
+                }
+            }
+        }
+        if (pop) {
+            if (sp == 0) break;
+            --sp;
+            lo = st_lo[sp * BLOCK];
+            const int hk = st_hi[sp * BLOCK];
+            hi = hk & 0x3fffffff; kind = (int) ((unsigned) hk >> 30);
+            bnd = st_b[sp * BLOCK];
+        }
+    }
+    best_d2 = best; best_idx = nn;
+    return nn_t;
+}

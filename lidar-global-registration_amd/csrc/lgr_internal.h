@@ -43,7 +43,7 @@ struct lgr_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
-    lgr_buf ws[128];
+    lgr_buf ws[160];
     void* pinned = nullptr;  // small pinned host scratch for read-backs
     size_t pinned_cap = 0;
     hipEvent_t ev[32];       // 0..8 stage timers (lgr_align), 9.. pairs around the match_mfma passes
@@ -127,9 +127,10 @@ enum {
     WS_WEIGHTS, WS_WEIGHTS_KNN, WS_WEIGHTS_TMP, WS_WEIGHTS_VALS, WS_WEIGHTS_SUM, WS_WEIGHTS_HOST,
     WS_GT_MISC, WS_GT_TERMS, WS_GT_ALIGNED, WS_GT_OVERLAP, WS_GT_FLAGS, WS_GT_KNN, WS_GT_DENS, WS_GT_CORR,   // lgr_analysis.hip
     WS_PD_TERMS, WS_PD_MISC, WS_PD_INLIERS, WS_PD_MASK,   // lgr_plane_dense.hip
+    WS_DBG_MISC, WS_DBG_MOVED, WS_DBG_FLAGS, WS_DBG_OVERLAP, WS_DBG_DENS, WS_DBG_SORT, WS_DBG_HOST_A, WS_DBG_HOST_B,   // lgr_debug.hip
     WS_COUNT
 };
-static_assert(WS_COUNT <= 128, "grow lgr_ctx::ws");
+static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");
 
 // returns device pointer of at least `bytes` (contents undefined unless kept); grows with 25% slack
 int lgr_ws(lgr_ctx* ctx, int slot, size_t bytes, void** out);

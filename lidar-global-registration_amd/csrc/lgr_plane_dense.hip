@@ -82,8 +82,6 @@ __global__ __launch_bounds__(PP_BLOCK) void plane_dense_compact_kernel(const int
     out[pos[i]] = lgr_corr{i, nn[i], dist[i], thr};   // pos[i] < number of inliers <= ns
 }
 
-bool aligned16(const void* p) { return ((uintptr_t) p & 15) == 0; }
-
 // everything between the argument checks and the final synchronisation of lgr_evaluate_plane_dense_dev
 int dense_eval(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* T16, int score_id, const lgr_metric_params* mp,
                float inlier_threshold, lgr_plane_dense_eval* out, lgr_corr* d_inliers, int32_t* d_nn) {

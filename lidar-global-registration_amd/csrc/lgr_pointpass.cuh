@@ -1,6 +1,6 @@
-// lgr_pointpass.cuh -- what the thread-per-point passes of lgr_analysis.hip and lgr_plane_dense.hip share: the branch-free
-// nearest-within-r walk, the wave-aggregated counter, the sequential f32 sum jobs and the exclusive scan of a flag array (the first half
-// of a compaction).  Everything here sits in an unnamed namespace: each translation unit gets its own copy of the kernels.
+// lgr_pointpass.cuh -- what the thread-per-point passes of lgr_analysis.hip, lgr_plane_dense.hip and lgr_debug.hip share: PCL's point
+// moves, the branch-free nearest-within-r walk, the wave-aggregated counter, the sequential f32 sum jobs, the move of a whole cloud and
+// the compaction of an overlap cloud (flags, their exclusive scan, the kept rows).  Everything here sits in an unnamed namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <rocprim/device/device_scan.hpp>
 
@@ -10,6 +10,21 @@
 namespace {
 
 constexpr int PP_BLOCK = 256;
+
+// pcl::detail::Transformer::se3 / so3
+__device__ __forceinline__ void se3(const float* __restrict__ M, float x, float y, float z, float& ox, float& oy, float& oz) {
+    ox = M[0] * x + (M[4] * y + (M[8] * z + M[12]));
+    oy = M[1] * x + (M[5] * y + (M[9] * z + M[13]));
+    oz = M[2] * x + (M[6] * y + (M[10] * z + M[14]));
+}
+__device__ __forceinline__ void so3(const float* __restrict__ M, float x, float y, float z, float& ox, float& oy, float& oz) {
+    ox = M[0] * x + (M[4] * y + M[8] * z);
+    oy = M[1] * x + (M[5] * y + M[9] * z);
+    oz = M[2] * x + (M[6] * y + M[10] * z);
+}
+__device__ __forceinline__ float sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+__device__ __forceinline__ bool fin(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
 
 // nearest grid point within r2 of p: sorted position or -1.  The candidate loop has no branch on the candidate: every lane offers every
 // candidate of its cells and keeps the better one by selects, so a wave never serialises on which lanes found something.
@@ -72,6 +87,61 @@ __global__ __launch_bounds__(PP_BLOCK) void gt_seqsum_kernel(GtSumJobs jobs, flo
         __syncthreads();
     }
     if (threadIdx.x == 0) out[blockIdx.x] = sum;
+}
+
+// a cloud moved by the column-major 4x4 M16 (device memory): rows {M p, 1 | M n, 0 | third quad copied} (pcl::transformPointCloudWithNormals)
+[[maybe_unused]] __global__ __launch_bounds__(PP_BLOCK) void pp_move_kernel(const float4* __restrict__ src, int ns, const float* __restrict__ M16, float4* __restrict__ out) {
+    __shared__ float G[16];
+    if (threadIdx.x < 16) G[threadIdx.x] = M16[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * PP_BLOCK + threadIdx.x;
+    if (i >= ns) return;
+    const float4 P = src[(size_t) i * 3], N = src[(size_t) i * 3 + 1];
+    float4 p, n;
+    se3(G, P.x, P.y, P.z, p.x, p.y, p.z);
+    so3(G, N.x, N.y, N.z, n.x, n.y, n.z);
+    p.w = 1.f; n.w = 0.f;
+    out[(size_t) i * 3] = p;
+    out[(size_t) i * 3 + 1] = n;
+    out[(size_t) i * 3 + 2] = src[(size_t) i * 3 + 2];
+}
+
+// compaction of an overlap cloud: flags of [first cloud | second cloud] in index order, then the kept rows
+[[maybe_unused]] __global__ __launch_bounds__(PP_BLOCK) void pp_flags_kernel(const uint8_t* __restrict__ ma, int na, const uint8_t* __restrict__ mb, int nb, int* __restrict__ flags) {
+    const int i = blockIdx.x * PP_BLOCK + threadIdx.x;
+    if (i < na + nb) flags[i] = (i < na ? ma[i] : mb[i - na]) ? 1 : 0;
+}
+[[maybe_unused]] __global__ __launch_bounds__(PP_BLOCK) void pp_compact_rows_kernel(const float4* __restrict__ a, int na, const float4* __restrict__ b, int nb,
+                                                                   const int* __restrict__ flags, const int* __restrict__ pos, float4* __restrict__ out) {
+    const int i = blockIdx.x * PP_BLOCK + threadIdx.x;
+    if (i >= na + nb || !flags[i]) return;
+    const float4* r = i < na ? a + (size_t) i * 3 : b + (size_t) (i - na) * 3;
+    float4* o = out + (size_t) pos[i] * 3;
+    o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t) p & 15) == 0; }
+
+// n <= 16 words of a device array -> host (through the pinned scratch; synchronises)
+inline int read_words(lgr_ctx* ctx, const void* d, int n, void* out) {
+    void* h;
+    LGR_TRY(lgr_pinned(ctx, 64, &h));
+    LGR_HIP(ctx, hipMemcpyAsync(h, d, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(out, h, (size_t) n * 4);
+    return LGR_OK;
+}
+
+// host clouds -> the WS_HOST_A / WS_HOST_B slots (nullptr for an empty cloud); the copies are ordered on the context's stream
+inline int stage_clouds(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, float** ds, float** dt) {
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12 + 4, ds));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12 + 4, dt));
+    if (ns) LGR_HIP(ctx, hipMemcpyAsync(*ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
+    if (nt) LGR_HIP(ctx, hipMemcpyAsync(*dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
+    if (!ns) *ds = nullptr;
+    if (!nt) *dt = nullptr;
+    return LGR_OK;
 }
 
 // pos[i] = number of set flags before i (flags are 0 / 1 ints), on ctx->stream; the scan's temporary storage is the WS_GRID_TMP slot

@@ -91,13 +91,7 @@ __device__ __forceinline__ float wt_max_pc(float pc1, float pc2) {
     const bool fin = isfinite(pc1) && isfinite(pc2);
     return fin ? (pc1 < pc2 ? pc2 : pc1) : 0.f;   // std::max(pc1, pc2)
 }
-__device__ __forceinline__ unsigned wt_key(float v) {   // order-preserving bits of a float
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float wt_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// (wt_key / wt_unkey, the order-preserving bits of a float, are in lgr_weights_math.h)
 
 __global__ __launch_bounds__(WB) void maxpc_key_kernel(const float* __restrict__ pc1, const float* __restrict__ pc2, int n, unsigned* __restrict__ keys) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) keys[i] = wt_key(wt_max_pc(pc1[i], pc2[i]));

@@ -14,6 +14,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #if defined(__HIPCC__)
 #define WT_HD __host__ __device__ __forceinline__
@@ -80,6 +81,30 @@ WT_HD int wt_nss_bin(float theta, float at) {
     if ((double) phi == 2.f * PI) phi = 0.f;      // (never true for a float)
     if (theta != theta) return -1;                // |nz| > 1: acosf is NaN (declared: not counted, weight 0)
     return (int) (floorf(theta * 8.f) * 8.f + floorf(phi * 8.f));
+}
+
+// order-preserving bits of a float (ascending keys <-> ascending values; -0 below +0, NaNs at the two ends) and back
+WT_HD uint32_t wt_key(float v) {
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+WT_HD float wt_unkey(uint32_t k) {
+    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+// utils.h quantile<float>(q, v) for any q in [0, 1] (saveColorizedWeights takes 0.01 and 0.99), same ranks and same formula
+WT_HD void wt_quantile_ranks_q(double q, long long n, long long* i, long long* j) {
+    *i = (long long) floor(q * (double) (n - 1));
+    *j = *i + 1 < n - 1 ? *i + 1 : n - 1;
+}
+WT_HD float wt_quantile_q(double q, long long n, long long i, long long j, float ith, float jth) {
+    if (n == 1) return ith;
+    if (i < j) return (float) ((double) ith * ((double) n * q - (double) i) + (double) jth * ((double) j - (double) n * q));
+    return ith;
 }
 
 // quantile(0.8, v) of n >= 1 values from the i-th and j-th smallest (i = floor(0.8 (n - 1)), j = min(i + 1, n - 1))

@@ -22,10 +22,13 @@
 // including this header: every access below is either `.points`, `.size()`, `.data()` or a
 // reinterpret of the contiguous storage, which the real types provide with the same layout.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cctype>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
+#include <iostream>
 #include <limits>
 #include <memory>
 #include <optional>
@@ -51,6 +54,18 @@ struct alignas(16) PointN {   // pcl::PointXYZINormal
 using PointN = LGR_COMPAT_POINT_T;
 #endif
 static_assert(sizeof(PointN) == 48, "PointN must be the 48-byte pcl::PointXYZINormal layout");
+
+#ifndef LGR_COMPAT_COLORED_POINT_T
+struct alignas(16) PointColoredN {   // pcl::PointXYZRGBNormal (include/common.h: PointColoredN)
+    float x = 0, y = 0, z = 0, _pad0 = 1.f;
+    float normal_x = 0, normal_y = 0, normal_z = 0, _pad1 = 0;
+    std::uint8_t b = 0, g = 0, r = 0, a = 255;
+    float curvature = 0, _pad2 = 0, _pad3 = 0;
+};
+#else
+using PointColoredN = LGR_COMPAT_COLORED_POINT_T;
+#endif
+static_assert(sizeof(PointColoredN) == 48, "PointColoredN must be the 48-byte pcl::PointXYZRGBNormal layout");
 
 #ifndef LGR_COMPAT_FPFH_T
 struct FPFH { float histogram[33]; };   // pcl::FPFHSignature33
@@ -96,6 +111,7 @@ template <class T> struct Cloud {   // the subset of pcl::PointCloud<T> the path
     bool empty() const { return points.empty(); }
 };
 using PointNCloud = Cloud<PointN>;
+using PointColoredNCloud = Cloud<PointColoredN>;
 using FPFHCloud = Cloud<FPFH>;
 using SHOTCloud = Cloud<SHOT>;
 using RoPS135Cloud = Cloud<RoPS135>;
@@ -554,6 +570,102 @@ inline void mergeOverlaps(const PointNCloud::ConstPtr& pcd1, const PointNCloud::
     for (size_t i = 0; i < pcd2->size(); ++i)
         if (m2[i]) dst->points.push_back(pcd2->points[i]);
     dst->width = (unsigned) dst->points.size(); dst->height = 1;
+}
+
+// ---- the debug layer (src/common.cpp:818-835, 859-906, 1149-1159; src/main.cpp:152-205) on the device: declared orders in DESIGN.md
+//      section 4.  The functions that write files (saveTemperatureMaps, savePointCloudWithCorrespondences, ...) are in lgr_io.hpp.
+constexpr int COLOR_BEIGE = LGR_COLOR_BEIGE, COLOR_RED = LGR_COLOR_RED, COLOR_PARAKEET = LGR_COLOR_PARAKEET, COLOR_BLUE = LGR_COLOR_BLUE,
+              COLOR_WHITE = LGR_COLOR_WHITE;
+enum class TemperatureType { Distance, NormalDifference };
+
+// src/common.cpp:818-835 (the library's kernels compute the same expression; compile without floating-point contraction to get their bits)
+inline int getColor(float v, float vmin, float vmax) {
+    float r = 1.f, g = 1.f, b = 1.f;
+    float dv = vmax - vmin;
+    v = std::max(vmin, std::min(v, vmax));
+    if (v < (vmin + dv / 3.f)) {
+        b = 1.f - 3.f * (v - vmin) / dv;
+    } else if (v < (vmin + 2.f * dv / 3.f)) {
+        b = 0.f;
+        g = 2.f - 3.f * (v - vmin) / dv;
+    } else {
+        b = 0.f;
+        g = 0.f;
+        r = 3.f - 3.f * (v - vmin) / dv;
+    }
+    auto c8 = [](float c) { const float x = 255.f * c; return x == x ? ((int) x & 255) : 0; };   // a NaN channel (vmin == vmax) is 0
+    return (c8(r) << 16) + (c8(g) << 8) + c8(b);
+}
+// src/common.cpp:1149-1159
+inline void setPointColor(PointColoredN& point, int color) {
+    point.r = (color >> 16) & 0xff;
+    point.g = (color >> 8) & 0xff;
+    point.b = (color >> 0) & 0xff;
+}
+inline void mixPointColor(PointColoredN& point, int color) {
+    point.r = point.r / 2 + ((color >> 16) & 0xff) / 2;
+    point.g = point.g / 2 + ((color >> 8) & 0xff) / 2;
+    point.b = point.b / 2 + ((color >> 0) & 0xff) / 2;
+}
+inline void setPointColor(PointColoredN& point, std::uint8_t red, std::uint8_t green, std::uint8_t blue) { point.r = red; point.g = green; point.b = blue; }
+inline const float* raw(const PointColoredNCloud& c) { return reinterpret_cast<const float*>(c.points.data()); }
+// pcl::copyPoint PointN -> PointColoredN: the fields both have (x y z, the normal, curvature)
+inline void copyPoint(const PointN& in, PointColoredN& out) {
+    out.x = in.x; out.y = in.y; out.z = in.z;
+    out.normal_x = in.normal_x; out.normal_y = in.normal_y; out.normal_z = in.normal_z;
+    out.curvature = in.curvature;
+}
+
+// pcl::transformPointCloudWithNormals on the host, in the order the library moves a cloud: x c0 + (y c1 + (z c2 + c3)),
+// a normal the same without c3; the other fields are copied.  in and out may be the same cloud.
+template <class PointT>
+inline void transformPointCloudWithNormals(const Cloud<PointT>& in, Cloud<PointT>& out, const Matrix4f& T) {
+    const float* M = T.data();
+    if (&in != &out) out = in;
+    for (PointT& p : out.points) {
+        const float x = p.x, y = p.y, z = p.z, nx = p.normal_x, ny = p.normal_y, nz = p.normal_z;
+        p.x = M[0] * x + (M[4] * y + (M[8] * z + M[12]));
+        p.y = M[1] * x + (M[5] * y + (M[9] * z + M[13]));
+        p.z = M[2] * x + (M[6] * y + (M[10] * z + M[14]));
+        p.normal_x = M[0] * nx + (M[4] * ny + M[8] * nz);
+        p.normal_y = M[1] * nx + (M[5] * ny + M[9] * nz);
+        p.normal_z = M[2] * nx + (M[6] * ny + M[10] * nz);
+    }
+}
+
+// src/common.cpp:859-906: colours `compared` and fills `temperatures`.  The library reads rows of 12 floats whose first two quads are the
+// point and the normal: the layout of PointColoredN as well.  Returns the number of temperatures below distance_max.
+inline int calculateTemperatureMap(PointColoredNCloud::Ptr& compared, PointColoredNCloud::Ptr& reference, TemperatureType type,
+                                   std::vector<float>& temperatures, float /* temperature_min: 0 in every caller */, float /* temperature_max */,
+                                   float distance_max) {
+    const int n = (int) compared->size();
+    temperatures.assign((size_t) n, type == TemperatureType::Distance ? distance_max : (float) M_PI / 2);
+    std::vector<std::int32_t> colors((size_t) n + 1, getColor(1.f, 0.f, 1.f));
+    lgr_temperature_out out{};
+    int n_below = 0;
+    if (type == TemperatureType::Distance) { out.temp_distance = temperatures.data(); out.color_distance = colors.data(); }
+    else { out.temp_normal = temperatures.data(); out.color_normal = colors.data(); }
+    check(lgr_temperature_map(context(), raw(*compared), n, raw(*reference), (int) reference->size(), distance_max, n ? &out : nullptr, &n_below),
+          "calculateTemperatureMap");
+    for (int i = 0; i < n; ++i) setPointColor(compared->points[(size_t) i], colors[(size_t) i]);
+    return n_below;
+}
+
+// src/main.cpp:152-205: the two printed lines, and the numbers beside them
+struct OverlapComparison { int count[2]; float weighted_count[2]; };
+inline OverlapComparison compareOverlaps(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& transformation,
+                                         const Matrix4f& transformation_gt, const AlignmentParameters& parameters) {
+    float tns[32];
+    std::memcpy(tns, transformation.data(), 64);
+    std::memcpy(tns + 16, transformation_gt.data(), 64);
+    OverlapComparison r{};
+    std::int32_t counts[2] = {0, 0};
+    check(lgr_compare_overlaps(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), tns, 2, parameters.distance_thr, counts,
+                               r.weighted_count, nullptr, nullptr, nullptr), "compareOverlaps");
+    r.count[0] = counts[0]; r.count[1] = counts[1];
+    std::cerr << "\tincorrect hypothesis: " << r.count[0] << " points, " << r.weighted_count[0] << "weighted points\n";
+    std::cerr << "\t  correct hypothesis: " << r.count[1] << " points, " << r.weighted_count[1] << "weighted points\n";
+    return r;
 }
 
 // ---- include/utils.h:13-25, include/metric.h: the metric estimators in their DENSE form (sparse = false), the form AlignmentAnalysis and

@@ -18,6 +18,7 @@
 // 48-byte PointXYZINormal layout, everything else keeps the point type's defaults (PCL's fromPCLPointCloud2 does the same:
 // fields the point type has but the file lacks stay as constructed).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -240,6 +241,147 @@ inline int save_ply(const std::string& file_name, const PointNCloud& cloud, bool
 // pcl::io::savePLYFileBinary / savePLYFileASCII for PointN clouds: x y z normal_x normal_y normal_z intensity curvature
 inline int savePLYFileBinary(const std::string& file_name, const PointNCloud& cloud) { return io_detail::save_ply(file_name, cloud, true); }
 inline int savePLYFileASCII(const std::string& file_name, const PointNCloud& cloud) { return io_detail::save_ply(file_name, cloud, false); }
+
+// pcl::io::savePLYFileBinary / savePLYFileASCII for PointColoredN clouds (pcl::PointXYZRGBNormal): x y z, red green blue (uchar), normal_x
+// normal_y normal_z, curvature -- the order of the point type's field list as we read PCL 1.12.1.  The same bytes
+// as lgr_amd/formats.py write_ply_colored.
+namespace io_detail {
+inline int save_ply_colored(const std::string& file_name, const PointColoredNCloud& cloud, bool binary) {
+    std::ofstream f(file_name, std::ios::binary);
+    if (!f.is_open()) return -1;
+    f << "ply\nformat " << (binary ? (host_little_endian() ? "binary_little_endian" : "binary_big_endian") : "ascii") << " 1.0\n";
+    f << "element vertex " << cloud.points.size() << "\n";
+    for (const char* n : {"x", "y", "z"}) f << "property float " << n << "\n";
+    for (const char* n : {"red", "green", "blue"}) f << "property uchar " << n << "\n";
+    for (const char* n : {"normal_x", "normal_y", "normal_z", "curvature"}) f << "property float " << n << "\n";
+    f << "end_header\n";
+    char buf[64];
+    for (const PointColoredN& pt : cloud.points) {
+        const float a[3] = {pt.x, pt.y, pt.z}, b[4] = {pt.normal_x, pt.normal_y, pt.normal_z, pt.curvature};
+        const unsigned char c[3] = {pt.r, pt.g, pt.b};
+        if (binary) {
+            f.write(reinterpret_cast<const char*>(a), 12);
+            f.write(reinterpret_cast<const char*>(c), 3);
+            f.write(reinterpret_cast<const char*>(b), 16);
+        } else {
+            for (int k = 0; k < 3; ++k) { std::snprintf(buf, sizeof buf, "%.9g", static_cast<double>(a[k])); f << (k ? " " : "") << buf; }
+            for (int k = 0; k < 3; ++k) f << " " << static_cast<int>(c[k]);
+            for (int k = 0; k < 4; ++k) { std::snprintf(buf, sizeof buf, "%.9g", static_cast<double>(b[k])); f << " " << buf; }
+            f << "\n";
+        }
+    }
+    return f.good() ? 0 : -1;
+}
+}  // namespace io_detail
+inline int savePLYFileBinary(const std::string& file_name, const PointColoredNCloud& cloud) { return io_detail::save_ply_colored(file_name, cloud, true); }
+inline int savePLYFileASCII(const std::string& file_name, const PointColoredNCloud& cloud) { return io_detail::save_ply_colored(file_name, cloud, false); }
+
+// include/utils.h:92-103
+template <typename T>
+inline void saveVector(const std::vector<T>& vs, const std::string& filepath) {
+    std::ofstream fout(filepath);
+    if (!fout.is_open()) perror(("error while opening file " + filepath).c_str());
+    fout << "value\n";
+    for (T v : vs) fout << v << "\n";
+    fout.close();
+}
+
+// ---- the files of generateDebugFiles / compareHypotheses (src/main.cpp:207-284).  A file is parameters.dir_path / <stem>.<extension>, the stem
+//      being the reference's `name` argument (its constructPath adds the test name and version in front).  The histogram PNGs are not
+//      written: plots.py is no part of this project.
+inline std::string debugPath(const AlignmentParameters& parameters, const std::string& stem, const std::string& extension = "ply") {
+    return (std::filesystem::path(parameters.dir_path) / (stem + "." + extension)).string();
+}
+
+// src/common.cpp:757-769
+inline void saveColorizedPointCloud(const PointNCloud::ConstPtr& pcd, const Matrix4f& transformation_gt, int color, const std::string& filepath) {
+    PointNCloud aligned;
+    transformPointCloudWithNormals(*pcd, aligned, transformation_gt);
+    PointColoredNCloud dst;
+    dst.points.resize(pcd->size());
+    for (std::size_t i = 0; i < pcd->size(); ++i) {
+        copyPoint(aligned.points[i], dst.points[i]);
+        setPointColor(dst.points[i], color);
+    }
+    savePLYFileBinary(filepath, dst);
+}
+
+// src/common.cpp:771-816 (the colours through lgr_color_correspondences; file downsampled_src / downsampled_tgt)
+inline void savePointCloudWithCorrespondences(const PointNCloud::ConstPtr& pcd, const std::shared_ptr<const std::vector<int>>& key_point_indices,
+                                              const Correspondences& correspondences, const Correspondences& correct_correspondences,
+                                              const Correspondences& inliers, const AlignmentParameters& parameters, const Matrix4f& transformation_gt,
+                                              bool is_source) {
+    PointNCloud aligned;
+    transformPointCloudWithNormals(*pcd, aligned, transformation_gt);
+    const int n = (int) pcd->size();
+    std::vector<std::int32_t> colors((std::size_t) n + 1, 0), kp(1, 0);
+    if (key_point_indices) kp.insert(kp.begin(), key_point_indices->begin(), key_point_indices->end());
+    auto list = [](const Correspondences& c) { return c.empty() ? nullptr : reinterpret_cast<const lgr_corr*>(c.data()); };
+    check(lgr_color_correspondences(context(), n, key_point_indices ? kp.data() : nullptr, key_point_indices ? (int) key_point_indices->size() : 0,
+                                    list(correspondences), (int) correspondences.size(), list(correct_correspondences), (int) correct_correspondences.size(),
+                                    list(inliers), (int) inliers.size(), is_source ? 1 : 0, colors.data()), "savePointCloudWithCorrespondences");
+    PointColoredNCloud dst;
+    dst.points.resize((std::size_t) n);
+    for (int i = 0; i < n; ++i) {
+        copyPoint(aligned.points[(std::size_t) i], dst.points[(std::size_t) i]);
+        setPointColor(dst.points[(std::size_t) i], colors[(std::size_t) i]);
+    }
+    savePLYFileBinary(debugPath(parameters, std::string("downsampled_") + (is_source ? "src" : "tgt")), dst);
+}
+
+// src/common.cpp:837-850
+inline void saveColorizedWeights(const PointNCloud::ConstPtr& pcd, std::vector<float>& weights, const std::string& name,
+                                 const AlignmentParameters& parameters, const Matrix4f& transformation_gt) {
+    const int n = (int) pcd->size();
+    std::vector<std::int32_t> colors((std::size_t) n + 1, 0);
+    check(lgr_color_weights(context(), weights.data(), n, colors.data(), nullptr), "saveColorizedWeights");
+    PointColoredNCloud dst;
+    dst.points.resize((std::size_t) n);
+    for (int i = 0; i < n; ++i) {
+        copyPoint(pcd->points[(std::size_t) i], dst.points[(std::size_t) i]);
+        setPointColor(dst.points[(std::size_t) i], colors[(std::size_t) i]);
+    }
+    transformPointCloudWithNormals(dst, dst, transformation_gt);
+    savePLYFileBinary(debugPath(parameters, name), dst);
+}
+
+// src/common.cpp:908-963: <name>_distances_{src,tgt}.csv, <name>_dists_{src,tgt}.ply (ASCII), <name>_normal_diffs_{src,tgt}.ply (binary);
+// one search per direction serves both temperature types
+inline void saveTemperatureMaps(PointNCloud::Ptr& src, PointNCloud::Ptr& tgt, const std::string& name, const AlignmentParameters& params,
+                                float distance_thr, const Matrix4f& transformation, bool normals_available = true) {
+    if (!normals_available) {
+        estimateNormalsPoints(params.normal_nr_points, src, {nullptr}, params.vp_src, false);
+        estimateNormalsPoints(params.normal_nr_points, tgt, {nullptr}, params.vp_tgt, false);
+    }
+    const std::size_t ns = src->size(), nt = tgt->size();
+    PointNCloud moved;
+    moved.points.resize(ns);
+    std::vector<float> t_src(ns + 1, distance_thr), t_tgt(nt + 1, distance_thr);
+    const std::int32_t top_d = getColor(distance_thr, 0.f, distance_thr), top_n = getColor((float) M_PI / 2, 0.f, (float) M_PI / 2);
+    std::vector<std::int32_t> cd_src(ns + 1, top_d), cn_src(ns + 1, top_n), cd_tgt(nt + 1, top_d), cn_tgt(nt + 1, top_n);
+    lgr_temperature_out os{}, ot{};
+    os.temp_distance = t_src.data(); os.color_distance = cd_src.data(); os.color_normal = cn_src.data();
+    ot.temp_distance = t_tgt.data(); ot.color_distance = cd_tgt.data(); ot.color_normal = cn_tgt.data();
+    int n_below[2];
+    check(lgr_temperature_maps(context(), raw(*src), (int) ns, raw(*tgt), (int) nt, transformation.data(), distance_thr, &os, &ot,
+                               ns ? reinterpret_cast<float*>(moved.points.data()) : nullptr, n_below), "saveTemperatureMaps");
+    if (ns == 0 || nt == 0) transformPointCloudWithNormals(*src, moved, transformation);   // (the library writes nothing for an empty cloud)
+    t_src.resize(ns); t_tgt.resize(nt);
+    auto keep = [&](std::vector<float>& t) { t.erase(std::remove_if(t.begin(), t.end(), [&](float d) { return d >= distance_thr; }), t.end()); };
+    keep(t_src); keep(t_tgt);
+    saveVector(t_src, debugPath(params, name + "_distances_src", "csv"));
+    saveVector(t_tgt, debugPath(params, name + "_distances_tgt", "csv"));
+    auto colored = [](const PointNCloud& c, const std::vector<std::int32_t>& col) {
+        PointColoredNCloud out;
+        out.points.resize(c.size());
+        for (std::size_t i = 0; i < c.size(); ++i) { copyPoint(c.points[i], out.points[i]); setPointColor(out.points[i], col[i]); }
+        return out;
+    };
+    savePLYFileASCII(debugPath(params, name + "_dists_src"), colored(moved, cd_src));
+    savePLYFileASCII(debugPath(params, name + "_dists_tgt"), colored(*tgt, cd_tgt));
+    savePLYFileBinary(debugPath(params, name + "_normal_diffs_src"), colored(moved, cn_src));
+    savePLYFileBinary(debugPath(params, name + "_normal_diffs_tgt"), colored(*tgt, cn_tgt));
+}
 
 // src/utils.cpp:13-24: split at every occurrence of the delimiter; an empty last piece is dropped, empty inner pieces stay
 inline void split(const std::string& str, std::vector<std::string>& tokens, const std::string& delimiter) {

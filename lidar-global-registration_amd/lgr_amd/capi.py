@@ -142,6 +142,15 @@ class MetricEval(C.Structure):
     _fields_ = [("metric", C.c_float), ("rmse", C.c_float), ("n_inliers", C.c_int32), ("n_correct_inliers", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class TemperatureOut(C.Structure):
+    """lgr_temperature_out (include/lgr.h): five optional per-point arrays of one temperature map."""
+    _fields_ = [("temp_distance", C.c_void_p), ("temp_normal", C.c_void_p), ("color_distance", C.c_void_p), ("color_normal", C.c_void_p), ("nn", C.c_void_p)]
+
+
+TEMP_FIELDS = ("temp_distance", "temp_normal", "color_distance", "color_normal", "nn")
+COLOR_BEIGE, COLOR_RED, COLOR_PARAKEET, COLOR_BLUE, COLOR_WHITE = 0xf8c471, 0xff0000, 0x03c04a, 0x0000ff, 0xffffff
+
+
 class LgrError(RuntimeError):
     pass
 
@@ -984,3 +993,177 @@ class Context:
                                             self._T16(T_gt) if T_gt is not None else None, int(metric_id), int(score_id),
                                             C.byref(mp) if mp is not None else None, C.byref(out), None, None))
         return out
+
+    # ---- the debug command: temperature maps, overlap comparison, colour passes (src/main.cpp:152-284, src/common.cpp:771-963) ----
+    def _temp_out_dev(self, n):
+        torch = self.torch
+        t = dict(temp_distance=self.empty((max(n, 1),), torch.float32), temp_normal=self.empty((max(n, 1),), torch.float32),
+                 color_distance=self.empty((max(n, 1),), torch.int32), color_normal=self.empty((max(n, 1),), torch.int32),
+                 nn=self.empty((max(n, 1),), torch.int32))
+        return t, TemperatureOut(*[t[k].data_ptr() for k in TEMP_FIELDS])
+
+    @staticmethod
+    def _temp_out_host(n):
+        t = dict(temp_distance=np.zeros(max(n, 1), np.float32), temp_normal=np.zeros(max(n, 1), np.float32), color_distance=np.zeros(max(n, 1), np.int32),
+                 color_normal=np.zeros(max(n, 1), np.int32), nn=np.zeros(max(n, 1), np.int32))
+        return t, TemperatureOut(*[t[k].ctypes.data for k in TEMP_FIELDS])
+
+    def temperature_map(self, compared, reference, distance_max):
+        """lgr_temperature_map_dev on cuda clouds [n, 12] -> dict(temp_distance, temp_normal (numpy float32), color_distance, color_normal
+        (numpy int32, 0x00RRGGBB), nn (numpy int32, -1 = none), n_below).  With an empty cloud the arrays are empty (nothing is written)."""
+        n, nr = compared.shape[0], reference.shape[0]
+        t, o = self._temp_out_dev(n)
+        nb = C.c_int(0)
+        self.check(_lib.lgr_temperature_map_dev(self.h, _ptr(compared), n, _ptr(reference), nr, C.c_float(distance_max), C.byref(o), C.byref(nb)))
+        self._join()
+        m = n if nr else 0
+        out = {k: v[:m].cpu().numpy() for k, v in t.items()}
+        out["n_below"] = nb.value
+        return out
+
+    def temperature_map_host(self, compared, reference, distance_max):
+        compared = np.ascontiguousarray(compared, np.float32); reference = np.ascontiguousarray(reference, np.float32)
+        n, nr = compared.shape[0], reference.shape[0]
+        t, o = self._temp_out_host(n)
+        nb = C.c_int(0)
+        self.check(_lib.lgr_temperature_map(self.h, _ptr(compared), n, _ptr(reference), nr, C.c_float(distance_max), C.byref(o), C.byref(nb)))
+        out = {k: v[:n if nr else 0] for k, v in t.items()}
+        out["n_below"] = nb.value
+        return out
+
+    def temperature_maps(self, src, tgt, T, distance_thr):
+        """lgr_temperature_maps_dev -> dict(src=<as temperature_map>, tgt=<...>, moved: cuda float32 [ns, 12], the source moved by T)"""
+        ns, nt = src.shape[0], tgt.shape[0]
+        a, oa = self._temp_out_dev(ns)
+        b, ob = self._temp_out_dev(nt)
+        moved = self.empty((max(ns, 1), 12), self.torch.float32)
+        nb = (C.c_int * 2)()
+        self.check(_lib.lgr_temperature_maps_dev(self.h, _ptr(src), ns, _ptr(tgt), nt, self._T16(T), C.c_float(distance_thr), C.byref(oa), C.byref(ob),
+                                                 _ptr(moved), nb))
+        self._join()
+        any_ = ns > 0 and nt > 0
+        s = {k: v[:ns if any_ else 0].cpu().numpy() for k, v in a.items()}
+        t = {k: v[:nt if any_ else 0].cpu().numpy() for k, v in b.items()}
+        s["n_below"], t["n_below"] = nb[0], nb[1]
+        return dict(src=s, tgt=t, moved=moved[:ns if any_ else 0])
+
+    def temperature_maps_host(self, src, tgt, T, distance_thr):
+        """lgr_temperature_maps: numpy in, numpy out (moved: numpy [ns, 12])"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        ns, nt = src.shape[0], tgt.shape[0]
+        a, oa = self._temp_out_host(ns)
+        b, ob = self._temp_out_host(nt)
+        moved = np.zeros((max(ns, 1), 12), np.float32)
+        nb = (C.c_int * 2)()
+        self.check(_lib.lgr_temperature_maps(self.h, _ptr(src), ns, _ptr(tgt), nt, self._T16(T), C.c_float(distance_thr), C.byref(oa), C.byref(ob),
+                                             _ptr(moved), nb))
+        any_ = ns > 0 and nt > 0
+        s = {k: v[:ns if any_ else 0] for k, v in a.items()}
+        t = {k: v[:nt if any_ else 0] for k, v in b.items()}
+        s["n_below"], t["n_below"] = nb[0], nb[1]
+        return dict(src=s, tgt=t, moved=moved[:ns if any_ else 0])
+
+    @staticmethod
+    def _tns16(Ts):
+        flat = np.concatenate([np.asarray(T, np.float32).T.reshape(16) for T in Ts]) if len(Ts) else np.zeros(0, np.float32)
+        return np.ascontiguousarray(flat, np.float32)
+
+    def compare_overlaps(self, src, tgt, Ts, distance_thr, with_masks=True):
+        """lgr_compare_overlaps_dev for the transformations Ts (4x4 each) -> dict(counts int32 [n], weighted float32 [n], counts2 int32 [n, 2],
+        mask_src uint8 [n, ns], mask_tgt uint8 [n, nt]) as numpy (masks only when asked for)"""
+        torch = self.torch
+        ns, nt, n = src.shape[0], tgt.shape[0], len(Ts)
+        tns = self._tns16(Ts)
+        counts = np.zeros(max(n, 1), np.int32); w = np.zeros(max(n, 1), np.float32); c2 = np.zeros((max(n, 1), 2), np.int32)
+        ms = torch.zeros((max(n * ns, 1),), dtype=torch.uint8, device=self._dev()) if with_masks else None
+        mt = torch.zeros((max(n * nt, 1),), dtype=torch.uint8, device=self._dev()) if with_masks else None
+        self.check(_lib.lgr_compare_overlaps_dev(self.h, _ptr(src), ns, _ptr(tgt), nt, _ptr(tns), n, C.c_float(distance_thr), _ptr(counts), _ptr(w), _ptr(c2),
+                                                 _ptr(ms), _ptr(mt)))
+        self._join()
+        out = dict(counts=counts[:n], weighted=w[:n], counts2=c2[:n])
+        if with_masks:
+            out["mask_src"] = ms[: n * ns].cpu().numpy().reshape(n, ns)
+            out["mask_tgt"] = mt[: n * nt].cpu().numpy().reshape(n, nt)
+        return out
+
+    def compare_overlaps_host(self, src, tgt, Ts, distance_thr, with_masks=True):
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        ns, nt, n = src.shape[0], tgt.shape[0], len(Ts)
+        tns = self._tns16(Ts)
+        counts = np.zeros(max(n, 1), np.int32); w = np.zeros(max(n, 1), np.float32); c2 = np.zeros((max(n, 1), 2), np.int32)
+        ms = np.zeros(max(n * ns, 1), np.uint8) if with_masks else None
+        mt = np.zeros(max(n * nt, 1), np.uint8) if with_masks else None
+        self.check(_lib.lgr_compare_overlaps(self.h, _ptr(src), ns, _ptr(tgt), nt, _ptr(tns), n, C.c_float(distance_thr), _ptr(counts), _ptr(w), _ptr(c2),
+                                             _ptr(ms), _ptr(mt)))
+        out = dict(counts=counts[:n], weighted=w[:n], counts2=c2[:n])
+        if with_masks:
+            out["mask_src"] = ms[: n * ns].reshape(n, ns)
+            out["mask_tgt"] = mt[: n * nt].reshape(n, nt)
+        return out
+
+    def nearest(self, q, pts):
+        """lgr_nearest_dev: q, pts cuda float32 [n, 12] -> (idx cuda int32 [nq], d2 cuda float32 [nq]); exact for queries anywhere"""
+        idx = self.empty((max(q.shape[0], 1),), self.torch.int32); d2 = self.empty((max(q.shape[0], 1),), self.torch.float32)
+        self.check(_lib.lgr_nearest_dev(self.h, _ptr(q), q.shape[0], _ptr(pts), pts.shape[0], _ptr(idx), _ptr(d2)))
+        self._join()
+        return idx[: q.shape[0]], d2[: q.shape[0]]
+
+    def color_map(self, values, vmin=None, vmax=None):
+        """getColor per value of a cuda float32 vector -> numpy int32 colours.  Without a range: saveColorizedWeights' 0.01 / 0.99 quantiles
+        (lgr_color_weights_dev), and the result is (colours, (q01, q99))."""
+        n = values.shape[0]
+        col = self.empty((max(n, 1),), self.torch.int32)
+        if vmin is None and vmax is None:
+            r = (C.c_float * 2)()
+            self.check(_lib.lgr_color_weights_dev(self.h, _ptr(values), n, _ptr(col), r))
+            self._join()
+            return col[:n].cpu().numpy(), (np.float32(r[0]), np.float32(r[1]))
+        self.check(_lib.lgr_color_map_dev(self.h, _ptr(values), n, C.c_float(vmin), C.c_float(vmax), _ptr(col)))
+        self._join()
+        return col[:n].cpu().numpy()
+
+    def color_map_host(self, values, vmin=None, vmax=None):
+        values = np.ascontiguousarray(values, np.float32)
+        n = values.shape[0]
+        col = np.zeros(max(n, 1), np.int32)
+        if vmin is None and vmax is None:
+            r = (C.c_float * 2)()
+            self.check(_lib.lgr_color_weights(self.h, _ptr(values), n, _ptr(col), r))
+            return col[:n], (np.float32(r[0]), np.float32(r[1]))
+        self.check(_lib.lgr_color_map(self.h, _ptr(values), n, C.c_float(vmin), C.c_float(vmax), _ptr(col)))
+        return col[:n]
+
+    @staticmethod
+    def _corr_host(c):
+        return np.zeros(0, CORR_DTYPE) if c is None else np.ascontiguousarray(np.asarray(c).view(CORR_DTYPE).reshape(-1))
+
+    def color_correspondences(self, n, key_points, corr, correct, inliers, is_source):
+        """lgr_color_correspondences_dev: the colours savePointCloudWithCorrespondences gives n points.  key_points: None (no key points: beige
+        base) or int32 indices; corr / correct / inliers: None or correspondences (numpy CORR_DTYPE or cuda int32 [c, 4]) -> numpy int32 [n]"""
+        torch = self.torch
+        lists = [self._corr_dev(self._corr_host(x) if x is None or isinstance(x, np.ndarray) else x) for x in (corr, correct, inliers)]
+        kp, n_kp = None, 0
+        if key_points is not None:
+            k = np.ascontiguousarray(key_points.cpu().numpy() if hasattr(key_points, "cpu") else key_points, np.int32)
+            n_kp = len(k)
+            kp = torch.from_numpy(np.concatenate([k, np.zeros(1, np.int32)])).to(self._dev())   # never a null pointer: "key points given"
+        col = self.empty((max(n, 1),), torch.int32)
+        args = []
+        for x in lists:
+            args += [_ptr(x) if x.shape[0] else None, x.shape[0]]
+        self.check(_lib.lgr_color_correspondences_dev(self.h, int(n), _ptr(kp), n_kp, *args, int(bool(is_source)), _ptr(col)))
+        self._join()
+        return col[:n].cpu().numpy()
+
+    def color_correspondences_host(self, n, key_points, corr, correct, inliers, is_source):
+        lists = [self._corr_host(x) for x in (corr, correct, inliers)]
+        kp, n_kp = None, 0
+        if key_points is not None:
+            n_kp = len(key_points)
+            kp = np.concatenate([np.ascontiguousarray(key_points, np.int32), np.zeros(1, np.int32)])
+        col = np.zeros(max(n, 1), np.int32)
+        args = []
+        for x in lists:
+            args += [_ptr(x) if x.shape[0] else None, x.shape[0]]
+        self.check(_lib.lgr_color_correspondences(self.h, int(n), _ptr(kp), n_kp, *args, int(bool(is_source)), _ptr(col)))
+        return col[:n]

@@ -141,7 +141,69 @@ def write_ply(path, pts, binary=True, with_normals=True):
                 f.write((" ".join("%.9g" % float(v) for v in row) + "\n").encode())   # 9 digits: reads back to the same float
 
 
+def write_ply_colored(path, pts, colors, binary=True):
+    """PointXYZRGBNormal cloud (the reference's PointColoredN) as pcl::io::savePLYFileBinary / savePLYFileASCII name its properties: x y z,
+    red green blue (uchar), normal_x normal_y normal_z, curvature -- the order of the point type's field list as we read PCL 1.12.1 (not
+    checked against a PCL build: DESIGN.md section 9).  colors: 0x00RRGGBB per point.  host/lgr_io.hpp writes the same bytes."""
+    pts = np.ascontiguousarray(pts, np.float32)
+    colors = np.ascontiguousarray(colors).astype(np.int64) & 0xffffff
+    n = pts.shape[0]
+    assert colors.shape == (n,), (colors.shape, n)
+    rec = np.zeros(n, np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3), ("nrm", "<f4", 3), ("curvature", "<f4")]))
+    rec["xyz"] = pts[:, 0:3]
+    rec["rgb"] = np.stack([(colors >> 16) & 255, (colors >> 8) & 255, colors & 255], 1)
+    rec["nrm"] = pts[:, 4:7]
+    rec["curvature"] = pts[:, 9]
+    with open(path, "wb") as f:
+        f.write(("ply\nformat %s 1.0\nelement vertex %d\n" % ("binary_little_endian" if binary else "ascii", n)).encode())
+        for name in ("x", "y", "z"):
+            f.write(("property float %s\n" % name).encode())
+        for name in ("red", "green", "blue"):
+            f.write(("property uchar %s\n" % name).encode())
+        for name in ("normal_x", "normal_y", "normal_z", "curvature"):
+            f.write(("property float %s\n" % name).encode())
+        f.write(b"end_header\n")
+        if binary:
+            rec.tofile(f)
+        else:
+            for r in rec:
+                vals = ["%.9g" % float(v) for v in r["xyz"]] + ["%d" % int(v) for v in r["rgb"]] + ["%.9g" % float(v) for v in r["nrm"]]
+                f.write((" ".join(vals + ["%.9g" % float(r["curvature"])]) + "\n").encode())
+
+
+def read_ply_colors(path):
+    """the colours of a PLY written by write_ply_colored, 0x00RRGGBB per point (read_ply gives the points and normals)"""
+    with open(path, "rb") as f:
+        names, types, n, fmt = [], [], 0, None
+        while True:
+            tok = f.readline().decode("ascii", "replace").split()
+            if tok and tok[0] == "format":
+                fmt = tok[1]
+            elif tok and tok[0] == "element":
+                n = int(tok[2])
+            elif tok and tok[0] == "property":
+                names.append(tok[2]); types.append(_PLY_TYPES[tok[1]])
+            elif tok and tok[0] == "end_header":
+                break
+        if fmt == "ascii":
+            raw = np.loadtxt(f, dtype=np.float64, max_rows=n, ndmin=2) if n else np.zeros((0, len(names)))
+            cols = {name: raw[:, i] for i, name in enumerate(names)}
+        else:
+            dt = np.dtype([(name, "<" + t) for name, t in zip(names, types)])
+            raw = np.frombuffer(f.read(n * dt.itemsize), dt, count=n)
+            cols = {name: raw[name] for name in names}
+    return ((cols["red"].astype(np.int32) << 16) + (cols["green"].astype(np.int32) << 8) + cols["blue"].astype(np.int32)).astype(np.int32)
+
+
 # ---------------------------------------------------------------------------------------------------------- CSV
+def save_vector(path, values):
+    """include/utils.h:92-103 saveVector: a `value` header, then one value per line as `ostream << float` prints it"""
+    with open(path, "w") as f:
+        f.write("value\n")
+        for v in np.asarray(values).reshape(-1):
+            f.write(_g(v) + "\n")
+
+
 def save_transformation(csv_path, name, T):
     """saveTransformation (src/common.cpp:127-153): append one row, header on creation."""
     exists = os.path.exists(csv_path)

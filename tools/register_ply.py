@@ -4,6 +4,7 @@
     python tools/register_ply.py source.ply target.ply [--keypoint iss|any] [--metric uniformity|combination|...]
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
+                                 [--debug-dir DIR]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
@@ -11,6 +12,12 @@ With --ground-truth: formats.get_transformation -> lgr_analysis_metric (the dens
 metric) + lgr_evaluate_gt (AlignmentAnalysis::start, src/analysis.cpp:218-246), printed in the order of AlignmentAnalysis::print (:248-272)
 and appended to results.csv as AlignmentAnalysis::save does (:274-328).  With --metrics-csv as well: estimateTestMetric's row
 (src/main.cpp:41-116) -- the correspondence metric and the dense closest-plane metric of the found transformation and of the ground truth.
+With --debug-dir: the files of generateDebugFiles and compareHypotheses (src/main.cpp:207-284) in DIR, each named <stem>.<ext> with the
+reference's `name` argument as the stem -- downsampled_tgt.ply (and downsampled_src.ply with a ground truth: key points beige, correspondences
+red, inliers blue, correct correspondences mixed with white), weights.ply under weighted_closest_plane, temperature_{distances_src,
+distances_tgt}.csv, temperature_{dists_src,dists_tgt}.ply (ASCII) and temperature_{normal_diffs_src,normal_diffs_tgt}.ply for the found
+transformation; with a ground truth the same six as temperature_gt_* and compareOverlaps' two lines.  The histogram PNGs are not written
+(plots.py is no part of this project).
 """
 import argparse
 import os
@@ -42,6 +49,7 @@ def main():
                     help="transformation CSV and the row that holds the ground truth: analyse the result against it")
     ap.add_argument("--results", default="results.csv", help="results.csv the analysis row is appended to (with --ground-truth)")
     ap.add_argument("--metrics-csv", default=None, help="metrics.csv estimateTestMetric's row is appended to (needs --ground-truth)")
+    ap.add_argument("--debug-dir", default=None, help="write the files of generateDebugFiles / compareHypotheses (src/main.cpp:207-284) there")
     a = ap.parse_args()
     if a.metrics_csv and not a.ground_truth:
         ap.error("--metrics-csv needs --ground-truth")
@@ -78,6 +86,61 @@ def main():
         formats.save_transformation(a.out, name, T)
     if a.ground_truth:
         analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
+    if a.debug_dir:
+        debug_files(ctx, capi, formats, a, p, clouds, T, lrf)
+
+
+def debug_files(ctx, capi, formats, a, p, clouds, T, lrf):
+    """generateDebugFiles, and with a ground truth compareHypotheses, for the alignment just made"""
+    import numpy as np
+    os.makedirs(a.debug_dir, exist_ok=True)
+    src, tgt = clouds
+    ns, nt = src.shape[0], tgt.shape[0]
+    T_gt = formats.get_transformation(a.ground_truth[0], a.ground_truth[1]) if a.ground_truth else None
+    written = []
+
+    def path(stem, ext="ply"):
+        written.append(stem + "." + ext)
+        return os.path.join(a.debug_dir, stem + "." + ext)
+
+    # one call per transformation: both temperature maps and the moved source (the clouds of the other files)
+    maps = {"temperature": ctx.temperature_maps(src, tgt, T, p.distance_thr)}
+    if T_gt is not None:
+        maps["temperature_gt"] = ctx.temperature_maps(src, tgt, T_gt, p.distance_thr)
+    desc = a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf)
+    corr = ctx.correspondences(src, tgt, p, descriptor=desc).cpu().numpy().view(capi.CORR_DTYPE).reshape(-1)
+    # metric_estimator->buildInliers(tn, inliers, error, rand) in the estimator's dense form
+    if a.metric in ("closest_plane", "weighted_closest_plane"):
+        inliers = ctx.evaluate_plane_dense(src, tgt, T, p.score_id, with_inliers=True).inliers
+    else:
+        mask, _, _, _ = ctx.evaluate(src, tgt, corr, T, metric_id=p.metric_id, score_id=p.score_id)
+        inliers = corr[np.asarray(mask.cpu().numpy() if hasattr(mask, "cpu") else mask, bool)]
+    kps = []
+    for cloud, radius in ((src, p.iss_radius_src), (tgt, p.iss_radius_tgt)):   # detectKeyPoints
+        k = ctx.iss_keypoints(cloud, radius).cpu().numpy() if a.keypoint == "iss" else np.arange(cloud.shape[0], dtype=np.int32)
+        kps.append(np.sort(k).astype(np.int32))
+    correct = corr[:0]
+    if T_gt is not None:
+        cm, _, _, _ = ctx.correct_correspondences(src, tgt, corr, T_gt)
+        correct = corr[cm.astype(bool)]
+        formats.write_ply_colored(path("downsampled_src"), maps["temperature_gt"]["moved"].cpu().numpy(),
+                                  ctx.color_correspondences(ns, kps[0], corr, correct, inliers, True))
+    formats.write_ply_colored(path("downsampled_tgt"), tgt.cpu().numpy(), ctx.color_correspondences(nt, kps[1], corr, correct, inliers, False))
+    if a.metric == "weighted_closest_plane":
+        w, _ = ctx.weights(src, a.weight, with_sum=False)
+        colors, _ = ctx.color_map(w)
+        formats.write_ply_colored(path("weights"), maps["temperature"]["moved"].cpu().numpy(), colors)
+    for stem, m in maps.items():
+        for side, cloud in (("src", m["moved"].cpu().numpy()), ("tgt", tgt.cpu().numpy())):
+            s = m[side]
+            formats.save_vector(path(f"{stem}_distances_{side}", "csv"), s["temp_distance"][s["temp_distance"] < np.float32(p.distance_thr)])
+            formats.write_ply_colored(path(f"{stem}_dists_{side}"), cloud, s["color_distance"], binary=False)
+            formats.write_ply_colored(path(f"{stem}_normal_diffs_{side}"), cloud, s["color_normal"], binary=True)
+    if T_gt is not None:
+        o = ctx.compare_overlaps(src, tgt, [T, T_gt], p.distance_thr, with_masks=False)
+        print(f"\tincorrect hypothesis: {o['counts'][0]} points, {formats._g(o['weighted'][0])}weighted points")
+        print(f"\t  correct hypothesis: {o['counts'][1]} points, {formats._g(o['weighted'][1])}weighted points")
+    print(f"wrote {len(written)} debug files to {a.debug_dir}: " + " ".join(written))
 
 
 def analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
