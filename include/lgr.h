@@ -521,6 +521,47 @@ int lgr_gror_node_degree_dev(lgr_ctx*, const float* d_src, const float* d_tgt, c
 int lgr_choose_best_hypothesis_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
                                    const float* tns16 /* host, n x 16 */, int n, float T_out16[16], int* best_index, float* uniformities /* host, n, or NULL */);
 int lgr_update_hypotheses(float* tns16, float* metrics, int n, int cap, const float* new_T16, float new_metric, float distance_thr);
+/* host twin of lgr_choose_best_hypothesis_dev: clouds and correspondences in host memory */
+int lgr_choose_best_hypothesis(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                               const float* tns16 /* n x 16 */, int n, float T_out16[16], int* best_index, float* uniformities /* n, or NULL */);
+
+/* ---- the loop with SAVE_MULTIPLE_HYPOTHESES set (src/sac_prerejective_omp.cpp:11): the set of distinct hypotheses ----
+ * The fold alone: src/hypotheses.cpp:14-48 updateHypotheses applied to n (transform, metric) items in the caller's order, starting from
+ * the empty set (the reference's call sites src/sac_prerejective_omp.cpp:143, :230, :261 fold the loop's hypotheses one by one).
+ * Returns the members in set order: their transforms (column-major, the items' own 16 floats), metrics and positions in the item list.
+ * 1 <= max_set <= LGR_HYPOTHESES_MAX, anything else is LGR_ERR_INVALID_ARG; a set that outgrows max_set at the end of any step is
+ * LGR_ERR_UNSUPPORTED (never a truncated set).  Transforms are read as R|t: an item's fourth row does not enter a decision. */
+#define LGR_HYPOTHESES_MAX 2048
+int lgr_fold_hypotheses_dev(lgr_ctx*, const float* d_tns16 /* n x 16 */, const float* d_metrics, int n, float distance_thr, int max_set,
+                            float* d_set_tns16 /* max_set x 16 */, float* d_set_metrics, int32_t* d_set_index, int* n_out /* host */);
+int lgr_fold_hypotheses(lgr_ctx*, const float* tns16, const float* metrics, int n, float distance_thr, int max_set,
+                        float* set_tns16, float* set_metrics, int32_t* set_index, int* n_out);
+
+/* One member of the set after the final block (src/sac_prerejective_omp.cpp:270-291 per member) */
+typedef struct {
+    float   loop_transformation[16];   /* column-major, as the loop produced it (the guess: as given) */
+    float   transformation[16];        /* after the refit over its inliers (:282) */
+    int32_t iteration;                 /* the iteration that produced it; -1: the guess (:139-143) */
+    float   loop_metric, metric;       /* in the loop (:230) / of the refit (:290) */
+    int32_t n_inliers, converged;      /* of the refit / enough inliers and a metric above the estimator's minimum (:277-281) */
+    float   uniformity;                /* chooseBestHypothesis' criterion of the refit (src/hypotheses.cpp:50-129) */
+} lgr_hypothesis;
+
+/* SampleConsensusPrerejectiveOMP::align with SAVE_MULTIPLE_HYPOTHESES: the loop of lgr_ransac_dev, every accepted hypothesis folded
+ * through updateHypotheses with params->distance_thr (:143 the guess, which passes no inlier gate; :230 / :261 every iteration that
+ * survives prerejection with >= MIN_NR_INLIERS inliers), the final block on every member (:270-291) and chooseBestHypothesis over the
+ * refit transforms (:293).  Declared order: one stream, the guess first, then the iterations ascending (the
+ * reference folds per OpenMP thread and merges the threads' sets in thread order).
+ * res: iterations, num_rejections, estimated_iters, best_iteration and best_metric_before_refit are lgr_ransac_dev's on the same input;
+ * converged = any member converged; transformation, n_inliers and metric are the chosen member's (identity, 0, 0 when none has a
+ * positive uniformity: *best_index = -1).  out receives *n_out <= max_set members in set order.
+ * Metrics uniformity and correspondences; the plane metrics, combination and alignment_id = gror return LGR_ERR_UNSUPPORTED, and so does
+ * a set that outgrows max_set (1 <= max_set <= LGR_HYPOTHESES_MAX, else LGR_ERR_INVALID_ARG).  c < n_samples: LGR_OK, empty set,
+ * identity, as lgr_ransac_ex_dev.  Always driven as a chain of launches (lgr_ctx_options.ransac_schedule does not apply). */
+int lgr_ransac_multi_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                         const lgr_params*, int max_set, lgr_result* res, lgr_hypothesis* out /* host, max_set */, int* n_out, int* best_index);
+int lgr_ransac_multi(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                     const lgr_params*, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index);
 
 /* ---- include/analysis.h:36-98 AlignmentAnalysis::start(transformation_gt, testname) (src/analysis.cpp:218-246): a transformation judged
  *      against a known ground truth.  What the reference leaves unordered (OpenMP reductions, kd-tree ties) has the declared orders of

@@ -128,6 +128,7 @@ enum {
     WS_GT_MISC, WS_GT_TERMS, WS_GT_ALIGNED, WS_GT_OVERLAP, WS_GT_FLAGS, WS_GT_KNN, WS_GT_DENS, WS_GT_CORR,   // lgr_analysis.hip
     WS_PD_TERMS, WS_PD_MISC, WS_PD_INLIERS, WS_PD_MASK,   // lgr_plane_dense.hip
     WS_DBG_MISC, WS_DBG_MOVED, WS_DBG_FLAGS, WS_DBG_OVERLAP, WS_DBG_DENS, WS_DBG_SORT, WS_DBG_HOST_A, WS_DBG_HOST_B,   // lgr_debug.hip
+    WS_HYP_SET, WS_HYP_ITEMS, WS_HYP_FINAL,   // lgr_hypotheses.hip, lgr_ransac_multi_dev
     WS_COUNT
 };
 static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");
@@ -256,6 +257,17 @@ static inline int lgr_stage_host_weights(lgr_ctx* ctx, int ns, const lgr_metric_
     *staged = **mp; staged->weights = dw; *mp = staged;
     return LGR_OK;
 }
+
+// ---- the set of distinct hypotheses (lgr_hypotheses.hip): the left fold of updateHypotheses (src/hypotheses.cpp:14-48) on the device ----
+// The set between two launches: members in set order as 12 floats R|t (the columns of R, then t), their metrics and source indices, and
+// the fold's state.  lgr_fold_begin empties it (WS_HYP_SET); lgr_fold_launch folds `n` items (d_n: the number lives on the device, n is
+// then its upper bound) in order into it -- item i is the transform d_T16 + 16 i with metric d_metric[i] and source index
+// d_index ? d_index[i] : index_base + i.  A set that would outgrow `cap` sets `overflow`, after which every later launch returns at once.
+struct lgr_fold_state { int n, overflow; float best; int peak; };
+struct lgr_fold_set { float* rt; float* metric; int32_t* index; lgr_fold_state* state; int cap; };
+int lgr_fold_begin(lgr_ctx* ctx, int cap, lgr_fold_set* out);
+int lgr_fold_launch(lgr_ctx* ctx, const lgr_fold_set& set, const float* d_T16, const float* d_metric, const int32_t* d_index, int index_base, int n,
+                    const int* d_n, float distance_thr);
 
 // ---- closest-plane metric on the device (lgr_plane.hip) ----
 struct lgr_plane_dev {

@@ -1947,3 +1947,242 @@ extern "C" int lgr_update_hypotheses(float* tns16, float* metrics, int n, int ca
             if (M[i] < 0.1 * new_metric) { T.erase(T.begin() + i); M.erase(M.begin() + i); }
     return flush();
 }
+
+extern "C" int lgr_choose_best_hypothesis(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                                          const float* tns16, int n, float T_out16[16], int* best_index, float* uniformities) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, src && tgt && (corr || c == 0) && (tns16 || n == 0) && T_out16 && n >= 0 && c >= 0 && ns > 0 && nt > 0, LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    float *ds, *dt;
+    lgr_corr* dc;
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, &ds));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, &dt));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
+    LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
+    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * 16, hipMemcpyHostToDevice, ctx->stream));
+    return lgr_choose_best_hypothesis_dev(ctx, ds, ns, dt, nt, dc, c, tns16, n, T_out16, best_index, uniformities);
+}
+
+// ---------------------------------------------------------------------------------------------------- the set of distinct hypotheses
+// SampleConsensusPrerejectiveOMP::align with SAVE_MULTIPLE_HYPOTHESES (src/sac_prerejective_omp.cpp:11): every accepted hypothesis goes
+// through updateHypotheses (:143, :230, :261), the final block runs on every member of the set (:270-291) and chooseBestHypothesis picks
+// the result (:293).  The loop above never scores a hypothesis that cannot beat the best one so far, so the set is built by a SECOND PASS
+// over [0, iterations) once the loop has ended and its best metric M* is known: an item below 0.1 * M* can only block or erase other such
+// items, and the prune after the last new best removes every one of them, so the fold of the items with !(metric < 0.1 * M*) is the fold of
+// all items.  Hypothesis generation is a pure function of (seed, iteration): the pass regenerates the round's hypotheses with the loop's
+// own kernels under the fixed gate that 0.1 * M* implies, keeps the candidates at or above 0.1 * M*, orders them by iteration (the
+// candidate list arrives in the order of an atomic append) and hands them to the fold (lgr_hypotheses.hip).
+namespace {
+__global__ void mh_begin_kernel(RState* __restrict__ S, int round_first, int nb, float gate_metric, int metric_id, int c) {
+    if (threadIdx.x != 0) return;
+    S->n_ok = 0; S->n_cand = 0; S->stop = 0;
+    S->round_first = round_first; S->round_nb = nb; S->round_batches = 1;
+    S->min_inliers = max(MIN_NR_INLIERS, rs_gate_dev(gate_metric, metric_id, c));
+}
+// candidate j (iteration offset list2[j]) is an item of the fold unless its metric is below 0.1 * M*
+__global__ void mh_keep_kernel(const RState* __restrict__ S, const int* __restrict__ list2, const float* __restrict__ metric, float m_star, int* __restrict__ kslot) {
+    const int n = S->n_cand;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
+        if (!((double) metric[j] < 0.1 * (double) m_star)) kslot[list2[j]] = j;
+}
+// the round's items in iteration order: one workgroup, an ordered block scan per 1024 iteration offsets
+__global__ __launch_bounds__(1024) void mh_order_kernel(const RState* __restrict__ S, const int* __restrict__ kslot, const float* __restrict__ Ts,
+                                                         const float* __restrict__ metric, float* __restrict__ item_T, float* __restrict__ item_m,
+                                                         int32_t* __restrict__ item_it, int* __restrict__ n_items) {
+    __shared__ int scan[1024 / 64 + 2];
+    const int tid = threadIdx.x, nb = S->round_nb, first = S->round_first;
+    int total = 0;
+    for (int o0 = 0; o0 < nb; o0 += 1024) {
+        const int off = o0 + tid;
+        const int j = off < nb ? kslot[off] : -1;
+        int tot;
+        const int pos = total + block_excl_scan_1024(j >= 0 ? 1 : 0, scan, tid, &tot);
+        if (j >= 0) {
+            const float4* s = reinterpret_cast<const float4*>(Ts + (size_t) off * 16);
+            float4* d = reinterpret_cast<float4*>(item_T + (size_t) pos * 16);
+            d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+            item_m[pos] = metric[j];
+            item_it[pos] = first + off;
+        }
+        total += tot;
+    }
+    if (tid == 0) n_items[0] = total;
+}
+
+struct ScheduleChain {   // the hypothesis set is always built on the launch chain (as the plane metrics are)
+    lgr_ctx* ctx; int32_t saved;
+    explicit ScheduleChain(lgr_ctx* c) : ctx(c), saved(c->opt.ransac_schedule) { c->opt.ransac_schedule = LGR_RANSAC_SCHEDULE_CHAIN; }
+    ~ScheduleChain() { ctx->opt.ransac_schedule = saved; }
+};
+}  // namespace
+
+extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                                    const lgr_params* p, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_TRY(check_params(ctx, p));
+    LGR_CHECK(ctx, p->metric_id == LGR_METRIC_UNIFORMITY || p->metric_id == LGR_METRIC_CORRESPONDENCES, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, p->alignment_id == LGR_ALIGN_RANSAC, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, max_set >= 1 && max_set <= LGR_HYPOTHESES_MAX, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, d_src && d_tgt && (d_corr || c == 0) && res && out && n_out && best_index && c >= 0 && ns > 0 && nt > 0, LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    auto t_start = std::chrono::steady_clock::now();
+    memset(res, 0, sizeof(*res));
+    for (int i = 0; i < 16; ++i) res->transformation[i] = (i % 5 == 0) ? 1.f : 0.f;
+    res->n_correspondences = c;
+    *n_out = 0; *best_index = -1;
+    if (c < p->n_samples) return LGR_OK;   // selectCorrespondences refuses (src/sac_prerejective_omp.cpp:36-42); identity, empty set
+    const uint64_t seed = p->fix_seed ? 566ull : p->seed;
+    Packed pk;
+    LGR_TRY(pack(ctx, d_src, ns, d_tgt, nt, d_corr, c, &pk));
+    const int max_iterations = std::min(comb_or_max(c, p->n_samples), p->max_iterations);
+    const int batch = std::max(1, p->ransac_batch);
+    uint8_t* d_mask;
+    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASK, (size_t) c + 16, &d_mask));
+    {
+        ScheduleChain chain(ctx);
+        LGR_TRY(ransac_device_schedule(ctx, d_src, d_tgt, d_corr, c, pk, p, seed, max_iterations, batch, d_mask, res));
+    }
+    const int iterations = res->iterations;
+    const float m_star = res->best_metric_before_refit;
+    res->converged = 0; res->n_inliers = 0; res->metric = 0.f;
+    for (int i = 0; i < 16; ++i) res->transformation[i] = (i % 5 == 0) ? 1.f : 0.f;
+
+    // ---- second pass: the loop's own buffers (the same slots and sizes: nothing is reallocated), the items of a round, the set
+    const int nb_max = (int) std::min<long long>((long long) batch * MAX_ROUND_BATCHES, std::max(max_iterations, 1));
+    BatchBuffers b;
+    LGR_TRY(batch_buffers(ctx, nb_max, &b));
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    RState* dS = &M->S;
+    float* d_ev = M->ev;
+    unsigned* maskT = nullptr;
+    int mask_cap = 0;
+    if (p->metric_id == LGR_METRIC_UNIFORMITY) {
+        const size_t words = mask_pitch(c);
+        mask_cap = (int) std::min<size_t>((size_t) nb_max, ((size_t) 2 << 30) / (words * 4));
+        if (mask_cap > 0) LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASKT, words * (size_t) mask_cap, &maskT));
+    }
+    const int g_metric = std::max(1, ctx->n_cu), g_count = 128 * std::max(1, ctx->n_cu);
+    float2* scratch = nullptr;
+    if (p->metric_id != LGR_METRIC_UNIFORMITY) LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_LIST, (size_t) g_metric * std::max(c, 1), &scratch));
+    float* item_T;
+    LGR_TRY(lgr_ws_t(ctx, WS_HYP_ITEMS, (size_t) nb_max * 19 + 16, &item_T));
+    float* item_m = item_T + (size_t) nb_max * 16;
+    int32_t* item_it = (int32_t*) (item_m + nb_max);
+    int* kslot = item_it + nb_max;
+    int* d_n_items = kslot + nb_max;
+    lgr_fold_set set;
+    LGR_TRY(lgr_fold_begin(ctx, max_set, &set));
+    LGR_HIP(ctx, hipFuncSetAttribute((const void*) metric_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) metric_smem()));
+    if (p->has_guess) {
+        // :139-143 the guess is the first item: the metric `evaluate` gives it, no inlier gate
+        LGR_HIP(ctx, hipMemcpyAsync(M->T, p->guess, 64, hipMemcpyHostToDevice, ctx->stream));
+        LGR_TRY(evaluate_one_dev(ctx, M->T, pk, c, p->metric_id, p->score_id, d_mask, d_ev, d_ev + 4));
+        LGR_TRY(lgr_fold_launch(ctx, set, M->T, d_ev + 4, nullptr, -1, 1, nullptr, p->distance_thr));
+    }
+    const float gate_metric = (float) (0.1 * (double) m_star);   // (rs_gate_dev's own margin is four orders of magnitude above this rounding)
+    for (int first = 0; first < iterations; first += nb_max) {
+        const int nb = std::min(nb_max, iterations - first);
+        mh_begin_kernel<<<1, 64, 0, ctx->stream>>>(dS, first, nb, gate_metric, p->metric_id, c);
+        LGR_HIP(ctx, hipMemsetAsync(kslot, 0xff, (size_t) nb * 4, ctx->stream));
+        LGR_NS_DISPATCH(p->n_samples, (rs_hyp_kernel<NS><<<cdiv(nb, 128), 128, 0, ctx->stream>>>(pk.P0, pk.P1, c, seed, dS, p->edge_thr_coef, b.Ts, b.list,
+                                                                                                  b.pos, b.counts)));
+        count_list_kernel<<<g_count, CB, 0, ctx->stream>>>(b.Ts, b.list, &dS->n_ok, pk.PP, pk.pstats, c, b.counts, maskT, mask_cap);
+        rs_cand_kernel<<<64, 1024, 0, ctx->stream>>>(dS, b.counts, b.list, b.list2, b.hpos);
+        metric_kernel<<<g_metric, MB, metric_smem(), ctx->stream>>>(b.Ts, b.list2, 0, pk.P0, pk.P1, pk.sstar, c, p->metric_id, p->score_id, b.metric, b.ninl,
+                                                                    nullptr, nullptr, scratch, maskT, b.hpos, mask_cap, nullptr, &dS->n_cand, &dS->n_ok);
+        mh_keep_kernel<<<64, 256, 0, ctx->stream>>>(dS, b.list2, b.metric, m_star, kslot);
+        mh_order_kernel<<<1, 1024, 0, ctx->stream>>>(dS, kslot, b.Ts, b.metric, item_T, item_m, item_it, d_n_items);
+        LGR_HIP(ctx, hipGetLastError());
+        LGR_TRY(lgr_fold_launch(ctx, set, item_T, item_m, item_it, 0, nb, d_n_items, p->distance_thr));
+    }
+    // ---- the set -> host
+    const size_t set_bytes = sizeof(lgr_fold_state) + (size_t) max_set * 14 * 4;
+    char* hs;
+    LGR_TRY(lgr_pinned(ctx, 64 + set_bytes, (void**) &hs));
+    LGR_HIP(ctx, hipMemcpyAsync(hs, set.state, sizeof(lgr_fold_state), hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(hs + 64, set.rt, (size_t) max_set * 14 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const lgr_fold_state fs = *(const lgr_fold_state*) hs;
+    if (fs.overflow) return lgr_fail(ctx, LGR_ERR_UNSUPPORTED, "the set of hypotheses outgrew max_set during the fold (a truncated set is never returned)", __FILE__, __LINE__);
+    const int n_set = fs.n;
+    {
+        const float* rt = (const float*) (hs + 64);
+        const float* sm = rt + (size_t) 12 * max_set;
+        const int32_t* si = (const int32_t*) (sm + max_set);
+        for (int k = 0; k < n_set; ++k) {
+            lgr_hypothesis& h = out[k];
+            memset(&h, 0, sizeof(h));
+            h.iteration = si[k]; h.loop_metric = sm[k];
+            if (si[k] < 0) memcpy(h.loop_transformation, p->guess, 64);
+            else {
+                for (int col = 0; col < 4; ++col)
+                    for (int r = 0; r < 3; ++r) h.loop_transformation[4 * col + r] = rt[(size_t) k * 12 + 3 * col + r];
+                h.loop_transformation[15] = 1.f;   // (umeyama_n's fourth row)
+            }
+        }
+    }
+    // ---- :270-291 the final block per member, enqueued blind; then chooseBestHypothesis' criterion of the refit (:293)
+    float* fin;
+    LGR_TRY(lgr_ws_t(ctx, WS_HYP_FINAL, (size_t) std::max(n_set, 1) * 44, &fin));
+    float* d_loopT = fin + (size_t) std::max(n_set, 1) * 12;
+    float* d_Tn = d_loopT + (size_t) std::max(n_set, 1) * 16;
+    for (int k = 0; k < n_set; ++k) {
+        LGR_HIP(ctx, hipMemcpyAsync(d_loopT + (size_t) k * 16, out[k].loop_transformation, 64, hipMemcpyHostToDevice, ctx->stream));
+        float* f = fin + (size_t) k * 12;
+        float* Tn = d_Tn + (size_t) k * 16;
+        LGR_TRY(evaluate_one_dev(ctx, d_loopT + (size_t) k * 16, pk, c, p->metric_id, p->score_id, d_mask, d_ev, f));
+        LGR_TRY(refit_launch(ctx, pk, c, d_mask, Tn));
+        LGR_TRY(evaluate_one_dev(ctx, Tn, pk, c, p->metric_id, p->score_id, d_mask, d_ev, f + 4));
+        LGR_TRY(evaluate_one_dev(ctx, Tn, pk, c, LGR_METRIC_UNIFORMITY, LGR_SCORE_MSE, d_mask, d_ev, f + 8));
+    }
+    if (n_set) {
+        std::vector<float> hf((size_t) n_set * 12), hT((size_t) n_set * 16);
+        LGR_HIP(ctx, hipMemcpyAsync(hf.data(), fin, hf.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        LGR_HIP(ctx, hipMemcpyAsync(hT.data(), d_Tn, hT.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const float min_tol = p->metric_id == LGR_METRIC_UNIFORMITY ? 0.3f : 0.0f;   // include/metric.h:97-99 / 73-75
+        float best = 0.f;
+        for (int k = 0; k < n_set; ++k) {
+            lgr_hypothesis& h = out[k];
+            const float* f = hf.data() + (size_t) k * 12;
+            int e_ninl, e2_ninl;
+            memcpy(&e_ninl, &f[1], 4); memcpy(&e2_ninl, &f[5], 4);
+            const bool enough = e_ninl > MIN_NR_FINAL_INLIERS || (float) e_ninl > MIN_INLIER_RATE * (float) c;
+            memcpy(h.transformation, hT.data() + (size_t) k * 16, 64);
+            h.converged = (enough && f[0] > min_tol) ? 1 : 0;
+            h.metric = f[4]; h.n_inliers = e2_ninl; h.uniformity = f[8];
+            if (h.converged) res->converged = 1;
+            if (h.uniformity > best) { best = h.uniformity; *best_index = k; }   // src/hypotheses.cpp:50-129: strict >, none positive -> identity
+        }
+        if (*best_index >= 0) {
+            const lgr_hypothesis& h = out[*best_index];
+            memcpy(res->transformation, h.transformation, 64);
+            res->n_inliers = h.n_inliers; res->metric = h.metric;
+        }
+    }
+    *n_out = n_set;
+    res->time_te = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    return LGR_OK;
+}
+
+extern "C" int lgr_ransac_multi(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                                const lgr_params* p, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, max_set >= 1 && max_set <= LGR_HYPOTHESES_MAX, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, src && tgt && (corr || c == 0) && res && ns > 0 && nt > 0 && c >= 0, LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    float *ds, *dt;
+    lgr_corr* dc;
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, &ds));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, &dt));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
+    LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
+    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * 16, hipMemcpyHostToDevice, ctx->stream));
+    return lgr_ransac_multi_dev(ctx, ds, ns, dt, nt, dc, c, p, max_set, res, out, n_out, best_index);
+}

@@ -8,7 +8,7 @@
 //   include/common.h:322-332, 360-370     estimateFeatures<FPFH>, estimateFeatures<SHOT>, estimateFeatures<RoPS135> (gravity frames)
 //   include/matching.h:373-376            matchBF<FPFH>, matchBF<SHOT>, matchBF<RoPS135>
 //   include/transformation.h:6-7          estimateOptimalRigidTransformation
-//   include/hypotheses.h:10-12            updateHypotheses
+//   include/hypotheses.h:10-16            updateHypotheses, chooseBestHypothesis (the decision; no hypotheses.csv side output)
 //   src/common.cpp:531-547, 644-655       calculateSmoothedDensities, estimateNormalsPoints
 //   include/analysis.h:14-34, 36-98       calculatePointCloudRmse, calculateOverlapRmse, calculateNormalDifference,
 //                                         buildCorrectCorrespondences, AlignmentAnalysis (start without its file side effects)
@@ -401,6 +401,22 @@ inline void updateHypotheses(std::vector<Matrix4f>& transformations, std::vector
     for (int i = 0; i < m; ++i) { std::memcpy(transformations[i].data(), &buf[16 * (size_t) i], 64); metrics[i] = met[i]; }
 }
 
+// ---- include/hypotheses.h:14-16 (src/hypotheses.cpp:50-129): the hypothesis whose correspondence inliers are spread most uniformly,
+// identity when none has a positive uniformity
+inline Matrix4f chooseBestHypothesis(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const CorrespondencesConstPtr& correspondences,
+                                     const AlignmentParameters& params, std::vector<Matrix4f>& tns) {
+    (void) params;
+    std::vector<float> buf(std::max<size_t>(tns.size(), 1) * 16);
+    for (size_t i = 0; i < tns.size(); ++i) std::memcpy(&buf[16 * i], tns[i].data(), 64);
+    Matrix4f out;
+    int best = -1;
+    check(lgr_choose_best_hypothesis(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(),
+                                     reinterpret_cast<const lgr_corr*>(correspondences->data()), (int) correspondences->size(), buf.data(), (int) tns.size(),
+                                     out.data(), &best, nullptr),
+          "chooseBestHypothesis");
+    return out;
+}
+
 // ---- include/correspondence_search.h:9-28
 class CorrespondenceSearch {
 public:
@@ -443,19 +459,35 @@ protected:
 };
 
 // ---- include/sac_prerejective_omp.h:21-56
+#ifndef LGR_SAVE_MULTIPLE_HYPOTHESES_MAX
+#define LGR_SAVE_MULTIPLE_HYPOTHESES_MAX 64   // members the set may hold under LGR_SAVE_MULTIPLE_HYPOTHESES (at most LGR_HYPOTHESES_MAX)
+#endif
 class SampleConsensusPrerejectiveOMP {
 public:
     SampleConsensusPrerejectiveOMP() = delete;
     SampleConsensusPrerejectiveOMP(PointNCloud::ConstPtr src, PointNCloud::ConstPtr tgt, CorrespondencesConstPtr correspondences,
                                    AlignmentParameters parameters)
         : src_(std::move(src)), tgt_(std::move(tgt)), correspondences_(std::move(correspondences)), parameters_(std::move(parameters)) {}
+    // A translation unit that defines LGR_SAVE_MULTIPLE_HYPOTHESES before this header gets the reference's SAVE_MULTIPLE_HYPOTHESES mode
+    // (src/sac_prerejective_omp.cpp:11): the set of distinct hypotheses, the final block on every member, chooseBestHypothesis' pick.
     AlignmentResult align() {
         lgr_params a = to_abi(parameters_);
-        lgr_metric_params m = to_metric_abi(parameters_);
         lgr_result r;
+#ifdef LGR_SAVE_MULTIPLE_HYPOTHESES
+        hypotheses_.assign(LGR_SAVE_MULTIPLE_HYPOTHESES_MAX, lgr_hypothesis{});
+        int n = 0;
+        best_hypothesis_ = -1;
+        const int rc = lgr_ransac_multi(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(),
+                                        reinterpret_cast<const lgr_corr*>(correspondences_->data()), (int) correspondences_->size(), &a,
+                                        LGR_SAVE_MULTIPLE_HYPOTHESES_MAX, &r, hypotheses_.data(), &n, &best_hypothesis_);
+        hypotheses_.resize(rc == LGR_OK ? n : 0);
+        check(rc, "SampleConsensusPrerejectiveOMP::align (multiple hypotheses)");
+#else
+        lgr_metric_params m = to_metric_abi(parameters_);
         check(lgr_ransac_ex(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(),
                             reinterpret_cast<const lgr_corr*>(correspondences_->data()), (int) correspondences_->size(), &a, &m, &r, nullptr),
               "SampleConsensusPrerejectiveOMP::align");
+#endif
         AlignmentResult out;
         out.src = src_; out.tgt = tgt_; out.correspondences = correspondences_;
         std::memcpy(out.transformation.data(), r.transformation, 64);
@@ -463,10 +495,16 @@ public:
         return out;
     }
     inline std::string getClassName() const { return "SampleConsensusPrerejectiveOMP"; }
+    // the set the last align() kept, in set order, and the index chooseBestHypothesis picked (-1: none; always empty / -1 without
+    // LGR_SAVE_MULTIPLE_HYPOTHESES)
+    inline const std::vector<lgr_hypothesis>& getHypotheses() const { return hypotheses_; }
+    inline int getBestHypothesisIndex() const { return best_hypothesis_; }
 protected:
     PointNCloud::ConstPtr src_, tgt_;
     CorrespondencesConstPtr correspondences_;
     AlignmentParameters parameters_;
+    std::vector<lgr_hypothesis> hypotheses_;
+    int best_hypothesis_ = -1;
 };
 
 // ---- include/alignment.h:6-19

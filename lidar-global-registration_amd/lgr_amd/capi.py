@@ -151,6 +151,22 @@ TEMP_FIELDS = ("temp_distance", "temp_normal", "color_distance", "color_normal",
 COLOR_BEIGE, COLOR_RED, COLOR_PARAKEET, COLOR_BLUE, COLOR_WHITE = 0xf8c471, 0xff0000, 0x03c04a, 0x0000ff, 0xffffff
 
 
+HYPOTHESES_MAX = 2048   # LGR_HYPOTHESES_MAX
+
+
+class Hypothesis(C.Structure):
+    """lgr_hypothesis (include/lgr.h): one member of the set of distinct hypotheses after the final block."""
+    _fields_ = [("loop_transformation", C.c_float * 16), ("transformation", C.c_float * 16), ("iteration", C.c_int32),
+                ("loop_metric", C.c_float), ("metric", C.c_float), ("n_inliers", C.c_int32), ("converged", C.c_int32),
+                ("uniformity", C.c_float)]
+
+    def loop_matrix(self):
+        return np.array(self.loop_transformation, dtype=np.float32).reshape(4, 4).T.copy()
+
+    def matrix(self):
+        return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
+
+
 class LgrError(RuntimeError):
     pass
 
@@ -768,6 +784,63 @@ class Context:
                                        C.byref(params), C.byref(res), _ptr(mask)))
         self._join()
         return res, mask[:c].cpu().numpy()
+
+    def ransac_multi(self, src, tgt, corr, params, max_set=64):
+        """lgr_ransac_multi_dev: the loop with the set of distinct hypotheses -> (Result, [Hypothesis] in set order, best_index)."""
+        corr = self._corr_dev(corr)
+        res = Result()
+        out = (Hypothesis * max(int(max_set), 1))()
+        n, bi = C.c_int(0), C.c_int(-1)
+        self.check(_lib.lgr_ransac_multi_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), corr.shape[0],
+                                             C.byref(params), int(max_set), C.byref(res), out, C.byref(n), C.byref(bi)))
+        return res, [out[i] for i in range(n.value)], bi.value
+
+    def ransac_multi_host(self, src, tgt, corr, params, max_set=64):
+        """lgr_ransac_multi: clouds [n, 12] float32 and correspondences (CORR_DTYPE) in host memory."""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        corr = np.ascontiguousarray(corr)
+        res = Result()
+        out = (Hypothesis * max(int(max_set), 1))()
+        n, bi = C.c_int(0), C.c_int(-1)
+        self.check(_lib.lgr_ransac_multi(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), corr.shape[0],
+                                         C.byref(params), int(max_set), C.byref(res), out, C.byref(n), C.byref(bi)))
+        return res, [out[i] for i in range(n.value)], bi.value
+
+    def fold_hypotheses(self, tns, metrics, distance_thr, max_set):
+        """lgr_fold_hypotheses_dev: updateHypotheses folded over the items in order.  tns: cuda float32 [n, 16] (column-major 4x4 rows),
+        metrics: cuda float32 [n] -> (set transforms [m, 16], set metrics [m], source indices [m]) as numpy arrays."""
+        n = int(metrics.shape[0])
+        cap = max(int(max_set), 1)
+        oT = self.empty((cap, 16), self.torch.float32); oM = self.empty((cap,), self.torch.float32); oI = self.empty((cap,), self.torch.int32)
+        m = C.c_int(0)
+        self.check(_lib.lgr_fold_hypotheses_dev(self.h, _ptr(tns) if n else None, _ptr(metrics) if n else None, n, C.c_float(distance_thr), int(max_set),
+                                                _ptr(oT), _ptr(oM), _ptr(oI), C.byref(m)))
+        self._join()
+        return oT[: m.value].cpu().numpy(), oM[: m.value].cpu().numpy(), oI[: m.value].cpu().numpy()
+
+    def fold_hypotheses_host(self, tns, metrics, distance_thr, max_set):
+        """lgr_fold_hypotheses: numpy float32 [n, 16] / [n] in, numpy out."""
+        tns = np.ascontiguousarray(tns, np.float32).reshape(-1, 16); metrics = np.ascontiguousarray(metrics, np.float32)
+        n = int(metrics.shape[0])
+        cap = max(int(max_set), 1)
+        oT = np.zeros((cap, 16), np.float32); oM = np.zeros(cap, np.float32); oI = np.zeros(cap, np.int32)
+        m = C.c_int(0)
+        self.check(_lib.lgr_fold_hypotheses(self.h, _ptr(tns) if n else None, _ptr(metrics) if n else None, n, C.c_float(distance_thr), int(max_set),
+                                            _ptr(oT), _ptr(oM), _ptr(oI), C.byref(m)))
+        return oT[: m.value].copy(), oM[: m.value].copy(), oI[: m.value].copy()
+
+    def choose_best_hypothesis_host(self, src, tgt, corr, tns):
+        """lgr_choose_best_hypothesis: host clouds and correspondences."""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        corr = np.ascontiguousarray(corr)
+        n = len(tns)
+        buf = np.ascontiguousarray(np.stack([np.asarray(T, np.float32).T.reshape(16) for T in tns]), np.float32) if n else np.zeros((1, 16), np.float32)
+        out = (C.c_float * 16)()
+        bi = C.c_int(-1)
+        uni = np.zeros(max(n, 1), np.float32)
+        self.check(_lib.lgr_choose_best_hypothesis(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), corr.shape[0],
+                                                   _ptr(buf), n, out, C.byref(bi), _ptr(uni)))
+        return bi.value, np.array(out, np.float32).reshape(4, 4).T.copy(), uni[:n].copy()
 
     def gror(self, src, tgt, corr, resolution, k_optimal=800):
         corr = self._corr_dev(corr)

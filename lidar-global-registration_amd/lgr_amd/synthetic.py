@@ -184,6 +184,51 @@ def make_correspondence_problem(n_pts=20000, c=5000, inlier_frac=0.4, sigma=0.01
     return dict(src=make_points(src), tgt=make_points(tgt), corr=corr, T_gt=T)
 
 
+def make_two_mode_problem(n_pts=4000, c=1500, f1=0.30, f2=0.18, sigma=0.01, thr=0.05, seed=11, extent=10.0):
+    """Correspondences with TWO plausible poses (the scenes the set of distinct hypotheses is for): the target holds the source under T1
+    and, behind it, under T2; a fraction f1 of the c correspondences follows T1, f2 follows T2, the rest point at random targets."""
+    rng = np.random.default_rng(seed)
+    src = rng.uniform(-extent, extent, (n_pts, 3))
+    src[:, 2] *= 0.2
+    T1, T2 = random_se3(rng), random_se3(rng)
+    tgt = np.concatenate([src @ T[:3, :3].T + T[:3, 3] + rng.normal(0, sigma, src.shape) for T in (T1, T2)])
+    perm = rng.permutation(n_pts)[:c]
+    match = rng.integers(0, 2 * n_pts, c)
+    order = rng.permutation(c)
+    n1, n2 = int(round(f1 * c)), int(round(f2 * c))
+    match[order[:n1]] = perm[order[:n1]]
+    match[order[n1:n1 + n2]] = perm[order[n1:n1 + n2]] + n_pts
+    corr = np.zeros(c, dtype=[("index_query", "<i4"), ("index_match", "<i4"), ("distance", "<f4"), ("threshold", "<f4")])
+    corr["index_query"] = perm
+    corr["index_match"] = match
+    corr["distance"] = rng.uniform(0, 50, c).astype(np.float32)
+    corr["threshold"] = thr
+    return dict(src=make_points(src), tgt=make_points(tgt), corr=corr, T1=T1, T2=T2)
+
+
+def make_pose_list(n=3000, k=12, seed=1):
+    """A list of n (transform, metric) items for the fold of updateHypotheses alone: poses scattered around k centres (rotations up to
+    25 degrees, translations up to 15 x 0.05 away: on both sides of the similarity thresholds at distance_thr = 0.05), metrics that tie,
+    fall below the 0.1 x best floor and keep producing new bests.  Returns (tns [n, 16] float32 column-major, metrics [n] float32)."""
+    rng = np.random.default_rng(seed)
+    centres = [random_se3(rng) for _ in range(k)]
+    tns = np.zeros((n, 16), np.float32)
+    metrics = np.zeros(n, np.float32)
+    for i in range(n):
+        T = centres[int(rng.integers(0, k))].copy()
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        ang = np.deg2rad(rng.uniform(0, 25))
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        dR = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * (K @ K)
+        T[:3, :3] = dR @ T[:3, :3]
+        T[:3, 3] = T[:3, 3] + rng.normal(size=3) * 0.05 * rng.uniform(0, 15)
+        m = [rng.uniform(0, 1), round(rng.uniform(0, 1), 1), rng.uniform(0, 0.05)][int(rng.integers(0, 3))]
+        tns[i] = T.astype(np.float32).T.reshape(16)
+        metrics[i] = np.float32(m * (0.2 + 0.8 * i / n))
+    return tns, metrics
+
+
 # tests/point2plane_distance.cpp:29-58 of the reference: its ground-truth transform and corner scene
 CORNER_GT = np.array([[0.0803703, -0.996763, -0.00201846, 1.2143], [0.996758, 0.080377, -0.00349969, -6.13404],
                       [0.00365057, -0.00173067, 0.999992, -1.17221], [0, 0, 0, 1]], np.float32)

@@ -4,7 +4,7 @@
     python tools/register_ply.py source.ply target.ply [--keypoint iss|any] [--metric uniformity|combination|...]
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
-                                 [--debug-dir DIR]
+                                 [--debug-dir DIR] [--hypotheses N]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
@@ -18,6 +18,9 @@ red, inliers blue, correct correspondences mixed with white), weights.ply under 
 distances_tgt}.csv, temperature_{dists_src,dists_tgt}.ply (ASCII) and temperature_{normal_diffs_src,normal_diffs_tgt}.ply for the found
 transformation; with a ground truth the same six as temperature_gt_* and compareOverlaps' two lines.  The histogram PNGs are not written
 (plots.py is no part of this project).
+With --hypotheses N (ransac, metrics uniformity and correspondences): the loop once more in the reference's SAVE_MULTIPLE_HYPOTHESES mode
+(src/sac_prerejective_omp.cpp:11) through lgr_ransac_multi -- the set of up to N distinct hypotheses, one line per member (id, iteration,
+loop metric, metric after the refit, inliers, uniformity, chosen); with --debug-dir the members also go through compareOverlaps.
 """
 import argparse
 import os
@@ -50,9 +53,13 @@ def main():
     ap.add_argument("--results", default="results.csv", help="results.csv the analysis row is appended to (with --ground-truth)")
     ap.add_argument("--metrics-csv", default=None, help="metrics.csv estimateTestMetric's row is appended to (needs --ground-truth)")
     ap.add_argument("--debug-dir", default=None, help="write the files of generateDebugFiles / compareHypotheses (src/main.cpp:207-284) there")
+    ap.add_argument("--hypotheses", type=int, default=0, metavar="N",
+                    help="also keep the set of up to N distinct hypotheses (ransac with uniformity / correspondences) and list its members")
     a = ap.parse_args()
     if a.metrics_csv and not a.ground_truth:
         ap.error("--metrics-csv needs --ground-truth")
+    if a.hypotheses and (a.alignment != "ransac" or a.metric not in ("uniformity", "correspondences")):
+        ap.error("--hypotheses needs --alignment ransac and --metric uniformity or correspondences")
 
     import numpy as np
     from lgr_amd import capi, formats, profile
@@ -88,6 +95,25 @@ def main():
         analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
     if a.debug_dir:
         debug_files(ctx, capi, formats, a, p, clouds, T, lrf)
+    if a.hypotheses:
+        hypotheses(ctx, capi, formats, a, p, clouds, lrf)
+
+
+def hypotheses(ctx, capi, formats, a, p, clouds, lrf):
+    """the set of distinct hypotheses of the same correspondences (lgr_ransac_multi), and with --debug-dir compareOverlaps over its members"""
+    src, tgt = clouds
+    desc = a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf)
+    corr = ctx.correspondences(src, tgt, p, descriptor=desc)
+    t = time.perf_counter()
+    res, hyps, best = ctx.ransac_multi(src, tgt, corr, p, max_set=a.hypotheses)
+    print(f"{len(hyps)} distinct hypotheses in {1e3 * (time.perf_counter() - t):.1f} ms (iterations={res.iterations} converged={res.converged}):")
+    print("\tid\titeration\tloop_metric\tmetric\tinliers\tuniformity\tchosen")
+    for k, h in enumerate(hyps):
+        print(f"\t{k}\t{h.iteration}\t{h.loop_metric:.6f}\t{h.metric:.6f}\t{h.n_inliers}\t{h.uniformity:.6f}\t{'*' if k == best else ''}")
+    if a.debug_dir and hyps:
+        o = ctx.compare_overlaps(src, tgt, [h.matrix() for h in hyps], p.distance_thr, with_masks=False)
+        for k in range(len(hyps)):
+            print(f"\thypothesis {k}: {o['counts'][k]} points, {formats._g(o['weighted'][k])}weighted points")
 
 
 def debug_files(ctx, capi, formats, a, p, clouds, T, lrf):
