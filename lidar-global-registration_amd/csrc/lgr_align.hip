@@ -11,6 +11,7 @@
 #include <climits>
 
 #include "lgr_internal.h"
+#include "lgr_pointpass.cuh"
 
 namespace {
 
@@ -659,15 +660,7 @@ extern "C" int lgr_correspondences(lgr_ctx* ctx, const float* src, int ns, const
     return lgr_correspondences_ex(ctx, src, ns, tgt, nt, p, nullptr, out, n_out);
 }
 
-// host entry points: both clouds to the device (WS_HOST_A / WS_HOST_B) on ctx->stream
-static int upload_clouds(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, float** ds, float** dt) {
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, dt));
-    LGR_HIP(ctx, hipMemcpyAsync(*ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(*dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    return LGR_OK;
-}
-
+// (the host entry points stage both clouds with stage_clouds, lgr_pointpass.cuh: WS_HOST_A / WS_HOST_B on ctx->stream)
 extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
                                       lgr_corr* out, int* n_out) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
@@ -679,7 +672,7 @@ extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, co
     float *ds, *dt;
     lgr_corr* dc;
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));
-    LGR_TRY(upload_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     LGR_TRY(lgr_correspondences_ex_dev(ctx, ds, ns, dt, nt, p, fp, dc, n_out));
     if (*n_out) LGR_HIP(ctx, hipMemcpyAsync(out, dc, (size_t) *n_out * 16, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -759,7 +752,7 @@ extern "C" int lgr_align_ex2(lgr_ctx* ctx, const float* src, int ns, const float
     if (ns < 2 || nt < 2) return lgr_align_ex2_dev(ctx, nullptr, 0, nullptr, 0, p, fp, mp, res);   // identity, not converged
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
-    LGR_TRY(upload_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     lgr_metric_params mpd;
     LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
     return lgr_align_ex2_dev(ctx, ds, ns, dt, nt, p, fp, mp, res);

@@ -22,6 +22,7 @@
 
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
+#include "lgr_pointpass.cuh"
 
 namespace {
 
@@ -486,17 +487,11 @@ extern "C" int lgr_gror(lgr_ctx* ctx, const float* src, int ns, const float* tgt
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, src && tgt && res && ns > 0 && nt > 0 && (corr || c == 0) && c >= 0, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm = nullptr;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12, &ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
+    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
     if (inlier_mask) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) c + 1, &dm));
-    LGR_HIP(ctx, hipMemcpyAsync(ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * 16, hipMemcpyHostToDevice, ctx->stream));
     LGR_TRY(lgr_gror_dev(ctx, ds, ns, dt, nt, dc, c, resolution, k_optimal, res, dm));
     if (inlier_mask && c) {
         LGR_HIP(ctx, hipMemcpyAsync(inlier_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));

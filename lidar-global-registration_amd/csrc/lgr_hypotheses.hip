@@ -18,6 +18,10 @@
 // rounded to float.
 #include <math.h>
 
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
 #include "lgr_internal.h"
 
 namespace {
@@ -244,4 +248,51 @@ extern "C" int lgr_fold_hypotheses(lgr_ctx* ctx, const float* tns16, const float
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return LGR_OK;
+}
+
+// src/hypotheses.cpp:14-48 updateHypotheses: pure host bookkeeping (the call sites are compiled out in the reference,
+// SAVE_MULTIPLE_HYPOTHESES false, src/sac_prerejective_omp.cpp:11); tns16 = n column-major 4x4, capacity cap.
+extern "C" int lgr_update_hypotheses(float* tns16, float* metrics, int n, int cap, const float* new_T16, float new_metric, float distance_thr) {
+    if (!tns16 || !metrics || !new_T16 || n < 0 || cap < n) return LGR_ERR_INVALID_ARG;
+    auto diff = [](const float* T1, const float* T2, float& angle, float& td) {
+        // src/analysis.cpp:19-24: angle of R1^-1 R2, |t1 - t2|
+        double R[9];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                double s = 0;
+                for (int k = 0; k < 3; ++k) s += (double) T1[4 * i + k] * (double) T2[4 * j + k];
+                R[3 * i + j] = s;
+            }
+        double tr = R[0] + R[4] + R[8];
+        double vx = R[7] - R[5], vy = R[2] - R[6], vz = R[3] - R[1];
+        angle = (float) std::atan2(0.5 * std::sqrt(vx * vx + vy * vy + vz * vz), 0.5 * (tr - 1.0));
+        double dx = (double) T1[12] - T2[12], dy = (double) T1[13] - T2[13], dz = (double) T1[14] - T2[14];
+        td = (float) std::sqrt(dx * dx + dy * dy + dz * dz);
+    };
+    std::vector<std::vector<float>> T(n, std::vector<float>(16));
+    std::vector<float> M(metrics, metrics + n);
+    for (int i = 0; i < n; ++i) memcpy(T[i].data(), tns16 + 16 * (size_t) i, 64);
+    float best = n == 0 ? 0.f : *std::max_element(M.begin(), M.end());
+    auto flush = [&]() {
+        int m = (int) T.size();
+        if (m > cap) return (int) LGR_ERR_INVALID_ARG;
+        for (int i = 0; i < m; ++i) { memcpy(tns16 + 16 * (size_t) i, T[i].data(), 64); metrics[i] = M[i]; }
+        return m;
+    };
+    if (new_metric < 0.1 * best) return flush();
+    std::vector<int> similar;
+    for (int i = (int) T.size() - 1; i >= 0; --i) {
+        float r, t;
+        diff(new_T16, T[i].data(), r, t);
+        bool is_similar = r < (M_PI / 9) && t < 20 * distance_thr;
+        if (is_similar) similar.push_back(i);
+        if (is_similar && M[i] > new_metric) return flush();
+    }
+    for (int idx : similar) { T.erase(T.begin() + idx); M.erase(M.begin() + idx); }
+    T.emplace_back(new_T16, new_T16 + 16);
+    M.push_back(new_metric);
+    if (new_metric > best)
+        for (int i = (int) T.size() - 1; i >= 0; --i)
+            if (M[i] < 0.1 * new_metric) { T.erase(T.begin() + i); M.erase(M.begin() + i); }
+    return flush();
 }

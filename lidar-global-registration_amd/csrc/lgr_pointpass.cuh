@@ -1,6 +1,7 @@
 // lgr_pointpass.cuh -- what the thread-per-point passes of lgr_analysis.hip, lgr_plane_dense.hip and lgr_debug.hip share: PCL's point
 // moves, the branch-free nearest-within-r walk, the wave-aggregated counter, the sequential f32 sum jobs, the move of a whole cloud and
-// the compaction of an overlap cloud (flags, their exclusive scan, the kept rows).  Everything here sits in an unnamed namespace: each translation unit gets its own copy of the kernels.
+// the compaction of an overlap cloud (flags, their exclusive scan, the kept rows).  Its host helpers -- the staging of host clouds and
+// correspondences (stage_clouds, stage_problem) and the scan of 0 / 1 flags (pp_scan_flags) -- also serve lgr_ransac.hip, lgr_gror.hip and lgr_align.hip.  Everything here sits in an unnamed namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <rocprim/device/device_scan.hpp>
 
@@ -54,7 +55,7 @@ __device__ __forceinline__ void wave_count(bool f, int* counter) {
 // 1-3 stage tile k + 1.  sq: the term is v * v (the squared smoothed densities of src/analysis.cpp:232).
 constexpr int GT_SUM_TILE = 4096, GT_SUM_JOBS = 4;
 struct GtSumJobs { const float* p[GT_SUM_JOBS]; int n[GT_SUM_JOBS]; int sq[GT_SUM_JOBS]; };
-__global__ __launch_bounds__(PP_BLOCK) void gt_seqsum_kernel(GtSumJobs jobs, float* __restrict__ out) {
+[[maybe_unused]] __global__ __launch_bounds__(PP_BLOCK) void gt_seqsum_kernel(GtSumJobs jobs, float* __restrict__ out) {
     __shared__ float4 tile[2][GT_SUM_TILE / 4];
     const float* __restrict__ w = jobs.p[blockIdx.x];
     const int n = jobs.n[blockIdx.x];
@@ -141,6 +142,14 @@ inline int stage_clouds(lgr_ctx* ctx, const float* src, int ns, const float* tgt
     if (nt) LGR_HIP(ctx, hipMemcpyAsync(*dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
     if (!ns) *ds = nullptr;
     if (!nt) *dt = nullptr;
+    return LGR_OK;
+}
+
+// ... and the correspondences of a registration problem -> the WS_HOST_C slot
+inline int stage_problem(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, float** ds, float** dt, lgr_corr** dc) {
+    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, ds, dt));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, dc));
+    if (c) LGR_HIP(ctx, hipMemcpyAsync(*dc, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
     return LGR_OK;
 }
 

@@ -120,6 +120,9 @@ TWO_MODE_ROWS = [   # metric_id, f1, f2, max_iterations, batch
     (1, 0.50, 0.20, 8000, 256),
     (0, 0.30, 0.18, 6000, 1000),
     (0, 0.50, 0.20, 8000, 256),
+    # batch 64: a second-pass round is 16 * 64 = 1024 iterations, so the 3584 iterations of the loop take three full rounds and one of 512
+    (1, 0.50, 0.20, 8000, 64),
+    (0, 0.50, 0.20, 8000, 64),
 ]
 POSE_LISTS = [(3000, 12, 1), (3000, 40, 2), (500, 3, 3)]   # n, K, seed
 DISTANCE_THR = 0.05
