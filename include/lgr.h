@@ -746,6 +746,60 @@ int lgr_color_correspondences_dev(lgr_ctx*, int n, const int32_t* d_kp_idx_or_nu
 int lgr_color_correspondences(lgr_ctx*, int n, const int32_t* kp_idx_or_null, int n_kp, const lgr_corr* corr, int c, const lgr_corr* correct,
                               int n_correct, const lgr_corr* inliers, int n_inliers, int is_source, int32_t* colors);   /* host twin */
 
+/* ---- iterated closest-plane refinement of a transform: the step of the reference's final block (src/sac_prerejective_omp.cpp:270-291 --
+ *      closest-plane inliers of the transform, estimateOptimalRigidTransformation over those pairs, evaluation of the result) in its DENSE
+ *      form, repeated while the metric rises.  Declared order:
+ *        thr = params.threshold > 0 ? params.threshold : calculatePointCloudDensity(tgt)          (once)
+ *        E = dense_eval(T0); T = T0; steps = 0                                                    (lgr_evaluate_plane_dense's values)
+ *        while steps < max_steps:
+ *            E.n_inliers < 3                   -> stop = NO_PAIRS
+ *            T' = refit over E's inlier pairs (source i, nearest target of i), ascending i        (lgr_refit_svd's arithmetic)
+ *            E' = dense_eval(T');  !(E'.metric > E.metric) -> stop = NO_GAIN, T stays             (a NaN or zero metric never wins)
+ *            T, E = T', E'; steps += 1
+ *        else stop = MAX_STEPS
+ *      Every float of every evaluated transform equals that statement bit for bit.  mp == NULL: closest_plane; mp != NULL: the weighted
+ *      estimator evaluates (harris / tomasi: LGR_ERR_UNSUPPORTED), the refit ignores weights as the reference's does.  An empty source is
+ *      LGR_OK with steps = 0, stop = NO_PAIRS and T0 returned (metric 0, rmse FLT_MAX).  nt < 2, max_steps outside
+ *      [0, LGR_REFINE_MAX_STEPS], score_id outside [0, 3], a NaN threshold or one above 1e18 and non-zero reserved words:
+ *      LGR_ERR_INVALID_ARG, before any work.  Point rows must be 16-byte aligned.
+ *      trace (optional, host, room for max_steps + 2 entries): every evaluated transform in order -- T0, each candidate, the rejected one
+ *      last; *n_trace receives the number written (steps + 1, one more with a rejected candidate).
+ *      The device path builds the target grid, the threshold and the weights once, then enqueues the steps in groups of LGR_REFINE_GROUP
+ *      and reads one small record per group: the transform, the counts and the inlier flags never pass through the host. ---- */
+#define LGR_REFINE_MAX_STEPS 1024
+#define LGR_REFINE_GROUP 4
+enum { LGR_REFINE_STOP_MAX_STEPS = 0, LGR_REFINE_STOP_NO_GAIN = 1, LGR_REFINE_STOP_NO_PAIRS = 2 };
+typedef struct {
+    int32_t score_id;      /* LGR_SCORE_* */
+    int32_t max_steps;     /* 0 .. LGR_REFINE_MAX_STEPS */
+    float   threshold;     /* <= 0: the target's density */
+    int32_t reserved[5];   /* 0 */
+} lgr_refine_params;
+void lgr_default_refine_params(lgr_refine_params* p);   /* MSE score, 10 steps, threshold 0 */
+typedef struct {
+    float   transformation[16];   /* column-major */
+    float   metric, rmse, score;  /* as lgr_plane_dense_eval */
+    int32_t n_inliers;
+} lgr_refine_step;
+typedef struct {
+    float   transformation[16];   /* the last accepted step (T0 when steps == 0) */
+    float   metric, rmse, score;
+    int32_t n_inliers;
+    float   threshold;            /* the inlier threshold used */
+    int32_t steps;                /* accepted steps */
+    int32_t stop;                 /* LGR_REFINE_STOP_* */
+    int32_t reserved0;            /* 0 */
+    lgr_refine_step first;        /* T0 and its evaluation */
+    lgr_refine_step rejected;     /* the candidate that lost (stop == NO_GAIN), zeroed otherwise */
+    int32_t reserved[4];          /* 0 */
+} lgr_refine_result;
+int lgr_refine_plane_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T0_16[16] /* host */,
+                         const lgr_refine_params*, const lgr_metric_params* mp_or_null, lgr_refine_result* out /* host */,
+                         lgr_refine_step* trace_or_null /* host */, int* n_trace_or_null);
+int lgr_refine_plane(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T0_16[16], const lgr_refine_params*,
+                     const lgr_metric_params* mp_or_null, lgr_refine_result* out, lgr_refine_step* trace_or_null,
+                     int* n_trace_or_null);   /* host twin */
+
 #ifdef __cplusplus
 }
 #endif

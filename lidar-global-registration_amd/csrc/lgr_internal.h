@@ -129,6 +129,7 @@ enum {
     WS_PD_TERMS, WS_PD_MISC, WS_PD_INLIERS, WS_PD_MASK,   // lgr_plane_dense.hip
     WS_DBG_MISC, WS_DBG_MOVED, WS_DBG_FLAGS, WS_DBG_OVERLAP, WS_DBG_DENS, WS_DBG_SORT, WS_DBG_HOST_A, WS_DBG_HOST_B,   // lgr_debug.hip
     WS_HYP_SET, WS_HYP_ITEMS, WS_HYP_FINAL,   // lgr_hypotheses.hip, lgr_ransac_multi_dev
+    WS_RF_STATE, WS_RF_TERMS, WS_RF_PAIRS, WS_RF_TRACE,   // lgr_refine.hip
     WS_COUNT
 };
 static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");
@@ -257,6 +258,14 @@ static inline int lgr_stage_host_weights(lgr_ctx* ctx, int ns, const lgr_metric_
     *staged = **mp; staged->weights = dw; *mp = staged;
     return LGR_OK;
 }
+
+// ---- the refit over flagged pairs, device-resident (lgr_ransac.hip; lgr_refine.hip's step) ----
+// estimateOptimalRigidTransformation over the pairs (P0[i], P1[i]) whose flag is set (0 / 1 ints), in ascending i, into d_Tout (16 floats):
+// lgr_refit_svd_dev's compaction and refit_kernel, on ctx->stream, nothing read back.  The kernel takes the number of pairs from
+// d_n[0] + d_n[1] when it runs: the caller keeps that equal to the number of set flags -- or 0, and the refit then returns at once with
+// NaNs in d_Tout.  c > 0.  lgr_refit_flagged_reserve sizes the workspace for c pairs, so that no launch after it has to grow (and synchronise).
+int lgr_refit_flagged_reserve(lgr_ctx* ctx, int c);
+int lgr_refit_flagged_launch(lgr_ctx* ctx, const float4* P0, const float4* P1, int c, int* d_flags, const int* d_n, float* d_Tout);
 
 // ---- the set of distinct hypotheses (lgr_hypotheses.hip): the left fold of updateHypotheses (src/hypotheses.cpp:14-48) on the device ----
 // The set between two launches: members in set order as 12 floats R|t (the columns of R, then t), their metrics and source indices, and

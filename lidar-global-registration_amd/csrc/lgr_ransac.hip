@@ -102,6 +102,17 @@ int refit_launch(lgr_ctx* ctx, const Packed& pk, int c, const uint8_t* d_mask, f
     return LGR_OK;
 }
 
+// the workspace of a refit over c flagged pairs: the scan's positions, the compacted pairs and the scan's temporary storage
+int refit_flagged_ws(lgr_ctx* ctx, int c, int** pos, float4** Q0, float4** Q1) {
+    LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_HIST, (size_t) c + 16 + 8 * ((size_t) c + 4), pos));
+    *Q0 = (float4*) (((uintptr_t) (*pos + (size_t) c) + 15) & ~(uintptr_t) 15);
+    *Q1 = *Q0 + c;
+    size_t tb = 0;
+    void* tmp;
+    LGR_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, *pos, *pos, 0, (size_t) c, rocprim::plus<int>(), ctx->stream));
+    return lgr_ws(ctx, WS_GRID_TMP, tb, &tmp);   // what pp_scan_flags will ask for
+}
+
 size_t metric_smem() { return (size_t) (30000 + 64) * 4; }
 
 int metric_launch(lgr_ctx* ctx, const float* Ts, const int* list2, int nh2, const Packed& pk, int c, int metric_id, int score_id,
@@ -140,6 +151,23 @@ int evaluate_one(lgr_ctx* ctx, const float* d_T, const Packed& pk, int c, int me
 }
 
 }  // namespace
+
+int lgr_refit_flagged_reserve(lgr_ctx* ctx, int c) {
+    int* pos;
+    float4 *Q0, *Q1;
+    return refit_flagged_ws(ctx, c, &pos, &Q0, &Q1);
+}
+
+int lgr_refit_flagged_launch(lgr_ctx* ctx, const float4* P0, const float4* P1, int c, int* d_flags, const int* d_n, float* d_Tout) {
+    int* pos;
+    float4 *Q0, *Q1;
+    LGR_TRY(refit_flagged_ws(ctx, c, &pos, &Q0, &Q1));
+    LGR_TRY(pp_scan_flags(ctx, d_flags, pos, (size_t) c));
+    compact_pairs_kernel<<<cdiv(c, 256), 256, 0, ctx->stream>>>(P0, P1, d_flags, pos, c, Q0, Q1);
+    refit_kernel<<<1, 256, 0, ctx->stream>>>(Q0, Q1, 0, d_Tout, d_n, d_n + 1);
+    LGR_HIP(ctx, hipGetLastError());
+    return LGR_OK;
+}
 
 // single transform under a plane metric: counter = 0xFFFFFFFE / 0xFFFFFFFF for the two evaluations of the final block.
 // closest_plane: inliers / rmse / metric from the plane test, pairs (sorted by source index) returned for the refit.

@@ -388,6 +388,29 @@ inline void estimateOptimalRigidTransformation(const PointNCloud::ConstPtr& src,
           "estimateOptimalRigidTransformation");
 }
 
+// ---- not in the reference: its final block's closest-plane step (src/sac_prerejective_omp.cpp:270-291) in the dense form, repeated while
+// the metric rises (lgr_refine_plane).  parameters.score_id scores the inliers; metric_id "weighted_closest_plane" evaluates with the
+// weights of parameters.weight_id, anything else with closest_plane.  The threshold is the target's density.
+inline Matrix4f refineTransformation(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn,
+                                     const AlignmentParameters& parameters, int max_steps, lgr_refine_result& result) {
+    lgr_refine_params rp;
+    lgr_default_refine_params(&rp);
+    rp.score_id = to_abi(parameters).score_id;
+    rp.max_steps = max_steps;
+    const lgr_metric_params mp = to_metric_abi(parameters);
+    check(lgr_refine_plane(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), tn.data(), &rp,
+                           parameters.metric_id == "weighted_closest_plane" ? &mp : nullptr, &result, nullptr, nullptr),
+          "refineTransformation");
+    Matrix4f out;
+    std::memcpy(out.data(), result.transformation, 64);
+    return out;
+}
+inline Matrix4f refineTransformation(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn,
+                                     const AlignmentParameters& parameters, int max_steps) {
+    lgr_refine_result result;
+    return refineTransformation(src, tgt, tn, parameters, max_steps, result);
+}
+
 // ---- include/hypotheses.h:10-12
 inline void updateHypotheses(std::vector<Matrix4f>& transformations, std::vector<float>& metrics, const Matrix4f& new_transformation,
                              float new_metric, const AlignmentParameters& parameters) {

@@ -142,6 +142,47 @@ class MetricEval(C.Structure):
     _fields_ = [("metric", C.c_float), ("rmse", C.c_float), ("n_inliers", C.c_int32), ("n_correct_inliers", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+REFINE_MAX_STEPS, REFINE_GROUP = 1024, 4   # LGR_REFINE_MAX_STEPS, LGR_REFINE_GROUP
+REFINE_STOP_MAX_STEPS, REFINE_STOP_NO_GAIN, REFINE_STOP_NO_PAIRS = 0, 1, 2
+REFINE_STOP_NAMES = ("max_steps", "no_gain", "no_pairs")
+
+
+class RefineParams(C.Structure):
+    """lgr_refine_params (include/lgr.h)"""
+    _fields_ = [("score_id", C.c_int32), ("max_steps", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+class RefineStep(C.Structure):
+    """lgr_refine_step (include/lgr.h): one evaluated transform of a refinement"""
+    _fields_ = [("transformation", C.c_float * 16), ("metric", C.c_float), ("rmse", C.c_float), ("score", C.c_float), ("n_inliers", C.c_int32)]
+
+    def matrix(self):
+        return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
+
+
+class RefineResult(C.Structure):
+    """lgr_refine_result (include/lgr.h): the last accepted step, why the loop ended, T0's evaluation and the candidate that lost"""
+    _fields_ = [("transformation", C.c_float * 16), ("metric", C.c_float), ("rmse", C.c_float), ("score", C.c_float), ("n_inliers", C.c_int32),
+                ("threshold", C.c_float), ("steps", C.c_int32), ("stop", C.c_int32), ("reserved0", C.c_int32), ("first", RefineStep),
+                ("rejected", RefineStep), ("reserved", C.c_int32 * 4)]
+    trace = None   # list of RefineStep (trace=True), set by Context.refine_plane*
+
+    def matrix(self):
+        return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
+
+
+def refine_params(score_id=None, max_steps=None, threshold=None):
+    p = RefineParams()
+    _lib.lgr_default_refine_params(C.byref(p))
+    if score_id is not None:
+        p.score_id = int(score_id)
+    if max_steps is not None:
+        p.max_steps = int(max_steps)
+    if threshold is not None:
+        p.threshold = float(threshold)
+    return p
+
+
 class TemperatureOut(C.Structure):
     """lgr_temperature_out (include/lgr.h): five optional per-point arrays of one temperature map."""
     _fields_ = [("temp_distance", C.c_void_p), ("temp_normal", C.c_void_p), ("color_distance", C.c_void_p), ("color_normal", C.c_void_p), ("nn", C.c_void_p)]
@@ -1040,6 +1081,29 @@ class Context:
         if with_nn:
             out.nn = nn[:ns].copy()
         return out
+
+    # ---- iterated closest-plane refinement (include/lgr.h lgr_refine_plane*) ----
+    def _refine(self, fn, src, tgt, T0, score_id, max_steps, threshold, metric_params, trace):
+        p = refine_params(score_id, max_steps, threshold)
+        out = RefineResult()
+        tr = (RefineStep * (max(p.max_steps, 0) + 2))() if trace else None
+        n_tr = C.c_int(0)
+        self.check(fn(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T0), C.byref(p),
+                      C.byref(metric_params) if metric_params is not None else None, C.byref(out), tr, C.byref(n_tr) if trace else None))
+        if trace:
+            out.trace = [tr[i] for i in range(n_tr.value)]
+        return out
+
+    def refine_plane(self, src, tgt, T0, score_id=SCORE_MSE, max_steps=10, threshold=None, metric_params=None, trace=False):
+        """lgr_refine_plane_dev on cuda clouds [n, 12]: T0 (4x4) refined by dense closest-plane steps while the metric rises -> RefineResult
+        (.matrix(), .steps, .stop, .first, .rejected; .trace with trace=True).  threshold None or <= 0: the target's density.
+        metric_params: a MetricParams (capi.metric_params: weight name or a cuda weight map) for the weighted estimator, None: closest_plane."""
+        return self._refine(_lib.lgr_refine_plane_dev, src, tgt, T0, score_id, max_steps, threshold, metric_params, trace)
+
+    def refine_plane_host(self, src, tgt, T0, score_id=SCORE_MSE, max_steps=10, threshold=None, metric_params=None, trace=False):
+        """lgr_refine_plane: numpy in (caller weights in metric_params a numpy float32 [ns]), RefineResult out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        return self._refine(_lib.lgr_refine_plane, src, tgt, T0, score_id, max_steps, threshold, metric_params, trace)
 
     def analysis_metric(self, src, tgt, corr, T, T_gt=None, metric_id=METRIC_UNIFORMITY, score_id=SCORE_MSE, weights=None, weight=None):
         """lgr_analysis_metric_dev: what AlignmentAnalysis::start's first statement and buildCorrectInliers yield under metric_id -> MetricEval

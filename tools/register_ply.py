@@ -4,7 +4,7 @@
     python tools/register_ply.py source.ply target.ply [--keypoint iss|any] [--metric uniformity|combination|...]
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
-                                 [--debug-dir DIR] [--hypotheses N]
+                                 [--debug-dir DIR] [--hypotheses N] [--refine N]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
@@ -21,6 +21,10 @@ transformation; with a ground truth the same six as temperature_gt_* and compare
 With --hypotheses N (ransac, metrics uniformity and correspondences): the loop once more in the reference's SAVE_MULTIPLE_HYPOTHESES mode
 (src/sac_prerejective_omp.cpp:11) through lgr_ransac_multi -- the set of up to N distinct hypotheses, one line per member (id, iteration,
 loop metric, metric after the refit, inliers, uniformity, chosen); with --debug-dir the members also go through compareOverlaps.
+With --refine N: after everything above, the found transformation goes through up to N dense closest-plane steps (lgr_refine_plane: inliers,
+refit, evaluation, while the metric rises) under the run's score -- and the run's weights under weighted_closest_plane; the evaluation before
+and after is printed, the refined transformation is appended to --out as a second row named <name>_refined, and with --ground-truth it is
+analysed like the first (a second results.csv row under that name).
 """
 import argparse
 import os
@@ -55,7 +59,10 @@ def main():
     ap.add_argument("--debug-dir", default=None, help="write the files of generateDebugFiles / compareHypotheses (src/main.cpp:207-284) there")
     ap.add_argument("--hypotheses", type=int, default=0, metavar="N",
                     help="also keep the set of up to N distinct hypotheses (ransac with uniformity / correspondences) and list its members")
+    ap.add_argument("--refine", type=int, default=0, metavar="N", help="refine the result by up to N dense closest-plane steps (lgr_refine_plane)")
     a = ap.parse_args()
+    if not 0 <= a.refine <= 1024:
+        ap.error("--refine takes 0 .. 1024 steps")
     if a.metrics_csv and not a.ground_truth:
         ap.error("--metrics-csv needs --ground-truth")
     if a.hypotheses and (a.alignment != "ransac" or a.metric not in ("uniformity", "correspondences")):
@@ -97,6 +104,27 @@ def main():
         debug_files(ctx, capi, formats, a, p, clouds, T, lrf)
     if a.hypotheses:
         hypotheses(ctx, capi, formats, a, p, clouds, lrf)
+    if a.refine:
+        refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
+
+
+def refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
+    """the found transformation through lgr_refine_plane; its row in --out and, with a ground truth, its analysis"""
+    import numpy as np
+    mp = capi.metric_params(a.weight) if a.metric == "weighted_closest_plane" else None
+    t = time.perf_counter()
+    r = ctx.refine_plane(clouds[0], clouds[1], T, score_id=p.score_id, max_steps=a.refine, metric_params=mp)
+    dt = time.perf_counter() - t
+    print(f"\nrefined in {1e3 * dt:.1f} ms: {r.steps} steps of at most {a.refine}, stopped by {capi.REFINE_STOP_NAMES[r.stop]} (threshold {r.threshold:.6g})")
+    for label, s in (("before", r.first), (" after", r)):
+        print(f"  {label}: metric={s.metric:.7f} inliers_rmse={s.rmse:.7f} inliers={s.n_inliers}")
+    Tr = r.matrix()
+    print(np.array2string(Tr, precision=6, suppress_small=True))
+    if a.out:
+        formats.save_transformation(a.out, name + "_refined", Tr)
+    if a.ground_truth:
+        a.metrics_csv = None   # estimateTestMetric's row belongs to the alignment
+        analyse(ctx, capi, formats, a, p, clouds, res, Tr, name + "_refined", lrf)
 
 
 def hypotheses(ctx, capi, formats, a, p, clouds, lrf):
