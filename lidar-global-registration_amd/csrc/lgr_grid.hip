@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "lgr_grid.cuh"
+#include "lgr_grid_rule.h"
 #include "lgr_knn_wave.cuh"
 
 namespace {
@@ -352,16 +353,7 @@ int lgr_grid_build(lgr_ctx* ctx, int sb, const float* d_pts, int n, float h, flo
         h = std::max(h, std::max(e[2] / 1024.f, 1e-6f));
     }
     int dim[3];
-    for (;;) {
-        double cells = 1;
-        for (int a = 0; a < 3; ++a) {
-            dim[a] = (int) std::floor((mx[a] - mn[a]) / h) + 1;   // same float expression as lgr_cellc
-            if (dim[a] < 1) dim[a] = 1;
-            cells *= dim[a];
-        }
-        if (cells <= 256e6) break;
-        h *= 2.f;
-    }
+    h = lgr_grid_cell_rule(mn, mx, h, dim);   // the cell cap and the per-axis bound: lgr_grid_rule.h
     int ncell = dim[0] * dim[1] * dim[2];
     unsigned *keys, *keys2;
     int *vals, *vals2, *start;

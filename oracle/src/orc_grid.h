@@ -40,10 +40,24 @@ struct Grid {
         }
         if (!(mn[0] <= mx[0])) { for (int a = 0; a < 3; ++a) { mn[a] = 0; mx[a] = 0; } }
         for (int a = 0; a < 3; ++a) origin[a] = mn[a];
+        // The cell size rule of DESIGN.md section 4 (restated from csrc/lgr_grid_rule.h): h is doubled while the box holds more than 256e6
+        // cells, or while its longest axis has more than 4096 cells at the caller's h (more than 2^20 after a doubling): past that the
+        // rounding of cellc can exceed the cell's margin over the search radius and the 27-cell visit would miss neighbours.  The dims are
+        // compared as floats before the cast, so an axis of more than 2^31 cells never reaches it.
+        const float h0 = h;
         for (;;) {
+            float d[3], dmax = 1.f;
             double cells = 1;
-            for (int a = 0; a < 3; ++a) { dim[a] = cellc(mx[a], a) + 1; if (dim[a] < 1) dim[a] = 1; cells *= dim[a]; }
-            if (cells <= 128e6) break;
+            for (int a = 0; a < 3; ++a) {
+                d[a] = std::floor((mx[a] - origin[a]) / h) + 1.f;   // cellc(mx[a], a) + 1
+                if (!(d[a] >= 1.f)) d[a] = 1.f;
+                cells *= d[a];
+                dmax = std::max(dmax, d[a]);
+            }
+            if (cells <= 256e6 && dmax <= (h == h0 ? 4096.f : 1048576.f)) {
+                for (int a = 0; a < 3; ++a) dim[a] = (int) d[a];
+                break;
+            }
             h *= 2.f;
         }
         size_t ncell = (size_t) dim[0] * dim[1] * dim[2];
