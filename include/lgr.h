@@ -466,6 +466,10 @@ int lgr_ransac_ex(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, 
                   const lgr_params*, const lgr_metric_params*, lgr_result*, uint8_t* final_mask);
 int lgr_ransac_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
                       const lgr_params*, const lgr_metric_params*, lgr_result* /* host */, uint8_t* d_final_mask);
+/* the plane metrics' early-out gate in the last lgr_ransac* call of this context (closest_plane, combination, weighted_closest_plane; 0, 0
+ * after any other metric): out2[0] hypotheses scored on their sparse plane subset, out2[1] those of them abandoned part-way through it
+ * because they could be neither the best nor a record.  Which ones are abandoned may differ between runs; the results never do. */
+int lgr_ransac_last_plane_gate(lgr_ctx*, unsigned* out2);
 /* the weight map of weight_id (out: n floats) and, when weights_sum != NULL, its sequential f32 sum.  nr_points: the neighbours of the
  * principal curvatures (exp_curvature, curvedness; 1..128, more returns LGR_ERR_UNSUPPORTED); the other maps ignore it. */
 int lgr_weights(lgr_ctx*, const float* pts, int n, int weight_id, int nr_points, float* out, float* weights_sum /* or NULL */);

@@ -66,6 +66,7 @@ struct lgr_ctx {
     lgr_helper* helper = nullptr;               // of an internal context: the host thread that drives it (opt.helper_contexts)
     lgr_match_stats mstats{};                   // lgr_match_last_*: the last match call of THIS context
     double mcheck[2] = {-1, -1};
+    unsigned plane_gate[2] = {0, 0};            // lgr_ransac_last_plane_gate: the last RANSAC call of THIS context
     unsigned long long mcover[8] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // lgr_match_last_check_cover
     bool internal = false;                      // an aux / aux2 context: works inside its owner's turn (lgr_turn)
     int turn_depth = 0;                         // public entry points call each other: only the outermost one takes the device's turn
@@ -300,14 +301,15 @@ int lgr_plane_setup(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt
 // counts are not the records), d_factor (optional) = per-hypothesis factor of the metric (combination: the correspondence metric);
 // a hypothesis whose upper bounds fall below both is abandoned -- it can be neither the best nor a record.  0 / INT_MAX / NULL: no gate.
 // dyn (the device-driven RANSAC schedule, round 5): the number of hypotheses, the counter base and the gate's two values are READ ON THE DEVICE from
-// these words when the launch runs (nh is then only an upper bound for the grid); a null member keeps the host's value.
+// these words when the launch runs (nh is then only an upper bound for the grid); a null member keeps the host's value.  n_gated (or null):
+// a counter that grows by one per hypothesis the gate abandons.
 // lgr_weights.hip: the weight map of weight_id (on ctx->stream); weights_sum / largest weight / non-finite count (synchronises); the weights
 // of a weighted_closest_plane run (mp NULL: constant), w_gate = max(largest weight, 0)
 int lgr_weights_map(lgr_ctx* ctx, const float* d_pts, int n, int weight_id, int nr_points, float* d_w);
 int lgr_weights_sum(lgr_ctx* ctx, const float* d_w, int n, float* sum, float* w_max, int* n_bad);
 int lgr_weights_prepare(lgr_ctx* ctx, const float* d_src, int ns, const lgr_metric_params* mp, const float** d_w, float* w_sum, float* w_gate);
 int lgr_weights_libm_launch(lgr_ctx* ctx, int fn, const float* d_a, long long n, float* d_out);
-struct lgr_plane_dyn { const int* nh; const int* counter_base; const float* best_prev; const int* record_prev; };
+struct lgr_plane_dyn { const int* nh; const int* counter_base; const float* best_prev; const int* record_prev; int* n_gated; };
 int lgr_plane_eval(lgr_ctx* ctx, const lgr_plane_dev& pd, const float* d_Ts, const int* d_list, int nh, unsigned counter_base, int score_id,
                    int* d_cnt, float* d_metric, float* d_rmse, int2* d_pairs, int* d_n_pairs, float best_prev = 0.f, int record_prev = 0x7fffffff,
                    const float* d_factor = nullptr, const lgr_plane_dyn* dyn = nullptr);

@@ -165,7 +165,11 @@ __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __res
             float m_max;
             if constexpr (W) m_max = (float) (((double) tsc / 4294967296.0 + (double) left * (double) w_gate) / (0.01 * (double) w_sum)) * fac * 1.00001f;
             else m_max = (float) (((double) tsc / 4294967296.0 + (double) left) / (0.01 * (double) (float) ns)) * fac * 1.00001f;
-            if (m_max < best_prev && tcnt + left < record_prev) { j_stop = done_pts; break; }
+            if (m_max < best_prev && tcnt + left < record_prev) {
+                if (tid == 0 && dyn.n_gated) atomicAdd(dyn.n_gated, 1);   // (lgr_ransac_last_plane_gate)
+                j_stop = done_pts;
+                break;
+            }
           }
         }
         for (int j = j_stop + tid; j < n_sp; j += PB) {   // gated out: release the rest of the subset
@@ -215,7 +219,7 @@ int lgr_plane_eval(lgr_ctx* ctx, const lgr_plane_dev& pd, const float* d_Ts, con
     if (nh <= 0) return LGR_OK;
     if (d_pairs) LGR_HIP(ctx, hipMemsetAsync(d_n_pairs, 0, 4, ctx->stream));
     int grid = std::min(nh, pd.n_wg);
-    const lgr_plane_dyn none{nullptr, nullptr, nullptr, nullptr};
+    const lgr_plane_dyn none{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (pd.w)
         plane_kernel<true><<<grid, PB, 0, ctx->stream>>>(pd.g, pd.d_src, pd.ns, pd.n_sp, pd.thr, pd.r2, pd.seed, d_Ts, d_list, nh, counter_base, score_id,
                                                          pd.visited, pd.claimed, d_cnt, d_metric, d_rmse, d_pairs, d_n_pairs, best_prev, record_prev, d_factor,

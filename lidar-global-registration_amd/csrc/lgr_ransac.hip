@@ -395,7 +395,7 @@ static int enqueue_round_front(lgr_ctx* ctx, const LoopBuffers& L, const Packed&
     count_list_kernel<<<L.g_count, CB, 0, ctx->stream>>>(b.Ts, b.list, &dS->n_ok, pk.PP, pk.pstats, c, b.counts, L.maskT, L.mask_cap);
     if (closest) {
         // every survivor on its sparse subset; its plane inliers are "the inliers" (gate: the loop's best metric and record so far)
-        const lgr_plane_dyn dyn{&dS->n_ok, &dS->round_first, &dS->final_metric, &dS->largest};
+        const lgr_plane_dyn dyn{&dS->n_ok, &dS->round_first, &dS->final_metric, &dS->largest, &dS->n_gated};
         LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list, nb_up, 0u, p->score_id, L.pl_cnt, L.pl_cp, nullptr, nullptr, nullptr, 0.f, 0, nullptr, &dyn));
         rs_plane_counts_kernel<<<64, 256, 0, ctx->stream>>>(dS, L.pl_cnt, b.counts);
     }
@@ -404,7 +404,7 @@ static int enqueue_round_front(lgr_ctx* ctx, const LoopBuffers& L, const Packed&
         rs_plane_pick_kernel<<<64, 256, 0, ctx->stream>>>(dS, b.hpos, L.pl_cnt, L.pl_cp, b.metric, b.ninl);
     } else if (plane) {   // combination: correspondences metric with the constant score (include/metric.h:191-192) x plane metric of the candidates
         LGR_TRY(metric_candidates(ctx, L, pk, c, LGR_METRIC_CORRESPONDENCES, LGR_SCORE_CONSTANT));
-        const lgr_plane_dyn dyn{&dS->n_cand, &dS->round_first, &dS->final_metric, &dS->int_max};   // (records are correspondence counts here: only the metric gates)
+        const lgr_plane_dyn dyn{&dS->n_cand, &dS->round_first, &dS->final_metric, &dS->int_max, &dS->n_gated};   // (records are correspondence counts here: only the metric gates)
         LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list2, nb_up, 0u, p->score_id, L.pl_cnt, L.pl_cp, nullptr, nullptr, nullptr, 0.f, 0x7fffffff, b.metric, &dyn));
         rs_plane_mul_kernel<<<64, 256, 0, ctx->stream>>>(dS, b.metric, L.pl_cp);
     } else {
@@ -533,8 +533,8 @@ static int ransac_device_schedule(lgr_ctx* ctx, const float* d_src, const float*
             first = false;
             LGR_TRY(enqueue_round(false));
             LGR_TRY(final_block_and_state());
-            if (ransac_debug) fprintf(stderr, "[lgr] ransac (device schedule) after %d rounds: done %d bound %d largest %d best metric %.4f stop %d (%d survivors, %d candidates in all)\n",
-                                      hS->rounds, hS->done, hS->bound, hS->largest, hS->final_metric, hS->stop, hS->tot_ok, hS->tot_cand);
+            if (ransac_debug) fprintf(stderr, "[lgr] ransac (device schedule) after %d rounds: done %d bound %d largest %d best metric %.4f stop %d (%d survivors, %d candidates in all, %d abandoned by the plane gate)\n",
+                                      hS->rounds, hS->done, hS->bound, hS->largest, hS->final_metric, hS->stop, hS->tot_ok, hS->tot_cand, hS->n_gated);
         } while (!hS->stop);
     }
     *out = *hS;
@@ -625,6 +625,7 @@ extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const
     memset(res, 0, sizeof(*res));
     for (int i = 0; i < 16; ++i) res->transformation[i] = (i % 5 == 0) ? 1.f : 0.f;
     res->n_correspondences = c;
+    ctx->plane_gate[0] = ctx->plane_gate[1] = 0;
     if (c < p->n_samples) return LGR_OK;   // selectCorrespondences refuses (src/sac_prerejective_omp.cpp:36-42); identity, not converged
     uint64_t seed = p->fix_seed ? 566ull : p->seed;
     Packed pk;
@@ -675,6 +676,8 @@ extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const
     // round (a looser gate than batch by batch: it still only abandons what can be neither the best nor a record).
     RState loop;
     LGR_TRY(ransac_device_schedule(ctx, d_src, d_tgt, d_corr, c, pk, p, seed, max_iterations, batch, LGR_RANSAC_SCHEDULE_CHAIN, &plane, guess_metric, nullptr, &loop));
+    ctx->plane_gate[0] = (unsigned) (closest ? loop.tot_ok : loop.tot_cand);   // closest_plane scores every survivor on its subset, combination the candidates
+    ctx->plane_gate[1] = (unsigned) loop.n_gated;
     // :265-296 final re-estimation
     uint8_t* d_mask = d_final_mask;
     if (!d_mask) LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASK, (size_t) c + 16, &d_mask));
@@ -707,6 +710,13 @@ extern "C" int lgr_ransac_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     fill_result(res, loop, hT, converged, e2.n_inl, e2.metric);
     res->time_te = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    return LGR_OK;
+}
+
+// lgr.h: hypotheses of the last RANSAC call that were scored on a sparse plane subset, and how many of them the gate of plane_kernel abandoned
+extern "C" int lgr_ransac_last_plane_gate(lgr_ctx* ctx, unsigned* out2) {
+    if (!ctx || !out2) return LGR_ERR_INVALID_ARG;
+    out2[0] = ctx->plane_gate[0]; out2[1] = ctx->plane_gate[1];
     return LGR_OK;
 }
 

@@ -49,7 +49,7 @@ struct RState {
     float Tn[16];
     float e_metric; int e_ninl; float e_rmse; int pad1;       // evaluation of best_T (the final block, :265-296)
     float e2_metric; int e2_ninl; float e2_rmse; int pad2;    // evaluation of the refit
-    int int_max, tot_ok, tot_cand, pad3;                       // (int_max: a constant the plane gate reads where the records are not plane counts; tot_*: survivors / candidates over all rounds, for LGR_RANSAC_DEBUG)
+    int int_max, tot_ok, tot_cand, n_gated;                    // (int_max: a constant the plane gate reads where the records are not plane counts; tot_*: survivors / candidates over all rounds, for LGR_RANSAC_DEBUG; n_gated: hypotheses the plane gate abandoned, lgr_ransac_last_plane_gate)
     unsigned long long phase_ticks[8];                         // resident kernel: 100 MHz ticks workgroup 0 spent per phase incl. its barrier (begin/replay, hyp, count, cand, metric)
     unsigned long long busy_max[8], busy_sum[8];               // ... and the workgroups' own work per phase (without the barrier): maximum and sum over the workgroups
 };

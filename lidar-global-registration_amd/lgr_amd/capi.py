@@ -804,6 +804,12 @@ class Context:
         self._join()
         return res, mask[:c].cpu().numpy()
 
+    def ransac_plane_gate(self):
+        """(hypotheses scored on a sparse plane subset, those of them the gate abandoned) in the last ransac / ransac_ex / align call"""
+        out = (C.c_uint * 2)()
+        self.check(_lib.lgr_ransac_last_plane_gate(self.h, out))
+        return out[0], out[1]
+
     def ransac_replay(self, src, tgt, corr, params, triples):
         torch = self.torch
         corr = self._corr_dev(corr)

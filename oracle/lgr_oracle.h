@@ -193,6 +193,10 @@ int orc_evaluate(const float* src, int ns, const float* tgt, int nt, const lgr_o
  * hypothesis / iteration index); pairs (optional, 2 ints per inlier): (source index, nearest target index), ascending */
 int orc_evaluate_plane(const float* src, int ns, const float* tgt, int nt, const float T[16], int score_id, uint64_t seed,
                        uint32_t counter, int* n_inl, float* score, float* rmse, float* metric, float* thr, int* pairs);
+/* the same for n transforms (Ts: n x 16, column-major each) and n counters on one set-up of the target grid: n_inl, score, metric [n],
+ * bit for bit the single call's; pairs (optional): max(n_sp, 1) x 2 ints per transform, the first n_inl[i] pairs of block i written */
+int orc_evaluate_plane_many(const float* src, int ns, const float* tgt, int nt, const float* Ts, const uint32_t* counters, int n,
+                            int score_id, uint64_t seed, int* n_inl, float* score, float* metric, float* thr, int* pairs);
 /* src/metric.cpp:103-123 */
 int orc_estimate_max_iterations(const float* src, const float* tgt, const lgr_orc_corr* corr, int c,
                                 const float T[16], float confidence, int nr_samples);

@@ -612,6 +612,26 @@ def evaluate_plane(src, tgt, T, score_id=SCORE_CONSTANT, seed=566, counter=0, wi
     return out
 
 
+def evaluate_plane_many(src, tgt, Ts16, counters, score_id=SCORE_CONSTANT, seed=566, with_pairs=False):
+    """orc_evaluate_plane for n transforms (Ts16: [n, 16] column-major, as replay returns them) and n counters on one set-up of the
+    target grid: dict of n_inl [n], score [n], metric [n], thr and (with_pairs) a list of n [n_inl, 2] arrays."""
+    src, tgt = _pts(src), _pts(tgt)
+    Ts16 = np.ascontiguousarray(Ts16, np.float32).reshape(-1, 16)
+    counters = np.ascontiguousarray(counters, np.uint32)
+    n = Ts16.shape[0]
+    assert counters.shape == (n,)
+    ninl, sc, me, th = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), C.c_float(0)
+    n_sp = max(int(0.01 * src.shape[0]), 1)
+    pairs = np.zeros((max(n, 1), n_sp, 2), np.int32) if with_pairs else None
+    rc = lib().orc_evaluate_plane_many(_p(src), src.shape[0], _p(tgt), tgt.shape[0], _p(Ts16), _p(counters), n, int(score_id), C.c_uint64(seed),
+                                       _p(ninl), _p(sc), _p(me), C.byref(th), _p(pairs))
+    assert rc == 0, rc
+    out = dict(n_inl=ninl, score=sc, metric=me, thr=th.value)
+    if with_pairs:
+        out["pairs"] = [pairs[i, : ninl[i]].copy() for i in range(n)]
+    return out
+
+
 def choose_best_hypothesis(src, tgt, corr, tns):
     src, tgt = _pts(src), _pts(tgt)
     corr = np.ascontiguousarray(corr, CORR_DTYPE)

@@ -481,6 +481,31 @@ extern "C" int orc_evaluate_plane(const float* src, int ns, const float* tgt, in
     return 0;
 }
 
+// the same for n transforms (Ts: n x 16) with n counters on ONE plane_setup (the target grid is the cost of a single call); every output is
+// the single call's bit for bit.  pairs (optional): 2 * n_sp ints per transform, the first 2 * n_inl[i] of block i written.
+extern "C" int orc_evaluate_plane_many(const float* src, int ns, const float* tgt, int nt, const float* Ts, const uint32_t* counters, int n,
+                                       int score_id, uint64_t seed, int* n_inl, float* score, float* metric, float* thr, int* pairs) {
+    if (ns < 1 || nt < 2 || n < 0) return -2;
+    PlaneCtx pc;
+    plane_setup(pc, src, ns, tgt, nt, seed);
+    *thr = pc.thr;
+#pragma omp parallel
+    {
+        std::vector<uint32_t> visited;
+        std::vector<std::pair<int, int>> list;
+#pragma omp for schedule(dynamic, 4)
+        for (int i = 0; i < n; ++i) {
+            PlaneEval e = plane_eval(pc, Ts + 16 * (size_t) i, counters[i], score_id, visited, pairs ? &list : nullptr);
+            n_inl[i] = e.n_inl; score[i] = e.score; metric[i] = e.metric;
+            if (pairs) {
+                int* o = pairs + 2 * (size_t) std::max(pc.n_sp, 1) * (size_t) i;
+                for (size_t k = 0; k < list.size(); ++k) { o[2 * k] = list[k].first; o[2 * k + 1] = list[k].second; }
+            }
+        }
+    }
+    return 0;
+}
+
 extern "C" int orc_estimate_max_iterations(const float* src, const float* tgt, const lgr_orc_corr* corr, int c,
                                            const float T[16], float confidence, int nr_samples) {
     return est_max_iter(src, tgt, corr, c, T, confidence, nr_samples);
