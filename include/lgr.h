@@ -48,10 +48,11 @@ enum {
     LGR_ERR_NO_DEVICE = -2,
     LGR_ERR_OOM = -3,
     LGR_ERR_HIP = -4,          /* a HIP runtime call failed; see lgr_last_error */
-    LGR_ERR_UNSUPPORTED = -5,  /* e.g. n_samples outside 3..8, randomness != 1, alignment teaser (throws in the reference) */
+    LGR_ERR_UNSUPPORTED = -5,  /* e.g. n_samples outside 3..8, randomness outside 1..LGR_RANDOMNESS_MAX (or > 1 with FLANN / a guess), alignment teaser */
     LGR_ERR_VOXEL_TOO_SMALL = -6
 };
 
+enum { LGR_RANDOMNESS_MAX = 8 };                                               /* the longest match list per key point */
 enum { LGR_MATCH_LR = 0, LGR_MATCH_ONE_SIDED = 1, LGR_MATCH_CLUSTER = 2 };      /* src/matching.cpp:21-75 */
 enum { LGR_METRIC_CORRESPONDENCES = 0, LGR_METRIC_UNIFORMITY = 1, LGR_METRIC_CLOSEST_PLANE = 2, LGR_METRIC_COMBINATION = 3,
        LGR_METRIC_WEIGHTED_CLOSEST_PLANE = 4 };   /* src/metric.cpp:272-301 */
@@ -73,7 +74,9 @@ typedef struct {
     float   confidence;          /* 0.999 */
     int32_t bf_block_size;       /* ALIGNMENT_BLOCK_SIZE (lgr_default_params: 10000); every shipped YAML sets 200000 (data/test.yaml:12) */
     int32_t cluster_k;           /* 40 */
-    int32_t randomness;          /* 1 (only 1, as data/test.yaml:14 says) */
+    int32_t randomness;          /* matches per key point and level before the vote, 1..LGR_RANDOMNESS_MAX (data/test.yaml:14 ships 1).
+                                    > 1: the brute-force matcher only (use_bfmatcher = 1, no guess, else LGR_ERR_UNSUPPORTED), and the
+                                    iss_radius_* of a side whose key points are voted on must be finite and > 0 (LGR_ERR_INVALID_ARG) */
     int32_t n_samples;           /* 3 (every shipped config); 3..8 accepted: sampler, polygon test and Umeyama are generic in it,
                                     src/sac_prerejective_omp.cpp:33-77,105-108,220 */
     int32_t alignment_id, matching_id, metric_id, score_id;
@@ -320,6 +323,27 @@ int lgr_match_rops(lgr_ctx*, const float* q135, int mq, const float* t135, int m
 int lgr_match_rops_dev(lgr_ctx*, const float* d_q135, int mq, const float* d_t135, int mt, int block, int32_t* d_idx, float* d_dist);
 int lgr_match2_rops_dev(lgr_ctx*, const float* d_a135, int ma, const float* d_b135, int mb, int block,
                         int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
+/* ---- include/matching.h:612-625 matchBF with randomness = k > 1, on rows of row_len 33 (FPFH), 135 (RoPS135) or 352 (SHOT), other
+ *      lengths and k outside 1..LGR_RANDOMNESS_MAX: LGR_ERR_UNSUPPORTED.  idx / dist are m x k: row i holds query i's matches in list
+ *      order, then -1 / 0.f.  The distances are those of lgr_match_bf / lgr_match_rops / lgr_match_shot.  Per bf block
+ *      cv::batchDistance's K-list: the first min(k, entries) rows in ascending (distance, index); the blocks' lists, ascending, go
+ *      entry by entry through updateMultivaluedCorrespondence (src/common.cpp:517-529: insert in front of the first entry whose
+ *      distance is not smaller, truncate to k), which leaves the first k of their union in (distance ascending, index DESCENDING)
+ *      (DESIGN.md section 4).  k = 1 is the one-match entry points' result.  An exact dense scan for every row length. ---- */
+int lgr_match_knn(lgr_ctx*, int row_len, const float* q, int mq, const float* t, int mt, int block, int k, int32_t* idx, float* dist);
+int lgr_match_knn_dev(lgr_ctx*, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, int32_t* d_idx, float* d_dist);
+/* both directions; the rows are packed once, each direction sweeps the distances itself */
+int lgr_match_knn2_dev(lgr_ctx*, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block, int k,
+                       int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
+/* ---- include/matching.h:327-352 the vote among a query's candidates: cand_idx / cand_dist are mq x width (1..64), entries < 0 are
+ *      skipped, an entry >= mt returns LGR_ERR_INVALID_ARG (the call synchronises to report it); train_pts: mt rows of 12 floats.
+ *      cnt(m1) = float sum over m2 >= m1, in list order, of r / max(dl, r) where dl = sqrtf((dx*dx + dy*dy) + dz*dz) < 32 * r,
+ *      r = iss_radius (finite, > 0); the largest cnt wins, then the smaller distance, strict compares from {0, 0}.
+ *      idx[i] / dist[i] = the winner's entry, or -1 / 0.f. ---- */
+int lgr_vote_matches(lgr_ctx*, const int32_t* cand_idx, const float* cand_dist, int mq, int width, const float* train_pts, int mt,
+                     float iss_radius, int32_t* idx, float* dist);
+int lgr_vote_matches_dev(lgr_ctx*, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
+                         float iss_radius, int32_t* d_idx, float* d_dist);
 /* ---- include/matching.h:373-376 matchFLANN<FPFH>(query_features, train_features, parameters), randomness 1 (:565-592):
  *      pcl::KdTreeFLANN is an exact search, so the nearest row is the one matchBF finds (the reference's own test asserts that,
  *      tests/flann_bf_matcher.h:82-83); what differs is the reported distance: sqrt of FLANN's L2_Simple (sequential sum of

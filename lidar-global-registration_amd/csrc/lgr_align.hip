@@ -449,6 +449,23 @@ static int match_dispatch(const CorrCall& c, const float* a_pts, const float* fa
     return LGR_OK;
 }
 
+// randomness = k > 1, single scale: the k nearest rows of both directions, then the vote per direction -- ij on the target key
+// points with their radius, ji on the source key points (include/matching.h:327-352 with one level)
+static int match_knn_vote(const CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    const lgr_params* p = c.p;
+    const int k = p->randomness, ns = c.ksizes[0], nt = c.ksizes[1];
+    const bool need_ji = c.both_dirs();
+    int32_t *cij, *cji = nullptr;
+    LGR_TRY(lgr_ws_t(ctx, WS_KNN_CAND_IJ, (size_t) 2 * ns * k, &cij));
+    if (need_ji) LGR_TRY(lgr_ws_t(ctx, WS_KNN_CAND_JI, (size_t) 2 * nt * k, &cji));
+    float *dij = (float*) (cij + (size_t) ns * k), *dji = need_ji ? (float*) (cji + (size_t) nt * k) : nullptr;
+    LGR_TRY(lgr_match_knn_core(ctx, c.d->len, c.feat[0], ns, c.feat[1], nt, p->bf_block_size, k, cij, dij, cji, dji));
+    LGR_TRY(lgr_vote_matches_core(ctx, cij, dij, ns, k, c.kclouds[1], nt, p->iss_radius_tgt, c.ij, c.dij));
+    if (need_ji) LGR_TRY(lgr_vote_matches_core(ctx, cji, dji, nt, k, c.kclouds[0], ns, p->iss_radius_src, c.ji, c.dji));
+    return LGR_OK;
+}
+
 static int ms_match_tables(CorrCall& c) {
     lgr_ctx* ctx = c.ctx;
     const int D = c.d->len;
@@ -456,7 +473,7 @@ static int ms_match_tables(CorrCall& c) {
     for (int s = 0; s < 2; ++s) LGR_TRY(ms_initialize(c, s, st[s]));
     tick(ctx, 4);
     const bool need_ji = c.both_dirs();
-    const int ns = c.ksizes[0], nt = c.ksizes[1];
+    const int ns = c.ksizes[0], nt = c.ksizes[1], kr = c.p->randomness;
     std::vector<std::vector<int>> mi_ij(ns), mi_ji(need_ji ? nt : 0);
     std::vector<std::vector<float>> md_ij(ns), md_ji(need_ji ? nt : 0);
     const int lo = std::max(st[0].min_l2, st[1].min_l2), hi = std::min(st[0].max_l2, st[1].max_l2);
@@ -467,9 +484,9 @@ static int ms_match_tables(CorrCall& c) {
         const int ma = (int) la.size(), mb = (int) lb.size();
         if (ma == 0 || mb == 0) continue;
         int32_t* r;
-        LGR_TRY(lgr_ws_t(ctx, WS_MS_RES, (size_t) 2 * (ma + mb) + 4, &r));
-        int32_t *ab_i = r, *ba_i = r + ma;
-        float *ab_d = (float*) (r + ma + mb), *ba_d = ab_d + ma;
+        LGR_TRY(lgr_ws_t(ctx, WS_MS_RES, (size_t) 2 * (ma + mb) * kr + 4, &r));
+        int32_t *ab_i = r, *ba_i = r + (size_t) ma * kr;
+        float *ab_d = (float*) (r + (size_t) (ma + mb) * kr), *ba_d = ab_d + (size_t) ma * kr;
         const float* fa = st[0].feat + st[0].feat_off[ia] * D;
         const float* fb = st[1].feat + st[1].feat_off[ib] * D;
         const float *pa = nullptr, *pb = nullptr;
@@ -480,17 +497,25 @@ static int ms_match_tables(CorrCall& c) {
             gather_rows12(ctx, c.kclouds[1], st[1].d_lists + st[1].feat_off[ib], mb, sub + (size_t) ma * 12);
             pa = sub; pb = sub + (size_t) ma * 12;
         }
-        LGR_TRY(match_dispatch(c, pa, fa, ma, pb, fb, mb, ab_i, ab_d, ba_i, ba_d));
-        std::vector<int32_t> h((size_t) 2 * (ma + mb));
+        // randomness > 1: the level's kr matches per key point, in list order (checked on entry: brute force, no guess)
+        if (kr > 1) LGR_TRY(lgr_match_knn_core(ctx, D, fa, ma, fb, mb, c.p->bf_block_size, kr, ab_i, ab_d, need_ji ? ba_i : nullptr, need_ji ? ba_d : nullptr));
+        else LGR_TRY(match_dispatch(c, pa, fa, ma, pb, fb, mb, ab_i, ab_d, ba_i, ba_d));
+        std::vector<int32_t> h((size_t) 2 * (ma + mb) * kr);
         LGR_HIP(ctx, hipMemcpyAsync(h.data(), r, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const int32_t *h_ab = h.data(), *h_ba = h.data() + ma;
-        const float *h_abd = (const float*) (h.data() + ma + mb), *h_bad = h_abd + ma;
+        const int32_t *h_ab = h.data(), *h_ba = h.data() + (size_t) ma * kr;
+        const float *h_abd = (const float*) (h.data() + (size_t) (ma + mb) * kr), *h_bad = h_abd + (size_t) ma * kr;
         for (int i = 0; i < ma; ++i)
-            if (h_ab[i] >= 0) { mi_ij[la[i]].push_back(lb[h_ab[i]]); md_ij[la[i]].push_back(h_abd[i]); }
+            for (int e = 0; e < kr; ++e) {
+                const size_t at = (size_t) i * kr + e;
+                if (h_ab[at] >= 0) { mi_ij[la[i]].push_back(lb[h_ab[at]]); md_ij[la[i]].push_back(h_abd[at]); }
+            }
         if (need_ji)
             for (int j = 0; j < mb; ++j)
-                if (h_ba[j] >= 0) { mi_ji[lb[j]].push_back(la[h_ba[j]]); md_ji[lb[j]].push_back(h_bad[j]); }
+                for (int e = 0; e < kr; ++e) {
+                    const size_t at = (size_t) j * kr + e;
+                    if (h_ba[at] >= 0) { mi_ji[lb[j]].push_back(la[h_ba[at]]); md_ji[lb[j]].push_back(h_bad[at]); }
+                }
     }
     std::vector<int32_t> ij(ns), ji(need_ji ? nt : 0);
     std::vector<float> dij(ns), dji(need_ji ? nt : 0);
@@ -514,7 +539,12 @@ static int check(CorrCall& c, const lgr_feature_params* fp) {
     LGR_TRY(feature_descriptor(ctx, p, fp, &c.d));
     if (c.sizes[0] < 2 || c.sizes[1] < 2) { *c.n_out = 0; c.empty = true; return LGR_OK; }   // the reference ends with an empty correspondence list
     LGR_CHECK(ctx, c.d_out != nullptr, LGR_ERR_INVALID_ARG);
-    LGR_CHECK(ctx, p->randomness == 1, LGR_ERR_UNSUPPORTED);        // data/test.yaml:14 "currently only 1 is supported"
+    LGR_CHECK(ctx, p->randomness >= 1 && p->randomness <= LGR_RANDOMNESS_MAX, LGR_ERR_UNSUPPORTED);
+    if (p->randomness > 1) {   // the k-nearest matcher is the brute-force one (include/matching.h:612-625); the vote needs the voted side's radius
+        LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);
+        LGR_CHECK(ctx, std::isfinite(p->iss_radius_tgt) && p->iss_radius_tgt > 0.f, LGR_ERR_INVALID_ARG);
+        LGR_CHECK(ctx, !c.both_dirs() || (std::isfinite(p->iss_radius_src) && p->iss_radius_src > 0.f), LGR_ERR_INVALID_ARG);
+    }
     LGR_CHECK(ctx, p->feature_nr_points > 0 && p->normal_nr_points >= 1 && p->normal_nr_points <= 64 && p->bf_block_size > 0 && p->scale_factor > 1.f,
               LGR_ERR_INVALID_ARG);
     // checked before any stage runs (this entry point builds the filter tables itself, so lgr_filter_dev's checks do not cover it):
@@ -597,7 +627,7 @@ static int features_and_match_single(CorrCall& c) {
     const auto t_feat0 = std::chrono::steady_clock::now();
     // The source cloud is done first (this thread): the matcher's query-side half (clustering, assignment, sort) runs right behind
     // its features, under the target cloud's feature kernels on the second context.
-    const bool prepare_query = p->use_bfmatcher && !p->has_guess && !c.d->dense;   // match_dispatch: the FPFH brute-force matcher will be called
+    const bool prepare_query = p->use_bfmatcher && !p->has_guess && !c.d->dense && p->randomness == 1;   // match_dispatch: the FPFH brute-force matcher will be called
     LGR_TRY(lgr_run_pair(ctx,
         [&](lgr_ctx* cx) {
             LGR_TRY(cloud_features(cx, 0, c.ms));
@@ -611,6 +641,7 @@ static int features_and_match_single(CorrCall& c) {
     for (int s = 0; s < 3; ++s) { c.ms[s] += ms_t[s]; sum += c.ms[s]; }
     if (sum > 0.f) for (int s = 0; s < 3; ++s) c.ms[s] *= wall / sum;
     tick(ctx, 4);
+    if (p->randomness > 1) return match_knn_vote(c);
     return match_dispatch(c, c.kclouds[0], c.feat[0], c.ksizes[0], c.kclouds[1], c.feat[1], c.ksizes[1], c.ij, c.dij, c.ji, c.dji);
 }
 

@@ -131,6 +131,7 @@ enum {
     WS_DBG_MISC, WS_DBG_MOVED, WS_DBG_FLAGS, WS_DBG_OVERLAP, WS_DBG_DENS, WS_DBG_SORT, WS_DBG_HOST_A, WS_DBG_HOST_B,   // lgr_debug.hip
     WS_HYP_SET, WS_HYP_ITEMS, WS_HYP_FINAL,   // lgr_hypotheses.hip, lgr_ransac_multi_dev
     WS_RF_STATE, WS_RF_TERMS, WS_RF_PAIRS, WS_RF_TRACE,   // lgr_refine.hip
+    WS_KNN_PART_A, WS_KNN_PART_B, WS_KNN_FLAG, WS_KNN_CAND_IJ, WS_KNN_CAND_JI,   // lgr_match_knn.hip; the pipeline's candidate lists
     WS_COUNT
 };
 static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");
@@ -247,6 +248,11 @@ int lgr_sort_pairs_u64(lgr_ctx* ctx, const unsigned long long* kin, unsigned lon
 // (d_a33, ma, mb, both directions) or dropped by lgr_match_prepare_cancel.
 int lgr_match_prepare(lgr_ctx* ctx, const float* d_a33, int ma, int mb, bool both);
 void lgr_match_prepare_cancel(lgr_ctx* ctx);
+// lgr_match_knn.hip: the k nearest rows per query (idx / dist m x k) and the vote among a query's candidates, without the turn
+int lgr_match_knn_core(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block, int k,
+                       int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d);
+int lgr_vote_matches_core(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
+                          float iss_radius, int32_t* d_idx, float* d_dist);
 // lgr_match_dense.hip: the exact dense matcher of the long descriptors, row_len 352 (SHOT) or 135 (RoPS), else LGR_ERR_UNSUPPORTED
 int lgr_match_dense(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block,
                     int32_t* ab_i, float* ab_d, int32_t* ba_i /* NULL: one direction */, float* ba_d);

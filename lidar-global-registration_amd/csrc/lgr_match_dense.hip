@@ -6,29 +6,9 @@
 // depend on scheduling.  The 33-d FPFH matcher is lgr_match.hip.
 #include <cfloat>
 
-#include "lgr_internal.h"
+#include "lgr_match_dense.cuh"
 
 namespace {
-
-// cv::hal::normL2Sqr_ (OpenCV 4.5.1, SSE baseline) for n = 352: 22 blocks of 16; acc[k][lane] += t * t for element
-// 16 b + 4 k + lane; s = ((acc0 + acc1) + acc2) + acc3 lane-wise; d2 = (s0 + s2) + (s1 + s3).  The 16 (k, lane) chains are independent,
-// so the rows are packed with the elements of one chain contiguous -- group (lane, k) = 4 lane + k, 22 elements in block order -- and
-// transposed (element-major, rows padded to 64) for coalesced tile loads.  A pair then runs the chains one after the other:
-// sl = acc(lane, 0) + acc(lane, 1) + acc(lane, 2) + acc(lane, 3) in that order, A = s0 + s2, B = s1 + s3, d2 = A + B: the same
-// operations on the same values as the SSE code.
-// The kernels are templated on the block count NB and the scalar tail TAIL (row length 16 NB + TAIL): SHOT is <22, 0>, RoPS135
-// <8, 7>, whose elements 128..134 follow the blocks as d2 += t * t one after the other (normL2Sqr_'s scalar loop).
-constexpr int MT = 64;                // rows per tile side
-template <int NB, int TAIL>
-__global__ void dense_pack_kernel(const float* __restrict__ rows, int m, int mpad, float* __restrict__ packed) {
-    constexpr int LEN = 16 * NB + TAIL;
-    const size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t) mpad * LEN) return;
-    const int r = (int) (e % mpad), p = (int) (e / mpad);   // p: packed element = group * NB + b, group = 4 lane + k; then the tail
-    const int grp = p / NB, b = p % NB, lane = grp >> 2, k = grp & 3;
-    const int col = (TAIL == 0 || p < 16 * NB) ? 16 * b + 4 * k + lane : p;
-    packed[e] = r < m ? rows[(size_t) r * LEN + col] : __uint_as_float(0x7fc00000u);
-}
 
 // rank of train row j among equal distances: a later bf block first, the lowest index inside a block
 __device__ __forceinline__ unsigned dense_tie_rank(int j, int block, int nb) { return (unsigned) (nb - 1 - j / block) * (unsigned) block + (unsigned) (j % block); }
@@ -38,7 +18,6 @@ template <int NB, int TAIL>
 __global__ __launch_bounds__(256) void dense_match_kernel(const float* __restrict__ pa, int ma, int mpa, const float* __restrict__ pb, int mb, int mpb,
                                                          int block, int nb_a, int nb_b, int splits, unsigned long long* __restrict__ key_ab,
                                                          unsigned long long* __restrict__ key_ba) {
-    static_assert(TAIL <= NB, "the tail is staged in the block buffers");
     __shared__ float4 sa[NB][MT / 4];
     __shared__ float4 sb[NB][MT / 4];
     __shared__ unsigned long long qmin[MT], tmin[MT];
@@ -50,69 +29,15 @@ __global__ __launch_bounds__(256) void dense_match_kernel(const float* __restric
     for (int tt = split; tt < n_tt; tt += splits) {
         const int t0 = tt * MT;
         if (tid < MT) tmin[tid] = ~0ull;
-        float sA[4][4], sB[4][4], sl[4][4], acc[4][4];
-        for (int grp = 0; grp < 16; ++grp) {
-            __syncthreads();
-            for (int e = tid; e < NB * (MT / 4); e += 256) {
-                const int b = e / (MT / 4), c = e % (MT / 4);
-                sa[b][c] = reinterpret_cast<const float4*>(pa + (size_t) (grp * NB + b) * mpa + q0)[c];
-                sb[b][c] = reinterpret_cast<const float4*>(pb + (size_t) (grp * NB + b) * mpb + t0)[c];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-            for (int b = 0; b < NB; ++b) {
-                const float4 a4 = sa[b][ty], b4 = sb[b][tx];
-                const float av[4] = {a4.x, a4.y, a4.z, a4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { const float t = av[i] - bv[j]; acc[i][j] = t * t + acc[i][j]; }
-            }
-            const int k = grp & 3, lane = grp >> 2;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    sl[i][j] = k == 0 ? acc[i][j] : sl[i][j] + acc[i][j];
-                    if (k == 3) {
-                        if (lane == 0) sA[i][j] = sl[i][j];
-                        else if (lane == 1) sB[i][j] = sl[i][j];
-                        else if (lane == 2) sA[i][j] = sA[i][j] + sl[i][j];
-                        else sB[i][j] = sB[i][j] + sl[i][j];
-                    }
-                }
-        }
-        if constexpr (TAIL > 0) {   // d2 = A + B, then d2 += t * t for the tail elements in order
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sA[i][j] = sA[i][j] + sB[i][j];
-            __syncthreads();
-            for (int e = tid; e < TAIL * (MT / 4); e += 256) {
-                const int b = e / (MT / 4), c = e % (MT / 4);
-                sa[b][c] = reinterpret_cast<const float4*>(pa + (size_t) (16 * NB + b) * mpa + q0)[c];
-                sb[b][c] = reinterpret_cast<const float4*>(pb + (size_t) (16 * NB + b) * mpb + t0)[c];
-            }
-            __syncthreads();
-            for (int b = 0; b < TAIL; ++b) {
-                const float4 a4 = sa[b][ty], b4 = sb[b][tx];
-                const float av[4] = {a4.x, a4.y, a4.z, a4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { const float t = av[i] - bv[j]; sA[i][j] = sA[i][j] + t * t; }
-            }
-        }
+        float d4[4][4];
+        dense_tile_distances<NB, TAIL>(pa, mpa, q0, pb, mpb, t0, sa, sb, d4);
         unsigned long long bq[4] = {~0ull, ~0ull, ~0ull, ~0ull}, bt[4] = {~0ull, ~0ull, ~0ull, ~0ull};
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int qi = q0 + 4 * ty + i, tj = t0 + 4 * tx + j;
-                const float d = TAIL > 0 ? sqrtf(sA[i][j]) : sqrtf(sA[i][j] + sB[i][j]);
+                const float d = d4[i][j];
                 if (!(qi < ma && tj < mb && d < FLT_MAX)) continue;   // NaN never enters (batchDistance's strict '<' against FLT_MAX)
                 const unsigned long long db = (unsigned long long) __float_as_uint(d) << 32;
                 const unsigned long long kq = db | dense_tie_rank(tj, block, nb_b), kt = db | dense_tie_rank(qi, block, nb_a);

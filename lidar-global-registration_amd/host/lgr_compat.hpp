@@ -300,36 +300,44 @@ inline void estimateFeatures<RoPS135>(const PointNCloud::ConstPtr& pcd, const Po
     features->width = (unsigned) m;
 }
 
-// ---- include/matching.h:373-376 (randomness = 1)
+// ---- include/matching.h:373-376, :594-634: every query's list of randomness matches (randomness = 1: the one-match entry points)
 template <class FeatureT>
 inline std::vector<MultivaluedCorrespondence> matchBF(const typename Cloud<FeatureT>::ConstPtr& query_features,
                                                       const typename Cloud<FeatureT>::ConstPtr& train_features,
                                                       const AlignmentParameters& parameters) {
     static_assert(sizeof(FeatureT) == 132 || sizeof(FeatureT) == 1444 || sizeof(FeatureT) == 540, "only FPFH, SHOT and RoPS135 are built on this path");
-    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness != 1 is not supported (data/test.yaml:14)");
+    const int k = parameters.randomness;
+    if (k < 1 || k > LGR_RANDOMNESS_MAX) throw std::runtime_error("lgr: randomness outside 1..LGR_RANDOMNESS_MAX is not supported");
     int mq = (int) query_features->size(), mt = (int) train_features->size();
-    std::vector<int32_t> idx(mq);
-    std::vector<float> dist(mq);
-    if constexpr (sizeof(FeatureT) == 540) {   // RoPS135: contiguous 135-float rows
-        check(lgr_match_rops(context(), reinterpret_cast<const float*>(query_features->points.data()), mq,
-                             reinterpret_cast<const float*>(train_features->points.data()), mt, parameters.bf_block_size, idx.data(), dist.data()),
-              "matchBF");
-    } else if constexpr (sizeof(FeatureT) == 1444) {   // SHOT352: the 352 descriptor floats of every row, without the frame
-        auto rows = [](const Cloud<FeatureT>& c) {
-            std::vector<float> r(c.size() * 352);
+    std::vector<int32_t> idx((std::size_t) mq * k);
+    std::vector<float> dist((std::size_t) mq * k);
+    // SHOT352: the 352 descriptor floats of every row, without the frame; RoPS135 and FPFH rows are contiguous
+    auto shot_rows = [](const Cloud<FeatureT>& c) {
+        std::vector<float> r(sizeof(FeatureT) == 1444 ? c.size() * 352 : 0);
+        if (sizeof(FeatureT) == 1444)
             for (std::size_t i = 0; i < c.size(); ++i) std::memcpy(r.data() + i * 352, &c.points[i], 352 * sizeof(float));
-            return r;
-        };
-        const std::vector<float> q = rows(*query_features), t = rows(*train_features);
-        check(lgr_match_shot(context(), q.data(), mq, t.data(), mt, parameters.bf_block_size, idx.data(), dist.data()), "matchBF");
+        return r;
+    };
+    const std::vector<float> q352 = shot_rows(*query_features), t352 = shot_rows(*train_features);
+    const float* q = sizeof(FeatureT) == 1444 ? q352.data() : reinterpret_cast<const float*>(query_features->points.data());
+    const float* t = sizeof(FeatureT) == 1444 ? t352.data() : reinterpret_cast<const float*>(train_features->points.data());
+    if (k > 1) {
+        constexpr int row_len = sizeof(FeatureT) == 540 ? 135 : sizeof(FeatureT) == 1444 ? 352 : 33;
+        check(lgr_match_knn(context(), row_len, q, mq, t, mt, parameters.bf_block_size, k, idx.data(), dist.data()), "matchBF");
+    } else if constexpr (sizeof(FeatureT) == 540) {
+        check(lgr_match_rops(context(), q, mq, t, mt, parameters.bf_block_size, idx.data(), dist.data()), "matchBF");
+    } else if constexpr (sizeof(FeatureT) == 1444) {
+        check(lgr_match_shot(context(), q, mq, t, mt, parameters.bf_block_size, idx.data(), dist.data()), "matchBF");
     } else {
-        check(lgr_match_bf(context(), reinterpret_cast<const float*>(query_features->points.data()), mq,
-                           reinterpret_cast<const float*>(train_features->points.data()), mt, parameters.bf_block_size, idx.data(), dist.data()),
-              "matchBF");
+        check(lgr_match_bf(context(), q, mq, t, mt, parameters.bf_block_size, idx.data(), dist.data()), "matchBF");
     }
     std::vector<MultivaluedCorrespondence> out(mq);
     for (int i = 0; i < mq; ++i)
-        if (idx[i] >= 0) { out[i].match_indices.push_back(idx[i]); out[i].distances.push_back(dist[i]); }
+        for (int e = 0; e < k; ++e)
+            if (idx[(std::size_t) i * k + e] >= 0) {
+                out[i].match_indices.push_back(idx[(std::size_t) i * k + e]);
+                out[i].distances.push_back(dist[(std::size_t) i * k + e]);
+            }
     return out;
 }
 
@@ -339,7 +347,7 @@ inline std::vector<MultivaluedCorrespondence> matchFLANN(const typename Cloud<Fe
                                                          const typename Cloud<FeatureT>::ConstPtr& train_features,
                                                          const AlignmentParameters& parameters) {
     static_assert(sizeof(FeatureT) == 132, "only FPFH is built on this path");
-    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness != 1 is not supported (data/test.yaml:14)");
+    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness > 1 is built for matchBF only");
     int mq = (int) query_features->size(), mt = (int) train_features->size();
     std::vector<int32_t> idx(mq);
     std::vector<float> dist(mq);
@@ -358,7 +366,7 @@ inline std::vector<MultivaluedCorrespondence> matchLocal(const PointNCloud::Cons
                                                          const typename Cloud<FeatureT>::ConstPtr& train_features,
                                                          const AlignmentParameters& parameters, const Matrix4f& guess) {
     static_assert(sizeof(FeatureT) == 132, "only FPFH is built on this path");
-    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness != 1 is not supported (data/test.yaml:14)");
+    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness > 1 is built for matchBF only");
     int mq = (int) query_features->size(), mt = (int) train_features->size();
     if ((int) query_pcd->size() != mq || (int) train_pcd->size() != mt) throw std::runtime_error("lgr: matchLocal: clouds and feature clouds differ in size");
     std::vector<int32_t> idx(mq);

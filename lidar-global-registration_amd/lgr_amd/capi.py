@@ -629,6 +629,51 @@ class Context:
         self.check(_lib.lgr_match_shot(self.h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), _ptr(idx), _ptr(dist)))
         return idx, dist
 
+    # ---- randomness > 1: the k nearest rows (row length 33, 135 or 352) and the vote among a query's candidates ----------------------
+    def match_knn(self, q, t, block=10000, k=2):
+        """exact matchBF with randomness = k on cuda float32 [m, 33 | 135 | 352] rows: (idx int32 [mq, k], dist float32 [mq, k]),
+        a query's matches in list order, then -1 / 0."""
+        torch = self.torch
+        q = q.contiguous(); t = t.contiguous()
+        idx = self.empty((q.shape[0], max(int(k), 0)), torch.int32)
+        dist = self.empty((q.shape[0], max(int(k), 0)), torch.float32)
+        self.check(_lib.lgr_match_knn_dev(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match_knn2(self, a, b, block=10000, k=2):
+        torch = self.torch
+        a = a.contiguous(); b = b.contiguous()
+        kk = max(int(k), 0)
+        ab_i = self.empty((a.shape[0], kk), torch.int32); ab_d = self.empty((a.shape[0], kk), torch.float32)
+        ba_i = self.empty((b.shape[0], kk), torch.int32); ba_d = self.empty((b.shape[0], kk), torch.float32)
+        self.check(_lib.lgr_match_knn2_dev(self.h, int(a.shape[1]), _ptr(a), a.shape[0], _ptr(b), b.shape[0], int(block), int(k),
+                                           _ptr(ab_i), _ptr(ab_d), _ptr(ba_i), _ptr(ba_d)))
+        return ab_i, ab_d, ba_i, ba_d
+
+    def match_knn_host(self, q, t, block=10000, k=2):
+        q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
+        idx = np.zeros((q.shape[0], max(int(k), 0)), np.int32); dist = np.zeros((q.shape[0], max(int(k), 0)), np.float32)
+        self.check(_lib.lgr_match_knn(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def vote_matches(self, cand_idx, cand_dist, train_pts, iss_radius):
+        """the vote of include/matching.h:327-352: cuda int32 / float32 [mq, width] candidates (entries < 0 skipped), cuda float32
+        [mt, 12] train key points -> (idx int32 [mq], dist float32 [mq])"""
+        torch = self.torch
+        ci = cand_idx.contiguous(); cd = cand_dist.contiguous(); tp = train_pts.contiguous()
+        idx = self.empty((ci.shape[0],), torch.int32); dist = self.empty((ci.shape[0],), torch.float32)
+        self.check(_lib.lgr_vote_matches_dev(self.h, _ptr(ci), _ptr(cd), ci.shape[0], int(ci.shape[1]), _ptr(tp), tp.shape[0], C.c_float(iss_radius),
+                                             _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def vote_matches_host(self, cand_idx, cand_dist, train_pts, iss_radius):
+        ci = np.ascontiguousarray(cand_idx, np.int32); cd = np.ascontiguousarray(cand_dist, np.float32)
+        tp = np.ascontiguousarray(train_pts, np.float32)
+        idx = np.zeros(ci.shape[0], np.int32); dist = np.zeros(ci.shape[0], np.float32)
+        self.check(_lib.lgr_vote_matches(self.h, _ptr(ci), _ptr(cd), ci.shape[0], int(ci.shape[1]), _ptr(tp), tp.shape[0], C.c_float(iss_radius),
+                                         _ptr(idx), _ptr(dist)))
+        return idx, dist
+
     def gravity_lrf(self, kps, surf, radius):
         """gravity-aligned frames: cuda float32 [m, 9]; SHOT frames where the normal is within 0.04 rad of the vertical (or NaN)."""
         out = self.empty((kps.shape[0], 9), self.torch.float32)

@@ -45,6 +45,8 @@ def main():
                     help="point weights of weighted_closest_plane (src/weights.cpp)")
     ap.add_argument("--matching", default="cluster", choices=["lr", "one_sided", "cluster"])
     ap.add_argument("--alignment", default="ransac", choices=["ransac", "gror"])
+    ap.add_argument("--randomness", type=int, default=1, metavar="K",
+                    help="matches kept per key point and level before the proximity vote, 1 .. 8 (include/matching.h:612-625, :327-352)")
     ap.add_argument("--descriptor", default="fpfh", choices=["fpfh", "shot", "rops"])
     ap.add_argument("--lrf", default="default", choices=["default", "gravity"],
                     help="local reference frames (SHOT: default only; RoPS: gravity only; FPFH ignores them)")
@@ -61,6 +63,8 @@ def main():
                     help="also keep the set of up to N distinct hypotheses (ransac with uniformity / correspondences) and list its members")
     ap.add_argument("--refine", type=int, default=0, metavar="N", help="refine the result by up to N dense closest-plane steps (lgr_refine_plane)")
     a = ap.parse_args()
+    if not 1 <= a.randomness <= 8:
+        ap.error("--randomness takes 1 .. 8")
     if not 0 <= a.refine <= 1024:
         ap.error("--refine takes 0 .. 1024 steps")
     if a.metrics_csv and not a.ground_truth:
@@ -83,7 +87,7 @@ def main():
     p = profile.default_profile(capi, ld["density_src"], ld["density_tgt"], keypoint=a.keypoint, metric=a.metric, matching=a.matching,
                                 alignment=a.alignment, feature_radius=a.feature_radius if a.feature_radius > 0 else None,
                                 distance_thr=a.distance_thr if a.distance_thr > 0 else None, iterations=a.iterations,
-                                normals_available=ld["normals_available"])
+                                normals_available=ld["normals_available"], randomness=a.randomness)
     t = time.perf_counter()
     lrf = {"default": capi.LRF_DEFAULT, "gravity": capi.LRF_GRAVITY}[a.lrf]
     if a.metric == "weighted_closest_plane":
