@@ -625,6 +625,51 @@ int lgr_evaluate_gt(lgr_ctx*, const float* src, int ns, const float* tgt, int nt
 int lgr_evaluate_gt_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c, const float T16[16] /* host */,
                         const float Tgt16[16] /* host */, float distance_thr, int converged, const uint8_t* d_inlier_mask_or_null,
                         lgr_gt_eval* out /* host */, uint8_t* d_correct_mask_or_null);
+/* n transforms judged against ONE ground truth: out[s] is, field for field and bit for bit, what lgr_evaluate_gt_dev returns for
+ * (T16s + 16 s, converged[s], inlier mask s) -- NaN and empty-cloud conventions and the declared orders included.  What
+ * AlignmentAnalysis::start computes from the ground truth alone runs once per call: the target's grid, the overlap set of
+ * calculateOverlapRmse (found at the ground truth, src/analysis.cpp:69-76: only the last distance, :77, uses the estimate), the correct
+ * correspondences and their uniformity, the normal difference and mergeOverlaps.  The transforms are taken LGR_GT_BATCH_CHUNK to a
+ * launch.  T16s: n x 16 column-major; d_inlier_masks: n x c bytes, mask s at offset s * c; the correct mask (c bytes) is the same for
+ * every member.  n == 0: LGR_OK, nothing written; n > LGR_GT_BATCH_MAX: LGR_ERR_UNSUPPORTED; otherwise the checks of lgr_evaluate_gt_dev. */
+enum { LGR_GT_BATCH_MAX = 64, LGR_GT_BATCH_CHUNK = 8 };
+int lgr_evaluate_gt_batch(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float* T16s /* n x 16 */, int n,
+                          const float Tgt16[16], float distance_thr, const int32_t* converged /* n */, const uint8_t* inlier_masks_or_null /* n x c */,
+                          lgr_gt_eval* out /* n */, uint8_t* correct_mask_or_null /* c */);
+int lgr_evaluate_gt_batch_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                              const float* T16s /* host, n x 16 */, int n, const float Tgt16[16] /* host */, float distance_thr,
+                              const int32_t* converged /* host, n */, const uint8_t* d_inlier_masks_or_null /* n x c bytes */,
+                              lgr_gt_eval* out /* host, n */, uint8_t* d_correct_mask_or_null /* c bytes */);
+
+/* ---- the `measure` test type (measureTestResults, src/main.cpp:312-382): n_times alignments of one pair that differ in the RANSAC
+ *      seed only, each judged against the ground truth, and the test_measurements.csv row over them.  The correspondence search does
+ *      not depend on the seed and runs once; the runs are lgr_ransac_ex_dev with fix_seed = 0 and seed = seeds[i] (seeds == NULL:
+ *      params->seed + i; the reference's std::random_device seeding is the caller's business); all runs are judged by one
+ *      lgr_evaluate_gt_batch_dev call with distance_thr = params->distance_thr and each run's final inlier mask.
+ *      runs[i].result is what lgr_align_ex2_dev returns for that seed, except time_cs and stage_ms[0..4]: the shared search's, the same
+ *      in every run.  1 <= n_times <= LGR_GT_BATCH_MAX, else LGR_ERR_INVALID_ARG; alignment_id = gror has no seed: one run
+ *      (src/main.cpp:350), out->n_times reports the runs made.  Whatever lgr_align_ex2_dev refuses is refused with its code before the
+ *      search starts; after those checks a distance_thr outside (0, 1e18] is LGR_ERR_INVALID_ARG (the evaluation's bound).  Aggregates, on the host as the reference states them (src/main.cpp:345-380, include/utils.h:68-88): a run
+ *      succeeds when eval.converged_and_overlap_ok; mae / sae, mte / ste and mrmse / srmse are mean and deviation of r_err, t_err and
+ *      overlap_rmse over the successful runs in run order, mtime / stime of (float) (time_cs + time_te) over all runs; the mean is the
+ *      sequential double sum from 0.0 divided by (float) size, the deviation std::sqrt of the sequential float sum of
+ *      (x - mean) * (x - mean) divided by (float) size (the population form); an empty list gives quiet NaN for both. ---- */
+typedef struct { uint64_t seed; lgr_result result; lgr_gt_eval eval; } lgr_measure_run;
+typedef struct {
+    int32_t n_times, n_success;
+    float   success_rate, mae, sae, mte, ste, mrmse, srmse, mtime, stime;   /* the columns of src/main.cpp:324 */
+    int32_t reserved[5];   /* 0 */
+} lgr_measurement;
+int lgr_measure(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, const lgr_feature_params* /* or NULL */,
+                const lgr_metric_params* /* or NULL */, const float Tgt16[16], const uint64_t* seeds_or_null, int n_times,
+                lgr_measure_run* runs /* n_times */, lgr_measurement* out);
+int lgr_measure_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params*, const lgr_feature_params* /* or NULL */,
+                    const lgr_metric_params* /* or NULL */, const float Tgt16[16] /* host */, const uint64_t* seeds_or_null /* host */, int n_times,
+                    lgr_measure_run* runs /* host, n_times */, lgr_measurement* out /* host */);
+/* the two aggregates alone, on host lists (include/utils.h:68-88 calculateMean / calculateStandardDeviation for float) */
+float lgr_measure_mean(const float* x, int n);
+float lgr_measure_deviation(const float* x, int n, float mean);
+
 /* src/analysis.cpp:45-88 calculateOverlapRmse (and :30-43 calculatePointCloudRmse, computed by the same pass; pcd_err may be NULL).
  * d_idx (optional, ns ints): the target point whose tangent plane source point i was measured against, -1 where the point was skipped. */
 int lgr_overlap_rmse_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16] /* host */, const float Tgt16[16] /* host */,

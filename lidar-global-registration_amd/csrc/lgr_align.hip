@@ -788,3 +788,146 @@ extern "C" int lgr_align_ex2(lgr_ctx* ctx, const float* src, int ns, const float
     LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
     return lgr_align_ex2_dev(ctx, ds, ns, dt, nt, p, fp, mp, res);
 }
+
+// ---- the `measure` test type (measureTestResults, src/main.cpp:312-382) ----
+// include/utils.h:68-74 calculateMean<float>: std::accumulate from the double 0.0, divided by (float) size, returned as float
+extern "C" float lgr_measure_mean(const float* x, int n) {
+    if (n <= 0 || !x) return std::numeric_limits<float>::quiet_NaN();
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) sum = sum + x[i];
+    return (float) (sum / (float) n);
+}
+
+// include/utils.h:76-88 calculateStandardDeviation<float>: the float sum of the squared differences in order, the population form
+extern "C" float lgr_measure_deviation(const float* x, int n, float mean) {
+    if (n <= 0 || !x) return std::numeric_limits<float>::quiet_NaN();
+    float deviation = 0.f;
+    for (int i = 0; i < n; ++i) deviation += (x[i] - mean) * (x[i] - mean);
+    return std::sqrt(deviation / (float) n);
+}
+
+// src/main.cpp:345-380 over the finished runs
+static void measure_aggregate(const lgr_measure_run* runs, int n, lgr_measurement* out) {
+    std::vector<float> r, t, o, time;
+    for (int i = 0; i < n; ++i) {
+        if (runs[i].eval.converged_and_overlap_ok) {
+            r.push_back(runs[i].eval.r_err); t.push_back(runs[i].eval.t_err); o.push_back(runs[i].eval.overlap_rmse);
+        }
+        time.push_back((float) (runs[i].result.time_cs + runs[i].result.time_te));
+    }
+    memset(out, 0, sizeof *out);
+    out->n_times = n; out->n_success = (int) r.size();
+    out->success_rate = (float) out->n_success / (float) n;
+    auto both = [](const std::vector<float>& v, float* mean, float* dev) {
+        *mean = lgr_measure_mean(v.data(), (int) v.size());
+        *dev = lgr_measure_deviation(v.data(), (int) v.size(), *mean);
+    };
+    both(r, &out->mae, &out->sae); both(t, &out->mte, &out->ste); both(o, &out->mrmse, &out->srmse); both(time, &out->mtime, &out->stime);
+}
+
+extern "C" int lgr_measure_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
+                               const lgr_metric_params* mp, const float Tgt16[16], const uint64_t* seeds, int n_times, lgr_measure_run* runs,
+                               lgr_measurement* out) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    // lgr_align_ex2_dev's own checks, in its order
+    LGR_CHECK(ctx, (d_src || ns == 0) && (d_tgt || nt == 0) && p && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, p->alignment_id == LGR_ALIGN_RANSAC || p->alignment_id == LGR_ALIGN_GROR, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, p->n_samples >= 3 && p->n_samples <= 8, LGR_ERR_UNSUPPORTED);
+    const Descriptor* descriptor;
+    LGR_TRY(feature_descriptor(ctx, p, fp, &descriptor));
+    LGR_CHECK(ctx, Tgt16 && runs && out && n_times >= 1 && n_times <= LGR_GT_BATCH_MAX, LGR_ERR_INVALID_ARG);
+    const bool ransac = p->alignment_id == LGR_ALIGN_RANSAC;
+    const int n = ransac ? n_times : 1;   // src/main.cpp:350
+    const bool empty = ns < 2 || nt < 2;
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    lgr_corr* dc = nullptr;
+    if (!empty) {
+        // ... and the checks of its two stages, before either runs: the search's (check) and the loop's, which a call without
+        // correspondences makes and then returns from (lgr_ransac_ex_dev: identity, no launch)
+        {
+            int n0 = 0;
+            lgr_corr none;   // check only asks for an output pointer; nothing is written through it
+            CorrCall probe(ctx, d_src, ns, d_tgt, nt, p, &none, &n0);
+            LGR_TRY(check(probe, fp));
+        }
+        lgr_result r0;
+        if (ransac) LGR_TRY(lgr_ransac_ex_dev(ctx, d_src, ns, d_tgt, nt, nullptr, 0, p, mp, &r0, nullptr));
+    }
+    // the evaluation's own bound (include/lgr.h), after everything lgr_align_ex2_dev would have refused; still before any work
+    LGR_CHECK(ctx, p->distance_thr > 0.f && p->distance_thr <= 1e18f, LGR_ERR_INVALID_ARG);
+    if (!empty) LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));
+    for (int i = 0; i < n; ++i) {
+        memset(&runs[i], 0, sizeof runs[i]);
+        runs[i].seed = seeds ? seeds[i] : p->seed + (uint64_t) i;
+        for (int k = 0; k < 16; ++k) runs[i].result.transformation[k] = (k % 5 == 0) ? 1.f : 0.f;   // a cloud without two points: identity, not converged
+    }
+    int c = 0;
+    uint8_t* d_masks = nullptr;
+    if (!empty) {
+        auto t0 = std::chrono::steady_clock::now();
+        LGR_TRY(lgr_correspondences_ex_dev(ctx, d_src, ns, d_tgt, nt, p, fp, dc, &c));
+        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const double time_cs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        float search_ms[12];
+        for (int k = 0; k < 12; ++k) search_ms[k] = ctx->stage_ms[k];
+        LGR_TRY(lgr_ws_t(ctx, WS_MEASURE_MASKS, (size_t) n * c + 16, &d_masks));
+        LGR_HIP(ctx, hipMemsetAsync(d_masks, 0, (size_t) n * c + 16, ctx->stream));   // (a run with c < n_samples writes no mask)
+        // WeightedClosestPlaneMetricEstimator::setSourceCloud once for all runs: lgr_weights_prepare sums a caller's weights with the kernel
+        // it sums its own map with, so handing the map over is bit-identical to letting each run compute it.  The constant map is not
+        // handed over: its sum is a closed form there (lgr_seqsum.h) and the map costs one fill.
+        lgr_metric_params mp_shared;
+        const lgr_metric_params* mp_run = mp;
+        if (ransac && p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE && mp && !mp->weights && mp->weight_id != LGR_WEIGHT_CONSTANT && c >= p->n_samples) {
+            float* d_w;
+            LGR_TRY(lgr_ws_t(ctx, WS_MEASURE_W, (size_t) ns + 64, &d_w));
+            LGR_TRY(lgr_weights_map(ctx, d_src, ns, mp->weight_id, 30, d_w));   // NORMAL_NR_POINTS (lgr_weights.hip)
+            mp_shared = *mp; mp_shared.weights = d_w; mp_run = &mp_shared;
+        }
+        lgr_params pr = *p;
+        pr.fix_seed = 0;   // src/main.cpp:339
+        for (int i = 0; i < n; ++i) {
+            pr.seed = runs[i].seed;
+            lgr_result* res = &runs[i].result;
+            tick(ctx, 7);
+            ctx->corr_trusted = true;   // dc was produced by the search above (lgr_check_corr)
+            const int rc = ransac ? lgr_ransac_ex_dev(ctx, d_src, ns, d_tgt, nt, dc, c, &pr, mp_run, res, d_masks + (size_t) i * c)
+                                  : lgr_gror_dev(ctx, d_src, ns, d_tgt, nt, dc, c, p->distance_thr, 800, res, d_masks + (size_t) i * c);
+            ctx->corr_trusted = false;
+            LGR_TRY(rc);
+            tick(ctx, 8);
+            LGR_HIP(ctx, hipEventSynchronize(ctx->ev[8]));
+            float t;
+            (void) hipEventElapsedTime(&t, ctx->ev[7], ctx->ev[8]);
+            res->time_cs = time_cs;
+            res->n_correspondences = c;
+            for (int k = 0; k < 12; ++k) res->stage_ms[k] = search_ms[k];
+            res->stage_ms[5] = t;
+        }
+    }
+    float T16s[LGR_GT_BATCH_MAX * 16];
+    int32_t conv[LGR_GT_BATCH_MAX];
+    lgr_gt_eval evals[LGR_GT_BATCH_MAX];
+    for (int i = 0; i < n; ++i) {
+        memcpy(T16s + 16 * i, runs[i].result.transformation, 64);
+        conv[i] = runs[i].result.converged;
+    }
+    LGR_TRY(lgr_evaluate_gt_batch_dev(ctx, d_src, ns, d_tgt, nt, dc, c, T16s, n, Tgt16, p->distance_thr, conv, c ? d_masks : nullptr, evals, nullptr));
+    for (int i = 0; i < n; ++i) runs[i].eval = evals[i];
+    measure_aggregate(runs, n, out);
+    return LGR_OK;
+}
+
+extern "C" int lgr_measure(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
+                           const lgr_metric_params* mp, const float Tgt16[16], const uint64_t* seeds, int n_times, lgr_measure_run* runs,
+                           lgr_measurement* out) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, (src || ns == 0) && (tgt || nt == 0) && p && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    float *ds, *dt;
+    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
+    lgr_metric_params mpd;
+    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
+    return lgr_measure_dev(ctx, ds, ns, dt, nt, p, fp, mp, Tgt16, seeds, n_times, runs, out);
+}

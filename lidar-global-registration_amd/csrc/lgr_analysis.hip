@@ -3,6 +3,8 @@
 // Replaces what AlignmentAnalysis::start computes when a ground truth is known (reference src/analysis.cpp:19-24, :30-43, :45-88, :141-185,
 // :187-206, :218-246 and mergeOverlaps, src/common.cpp:558-591): several full-cloud kd-tree passes on the CPU there, one query per point,
 // each independent of the others.  Here every pass is a kernel with a thread per point over a uniform grid (lgr_grid.cuh).
+// lgr_evaluate_gt_batch* judges n estimates against one ground truth: what the ground truth alone decides runs once, the rest per
+// chunk of LGR_GT_BATCH_CHUNK estimates (gt_foot_kernel, gt_batch_kernel, run_points_batch).
 //
 // Declared orders (shared with the CPU statement tests/cpp/analysis_ref.cpp):
 //   * a point moves in PCL's se3 order x * c0 + (y * c1 + (z * c2 + c3)), a normal the same without c3; no contraction;
@@ -16,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <vector>
 
 #include "lgr_grid.cuh"
 #include "lgr_internal.h"
@@ -81,6 +84,95 @@ __global__ __launch_bounds__(AB) void gt_point_kernel(GridDev g, const float4* _
     wave_count(correct, counters + 1);
     wave_count(correct && inl, counters + 2);
     wave_count(inl, counters + 3);
+}
+
+// ---- n estimates against one ground truth (lgr_evaluate_gt_batch_dev): gt_point_kernel split where the estimate enters ----
+constexpr int GTB_CHUNK = LGR_GT_BATCH_CHUNK;
+static_assert(2 * GTB_CHUNK <= GT_SUM_JOBS_WIDE, "two sum jobs per transform of a chunk");
+struct GtBatchMats { float T[16], D[16]; };   // one estimate and its D = T^-1 * G (column-major)
+
+// What gt_point_kernel computes from the ground truth alone, once per batch.  Thread i walks the target's grid for source point i and
+// keeps the foot point on the tangent plane (src/analysis.cpp:69-76) as foot[i] = (q, 1), or (0, 0, 0, 0) where the point is skipped;
+// for correspondence i it writes the correct flag.  counters: [0] overlap_size, [1] correct correspondences.
+__global__ __launch_bounds__(AB) void gt_foot_kernel(GridDev g, const float4* __restrict__ src, int ns, const float4* __restrict__ tgt,
+                                                     const lgr_corr* __restrict__ corr, int c, const GtMats* __restrict__ mats, float thr, float r2,
+                                                     float4* __restrict__ foot, uint8_t* __restrict__ correct_out, int* __restrict__ counters) {
+    __shared__ float G[16];
+    if (threadIdx.x < 16) G[threadIdx.x] = mats->G[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * AB + threadIdx.x;
+    bool counted = false;
+    if (i < ns) {
+        const float4 P = src[(size_t) i * 3];
+        float gx, gy, gz;
+        se3(G, P.x, P.y, P.z, gx, gy, gz);
+        float d2;
+        int j;
+        const int t = nearest_within(g, gx, gy, gz, r2, d2, j);
+        float4 F = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t >= 0) {
+            const float4 Q = g.pxyz[t], N = g.pnrm[t];
+            if (lgr_finite3(N.x, N.y, N.z)) {
+                const float s = dot3(gx - Q.x, gy - Q.y, gz - Q.z, N.x, N.y, N.z);
+                const float qx = gx - s * N.x, qy = gy - s * N.y, qz = gz - s * N.z;   // point_on_plane
+                if (!(__builtin_sqrtf(sq3(gx - qx, gy - qy, gz - qz)) > thr)) {
+                    F = make_float4(qx, qy, qz, 1.f);
+                    counted = true;
+                }
+            }
+        }
+        foot[i] = F;
+    }
+    wave_count(counted, counters + 0);
+    bool correct = false;
+    if (i < c) {
+        const lgr_corr cr = corr[i];
+        const float4 P = src[(size_t) cr.index_query * 3], Q = tgt[(size_t) cr.index_match * 3];
+        float gx, gy, gz;
+        se3(G, P.x, P.y, P.z, gx, gy, gz);
+        const float e = __builtin_sqrtf(sq3(gx - Q.x, gy - Q.y, gz - Q.z));
+        correct = e < cr.threshold;
+        correct_out[i] = correct ? 1 : 0;
+    }
+    wave_count(correct, counters + 1);
+}
+
+// ... and what depends on the estimate, for the m <= GTB_CHUNK estimates of a chunk in one launch: thread i reads source point i and its
+// foot point once and writes, per estimate s, the point-cloud term to terms[(2 s) ns + i] and the overlap term to terms[(2 s + 1) ns + i]
+// (+0 for a skipped point); no grid walk.  With inlier masks (m x c bytes) it counts per s the inliers -> counters[2 s] and the correct
+// inliers -> counters[2 s + 1].
+__global__ __launch_bounds__(AB) void gt_batch_kernel(const float4* __restrict__ src, int ns, const float4* __restrict__ foot,
+                                                      const GtBatchMats* __restrict__ mats, int m, float* __restrict__ terms,
+                                                      const uint8_t* __restrict__ correct, const uint8_t* __restrict__ inl_masks, int c,
+                                                      int* __restrict__ counters) {
+    __shared__ GtBatchMats M[GTB_CHUNK];
+    for (int k = threadIdx.x; k < 32 * m; k += AB) ((float*) M)[k] = ((const float*) mats)[k];
+    __syncthreads();
+    const int i = blockIdx.x * AB + threadIdx.x;
+    if (i < ns) {
+        const float4 P = src[(size_t) i * 3], Q = foot[i];
+        const bool counted = Q.w != 0.f;
+        for (int s = 0; s < m; ++s) {
+            float bx, by, bz;
+            se3(M[s].D, P.x, P.y, P.z, bx, by, bz);
+            terms[(size_t) (2 * s) * ns + i] = sq3(P.x - bx, P.y - by, P.z - bz);   // dist2(p, D p), src/analysis.cpp:26-28
+            float term = 0.f;
+            if (counted) {
+                float ax, ay, az;
+                se3(M[s].T, P.x, P.y, P.z, ax, ay, az);
+                const float d = __builtin_sqrtf(sq3(ax - Q.x, ay - Q.y, az - Q.z));   // src/analysis.cpp:77
+                term = d * d;
+            }
+            terms[(size_t) (2 * s + 1) * ns + i] = term;
+        }
+    }
+    if (!inl_masks) return;   // (uniform)
+    const bool correct_i = i < c && correct[i];
+    for (int s = 0; s < m; ++s) {
+        const bool inl = i < c && inl_masks[(size_t) s * c + i];
+        wave_count(inl, counters + 2 * s);
+        wave_count(inl && correct_i, counters + 2 * s + 1);
+    }
 }
 
 // one pass of mergeOverlaps (src/common.cpp:563-584): compared point i is in the overlap when its nearest reference point within the
@@ -159,15 +251,19 @@ void rot_trans_diff(const float* T1, const float* T2, float* angle, float* tdist
 }
 
 // T, G and D = T^-1 * G (the inverse by lgr_inverse4, the product in f32, each entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3) -> device
+void form_D(const float* T, const float* G, float* D) {
+    float inv[16];
+    lgr_inverse4(T, inv);
+    for (int col = 0; col < 4; ++col)
+        for (int r = 0; r < 4; ++r)
+            D[4 * col + r] = ((inv[r] * G[4 * col] + inv[4 + r] * G[4 * col + 1]) + inv[8 + r] * G[4 * col + 2]) + inv[12 + r] * G[4 * col + 3];
+}
+
 int upload_mats(lgr_ctx* ctx, const float* T16, const float* G16, const GtMats** d_mats, int** d_counters, float** d_sums) {
     GtMats m;
     memcpy(m.T, T16 ? T16 : G16, 64);
     memcpy(m.G, G16, 64);
-    float inv[16];
-    lgr_inverse4(m.T, inv);
-    for (int col = 0; col < 4; ++col)
-        for (int r = 0; r < 4; ++r)
-            m.D[4 * col + r] = ((inv[r] * m.G[4 * col] + inv[4 + r] * m.G[4 * col + 1]) + inv[8 + r] * m.G[4 * col + 2]) + inv[12 + r] * m.G[4 * col + 3];
+    form_D(m.T, m.G, m.D);
     char* d;
     LGR_TRY(lgr_ws_t(ctx, WS_GT_MISC, 512, &d));
     LGR_HIP(ctx, hipMemsetAsync(d + 192, 0, 320, ctx->stream));
@@ -228,6 +324,64 @@ int run_correct(lgr_ctx* ctx, const GtState& st, const float* d_src, const float
                                                         nullptr, nullptr, d_inl, d_correct, st.counters);
     LGR_HIP(ctx, hipGetLastError());
     return read_words(ctx, st.counters + 1, 3, out3);
+}
+
+// run_points for n estimates (quantities 2, 3, 6 and 7's count): ONE grid walk and ONE correct-correspondence pass (gt_foot_kernel), then
+// per chunk of GTB_CHUNK estimates one gt_batch_kernel and one launch of sum jobs; one upload before and one read-back after all chunks.
+// shared: overlap_size and n_correct of every member.  d_inls: n x c bytes or nullptr.
+struct BatchPoints { float pcd_err, overlap_rmse; int n_correct_inl, n_inl; };
+int run_points_batch(lgr_ctx* ctx, const GtState& st, const GridDev& g, const float* d_src, int ns, const float* d_tgt, const lgr_corr* d_corr, int c,
+                     const float* T16s, int n, const float* G16, const uint8_t* d_inls, uint8_t* d_correct, int shared[2], BatchPoints* out) {
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    shared[0] = shared[1] = 0;
+    for (int s = 0; s < n; ++s) out[s] = BatchPoints{nan, nan, 0, 0};
+    if (ns == 0) return LGR_OK;   // (no source point: no correspondence either)
+    // WS_GTB_MISC: the n estimates' matrices, then 4 + 4 n result words: overlap_size, correct correspondences, two unused, per estimate
+    // (inliers, correct inliers), then per estimate (sum of point-cloud terms, sum of overlap terms)
+    std::vector<GtBatchMats> hm((size_t) n);
+    for (int s = 0; s < n; ++s) {
+        memcpy(hm[s].T, T16s + 16 * s, 64);
+        form_D(hm[s].T, G16, hm[s].D);
+    }
+    char* d_misc;
+    const size_t mats_bytes = (size_t) n * sizeof(GtBatchMats), res_words = 4 + 4 * (size_t) n;
+    LGR_TRY(lgr_ws_t(ctx, WS_GTB_MISC, mats_bytes + res_words * 4, &d_misc));
+    const GtBatchMats* d_mats = (const GtBatchMats*) d_misc;
+    int* d_res = (int*) (d_misc + mats_bytes);
+    int* d_cnt = d_res + 4;
+    float* d_sums = (float*) (d_res + 4 + 2 * n);
+    float4* foot;
+    float* terms;
+    LGR_TRY(lgr_ws_t(ctx, WS_GTB_FOOT, (size_t) ns + 1, &foot));
+    LGR_TRY(lgr_ws_t(ctx, WS_GTB_TERMS, (size_t) 2 * GTB_CHUNK * ns + 8, &terms));
+    LGR_HIP(ctx, hipMemsetAsync(d_res, 0, res_words * 4, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(d_misc, hm.data(), mats_bytes, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));   // hm is pageable memory of this frame
+    const int blocks = cdiv(std::max(ns, c), AB);
+    gt_foot_kernel<<<blocks, AB, 0, ctx->stream>>>(g, (const float4*) d_src, ns, (const float4*) d_tgt, d_corr, c, st.mats, st.thr, st.r2, foot, d_correct, d_res);
+    for (int s0 = 0; s0 < n; s0 += GTB_CHUNK) {
+        const int m = std::min(GTB_CHUNK, n - s0);
+        gt_batch_kernel<<<blocks, AB, 0, ctx->stream>>>((const float4*) d_src, ns, foot, d_mats + s0, m, terms, d_correct,
+                                                       d_inls ? d_inls + (size_t) s0 * c : nullptr, c, d_cnt + 2 * s0);
+        GtSumJobsWide jobs{};
+        for (int j = 0; j < 2 * m; ++j) jobs.p[j] = terms + (size_t) j * ns;
+        jobs.n = ns;
+        gt_seqsum_wide_kernel<<<2 * m, AB, 0, ctx->stream>>>(jobs, d_sums + 2 * s0);   // (the next chunk's terms wait for these sums: one stream)
+    }
+    LGR_HIP(ctx, hipGetLastError());
+    void* h;
+    LGR_TRY(lgr_pinned(ctx, res_words * 4, &h));
+    LGR_HIP(ctx, hipMemcpyAsync(h, d_res, res_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int* hi = (const int*) h;
+    const float* hs = (const float*) (hi + 4 + 2 * n);
+    shared[0] = hi[0]; shared[1] = hi[1];
+    for (int s = 0; s < n; ++s) {
+        out[s].pcd_err = std::sqrt(hs[2 * s] / (float) ns);
+        out[s].overlap_rmse = hi[0] ? std::sqrt(hs[2 * s + 1] / (float) hi[0]) : nan;
+        out[s].n_inl = hi[4 + 2 * s]; out[s].n_correct_inl = hi[4 + 2 * s + 1];
+    }
+    return LGR_OK;
 }
 
 int align_source(lgr_ctx* ctx, const GtState& st, const float* d_src, int ns, float** d_aligned) {
@@ -450,6 +604,56 @@ extern "C" int lgr_evaluate_gt_dev(lgr_ctx* ctx, const float* d_src, int ns, con
     return LGR_OK;
 }
 
+// n estimates against one ground truth.  What AlignmentAnalysis::start computes from the ground truth alone -- the overlap set of
+// calculateOverlapRmse (src/analysis.cpp:69-76), the correct correspondences and their uniformity, the normal difference, mergeOverlaps
+// with its two density passes -- runs once; only the last distance of the overlap error (:77), the point-cloud error and the counts
+// of an inlier mask run per estimate, GTB_CHUNK estimates to a launch (run_points_batch).
+extern "C" int lgr_evaluate_gt_batch_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c, const float* T16s,
+                                         int n, const float Tgt16[16], float distance_thr, const int32_t* converged, const uint8_t* d_inlier_masks,
+                                         lgr_gt_eval* out, uint8_t* d_correct_mask) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, n >= 0, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, n <= LGR_GT_BATCH_MAX, LGR_ERR_UNSUPPORTED);
+    GT_CHECK_CLOUDS(ctx);
+    LGR_CHECK(ctx, Tgt16 && c >= 0 && (d_corr || c == 0) && (n == 0 || (T16s && converged && out)), LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, c == 0 || (ns > 0 && nt > 0), LGR_ERR_INVALID_ARG);   // a correspondence needs a point on either side
+    if (n == 0) return LGR_OK;
+    GtState st;
+    LGR_TRY(begin(ctx, nullptr, Tgt16, distance_thr, &st));   // (the state's own estimate is the ground truth: nothing below reads it)
+    LGR_TRY(lgr_check_corr(ctx, d_corr, c, ns, nt));   // before any kernel gathers points through the indices
+    lgr_corr* d_cc = nullptr;
+    uint8_t *d_correct = d_correct_mask, *d_own = nullptr;
+    if (c > 0) LGR_TRY(corr_storage(ctx, c, &d_cc, &d_own));
+    if (!d_correct) d_correct = d_own;
+    GridDev g{};
+    if (ns > 0) LGR_TRY(target_grid(ctx, st, d_tgt, nt, &g));
+    int shared[2];
+    BatchPoints bp[LGR_GT_BATCH_MAX];
+    LGR_TRY(run_points_batch(ctx, st, g, d_src, ns, d_tgt, d_corr, c, T16s, n, Tgt16, c > 0 ? d_inlier_masks : nullptr, d_correct, shared, bp));
+    lgr_gt_eval e;   // the fields every member shares
+    memset(&e, 0, sizeof e);
+    e.overlap_size = shared[0];
+    e.n_correspondences = c; e.n_correct_correspondences = shared[1];
+    float* d_aligned;
+    LGR_TRY(align_source(ctx, st, d_src, ns, &d_aligned));
+    LGR_TRY(run_normal_diff(ctx, st, d_aligned, ns, d_tgt, nt, &e.normal_diff, &e.n_normal_overlap));
+    int n2[2];
+    LGR_TRY(run_merge(ctx, st, g, d_src, d_aligned, ns, d_tgt, nt, nullptr, nullptr, n2, &e.overlap, &e.overlap_area));
+    e.n_overlap_src = n2[0]; e.n_overlap_tgt = n2[1]; e.n_overlap = n2[0] + n2[1];
+    LGR_TRY(run_uniformity(ctx, st, d_src, ns, d_tgt, nt, d_corr, c, d_correct, d_cc, shared[1], Tgt16, &e.corr_uniformity));
+    for (int s = 0; s < n; ++s) {
+        out[s] = e;
+        rot_trans_diff(T16s + 16 * s, Tgt16, &out[s].r_err, &out[s].t_err);
+        out[s].pcd_err = bp[s].pcd_err; out[s].overlap_rmse = bp[s].overlap_rmse;
+        out[s].n_inliers = bp[s].n_inl; out[s].n_correct_inliers = bp[s].n_correct_inl;
+        out[s].converged = converged[s] ? 1 : 0;
+        out[s].converged_and_overlap_ok = (converged[s] && out[s].overlap_rmse < distance_thr) ? 1 : 0;
+    }
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LGR_OK;
+}
+
 namespace {
 // (stage_clouds, host clouds -> the WS_HOST_A / WS_HOST_B slots, is in lgr_pointpass.cuh)
 #define GT_CHECK_HOST_CLOUDS(ctx) LGR_CHECK(ctx, ns >= 0 && nt >= 0 && (src || ns == 0) && (tgt || nt == 0), LGR_ERR_INVALID_ARG)
@@ -513,6 +717,29 @@ extern "C" int lgr_correct_correspondences(lgr_ctx* ctx, const float* src, int n
     LGR_TRY(lgr_correct_correspondences_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, Tgt16, (c && inlier_mask) ? dm : nullptr,
                                             (c && correct_mask) ? dm + c : nullptr, n3));
     if (c && correct_mask) LGR_HIP(ctx, hipMemcpyAsync(correct_mask, dm + c, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LGR_OK;
+}
+
+extern "C" int lgr_evaluate_gt_batch(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float* T16s, int n,
+                                     const float Tgt16[16], float distance_thr, const int32_t* converged, const uint8_t* inlier_masks, lgr_gt_eval* out,
+                                     uint8_t* correct_mask) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, ns >= 0 && nt >= 0 && c >= 0 && n >= 0 && (src || ns == 0) && (tgt || nt == 0) && (corr || c == 0) && Tgt16, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, n <= LGR_GT_BATCH_MAX, LGR_ERR_UNSUPPORTED);
+    float *ds, *dt;
+    lgr_corr* dc;
+    uint8_t* dm;   // the correct mask, then the n inlier masks
+    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) (n + 1) * c + 16, &dm));
+    const bool masks = c && n && inlier_masks;
+    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
+    if (masks) LGR_HIP(ctx, hipMemcpyAsync(dm + c, inlier_masks, (size_t) n * c, hipMemcpyHostToDevice, ctx->stream));
+    LGR_TRY(lgr_evaluate_gt_batch_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, T16s, n, Tgt16, distance_thr, converged, masks ? dm + c : nullptr, out,
+                                      (c && correct_mask) ? dm : nullptr));
+    if (c && n && correct_mask) LGR_HIP(ctx, hipMemcpyAsync(correct_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return LGR_OK;
 }

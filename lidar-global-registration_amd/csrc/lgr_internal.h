@@ -132,6 +132,8 @@ enum {
     WS_HYP_SET, WS_HYP_ITEMS, WS_HYP_FINAL,   // lgr_hypotheses.hip, lgr_ransac_multi_dev
     WS_RF_STATE, WS_RF_TERMS, WS_RF_PAIRS, WS_RF_TRACE,   // lgr_refine.hip
     WS_KNN_PART_A, WS_KNN_PART_B, WS_KNN_FLAG, WS_KNN_CAND_IJ, WS_KNN_CAND_JI,   // lgr_match_knn.hip; the pipeline's candidate lists
+    WS_GTB_MISC, WS_GTB_FOOT, WS_GTB_TERMS,   // lgr_analysis.hip: lgr_evaluate_gt_batch_dev
+    WS_MEASURE_MASKS, WS_MEASURE_W,           // lgr_align.hip: lgr_measure_dev
     WS_COUNT
 };
 static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");

@@ -53,13 +53,13 @@ __device__ __forceinline__ void wave_count(bool f, int* counter) {
 
 // Sequential f32 sums in index order, one workgroup per job: lane 0 adds tile k (one dependent chain, float4 reads from LDS) while waves
 // 1-3 stage tile k + 1.  sq: the term is v * v (the squared smoothed densities of src/analysis.cpp:232).
-constexpr int GT_SUM_TILE = 4096, GT_SUM_JOBS = 4;
+constexpr int GT_SUM_TILE = 4096, GT_SUM_JOBS = 4, GT_SUM_JOBS_WIDE = 16;
 struct GtSumJobs { const float* p[GT_SUM_JOBS]; int n[GT_SUM_JOBS]; int sq[GT_SUM_JOBS]; };
-[[maybe_unused]] __global__ __launch_bounds__(PP_BLOCK) void gt_seqsum_kernel(GtSumJobs jobs, float* __restrict__ out) {
+// the jobs of one chunk of a batched evaluation (lgr_evaluate_gt_batch_dev: two sums per transform), every one over n terms
+struct GtSumJobsWide { const float* p[GT_SUM_JOBS_WIDE]; int n; };
+// one job, by the whole workgroup; the sum is lane 0's return value
+__device__ __forceinline__ float gt_seqsum_job(const float* __restrict__ w, const int n, const bool sq) {
     __shared__ float4 tile[2][GT_SUM_TILE / 4];
-    const float* __restrict__ w = jobs.p[blockIdx.x];
-    const int n = jobs.n[blockIdx.x];
-    const bool sq = jobs.sq[blockIdx.x] != 0;
     float sum = 0.f;
     auto stage = [&](int b, int k, int t0, int stride) {
         float* dst = (float*) tile[k];
@@ -87,6 +87,14 @@ struct GtSumJobs { const float* p[GT_SUM_JOBS]; int n[GT_SUM_JOBS]; int sq[GT_SU
         }
         __syncthreads();
     }
+    return sum;
+}
+[[maybe_unused]] __global__ __launch_bounds__(PP_BLOCK) void gt_seqsum_kernel(GtSumJobs jobs, float* __restrict__ out) {
+    const float sum = gt_seqsum_job(jobs.p[blockIdx.x], jobs.n[blockIdx.x], jobs.sq[blockIdx.x] != 0);
+    if (threadIdx.x == 0) out[blockIdx.x] = sum;
+}
+[[maybe_unused]] __global__ __launch_bounds__(PP_BLOCK) void gt_seqsum_wide_kernel(GtSumJobsWide jobs, float* __restrict__ out) {
+    const float sum = gt_seqsum_job(jobs.p[blockIdx.x], jobs.n, false);
     if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 

@@ -448,6 +448,25 @@ inline Matrix4f chooseBestHypothesis(const PointNCloud::ConstPtr& src, const Poi
     return out;
 }
 
+// descriptor_id / lrf_id -> lgr_feature_params: "fpfh" or "shot" (the struct default, include/common.h:148) or "rops".  The frames matter to
+// SHOT and RoPS only (FPFH never reads lrf_id, include/common.h:366,407)
+inline lgr_feature_params to_feature_abi(const AlignmentParameters& parameters_) {
+    lgr_feature_params f;
+    lgr_default_feature_params(&f);
+    if (parameters_.descriptor_id == "shot") {
+        f.descriptor_id = LGR_DESCRIPTOR_SHOT;
+        if (!lrf_is_default(parameters_.lrf_id)) f.lrf_id = LGR_LRF_GRAVITY;
+    } else if (parameters_.descriptor_id == "rops") {   // gravity frames only (estimateFeatures<RoPS135> above)
+        if (!lrf_is_gravity(parameters_.lrf_id))
+            throw std::runtime_error("lgr: RoPS is built on gravity frames only (lrf '" + parameters_.lrf_id + "' needs a triangulation or the ground truth)");
+        f.descriptor_id = LGR_DESCRIPTOR_ROPS;
+        f.lrf_id = LGR_LRF_GRAVITY;
+    } else if (parameters_.descriptor_id != "fpfh") {
+        throw std::runtime_error("lgr: only descriptors 'fpfh', 'shot' and 'rops' are built on the device path");
+    }
+    return f;
+}
+
 // ---- include/correspondence_search.h:9-28
 class CorrespondenceSearch {
 public:
@@ -463,19 +482,7 @@ public:
         // key points: "iss" or every point (src/common.cpp:657-691; other ids fall back to every point there too)
         // descriptor: "fpfh" or "shot" (the struct default, include/common.h:148).  The frames matter to SHOT only (FPFH never reads lrf_id,
         // include/common.h:366,407): "gt" / "gravity" give LGR_ERR_UNSUPPORTED there, every other id is the default frame.
-        lgr_feature_params f;
-        lgr_default_feature_params(&f);
-        if (parameters_.descriptor_id == "shot") {
-            f.descriptor_id = LGR_DESCRIPTOR_SHOT;
-            if (!lrf_is_default(parameters_.lrf_id)) f.lrf_id = LGR_LRF_GRAVITY;
-        } else if (parameters_.descriptor_id == "rops") {   // gravity frames only (estimateFeatures<RoPS135> above)
-            if (!lrf_is_gravity(parameters_.lrf_id))
-                throw std::runtime_error("lgr: RoPS is built on gravity frames only (lrf '" + parameters_.lrf_id + "' needs a triangulation or the ground truth)");
-            f.descriptor_id = LGR_DESCRIPTOR_ROPS;
-            f.lrf_id = LGR_LRF_GRAVITY;
-        } else if (parameters_.descriptor_id != "fpfh") {
-            throw std::runtime_error("lgr: only descriptors 'fpfh', 'shot' and 'rops' are built on the device path");
-        }
+        lgr_feature_params f = to_feature_abi(parameters_);
         lgr_params a = to_abi(parameters_);
         auto out = std::make_shared<Correspondences>(src_->size());
         int n = 0;
@@ -571,6 +578,50 @@ inline AlignmentResult alignPointClouds(const PointNCloud::ConstPtr& src, const 
     return result;
 }
 
+
+// ---- include/utils.h:68-88: the two aggregates of the measure test type, under the reference's names and in its arithmetic (the mean is a
+//      double sum divided by (T) size; the deviation a T sum of squared differences, the population form; quiet NaN for an empty list)
+template <typename T>
+T calculateMean(const std::vector<T>& values) {
+    if (values.empty()) return (T) std::numeric_limits<float>::quiet_NaN();
+    double sum = 0.0;
+    for (const T& x : values) sum += x;
+    return (T) (sum / (T) values.size());
+}
+template <typename T>
+T calculateStandardDeviation(const std::vector<T>& values) {
+    if (values.empty()) return (T) std::numeric_limits<float>::quiet_NaN();
+    const T mean = calculateMean(values);
+    T squares = 0;
+    for (const T& x : values) {
+        const T d = x - mean;
+        squares += d * d;
+    }
+    return std::sqrt(squares / (T) values.size());
+}
+
+// ---- the loop of measureTestResults (src/main.cpp:338-380) for one parameter set: n_times alignments that differ in the RANSAC seed only
+//      (seeds empty: the ABI's default seed + i), one correspondence search, every run judged against the ground truth (lgr_measure).
+//      No file side effects: the test_measurements.csv row is the caller's (its columns are the measurement's fields in order).
+struct MeasurementResult {
+    lgr_measurement measurement;          // success_rate, mae, sae, mte, ste, mrmse, srmse, mtime, stime
+    std::vector<lgr_measure_run> runs;    // the runs made, in order: seed, lgr_result, lgr_gt_eval
+};
+inline MeasurementResult measureAlignment(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const AlignmentParameters& parameters,
+                                          const Matrix4f& transformation_gt, int n_times = 10, const std::vector<uint64_t>& seeds = {}) {
+    if (parameters.alignment_id == "teaser") throw std::runtime_error("Not implemented: support TEASER");   // src/alignment.cpp:40
+    if (!seeds.empty() && (int) seeds.size() != n_times) throw std::invalid_argument("lgr: measureAlignment takes one seed per run");
+    lgr_params a = to_abi(parameters);
+    a.fix_seed = 0;   // src/main.cpp:339
+    lgr_feature_params f = to_feature_abi(parameters);
+    lgr_metric_params m = to_metric_abi(parameters);
+    MeasurementResult out;
+    out.runs.assign(n_times > 0 ? (size_t) n_times : 1, lgr_measure_run{});
+    check(lgr_measure(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), &a, &f, &m, transformation_gt.data(),
+                      seeds.empty() ? nullptr : seeds.data(), n_times, out.runs.data(), &out.measurement), "measureAlignment");
+    out.runs.resize((size_t) out.measurement.n_times);
+    return out;
+}
 
 // ---- include/analysis.h, include/common.h:294: the ground-truth analysis on the device (declared orders: DESIGN.md section 4).  Each free
 //      function runs its own pass only (the host building blocks of lgr.h); AlignmentAnalysis runs the whole evaluation once.

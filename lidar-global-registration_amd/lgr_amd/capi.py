@@ -208,6 +208,21 @@ class Hypothesis(C.Structure):
         return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
 
 
+GT_BATCH_MAX, GT_BATCH_CHUNK = 64, 8   # LGR_GT_BATCH_MAX, LGR_GT_BATCH_CHUNK
+
+
+class MeasureRun(C.Structure):
+    """lgr_measure_run (include/lgr.h): one seeded run of Context.measure*: its seed, its alignment and its ground-truth evaluation."""
+    _fields_ = [("seed", C.c_uint64), ("result", Result), ("eval", GtEval)]
+
+
+class Measurement(C.Structure):
+    """lgr_measurement (include/lgr.h): the test_measurements.csv columns over the runs (src/main.cpp:324)."""
+    _fields_ = [("n_times", C.c_int32), ("n_success", C.c_int32), ("success_rate", C.c_float), ("mae", C.c_float), ("sae", C.c_float),
+                ("mte", C.c_float), ("ste", C.c_float), ("mrmse", C.c_float), ("srmse", C.c_float), ("mtime", C.c_float), ("stime", C.c_float),
+                ("reserved", C.c_int32 * 5)]
+
+
 class LgrError(RuntimeError):
     pass
 
@@ -225,6 +240,10 @@ ABI_VERSION = 5      # LGR_VERSION of the include/lgr.h these structures mirror
 _lib = load()
 _lib.lgr_last_error.restype = C.c_char_p
 _lib.lgr_last_error.argtypes = [C.c_void_p]
+_lib.lgr_measure_mean.restype = C.c_float
+_lib.lgr_measure_mean.argtypes = [C.c_void_p, C.c_int]
+_lib.lgr_measure_deviation.restype = C.c_float
+_lib.lgr_measure_deviation.argtypes = [C.c_void_p, C.c_int, C.c_float]
 if _lib.lgr_version() != ABI_VERSION:     # a stale liblgr_hip.so would read lgr_params / call lgr_match_last_* with another layout
     raise ImportError(f"{LIB_PATH} has ABI revision {_lib.lgr_version()}, this binding needs {ABI_VERSION}: rebuild it (make -C {_CSRC})")
 
@@ -1029,6 +1048,79 @@ class Context:
                                         C.c_float(distance_thr), int(bool(converged)), _ptr(im), C.byref(out), _ptr(cm)))
         out.correct_mask = cm[:c]
         return out
+
+    @staticmethod
+    def _batch_args(Ts, converged, inlier_masks, c):
+        n = len(Ts)
+        assert inlier_masks is None or tuple(inlier_masks.shape) == (n, c), "one mask of c bytes per transform"
+        assert converged is None or len(converged) == n, "one flag per transform"
+        conv = np.ones(max(n, 1), np.int32)
+        if converged is not None and n:
+            conv[:] = [int(bool(x)) for x in converged]
+        return n, Context._tns16(Ts), conv, (GtEval * max(n, 1))()
+
+    def evaluate_gt_batch(self, src, tgt, corr, Ts, T_gt, distance_thr, converged=None, inlier_masks=None):
+        """lgr_evaluate_gt_batch_dev: the transforms Ts (4x4 each, at most GT_BATCH_MAX) judged against one ground truth.  converged: one flag
+        per transform (None: all true); inlier_masks: [n, c] bytes (numpy or cuda uint8).  Returns a list of GtEval, each with
+        .correct_mask (numpy uint8 [c], the same array for every member)."""
+        torch = self.torch
+        corr = self._corr_dev(corr)
+        c = corr.shape[0]
+        n, buf, conv, out = self._batch_args(Ts, converged, inlier_masks, c)
+        if isinstance(inlier_masks, np.ndarray):
+            inlier_masks = torch.from_numpy(np.ascontiguousarray(inlier_masks, np.uint8)).to(self._dev())
+        elif inlier_masks is not None:
+            inlier_masks = inlier_masks.contiguous()
+        cm = self.empty((max(c, 1),), torch.uint8)
+        self.check(_lib.lgr_evaluate_gt_batch_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), c, _ptr(buf), n, self._T16(T_gt),
+                                                  C.c_float(distance_thr), _ptr(conv), _ptr(inlier_masks), out, _ptr(cm)))
+        self._join()
+        mask = cm[:c].cpu().numpy()
+        res = [out[i] for i in range(n)]
+        for e in res:
+            e.correct_mask = mask
+        return res
+
+    def evaluate_gt_batch_host(self, src, tgt, corr, Ts, T_gt, distance_thr, converged=None, inlier_masks=None):
+        """lgr_evaluate_gt_batch: numpy in, a list of GtEval out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        corr = np.ascontiguousarray(corr)
+        c = corr.shape[0]
+        n, buf, conv, out = self._batch_args(Ts, converged, inlier_masks, c)
+        im = None if inlier_masks is None else np.ascontiguousarray(inlier_masks, np.uint8)
+        cm = np.zeros(max(c, 1), np.uint8)
+        self.check(_lib.lgr_evaluate_gt_batch(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), c, _ptr(buf), n, self._T16(T_gt),
+                                              C.c_float(distance_thr), _ptr(conv), _ptr(im), out, _ptr(cm)))
+        res = [out[i] for i in range(n)]
+        for e in res:
+            e.correct_mask = cm[:c]
+        return res
+
+    # ---- the measure test type (measureTestResults, src/main.cpp:312-382) ------------------------------------
+    @staticmethod
+    def _measure_args(n_times, seeds):
+        n = int(n_times)
+        assert seeds is None or len(seeds) == n, "one seed per run"
+        sd = None if seeds is None else (C.c_uint64 * max(n, 1))(*[int(s) for s in seeds])
+        return n, sd, (MeasureRun * max(n, 1))(), Measurement()
+
+    def measure(self, src, tgt, params, T_gt, n_times=10, seeds=None, descriptor="fpfh", mparams=None):
+        """lgr_measure_dev: n_times seeded alignments of one pair (seeds None: params.seed + i) judged against T_gt in one batch.
+        Returns (Measurement, [MeasureRun] of the runs made)."""
+        n, sd, runs, m = self._measure_args(n_times, seeds)
+        f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+        self.check(_lib.lgr_measure_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
+                                        C.byref(mparams) if mparams is not None else None, self._T16(T_gt), sd, n, runs, C.byref(m)))
+        return m, [runs[i] for i in range(m.n_times)]
+
+    def measure_host(self, src, tgt, params, T_gt, n_times=10, seeds=None, descriptor="fpfh", mparams=None):
+        """lgr_measure: clouds [n, 12] float32 in host memory"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        n, sd, runs, m = self._measure_args(n_times, seeds)
+        f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+        self.check(_lib.lgr_measure(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params), C.byref(f),
+                                    C.byref(mparams) if mparams is not None else None, self._T16(T_gt), sd, n, runs, C.byref(m)))
+        return m, [runs[i] for i in range(m.n_times)]
 
     def overlap_rmse(self, src, tgt, T, T_gt, distance_thr):
         """lgr_overlap_rmse_dev -> (overlap_rmse, overlap_size, pcd_err, idx numpy int32 [ns]: the target point a source point was measured

@@ -277,3 +277,15 @@ def metrics_row(testname, found, gt):
     for m_corr, m_icp, n_corr, n_icp in (found, gt):
         out += [_g(float(m_corr)), _g(float(m_icp)), _g(int(n_corr)), _g(int(n_icp))]
     return ",".join(out)
+
+
+MEASUREMENTS_HEADER = "testname,success_rate,mae,sae,mte,ste,mrmse,srmse,mtime,stime"
+MEASUREMENTS_FIELDS = ("success_rate", "mae", "sae", "mte", "ste", "mrmse", "srmse", "mtime", "stime")
+
+
+def measurements_row(name, m):
+    """One row of test_measurements.csv as measureTestResults streams it (src/main.cpp:324,376-380): the name, the success rate, then mean
+    and deviation of the rotation, translation and overlap error and of the running time (floats as ostream << float prints them).
+    m: a capi.Measurement, or any object or mapping with those nine fields."""
+    get = (lambda k: m[k]) if isinstance(m, dict) else (lambda k: getattr(m, k))
+    return ",".join([name] + [_g(float(get(k))) for k in MEASUREMENTS_FIELDS])

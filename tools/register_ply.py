@@ -5,6 +5,7 @@
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
                                  [--debug-dir DIR] [--hypotheses N] [--refine N]
+                                 [--measure N [--measure-seed S0] [--measurements test_measurements.csv]]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
@@ -25,6 +26,11 @@ With --refine N: after everything above, the found transformation goes through u
 refit, evaluation, while the metric rises) under the run's score -- and the run's weights under weighted_closest_plane; the evaluation before
 and after is printed, the refined transformation is appended to --out as a second row named <name>_refined, and with --ground-truth it is
 analysed like the first (a second results.csv row under that name).
+With --measure N (needs --ground-truth): the reference's `measure` test type (measureTestResults, src/main.cpp:312-382) through lgr_measure --
+N alignments that differ in the RANSAC seed only (S0, S0 + 1, ...; S0 defaults to the profile's seed), one correspondence search for all of
+them, all judged against the ground truth in one batch; one line per run, then the aggregate row, appended to --measurements when given
+(with the header when the file is new).  With --hypotheses N and --ground-truth the members of the set are judged the same way
+(lgr_evaluate_gt_batch) and their rotation, translation and overlap error are listed.
 """
 import argparse
 import os
@@ -62,7 +68,15 @@ def main():
     ap.add_argument("--hypotheses", type=int, default=0, metavar="N",
                     help="also keep the set of up to N distinct hypotheses (ransac with uniformity / correspondences) and list its members")
     ap.add_argument("--refine", type=int, default=0, metavar="N", help="refine the result by up to N dense closest-plane steps (lgr_refine_plane)")
+    ap.add_argument("--measure", type=int, default=0, metavar="N",
+                    help="the measure test type: N seeded runs judged against --ground-truth, and their test_measurements.csv row")
+    ap.add_argument("--measure-seed", type=int, default=None, metavar="S0", help="seed of the first run (default: the profile's seed); run i uses S0 + i")
+    ap.add_argument("--measurements", default=None, metavar="PATH", help="test_measurements.csv the aggregate row is appended to (with --measure)")
     a = ap.parse_args()
+    if a.measure and not a.ground_truth:
+        ap.error("--measure needs --ground-truth")
+    if not 0 <= a.measure <= 64:
+        ap.error("--measure takes 1 .. 64 runs")
     if not 1 <= a.randomness <= 8:
         ap.error("--randomness takes 1 .. 8")
     if not 0 <= a.refine <= 1024:
@@ -110,6 +124,38 @@ def main():
         hypotheses(ctx, capi, formats, a, p, clouds, lrf)
     if a.refine:
         refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
+    if a.measure:
+        measure(ctx, capi, formats, a, p, clouds, name, lrf)
+
+
+def measure(ctx, capi, formats, a, p, clouds, name, lrf):
+    """measureTestResults: the seeded runs, one line each, and the aggregate row"""
+    import numpy as np
+    T_gt = formats.get_transformation(a.ground_truth[0], a.ground_truth[1])
+    s0 = p.seed if a.measure_seed is None else a.measure_seed
+    mp = capi.metric_params(a.weight) if a.metric == "weighted_closest_plane" else None
+    t = time.perf_counter()
+    m, runs = ctx.measure(clouds[0], clouds[1], p, T_gt, n_times=a.measure, seeds=[s0 + i for i in range(a.measure)],
+                          descriptor=capi.feature_params(a.descriptor, lrf_id=lrf), mparams=mp)
+    dt = time.perf_counter() - t
+    deg = 180.0 / np.pi
+    print(f"\nmeasured {m.n_times} runs in {1e3 * dt:.1f} ms (one correspondence search: {1e3 * runs[0].result.time_cs:.1f} ms):")
+    print("\trun\tseed\tconverged\tsuccess\tinliers\tr_err (deg)\tt_err\toverlap_rmse\ttime (s)")
+    for i, r in enumerate(runs):
+        e = r.eval
+        print(f"\t{i}\t{r.seed}\t{r.result.converged}\t{e.converged_and_overlap_ok}\t{r.result.n_inliers}\t{deg * e.r_err:.7f}\t{e.t_err:.7f}\t{e.overlap_rmse:.7f}"
+              f"\t{r.result.time_cs + r.result.time_te:.6f}")
+    row = formats.measurements_row(name + "_measure", m)
+    print(f"success: {m.n_success}/{m.n_times}")
+    print(formats.MEASUREMENTS_HEADER)
+    print(row)
+    if a.measurements:
+        new = not os.path.exists(a.measurements)
+        with open(a.measurements, "a") as f:
+            if new:
+                f.write(formats.MEASUREMENTS_HEADER + "\n")
+            f.write(row + "\n")
+        print(f"appended the measurement row to {a.measurements}" + (" (new file)" if new else ""))
 
 
 def refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
@@ -142,6 +188,17 @@ def hypotheses(ctx, capi, formats, a, p, clouds, lrf):
     print("\tid\titeration\tloop_metric\tmetric\tinliers\tuniformity\tchosen")
     for k, h in enumerate(hyps):
         print(f"\t{k}\t{h.iteration}\t{h.loop_metric:.6f}\t{h.metric:.6f}\t{h.n_inliers}\t{h.uniformity:.6f}\t{'*' if k == best else ''}")
+    if a.ground_truth and hyps:
+        # every member against the ground truth: what the ground truth alone decides is computed once per batch (lgr_evaluate_gt_batch)
+        import numpy as np
+        T_gt = formats.get_transformation(a.ground_truth[0], a.ground_truth[1])
+        evals = []
+        for k0 in range(0, len(hyps), capi.GT_BATCH_MAX):
+            part = hyps[k0:k0 + capi.GT_BATCH_MAX]
+            evals += ctx.evaluate_gt_batch(src, tgt, corr, [h.matrix() for h in part], T_gt, p.distance_thr, [h.converged for h in part])
+        print("\tid\tr_err (deg)\tt_err\toverlap_rmse\tsuccess\tchosen")
+        for k, e in enumerate(evals):
+            print(f"\thypothesis {k} analysis:\t{180.0 / np.pi * e.r_err:.7f}\t{e.t_err:.7f}\t{e.overlap_rmse:.7f}\t{e.converged_and_overlap_ok}\t{'*' if k == best else ''}")
     if a.debug_dir and hyps:
         o = ctx.compare_overlaps(src, tgt, [h.matrix() for h in hyps], p.distance_thr, with_masks=False)
         for k in range(len(hyps)):
