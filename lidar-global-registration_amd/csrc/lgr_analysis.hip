@@ -655,7 +655,7 @@ extern "C" int lgr_evaluate_gt_batch_dev(lgr_ctx* ctx, const float* d_src, int n
 }
 
 namespace {
-// (stage_clouds, host clouds -> the WS_HOST_A / WS_HOST_B slots, is in lgr_pointpass.cuh)
+// (stage_clouds and stage_problem, host clouds and correspondences -> the WS_HOST_A / B / C slots, are in lgr_pointpass.cuh)
 #define GT_CHECK_HOST_CLOUDS(ctx) LGR_CHECK(ctx, ns >= 0 && nt >= 0 && (src || ns == 0) && (tgt || nt == 0), LGR_ERR_INVALID_ARG)
 }  // namespace
 
@@ -709,10 +709,8 @@ extern "C" int lgr_correct_correspondences(lgr_ctx* ctx, const float* src, int n
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
+    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) 2 * c + 16, &dm));
-    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
     if (c && inlier_mask) LGR_HIP(ctx, hipMemcpyAsync(dm, inlier_mask, (size_t) c, hipMemcpyHostToDevice, ctx->stream));
     LGR_TRY(lgr_correct_correspondences_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, Tgt16, (c && inlier_mask) ? dm : nullptr,
                                             (c && correct_mask) ? dm + c : nullptr, n3));
@@ -731,11 +729,9 @@ extern "C" int lgr_evaluate_gt_batch(lgr_ctx* ctx, const float* src, int ns, con
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm;   // the correct mask, then the n inlier masks
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
+    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) (n + 1) * c + 16, &dm));
     const bool masks = c && n && inlier_masks;
-    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
     if (masks) LGR_HIP(ctx, hipMemcpyAsync(dm + c, inlier_masks, (size_t) n * c, hipMemcpyHostToDevice, ctx->stream));
     LGR_TRY(lgr_evaluate_gt_batch_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, T16s, n, Tgt16, distance_thr, converged, masks ? dm + c : nullptr, out,
                                       (c && correct_mask) ? dm : nullptr));
@@ -753,10 +749,8 @@ extern "C" int lgr_evaluate_gt(lgr_ctx* ctx, const float* src, int ns, const flo
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
+    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) 2 * c + 16, &dm));
-    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
     if (c && inlier_mask) LGR_HIP(ctx, hipMemcpyAsync(dm, inlier_mask, (size_t) c, hipMemcpyHostToDevice, ctx->stream));
     LGR_TRY(lgr_evaluate_gt_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, T16, Tgt16, distance_thr, converged,
                                 (c && inlier_mask) ? dm : nullptr, out, (c && correct_mask) ? dm + c : nullptr));

@@ -166,6 +166,25 @@ __device__ __forceinline__ void lgr_visit27(const GridDev& g, float qx, float qy
         }
 }
 
+// nearest grid point within r2 of p: sorted position or -1.  The candidate loop has no branch on the candidate: every lane offers every
+// candidate of its cells and keeps the better one by selects, so a wave never serialises on which lanes found something.
+__device__ __forceinline__ int nearest_within(const GridDev& g, float px, float py, float pz, float r2, float& best_d2, int& best_idx) {
+    int nn = -1, nn_t = -1;
+    float best = 0.f;
+    if (g.n > 0 && lgr_finite3(px, py, pz))
+        lgr_visit27(g, px, py, pz, [&](int t, const float4& Q) {
+            const float d2 = lgr_dist2(px, py, pz, Q.x, Q.y, Q.z);
+            const int qi = __float_as_int(Q.w);
+            const bool take = (d2 < r2) && (nn < 0 || d2 < best || (d2 == best && qi < nn));
+            nn = take ? qi : nn;
+            nn_t = take ? t : nn_t;
+            best = take ? d2 : best;
+        });
+    best_d2 = best;
+    best_idx = nn;
+    return nn_t;
+}
+
 // ---- exact nearest neighbour whose cost does not depend on where the query lies (lgr_debug.hip) ----
 // lgr_knn_query centres its rings on the query's own cell: right for a query inside the cloud, cubic in the separation (and an
 // out-of-range cell index) for one far outside it.  Here the search descends the grid itself.  cell_start is an exclusive prefix sum over

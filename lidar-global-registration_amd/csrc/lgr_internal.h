@@ -303,6 +303,17 @@ struct lgr_plane_dev {
     float w_sum = 0.f, w_gate = 0.f;
 };
 int lgr_plane_setup(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, uint64_t seed, lgr_plane_dev* out);
+// What every user of the metric sets up over the target: the inlier threshold -- the caller's, or when that is not positive the target's
+// 0.8 density quantile (ClosestPlaneMetricEstimator::setTargetCloud) --, the search radius 2 x threshold (DIST_TO_PLANE_COEFFICIENT),
+// LGR_ERR_INVALID_ARG unless 0 < radius <= radius_max, and the grid over the target in WS_GRID_C with cell 1.001 x radius.
+struct lgr_plane_target { float thr, radius; GridDev g; };
+int lgr_plane_target_setup(lgr_ctx* ctx, const float* d_tgt, int nt, float threshold, float radius_max, lgr_plane_target* out);
+// the figures of a dense evaluation from its two sequential sums and its inlier count; denom: (float) ns, with weights weights_sum.
+// score / ((sparse_ ? SPARSE_POINTS_FRACTION : 1.f) * denom): the macro is a double, so is everything after the ternary (src/metric.cpp:199)
+__host__ __device__ inline void lgr_plane_figures(float score, float sqsum, int n, float denom, float* rmse, float* metric) {
+    *rmse = n ? sqrtf(sqsum / (float) n) : 3.4028234663852886e38f;   // FLT_MAX without an inlier
+    *metric = (float) ((double) score / (1.0 * (double) denom));
+}
 // hypothesis h in [0, nh): transform d_Ts + 16 * off, Philox counter = counter_base + off, off = d_list ? d_list[h] : h.
 // d_rmse / d_pairs (+ d_n_pairs) optional; pairs = (source index, nearest target index) of the inliers, unordered.
 // Gate (RANSAC batches): best_prev = best metric of the earlier batches, record_prev = their record inlier count (INT_MAX when the plane

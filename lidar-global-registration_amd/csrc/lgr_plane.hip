@@ -4,7 +4,8 @@
 // RANSAC loop uses it: always on a sparse 1 % subset of the source cloud (sparse = true,
 // src/sac_prerejective_omp.cpp:109).  For every subset point: transform, nearest target point within
 // 2 x inlier_threshold (inlier_threshold = calculatePointCloudDensity(tgt)), distance to its tangent plane, inlier when
-// below the threshold; metric = score / (0.01 |src|).
+// below the threshold; metric = score / (0.01 |src|).  The move, the distance and the score value are lgr_plane_point.cuh's, the ones the
+// dense evaluation uses; the subset, the sums and the gate below are this file's own.
 //
 // Canonical choices shared with the oracle (oracle/src/orc_ransac.cpp, plane_eval): the reference draws the subset
 // from the thread's mt19937 stream, here draw j of hypothesis `counter` is Philox4x32-10(counter, j / 4, 0x5A17, 0)[j % 4]
@@ -15,10 +16,12 @@
 // One 256-thread workgroup per hypothesis (persistent grid): phase A claims the subset, phase B evaluates it
 // (27-cell scan of a uniform grid over the target with cell = 1.001 x radius) and releases the bits.
 #include <algorithm>
+#include <limits>
 
 #include "lgr_grid.cuh"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
+#include "lgr_plane_point.cuh"
 
 namespace {
 
@@ -99,16 +102,14 @@ __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __res
             const int idx = claimed[j];
             atomicAnd(&visited[idx >> 5], ~(1u << (idx & 31)));
             const float* s = src + (size_t) idx * 12;
-            const float sx = s[0], sy = s[1], sz = s[2];
-            // Eigen Matrix4f * Vector4f on SSE: ((c0 x + c1 y) + c2 z) + c3
-            const float px = ((Tr[0] * sx + Tr[4] * sy) + Tr[8] * sz) + Tr[12];
-            const float py = ((Tr[1] * sx + Tr[5] * sy) + Tr[9] * sz) + Tr[13];
-            const float pz = ((Tr[2] * sx + Tr[6] * sy) + Tr[10] * sz) + Tr[14];
+            float px, py, pz;
+            plane_move(Tr, s[0], s[1], s[2], px, py, pz);
             if (!lgr_finite3(px, py, pz)) continue;
             int nn = -1, nn_t = -1;
             float best = 0.f;
-            // the 27 cells around the moved point, (z, y) row by row (three x-cells are contiguous in memory); four candidate loads are
-            // issued before the first compare -- one load per candidate, each waited for, was ~150 dependent round trips per point
+            // a hand copy of lgr_visit27's walk (lgr_grid.cuh), whose x-range test sits outside the row loops here: the 27 cells around the
+            // moved point, (z, y) row by row (three x-cells are contiguous in memory); four candidate loads are issued before the first
+            // compare -- one load per candidate, each waited for, was ~150 dependent round trips per point
             auto offer = [&](int t, const float4& Q) {
                 float d2 = lgr_dist2(px, py, pz, Q.x, Q.y, Q.z);
                 if (!(d2 < r2)) return;
@@ -136,14 +137,11 @@ __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __res
             }
             if (nn < 0) continue;
             const float4 Q = g.pxyz[nn_t], N = g.pnrm[nn_t];
-            const float dist = fabsf((N.x * (Q.x - px) + N.y * (Q.y - py)) + N.z * (Q.z - pz));
+            const float dist = plane_dist(Q, N, px, py, pz);
             if (!(dist < thr)) continue;
             ++cnt;
-            float value = 1.f;
-            if (score_id == LGR_SCORE_MAE) value = fabsf(dist - thr) / thr;
-            else if (score_id == LGR_SCORE_MSE) value = (dist - thr) * (dist - thr) / (thr * thr);
-            else if (score_id == LGR_SCORE_EXP) value = lgr_expf(-dist * dist / (2 * thr * thr));
-            if constexpr (W) value *= w[idx];   // calculateScore: value *= weights[inlier.index_query]
+            float value = plane_score(dist, thr, score_id);
+            if constexpr (W) value *= w[idx];
             sc += (long long) ((double) value * 4294967296.0);
             const float rel = dist / thr;
             sq += (long long) ((double) (rel * rel) * 4294967296.0);
@@ -194,15 +192,22 @@ __global__ __launch_bounds__(PB) void plane_kernel(GridDev g, const float* __res
 
 }  // namespace
 
+int lgr_plane_target_setup(lgr_ctx* ctx, const float* d_tgt, int nt, float threshold, float radius_max, lgr_plane_target* out) {
+    out->thr = threshold;
+    if (!(out->thr > 0.f)) LGR_TRY(lgr_cloud_density_dev(ctx, d_tgt, nt, 0.8f, &out->thr));
+    out->radius = 2 * out->thr;
+    LGR_CHECK(ctx, out->radius > 0.f && out->radius <= radius_max, LGR_ERR_INVALID_ARG);
+    LGR_TRY(lgr_grid_build(ctx, WS_GRID_C, d_tgt, nt, out->radius * 1.001f, 0.f, &out->g));
+    return LGR_OK;
+}
+
 int lgr_plane_setup(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, uint64_t seed, lgr_plane_dev* out) {
     LGR_CHECK(ctx, ns > 0 && nt > 1, LGR_ERR_INVALID_ARG);
-    float density = 0.f;
-    LGR_TRY(lgr_cloud_density_dev(ctx, d_tgt, nt, 0.8f, &density));   // ClosestPlaneMetricEstimator::setTargetCloud
-    out->thr = density;
-    const float radius = 2 * out->thr;                                 // DIST_TO_PLANE_COEFFICIENT * inlier_threshold
-    out->r2 = radius * radius;
-    LGR_CHECK(ctx, radius > 0.f, LGR_ERR_INVALID_ARG);
-    LGR_TRY(lgr_grid_build(ctx, WS_GRID_C, d_tgt, nt, radius * 1.001f, 0.f, &out->g));
+    lgr_plane_target pt;
+    LGR_TRY(lgr_plane_target_setup(ctx, d_tgt, nt, 0.f, std::numeric_limits<float>::infinity(), &pt));   // (any positive radius)
+    out->thr = pt.thr;
+    out->r2 = pt.radius * pt.radius;
+    out->g = pt.g;
     out->n_sp = (int) (0.01 * (float) ns);
     out->ns = ns; out->d_src = d_src; out->seed = seed;
     out->n_wg = std::max(1, 8 * ctx->n_cu);   // resident workgroups: the evaluation is a chain of dependent gathers, more waves in flight hide them

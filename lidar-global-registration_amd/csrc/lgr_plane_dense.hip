@@ -6,36 +6,27 @@
 // with one kd-tree radius search per point there.  Here one thread per source point walks the 27 cells of a uniform grid over the target
 // (lgr_grid.cuh, cell = 1.001 x radius) and writes its terms; the two float sums are then taken in the reference's loop order.
 //
-// Declared orders (shared with the CPU statement tests/cpp/plane_dense_ref.cpp).  Every per-point expression is the
-// one plane_kernel (lgr_plane.hip) evaluates for a point of its sparse subset, so a point gets the same bits from either:
-//   * the moved point is ((c0 x + c1 y) + c2 z) + c3 per row (Eigen Matrix4f * Vector4f); a non-finite moved point is skipped;
-//   * the nearest target within r = 2 x threshold: strict d2 < r * r with lgr_dist2, the smallest squared distance, then the lowest
-//     index; non-finite target points never answer;
-//   * dist = |(N.x (Q.x - px) + N.y (Q.y - py)) + N.z (Q.z - pz)|, an inlier iff dist < threshold (a NaN distance is none);
-//   * the value of an inlier is plane_kernel's score expression (lgr_expf for EXP), times w[idx] in f32 under weights;
+// Declared orders (shared with the CPU statement tests/cpp/plane_dense_ref.cpp).  The per-point rules -- move, nearest
+// target, plane distance, inlier test, value -- are lgr_plane_point.cuh's, shared with plane_kernel (lgr_plane.hip).  This file's own:
 //   * score and the squared-error sum are SEQUENTIAL f32 sums in ascending source index -- the reference's loop -- not the sparse
 //     kernel's 2^-32 fixed-point sums.  Every point writes its two terms to a buffer first, a point that is no inlier writes +0: a
 //     running f32 sum that started at +0 is never -0 (x + (-x) and (+0) + (-0) both round to +0), and adding +0 to anything but -0
 //     returns it unchanged, whatever the signs of the other terms -- so the sum over all points is the sum over the inliers;
-//   * rmse = sqrtf(sum / (float) n_inliers), FLT_MAX without an inlier; metric = (float) ((double) score / (1.0 * (double) (float) ns))
-//     (SPARSE_POINTS_FRACTION is a double macro: the ternary of src/metric.cpp:199 and the division are in double), with weights the
-//     denominator is (double) weights_sum;
+//   * rmse and metric are lgr_plane_figures (lgr_internal.h) with the denominator (float) ns, with weights weights_sum;
 //   * the inlier list is {source index, nearest target index, dist, threshold} in ascending source index (flags -> exclusive scan).
 #include <algorithm>
-#include <cfloat>
-#include <cmath>
 
 #include "lgr_grid.cuh"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
+#include "lgr_plane_point.cuh"
 #include "lgr_pointpass.cuh"
 
 namespace {
 
 struct PdT { float m[16]; };   // the transform, column-major, as a kernel argument
 
-// pass 1: thread i handles source point i.  No branch inside the candidate loop (nearest_within, lgr_pointpass.cuh); what follows the
-// walk is a handful of selects, so the lanes of a wave only differ in how many candidates their cells hold.
+// pass 1: thread i handles source point i (plane_dense_point) and writes its nearest target, distance, terms and flag
 template <bool W>
 __global__ __launch_bounds__(PP_BLOCK) void plane_dense_kernel(GridDev g, const float4* __restrict__ src, int ns, PdT T, float thr, float r2, int score_id,
                                                               const float* __restrict__ w, int32_t* __restrict__ nn_out, float* __restrict__ dist_out,
@@ -44,32 +35,12 @@ __global__ __launch_bounds__(PP_BLOCK) void plane_dense_kernel(GridDev g, const 
     const int i = blockIdx.x * PP_BLOCK + threadIdx.x;
     bool inl = false;
     if (i < ns) {
-        const float4 P = src[(size_t) i * 3];
-        // Eigen Matrix4f * Vector4f on SSE: ((c0 x + c1 y) + c2 z) + c3
-        const float px = ((T.m[0] * P.x + T.m[4] * P.y) + T.m[8] * P.z) + T.m[12];
-        const float py = ((T.m[1] * P.x + T.m[5] * P.y) + T.m[9] * P.z) + T.m[13];
-        const float pz = ((T.m[2] * P.x + T.m[6] * P.y) + T.m[10] * P.z) + T.m[14];
-        float d2;
-        int j;
-        const int t = nearest_within(g, px, py, pz, r2, d2, j);   // (a non-finite moved point walks nothing: -1)
-        float dist = 0.f, value = 0.f, sq = 0.f;
-        if (t >= 0) {
-            const float4 Q = g.pxyz[t], N = g.pnrm[t];
-            dist = fabsf((N.x * (Q.x - px) + N.y * (Q.y - py)) + N.z * (Q.z - pz));
-            inl = dist < thr;
-            if (inl) {
-                value = 1.f;
-                if (score_id == LGR_SCORE_MAE) value = fabsf(dist - thr) / thr;
-                else if (score_id == LGR_SCORE_MSE) value = (dist - thr) * (dist - thr) / (thr * thr);
-                else if (score_id == LGR_SCORE_EXP) value = lgr_expf(-dist * dist / (2 * thr * thr));
-                if constexpr (W) value *= w[i];   // calculateScore: value *= weights[inlier.index_query]
-                sq = dist * dist;
-            }
-        }
-        nn_out[i] = j;
-        dist_out[i] = dist;
-        term_val[i] = inl ? value : 0.f;
-        term_sq[i] = inl ? sq : 0.f;
+        const PlanePoint p = plane_dense_point<W>(g, src[(size_t) i * 3], T.m, thr, r2, score_id, w, i);
+        inl = p.inl;
+        nn_out[i] = p.j;
+        dist_out[i] = p.dist;
+        term_val[i] = p.value;
+        term_sq[i] = p.sq;
         flags[i] = inl ? 1 : 0;
     }
     wave_count(inl, counter);
@@ -88,12 +59,10 @@ int dense_eval(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int
     const float* d_w = nullptr;
     float w_sum = 0.f, w_gate = 0.f;
     if (mp) LGR_TRY(lgr_weights_prepare(ctx, d_src, ns, mp, &d_w, &w_sum, &w_gate));   // harris / tomasi: LGR_ERR_UNSUPPORTED
-    float thr = inlier_threshold;
-    if (!(thr > 0.f)) LGR_TRY(lgr_cloud_density_dev(ctx, d_tgt, nt, 0.8f, &thr));   // ClosestPlaneMetricEstimator::setTargetCloud
-    const float radius = 2 * thr;                                                    // DIST_TO_PLANE_COEFFICIENT * inlier_threshold
-    LGR_CHECK(ctx, radius > 0.f && radius <= 2e18f, LGR_ERR_INVALID_ARG);
-    GridDev g{};
-    LGR_TRY(lgr_grid_build(ctx, WS_GRID_C, d_tgt, nt, radius * 1.001f, 0.f, &g));
+    lgr_plane_target pt;
+    LGR_TRY(lgr_plane_target_setup(ctx, d_tgt, nt, inlier_threshold, 2e18f, &pt));
+    const float thr = pt.thr, radius = pt.radius;
+    const GridDev& g = pt.g;
     const size_t nn = ((size_t) ns + 63) & ~(size_t) 63;
     int32_t* buf;
     char* misc;
@@ -134,9 +103,7 @@ int dense_eval(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int
     out->n_inliers = n_inl;
     out->threshold = thr;
     out->score = s2[0];
-    out->rmse = n_inl ? std::sqrt(s2[1] / (float) n_inl) : FLT_MAX;
-    // score / ((sparse_ ? SPARSE_POINTS_FRACTION : 1.f) * (float) src_->size()): the macro is a double, so is everything after the ternary
-    out->metric = (float) ((double) s2[0] / (1.0 * (double) (d_w ? w_sum : (float) ns)));
+    lgr_plane_figures(s2[0], s2[1], n_inl, d_w ? w_sum : (float) ns, &out->rmse, &out->metric);
     return LGR_OK;
 }
 
@@ -201,16 +168,6 @@ extern "C" int lgr_analysis_metric_dev(lgr_ctx* ctx, const float* d_src, int ns,
     return LGR_OK;
 }
 
-namespace {
-int stage_pair(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, float** ds, float** dt) {
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12 + 4, ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12 + 4, dt));
-    LGR_HIP(ctx, hipMemcpyAsync(*ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(*dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    return LGR_OK;
-}
-}  // namespace
-
 extern "C" int lgr_evaluate_plane_dense(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T16[16], int score_id,
                                         const lgr_metric_params* mp, float inlier_threshold, lgr_plane_dense_eval* out, lgr_corr* inliers, int32_t* nn) {
     lgr_turn turn__(ctx);
@@ -220,7 +177,7 @@ extern "C" int lgr_evaluate_plane_dense(lgr_ctx* ctx, const float* src, int ns, 
     float *ds, *dt;
     lgr_corr* di = nullptr;
     int32_t* dn = nullptr;
-    LGR_TRY(stage_pair(ctx, src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     lgr_metric_params staged;
     LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &staged));
     if (inliers) LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) ns + 1, &di));
@@ -243,11 +200,9 @@ extern "C" int lgr_analysis_metric(lgr_ctx* ctx, const float* src, int ns, const
     float *ds, *dt;
     lgr_corr *dc, *di = nullptr;
     uint8_t* dm = nullptr;
-    LGR_TRY(stage_pair(ctx, src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
     lgr_metric_params staged;
     LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &staged));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, &dc));
-    if (c) LGR_HIP(ctx, hipMemcpyAsync(dc, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
     if (inlier_mask && !plane && c) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) c + 16, &dm));
     if (inliers && plane) LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) ns + 1, &di));
     LGR_TRY(lgr_analysis_metric_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, T16, Tgt16, metric_id, score_id, mp, out, dm, di));

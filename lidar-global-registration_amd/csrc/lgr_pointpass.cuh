@@ -1,5 +1,5 @@
 // lgr_pointpass.cuh -- what the thread-per-point passes of lgr_analysis.hip, lgr_plane_dense.hip and lgr_debug.hip share: PCL's point
-// moves, the branch-free nearest-within-r walk, the wave-aggregated counter, the sequential f32 sum jobs, the move of a whole cloud and
+// moves, the wave-aggregated counter, the sequential f32 sum jobs, the move of a whole cloud and
 // the compaction of an overlap cloud (flags, their exclusive scan, the kept rows).  Its host helpers -- the staging of host clouds and
 // correspondences (stage_clouds, stage_problem) and the scan of 0 / 1 flags (pp_scan_flags) -- also serve lgr_ransac.hip, lgr_gror.hip and lgr_align.hip.  Everything here sits in an unnamed namespace: each translation unit gets its own copy of the kernels.
 #pragma once
@@ -26,25 +26,6 @@ __device__ __forceinline__ void so3(const float* __restrict__ M, float x, float 
 __device__ __forceinline__ float sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 __device__ __forceinline__ bool fin(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
-
-// nearest grid point within r2 of p: sorted position or -1.  The candidate loop has no branch on the candidate: every lane offers every
-// candidate of its cells and keeps the better one by selects, so a wave never serialises on which lanes found something.
-__device__ __forceinline__ int nearest_within(const GridDev& g, float px, float py, float pz, float r2, float& best_d2, int& best_idx) {
-    int nn = -1, nn_t = -1;
-    float best = 0.f;
-    if (g.n > 0 && lgr_finite3(px, py, pz))
-        lgr_visit27(g, px, py, pz, [&](int t, const float4& Q) {
-            const float d2 = lgr_dist2(px, py, pz, Q.x, Q.y, Q.z);
-            const int qi = __float_as_int(Q.w);
-            const bool take = (d2 < r2) && (nn < 0 || d2 < best || (d2 == best && qi < nn));
-            nn = take ? qi : nn;
-            nn_t = take ? t : nn_t;
-            best = take ? d2 : best;
-        });
-    best_d2 = best;
-    best_idx = nn;
-    return nn_t;
-}
 
 __device__ __forceinline__ void wave_count(bool f, int* counter) {
     const unsigned long long m = __ballot(f);

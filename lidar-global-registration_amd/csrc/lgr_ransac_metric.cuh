@@ -229,9 +229,10 @@ __device__ __forceinline__ void metric_body(const int tid, const int wg, const i
         }
     }
     // The score and the rmse are sequential float sums over the inliers in correspondence order (src/metric.cpp:55-81, 147-155); their TERMS are not:
-    // the whole workgroup turns the list's (distance, threshold) entries into (distance^2, score term) in place -- the same expressions, by another
-    // thread -- and one lane adds them up with its reads running sixteen terms ahead of the two dependent chains.  (Round 5: as one loop on one lane,
-    // every term waited for its own global load and its division.)
+    // the whole workgroup turns the list's (distance, threshold) entries into (distance^2, score term) in place -- plane_score's expressions
+    // (lgr_plane_point.cuh) with (d, t) for (dist, thr), by another thread; a copy, because the call changed the code of metric_kernel and
+    // rs_resident_kernel -- and one lane adds them up with its reads running sixteen terms ahead of the two dependent chains.  (Round 5: as
+    // one loop on one lane, every term waited for its own global load and its division.)
     if (lst && (!uni || rmse_out)) {   // (workgroup uniform)
         for (int j = tid; j < n_inl; j += MB) {
             const float2 dt = lst[j];

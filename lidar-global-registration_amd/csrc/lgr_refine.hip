@@ -3,7 +3,7 @@
 // The step is the one the reference's final block takes once (src/sac_prerejective_omp.cpp:270-291): the closest-plane inliers of the
 // transform, estimateOptimalRigidTransformation over those pairs, the evaluation of the result -- here in the DENSE form of the estimator
 // (every source point, lgr_plane_dense.hip) and repeated while the metric rises.  Declared order: DESIGN.md section 4; the CPU statement is
-// tests/refine_ref_lib.py.  Every per-point expression is plane_dense_kernel's, the two sums keep gt_seqsum_kernel's order, the refit is
+// tests/refine_ref_lib.py.  The per-point body is plane_dense_kernel's (lgr_plane_point.cuh), the two sums are gt_seqsum_job's, the refit is
 // lgr_refit_svd_dev's (lgr_refit_flagged_launch), so every evaluated transform and its figures carry the bits of
 // lgr_evaluate_plane_dense_dev + lgr_refit_svd_dev driven from the host.
 //
@@ -18,11 +18,11 @@
 // at once (the refit through a pair count of 0), and S.cur, S.first, S.rejected and the trace stay as they are.
 #include <algorithm>
 #include <cfloat>
-#include <cmath>
 
 #include "lgr_grid.cuh"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
+#include "lgr_plane_point.cuh"
 #include "lgr_pointpass.cuh"
 
 namespace {
@@ -38,8 +38,8 @@ struct RfState {
 };
 static_assert(sizeof(RfState) % 16 == 0, "RfState is copied and cleared in one piece");
 
-// plane_dense_kernel (lgr_plane_dense.hip) with the transform read from device memory and the target's half of the pair written next to the
-// terms.  Tc and done are wave-uniform addresses: scalar loads, no divergence; the walk is the gather-bound part, as there.
+// plane_dense_kernel's per-point body (plane_dense_point, lgr_plane_point.cuh) with the transform read from device memory and the target's
+// half of the pair written next to the terms.  Tc and done are wave-uniform addresses: scalar loads, no divergence.
 template <bool W>
 __global__ __launch_bounds__(PP_BLOCK) void refine_dense_kernel(GridDev g, const float4* __restrict__ src, int ns, const int* __restrict__ done, const float* __restrict__ T,
                                                                int* __restrict__ counter, float thr, float r2, int score_id, const float* __restrict__ w, float* __restrict__ term_val,
@@ -48,34 +48,12 @@ __global__ __launch_bounds__(PP_BLOCK) void refine_dense_kernel(GridDev g, const
     const int i = blockIdx.x * PP_BLOCK + threadIdx.x;
     bool inl = false;
     if (i < ns) {
-        const float4 P = src[(size_t) i * 3];
-        // Eigen Matrix4f * Vector4f on SSE: ((c0 x + c1 y) + c2 z) + c3
-        const float px = ((T[0] * P.x + T[4] * P.y) + T[8] * P.z) + T[12];
-        const float py = ((T[1] * P.x + T[5] * P.y) + T[9] * P.z) + T[13];
-        const float pz = ((T[2] * P.x + T[6] * P.y) + T[10] * P.z) + T[14];
-        float d2;
-        int j;
-        const int t = nearest_within(g, px, py, pz, r2, d2, j);   // (a non-finite moved point walks nothing: -1)
-        float value = 0.f, sq = 0.f;
-        float4 Q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t >= 0) {
-            Q = g.pxyz[t];
-            const float4 N = g.pnrm[t];
-            const float dist = fabsf((N.x * (Q.x - px) + N.y * (Q.y - py)) + N.z * (Q.z - pz));
-            inl = dist < thr;
-            if (inl) {
-                value = 1.f;
-                if (score_id == LGR_SCORE_MAE) value = fabsf(dist - thr) / thr;
-                else if (score_id == LGR_SCORE_MSE) value = (dist - thr) * (dist - thr) / (thr * thr);
-                else if (score_id == LGR_SCORE_EXP) value = lgr_expf(-dist * dist / (2 * thr * thr));
-                if constexpr (W) value *= w[i];
-                sq = dist * dist;
-            }
-        }
-        term_val[i] = inl ? value : 0.f;
-        term_sq[i] = inl ? sq : 0.f;
+        const PlanePoint p = plane_dense_point<W>(g, src[(size_t) i * 3], T, thr, r2, score_id, w, i);
+        inl = p.inl;
+        term_val[i] = p.value;
+        term_sq[i] = p.sq;
         flags[i] = inl ? 1 : 0;
-        P1[i] = make_float4(Q.x, Q.y, Q.z, 0.f);   // the grid's copy of tgt[nn]: the same bits
+        P1[i] = make_float4(p.Q.x, p.Q.y, p.Q.z, 0.f);   // the grid's copy of tgt[nn]: the same bits
     }
     wave_count(inl, counter);
 }
@@ -88,41 +66,14 @@ __global__ __launch_bounds__(PP_BLOCK) void refine_pack_src_kernel(const float4*
     P0[i] = make_float4(P.x, P.y, P.z, 0.f);
 }
 
-// gt_seqsum_kernel's two jobs (block 0: the values, block 1: the squared distances) and its schedule -- lane 0 adds tile k in index order
-// while waves 1-3 stage tile k + 1 -- skipped behind the stop.  (A kernel of its own and not a shared body: moving the loop of
-// lgr_pointpass.cuh into a function changed the code of gt_seqsum_kernel in its three translation units.)
+// gt_seqsum_kernel's two jobs (block 0: the values, block 1: the squared distances), skipped behind the stop
 __global__ __launch_bounds__(PP_BLOCK) void refine_sum_kernel(const float* __restrict__ val, const float* __restrict__ sq, int n, RfState* __restrict__ S) {
-    __shared__ float4 tile[2][GT_SUM_TILE / 4];
     if (S->done) return;
-    const float* __restrict__ w = blockIdx.x ? sq : val;
-    float sum = 0.f;
-    auto stage = [&](int b, int k, int t0, int stride) {
-        float* dst = (float*) tile[k];
-        const int len = min(GT_SUM_TILE, n - b);
-        for (int t = t0; t < len; t += stride) dst[t] = w[b + t];
-    };
-    stage(0, 0, threadIdx.x, PP_BLOCK);
-    __syncthreads();
-    int k = 0;
-    for (int b = 0; b < n; b += GT_SUM_TILE, k ^= 1) {
-        if (threadIdx.x >= 64) {
-            if (b + GT_SUM_TILE < n) stage(b + GT_SUM_TILE, k ^ 1, threadIdx.x - 64, PP_BLOCK - 64);
-        } else if (threadIdx.x == 0) {
-            const int len = min(GT_SUM_TILE, n - b), n4 = len >> 2;
-            const float4* t = tile[k];
-#pragma unroll 8
-            for (int q = 0; q < n4; ++q) {
-                const float4 v = t[q];
-                sum += v.x; sum += v.y; sum += v.z; sum += v.w;
-            }
-            for (int r = 4 * n4; r < len; ++r) sum += ((const float*) t)[r];
-        }
-        __syncthreads();
-    }
+    const float sum = gt_seqsum_job(blockIdx.x ? sq : val, n, false);
     if (threadIdx.x == 0) S->sums[blockIdx.x] = sum;
 }
 
-// one thread: the figures of the evaluation in flight (dense_eval's host arithmetic, lgr_plane_dense.hip), then the statement's compare
+// one thread: the figures of the evaluation in flight (lgr_plane_figures, as dense_eval takes them on the host), then the statement's compare
 __global__ void refine_decide_kernel(RfState* __restrict__ S, lgr_refine_step* __restrict__ trace, float denom, int max_steps, int first) {
     if (threadIdx.x != 0 || S->done) return;
     lgr_refine_step c;
@@ -130,8 +81,7 @@ __global__ void refine_decide_kernel(RfState* __restrict__ S, lgr_refine_step* _
     const int n = S->counter;
     c.n_inliers = n;
     c.score = S->sums[0];
-    c.rmse = n ? sqrtf(S->sums[1] / (float) n) : FLT_MAX;
-    c.metric = (float) ((double) S->sums[0] / (1.0 * (double) denom));
+    lgr_plane_figures(S->sums[0], S->sums[1], n, denom, &c.rmse, &c.metric);
     trace[S->n_eval] = c;   // n_eval <= max_steps + 1 < the buffer's max_steps + 2
     S->n_eval += 1;
     S->counter = 0;
@@ -206,12 +156,10 @@ extern "C" int lgr_refine_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, co
     }
     if (mp) LGR_TRY(lgr_weights_prepare(ctx, d_src, ns, mp, &d_w, &w_sum, &w_gate));   // harris / tomasi: LGR_ERR_UNSUPPORTED
     // ---- set-up: threshold, grid, buffers (every synchronisation that is not a group's read-back happens here)
-    float thr = p->threshold;
-    if (!(thr > 0.f)) LGR_TRY(lgr_cloud_density_dev(ctx, d_tgt, nt, 0.8f, &thr));   // ClosestPlaneMetricEstimator::setTargetCloud
-    const float radius = 2 * thr;                                                    // DIST_TO_PLANE_COEFFICIENT * inlier_threshold
-    LGR_CHECK(ctx, radius > 0.f && radius <= 2e18f, LGR_ERR_INVALID_ARG);
-    GridDev g{};
-    LGR_TRY(lgr_grid_build(ctx, WS_GRID_C, d_tgt, nt, radius * 1.001f, 0.f, &g));
+    lgr_plane_target pt;
+    LGR_TRY(lgr_plane_target_setup(ctx, d_tgt, nt, p->threshold, 2e18f, &pt));
+    const float thr = pt.thr, radius = pt.radius;
+    const GridDev& g = pt.g;
     const int max_steps = p->max_steps;
     const size_t nn = ((size_t) ns + 63) & ~(size_t) 63;
     RfState* S;

@@ -146,6 +146,18 @@ def test_source_sizes_across_launch_geometry(lgr, pair, ns):
     check(lgr.evaluate_plane_dense_host(s, tgt, T, 2, threshold=thr, with_inliers=True, with_nn=True), ref)
 
 
+@pytest.mark.parametrize("ns", [4095, 4096, 4097, 8193])
+def test_source_sizes_across_sum_tiles(lgr, pair, ns):
+    """the sequential sums take their terms in tiles of 4096 (GT_SUM_TILE, staged one ahead): a tile short of one term, exactly one, one
+    term into the second, one term into the third.  The source is the fixture's repeated and cut to ns."""
+    src, tgt, T, thr = (pair[k] for k in ("src", "tgt", "T", "thr"))
+    s = np.concatenate([src] * 3)[:ns]
+    ref = P.evaluate(s, tgt, T, 2, thr)
+    assert ref["n_inliers"] > ns // 10
+    check(lgr.evaluate_plane_dense(cuda(s), cuda(tgt), T, 2, with_inliers=True, with_nn=True), ref)
+    check(lgr.evaluate_plane_dense_host(s, tgt, T, 2, threshold=thr, with_inliers=True, with_nn=True), ref)
+
+
 def test_non_finite_points_and_normals(lgr, pair):
     src, tgt, T, thr = (pair[k] for k in ("src", "tgt", "T", "thr"))
     full = P.evaluate(src, tgt, T, 1, thr)

@@ -157,6 +157,16 @@ def test_source_sizes(lgr, oracle, pair, ns):
     check(lgr.refine_plane_host(s, pair["tgt"], pair["T0"], MSE, 6, threshold=pair["thr"], trace=True), ref)
 
 
+@pytest.mark.parametrize("ns", [4095, 4096, 4097, 8193])
+def test_source_sizes_across_sum_tiles(lgr, oracle, pair, ns):
+    """refine_sum_kernel takes its terms in tiles of 4096 (GT_SUM_TILE, staged one ahead): a tile short of one term, exactly one, one
+    term into the second, one term into the third.  The source is the fixture's repeated and cut to ns; two steps."""
+    s = np.concatenate([pair["src"]] * 3)[:ns]
+    ref = R.refine(oracle, s, pair["tgt"], pair["T0"], MSE, pair["thr"], 2)
+    assert ref["first"]["n_inliers"] > ns // 10 and len(ref["trace"]) >= 2
+    check(lgr.refine_plane(cuda(s), pair["d_tgt"], pair["T0"], MSE, 2, threshold=pair["thr"], trace=True), ref)
+
+
 def test_non_finite_points_and_normals(lgr, oracle, pair):
     src, tgt, T0, thr = (pair[k] for k in ("src", "tgt", "T0", "thr"))
     s_bad = src.copy()
