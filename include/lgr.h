@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-/* ABI revision.  5 (round 5): lgr_ctx_options.arithmetic / pcl_neighbour_cap and lgr_match_options.auto_dense / irregular_rows (former reserved words: a host that zeroes
+/* ABI revision.  Still 5 with the ratio matcher: lgr_feature_params.ratio_k takes the first of that struct's reserved words (a host that
+ * zeroes them gets k = 2, MATCHING_RATIO_K, and the word is read under LGR_MATCH_RATIO only), LGR_MATCH_RATIO and the lgr_ratio_test* /
+ * lgr_match_ratio* entry points are additions.  5 (round 5): lgr_ctx_options.arithmetic / pcl_neighbour_cap and lgr_match_options.auto_dense / irregular_rows (former reserved words: a host that zeroes
  * them keeps the default arithmetic and switches auto_dense and the irregular-row lane off), lgr_match_last_lbstats, lgr_match_last_irregular, lgr_selfcheck_philox,
  * lgr_selfcheck_libm added; the DEFAULT arithmetic of the normals and pair features changed to PCL's own sequences (results differ from
  * revision 4 at rounding level).  4 (round 4): lgr_match_options.split_sweep / kept_cap and lgr_ctx_options.concurrent_contexts (former reserved words: a host that
@@ -48,12 +50,14 @@ enum {
     LGR_ERR_NO_DEVICE = -2,
     LGR_ERR_OOM = -3,
     LGR_ERR_HIP = -4,          /* a HIP runtime call failed; see lgr_last_error */
-    LGR_ERR_UNSUPPORTED = -5,  /* e.g. n_samples outside 3..8, randomness outside 1..LGR_RANDOMNESS_MAX (or > 1 with FLANN / a guess), alignment teaser */
+    LGR_ERR_UNSUPPORTED = -5,  /* e.g. n_samples outside 3..8, randomness outside 1..LGR_RANDOMNESS_MAX (or > 1 with FLANN / a guess), alignment teaser,
+                                  LGR_MATCH_RATIO with ratio_k outside 2..LGR_RANDOMNESS_MAX, randomness > 1, FLANN or a guess */
     LGR_ERR_VOXEL_TOO_SMALL = -6
 };
 
 enum { LGR_RANDOMNESS_MAX = 8 };                                               /* the longest match list per key point */
-enum { LGR_MATCH_LR = 0, LGR_MATCH_ONE_SIDED = 1, LGR_MATCH_CLUSTER = 2 };      /* src/matching.cpp:21-75 */
+enum { LGR_MATCH_LR = 0, LGR_MATCH_ONE_SIDED = 1, LGR_MATCH_CLUSTER = 2, LGR_MATCH_RATIO = 3 };   /* src/matching.cpp:21-75 */
+#define LGR_MATCHING_RATIO_THRESHOLD 1.1f   /* MATCHING_RATIO_THRESHOLD include/common.h:50: what the pipeline uses under LGR_MATCH_RATIO */
 enum { LGR_METRIC_CORRESPONDENCES = 0, LGR_METRIC_UNIFORMITY = 1, LGR_METRIC_CLOSEST_PLANE = 2, LGR_METRIC_COMBINATION = 3,
        LGR_METRIC_WEIGHTED_CLOSEST_PLANE = 4 };   /* src/metric.cpp:272-301 */
 enum { LGR_SCORE_CONSTANT = 0, LGR_SCORE_MAE = 1, LGR_SCORE_MSE = 2, LGR_SCORE_EXP = 3 };
@@ -344,6 +348,18 @@ int lgr_vote_matches(lgr_ctx*, const int32_t* cand_idx, const float* cand_dist, 
                      float iss_radius, int32_t* idx, float* dist);
 int lgr_vote_matches_dev(lgr_ctx*, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
                          float iss_radius, int32_t* d_idx, float* d_dist);
+/* ---- include/matching.h:470-473 RatioMatcher::match_impl is a TODO in the reference; DESIGN.md section 4 states what is built: Lowe's
+ *      ratio test on a query's list of lgr_match_knn*.  knn_idx / knn_dist are mq x k, a row in list order, then -1 / 0.f.  idx[i] /
+ *      dist[i] = the row's first entry iff the row has k entries and dist[first] * threshold < dist[k-th] (one f32 multiply, a strict
+ *      compare: equal distances never pass, a list shorter than k is dropped), else -1 / 0.f.  k outside 2..LGR_RANDOMNESS_MAX:
+ *      LGR_ERR_UNSUPPORTED; a threshold that is not finite and > 0: LGR_ERR_INVALID_ARG.  mq = 0 writes nothing. ---- */
+int lgr_ratio_test(lgr_ctx*, const int32_t* knn_idx, const float* knn_dist, int mq, int k, float threshold, int32_t* idx, float* dist);
+int lgr_ratio_test_dev(lgr_ctx*, const int32_t* d_knn_idx, const float* d_knn_dist, int mq, int k, float threshold, int32_t* d_idx, float* d_dist);
+/* the fused form: lgr_match_knn_dev's sweep of one direction with the test where its lists are decoded (the mq x k table is never
+ * written).  Bit-equal to lgr_match_knn_dev followed by lgr_ratio_test_dev; idx / dist hold mq entries.  Arguments as lgr_match_knn*. */
+int lgr_match_ratio(lgr_ctx*, int row_len, const float* q, int mq, const float* t, int mt, int block, int k, float threshold, int32_t* idx, float* dist);
+int lgr_match_ratio_dev(lgr_ctx*, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, float threshold,
+                        int32_t* d_idx, float* d_dist);
 /* ---- include/matching.h:373-376 matchFLANN<FPFH>(query_features, train_features, parameters), randomness 1 (:565-592):
  *      pcl::KdTreeFLANN is an exact search, so the nearest row is the one matchBF finds (the reference's own test asserts that,
  *      tests/flann_bf_matcher.h:82-83); what differs is the reported distance: sqrt of FLANN's L2_Simple (sequential sum of
@@ -403,7 +419,8 @@ int lgr_smoothed_densities(lgr_ctx*, const float* pts, int n, int k, float* out)
 int lgr_smoothed_densities_dev(lgr_ctx*, const float* d_pts, int n, int k, float* d_out);
 int lgr_knn_dev(lgr_ctx*, const float* d_q, int nq, const float* d_pts, int n, int k, int32_t* d_idx, float* d_d2);
 
-/* ---- include/matching.h:395-411 / 428-453 / 492-550 match_impl of OneSided / LeftToRight / Cluster matcher ---- */
+/* ---- include/matching.h:395-411 / 428-453 / 492-550 match_impl of OneSided / LeftToRight / Cluster matcher.  LGR_MATCH_RATIO is
+ *      LGR_MATCH_ONE_SIDED over the table it is given (the ratio test has already dropped entries: ij_idx < 0 is skipped) ---- */
 int lgr_filter_dev(lgr_ctx*, int matching_id, const float* d_src, int ns, const float* d_tgt, int nt,
                    const int32_t* d_ij_idx, const float* d_ij_dist, const int32_t* d_ji_idx, const float* d_ji_dist,
                    float distance_thr, int cluster_k, lgr_corr* d_out, int* n_out /* host */);
@@ -424,13 +441,20 @@ int lgr_correspondences_dev(lgr_ctx*, const float* d_src, int ns, const float* d
  * does); LGR_LRF_DEFAULT returns LGR_ERR_UNSUPPORTED (the reference triangulates the cloud with
  * GreedyProjectionTriangulation for it), LGR_LRF_GT too (this struct has no ground-truth channel), other values
  * LGR_ERR_INVALID_ARG; use_bfmatcher = 0, has_guess and LGR_ARITH_PCL are refused as for SHOT.
- * lgr_result.stage_ms[2] ("fpfh") carries the descriptor stage, whichever descriptor ran (for RoPS: frames and rows). */
+ * lgr_result.stage_ms[2] ("fpfh") carries the descriptor stage, whichever descriptor ran (for RoPS: frames and rows).
+ * matching_id = LGR_MATCH_RATIO (every descriptor; lgr_correspondences*, lgr_align*, lgr_measure*): only source -> target is matched;
+ * per level the candidate of lgr_match_ratio_dev(bf_block_size, ratio_k, LGR_MATCHING_RATIO_THRESHOLD), the levels' candidates through
+ * the vote of the multi-scale path, then the one-sided output.  It needs randomness = 1 and the brute-force matcher without a guess,
+ * else LGR_ERR_UNSUPPORTED, checked before any stage runs. */
 enum { LGR_DESCRIPTOR_FPFH = 0, LGR_DESCRIPTOR_SHOT = 1, LGR_DESCRIPTOR_ROPS = 2 };
 enum { LGR_LRF_DEFAULT = 0, LGR_LRF_GRAVITY = 1, LGR_LRF_GT = 2 };   /* SHOT: default only; RoPS: gravity only */
 typedef struct {
     int32_t descriptor_id;   /* LGR_DESCRIPTOR_FPFH / LGR_DESCRIPTOR_SHOT / LGR_DESCRIPTOR_ROPS */
     int32_t lrf_id;          /* LGR_LRF_DEFAULT (SHOT) / LGR_LRF_GRAVITY (RoPS) */
-    int32_t reserved[6];     /* 0 */
+    int32_t ratio_k;         /* LGR_MATCH_RATIO only (AlignmentParameters::ratio_k, include/common.h:146): the list length of the ratio test,
+                                2..LGR_RANDOMNESS_MAX; 0 = 2 (MATCHING_RATIO_K, include/common.h:51); anything else LGR_ERR_UNSUPPORTED.
+                                The first of the former reserved words; other matchers do not read it.  A NULL struct means 2. */
+    int32_t reserved[5];     /* 0 */
 } lgr_feature_params;
 void lgr_default_feature_params(lgr_feature_params* f);      /* FPFH, default frames */
 int lgr_correspondences_ex(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_params*, const lgr_feature_params*,

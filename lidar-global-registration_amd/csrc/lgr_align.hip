@@ -1,4 +1,4 @@
-// lgr_align.hip -- match filters (OneSided / LeftToRight / Cluster), correspondence search and alignPointClouds.
+// lgr_align.hip -- match filters (OneSided / LeftToRight / Cluster / Ratio), correspondence search and alignPointClouds.
 //
 //   include/matching.h:395-411, 428-453, 492-550  -> lgr_filter_dev
 //   src/correspondence_search.cpp:4-15 + include/matching.h:148-262 (keypoint 'any', single scale) -> lgr_correspondences*
@@ -119,6 +119,7 @@ extern "C" int lgr_filter_dev(lgr_ctx* ctx, int matching_id, const float* d_src,
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, d_src && d_tgt && d_ij_idx && d_ij_dist && d_out && n_out && ns > 1 && nt > 1, LGR_ERR_INVALID_ARG);
+    if (matching_id == LGR_MATCH_RATIO) matching_id = LGR_MATCH_ONE_SIDED;   // OneSidedMatcher's loop over the entries the ratio test left
     LGR_CHECK(ctx, matching_id == LGR_MATCH_LR || matching_id == LGR_MATCH_ONE_SIDED || matching_id == LGR_MATCH_CLUSTER, LGR_ERR_INVALID_ARG);
     if (matching_id != LGR_MATCH_ONE_SIDED) LGR_CHECK(ctx, d_ji_idx && d_ji_dist, LGR_ERR_INVALID_ARG);
     if (matching_id == LGR_MATCH_CLUSTER) LGR_CHECK(ctx, cluster_k >= 1 && cluster_k <= 64, LGR_ERR_INVALID_ARG);
@@ -250,6 +251,7 @@ struct CorrCall {
     float *feat[2], *surf[2], *dij, *dji;    // workspace: rows and down-sampled surfaces per cloud, the matches of both directions
     int32_t *ij, *ji;
     FilterTables ftab;
+    int ratio_k = 0;                         // LGR_MATCH_RATIO: the list length of the ratio test (check)
     float ms[3] = {0, 0, 0};
     // lgr_aux_job keeps a REFERENCE to its callable, so `tables` has to outlive the posted job: it is declared in front of the guard
     // that waits for the job, members are destroyed in reverse order, and so every exit of the entry point waits first.  The
@@ -269,7 +271,8 @@ struct CorrCall {
     CorrCall(const CorrCall&) = delete;
     const float* vp(int side) const { return side == 0 ? (p->has_vp_src ? p->vp_src : nullptr) : (p->has_vp_tgt ? p->vp_tgt : nullptr); }
     float iss_radius(int side) const { return side == 0 ? p->iss_radius_src : p->iss_radius_tgt; }
-    bool both_dirs() const { return p->matching_id != LGR_MATCH_ONE_SIDED; }
+    bool ratio() const { return p->matching_id == LGR_MATCH_RATIO; }
+    bool both_dirs() const { return p->matching_id != LGR_MATCH_ONE_SIDED && !ratio(); }
 };
 
 // One level of one cloud (include/matching.h:234-248; the single-scale search has one level): down-sample `in` into `surf`, normals,
@@ -466,6 +469,11 @@ static int match_knn_vote(const CorrCall& c) {
     return LGR_OK;
 }
 
+// matching ratio: a level's candidate per source key point, from the k-nearest sweep of the one direction
+static int match_ratio(const CorrCall& c, const float* fa, int ma, const float* fb, int mb, int32_t* ab_i, float* ab_d) {
+    return lgr_match_ratio_core(c.ctx, c.d->len, fa, ma, fb, mb, c.p->bf_block_size, c.ratio_k, LGR_MATCHING_RATIO_THRESHOLD, ab_i, ab_d);
+}
+
 static int ms_match_tables(CorrCall& c) {
     lgr_ctx* ctx = c.ctx;
     const int D = c.d->len;
@@ -498,7 +506,8 @@ static int ms_match_tables(CorrCall& c) {
             pa = sub; pb = sub + (size_t) ma * 12;
         }
         // randomness > 1: the level's kr matches per key point, in list order (checked on entry: brute force, no guess)
-        if (kr > 1) LGR_TRY(lgr_match_knn_core(ctx, D, fa, ma, fb, mb, c.p->bf_block_size, kr, ab_i, ab_d, need_ji ? ba_i : nullptr, need_ji ? ba_d : nullptr));
+        if (c.ratio()) LGR_TRY(match_ratio(c, fa, ma, fb, mb, ab_i, ab_d));   // (checked on entry: kr = 1, brute force, no guess)
+        else if (kr > 1) LGR_TRY(lgr_match_knn_core(ctx, D, fa, ma, fb, mb, c.p->bf_block_size, kr, ab_i, ab_d, need_ji ? ba_i : nullptr, need_ji ? ba_d : nullptr));
         else LGR_TRY(match_dispatch(c, pa, fa, ma, pb, fb, mb, ab_i, ab_d, ba_i, ba_d));
         std::vector<int32_t> h((size_t) 2 * (ma + mb) * kr);
         LGR_HIP(ctx, hipMemcpyAsync(h.data(), r, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -540,6 +549,11 @@ static int check(CorrCall& c, const lgr_feature_params* fp) {
     if (c.sizes[0] < 2 || c.sizes[1] < 2) { *c.n_out = 0; c.empty = true; return LGR_OK; }   // the reference ends with an empty correspondence list
     LGR_CHECK(ctx, c.d_out != nullptr, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, p->randomness >= 1 && p->randomness <= LGR_RANDOMNESS_MAX, LGR_ERR_UNSUPPORTED);
+    if (c.ratio()) {   // the ratio test reads one k-nearest list per key point and level: the brute-force matcher, one direction
+        LGR_CHECK(ctx, p->randomness == 1 && p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);
+        c.ratio_k = fp && fp->ratio_k ? fp->ratio_k : 2;   // MATCHING_RATIO_K include/common.h:51
+        LGR_CHECK(ctx, c.ratio_k >= 2 && c.ratio_k <= LGR_RANDOMNESS_MAX, LGR_ERR_UNSUPPORTED);
+    }
     if (p->randomness > 1) {   // the k-nearest matcher is the brute-force one (include/matching.h:612-625); the vote needs the voted side's radius
         LGR_CHECK(ctx, p->use_bfmatcher && !p->has_guess, LGR_ERR_UNSUPPORTED);
         LGR_CHECK(ctx, std::isfinite(p->iss_radius_tgt) && p->iss_radius_tgt > 0.f, LGR_ERR_INVALID_ARG);
@@ -549,7 +563,8 @@ static int check(CorrCall& c, const lgr_feature_params* fp) {
               LGR_ERR_INVALID_ARG);
     // checked before any stage runs (this entry point builds the filter tables itself, so lgr_filter_dev's checks do not cover it):
     // the cluster filter keeps at most 64 spatial neighbours per point (filter_flags<64>)
-    LGR_CHECK(ctx, p->matching_id == LGR_MATCH_LR || p->matching_id == LGR_MATCH_ONE_SIDED || p->matching_id == LGR_MATCH_CLUSTER, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, p->matching_id == LGR_MATCH_LR || p->matching_id == LGR_MATCH_ONE_SIDED || p->matching_id == LGR_MATCH_CLUSTER || c.ratio(),
+              LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, p->matching_id != LGR_MATCH_CLUSTER || (p->cluster_k >= 1 && p->cluster_k <= 64), LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     *c.n_out = 0;
@@ -627,7 +642,7 @@ static int features_and_match_single(CorrCall& c) {
     const auto t_feat0 = std::chrono::steady_clock::now();
     // The source cloud is done first (this thread): the matcher's query-side half (clustering, assignment, sort) runs right behind
     // its features, under the target cloud's feature kernels on the second context.
-    const bool prepare_query = p->use_bfmatcher && !p->has_guess && !c.d->dense && p->randomness == 1;   // match_dispatch: the FPFH brute-force matcher will be called
+    const bool prepare_query = p->use_bfmatcher && !p->has_guess && !c.d->dense && p->randomness == 1 && !c.ratio();   // match_dispatch: the FPFH brute-force matcher will be called
     LGR_TRY(lgr_run_pair(ctx,
         [&](lgr_ctx* cx) {
             LGR_TRY(cloud_features(cx, 0, c.ms));
@@ -641,6 +656,7 @@ static int features_and_match_single(CorrCall& c) {
     for (int s = 0; s < 3; ++s) { c.ms[s] += ms_t[s]; sum += c.ms[s]; }
     if (sum > 0.f) for (int s = 0; s < 3; ++s) c.ms[s] *= wall / sum;
     tick(ctx, 4);
+    if (c.ratio()) return match_ratio(c, c.feat[0], c.ksizes[0], c.feat[1], c.ksizes[1], c.ij, c.dij);   // one level: the vote is the identity
     if (p->randomness > 1) return match_knn_vote(c);
     return match_dispatch(c, c.kclouds[0], c.feat[0], c.ksizes[0], c.kclouds[1], c.feat[1], c.ksizes[1], c.ij, c.dij, c.ji, c.dji);
 }
@@ -655,7 +671,7 @@ static int finish(CorrCall& c) {
         (void) hipSetDevice(ctx->device);
         if (rc_tab != LGR_OK) { ctx->err = ctx->aux2->err; return rc_tab; }
     }
-    LGR_TRY(filter_core(ctx, p->matching_id, c.ksizes[0], c.ij, c.dij, c.ji, c.dji, p->distance_thr, p->cluster_k, c.ftab, c.d_out, c.n_out));
+    LGR_TRY(filter_core(ctx, c.ratio() ? (int) LGR_MATCH_ONE_SIDED : p->matching_id, c.ksizes[0], c.ij, c.dij, c.ji, c.dji, p->distance_thr, p->cluster_k, c.ftab, c.d_out, c.n_out));
     if (c.kidx[0] && *c.n_out) finalize_kernel<<<cdiv(*c.n_out, 256), 256, 0, ctx->stream>>>(c.d_out, *c.n_out, c.kidx[0], c.kidx[1]);
     tick(ctx, 6);
     LGR_HIP(ctx, hipEventSynchronize(ctx->ev[6]));

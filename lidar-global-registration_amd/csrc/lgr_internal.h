@@ -255,6 +255,10 @@ int lgr_match_knn_core(lgr_ctx* ctx, int row_len, const float* d_a, int ma, cons
                        int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d);
 int lgr_vote_matches_core(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
                           float iss_radius, int32_t* d_idx, float* d_dist);
+// ... and the ratio test: fused into one direction's sweep (d_idx / d_dist: mq entries), and on a caller's table
+int lgr_match_ratio_core(lgr_ctx* ctx, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, float threshold,
+                         int32_t* d_idx, float* d_dist);
+int lgr_ratio_test_core(lgr_ctx* ctx, const int32_t* d_knn_idx, const float* d_knn_dist, int mq, int k, float threshold, int32_t* d_idx, float* d_dist);
 // lgr_match_dense.hip: the exact dense matcher of the long descriptors, row_len 352 (SHOT) or 135 (RoPS), else LGR_ERR_UNSUPPORTED
 int lgr_match_dense(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block,
                     int32_t* ab_i, float* ab_d, int32_t* ba_i /* NULL: one direction */, float* ba_d);

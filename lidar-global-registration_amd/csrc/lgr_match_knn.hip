@@ -1,8 +1,10 @@
-// lgr_match_knn.hip -- the exact k-nearest brute-force matcher (randomness > 1) and the proximity vote over a query's candidates.
+// lgr_match_knn.hip -- the exact k-nearest brute-force matcher (randomness > 1), the proximity vote over a query's candidates and the
+// ratio test over a query's list.
 //
 //   include/matching.h:612-625 matchBF with knnMatch(.., randomness), src/common.cpp:517-529 updateMultivaluedCorrespondence
 //                                                                                    -> lgr_match_knn*, lgr_match_knn2_dev
 //   include/matching.h:327-352 the vote of match_multiscale                          -> lgr_vote_matches*
+//   include/matching.h:470-473 RatioMatcher (a TODO there: DESIGN.md section 4 states it) -> lgr_ratio_test*, lgr_match_ratio*
 // The pair distances are lgr_match_dense.cuh's (OpenCV's float sequence); the selection is DESIGN.md section 4's two-stage order:
 // inside a bf block the first k rows in ascending (d, index) -- order P --, across blocks the first k of the blocks' lists in ascending
 // (d, index DESCENDING) -- order F: a later insertion goes in front of equal distances, blocks and their lists are fed ascending.
@@ -126,8 +128,14 @@ __global__ __launch_bounds__(256) void knn_match_kernel(const float* __restrict_
     for (int e = tid; e < k * MT; e += 256) part[((size_t) split * mpa + q0 + e % MT) * k + e / MT] = mrg[e / MT][e % MT];
 }
 
-// the first k of the splits' lists in order F, decoded: 64 queries per block, the list in LDS
-__global__ __launch_bounds__(64) void knn_merge_kernel(const unsigned long long* __restrict__ part, int m, int mpa, int k, int splits,
+// The ratio test: a list's first entry is the query's candidate iff the list has k entries and
+// d_first * thr < d_kth -- one f32 multiply (no contraction: there is no add), a strict compare.  Equal distances and NaN never pass.
+__device__ __forceinline__ bool ratio_passes(float d_first, float d_kth, float thr) { return __fmul_rn(d_first, thr) < d_kth; }
+
+// the first k of the splits' lists in order F, decoded: 64 queries per block, the list in LDS.  RATIO: idx / dist hold one entry per
+// query, the candidate of the ratio test on its list (or -1 / 0.f), instead of the m x k table.
+template <bool RATIO>
+__global__ __launch_bounds__(64) void knn_merge_kernel(const unsigned long long* __restrict__ part, int m, int mpa, int k, int splits, float thr,
                                                       int32_t* __restrict__ idx, float* __restrict__ dist) {
     __shared__ unsigned long long lst[KMAX][MT];
     const int tid = threadIdx.x, q = blockIdx.x * MT + tid;
@@ -139,6 +147,13 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const unsigned long long*
             if (key == NONE) break;
             knn_insert(lst, tid, k, key);
         }
+    if (RATIO) {
+        const unsigned long long first = lst[0][tid], kth = lst[k - 1][tid];
+        const bool keep = kth != NONE && ratio_passes(__uint_as_float((unsigned) (first >> 32)), __uint_as_float((unsigned) (kth >> 32)), thr);
+        idx[q] = keep ? (int32_t) ~(unsigned) first : -1;
+        dist[q] = keep ? __uint_as_float((unsigned) (first >> 32)) : 0.f;
+        return;
+    }
     for (int e = 0; e < k; ++e) {
         const unsigned long long key = lst[e][tid];
         idx[(size_t) q * k + e] = key == NONE ? -1 : (int32_t) ~(unsigned) key;
@@ -147,7 +162,8 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const unsigned long long*
 }
 
 template <int NB, int TAIL>
-int knn_sweep(lgr_ctx* ctx, const float* pa, int ma, int mpa, const float* pb, int mb, int mpb, int block, int k, int slot, int32_t* idx, float* dist) {
+int knn_sweep(lgr_ctx* ctx, const float* pa, int ma, int mpa, const float* pb, int mb, int mpb, int block, int k, int slot, int32_t* idx, float* dist,
+              const float* ratio_thr = nullptr) {
     // splits are runs of whole bf blocks (the two-stage order needs a block's rows in one list); at most 8 thread blocks per CU in all
     const int n_qt = mpa / MT, nb = cdiv(mb, block);
     const int want = std::max(1, std::min(std::min(nb, cdiv(mb, MT)), cdiv(8 * ctx->n_cu, n_qt)));
@@ -155,19 +171,22 @@ int knn_sweep(lgr_ctx* ctx, const float* pa, int ma, int mpa, const float* pb, i
     unsigned long long* part;
     LGR_TRY(lgr_ws_t(ctx, slot, (size_t) splits * mpa * k, &part));
     knn_match_kernel<NB, TAIL><<<n_qt * splits, 256, 0, ctx->stream>>>(pa, ma, mpa, pb, mb, mpb, block, k, splits, bps, part);
-    knn_merge_kernel<<<n_qt, MT, 0, ctx->stream>>>(part, ma, mpa, k, splits, idx, dist);
+    if (ratio_thr) knn_merge_kernel<true><<<n_qt, MT, 0, ctx->stream>>>(part, ma, mpa, k, splits, *ratio_thr, idx, dist);
+    else knn_merge_kernel<false><<<n_qt, MT, 0, ctx->stream>>>(part, ma, mpa, k, splits, 0.f, idx, dist);
     LGR_HIP(ctx, hipGetLastError());
     return LGR_OK;
 }
 
 template <int NB, int TAIL>
-int knn_match(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int k, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
+int knn_match(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int k, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d,
+              const float* ratio_thr) {
     constexpr int LEN = 16 * NB + TAIL;
     LGR_CHECK(ctx, (d_a || ma == 0) && (d_b || mb == 0) && ma >= 0 && mb >= 0 && block > 0 && (ab_i || ma == 0) && (ab_d || ma == 0), LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     const bool both = ba_i != nullptr;
+    const size_t width = ratio_thr ? 1 : k;   // entries per query of ab_i / ab_d (the ratio form is one direction: ba_i is NULL)
     if (ma == 0 || mb == 0) {
-        if (ma) { LGR_HIP(ctx, hipMemsetAsync(ab_i, 0xff, (size_t) ma * k * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(ab_d, 0, (size_t) ma * k * 4, ctx->stream)); }
+        if (ma) { LGR_HIP(ctx, hipMemsetAsync(ab_i, 0xff, (size_t) ma * width * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(ab_d, 0, (size_t) ma * width * 4, ctx->stream)); }
         if (mb && both) { LGR_HIP(ctx, hipMemsetAsync(ba_i, 0xff, (size_t) mb * k * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(ba_d, 0, (size_t) mb * k * 4, ctx->stream)); }
         return LGR_OK;
     }
@@ -177,7 +196,7 @@ int knn_match(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, 
     LGR_TRY(lgr_ws_t(ctx, WS_DENSE_PACK_B, (size_t) mpb * LEN, &pb));
     dense_pack_kernel<NB, TAIL><<<cdiv((long long) mpa * LEN, 256), 256, 0, ctx->stream>>>(d_a, ma, mpa, pa);
     dense_pack_kernel<NB, TAIL><<<cdiv((long long) mpb * LEN, 256), 256, 0, ctx->stream>>>(d_b, mb, mpb, pb);
-    LGR_TRY((knn_sweep<NB, TAIL>(ctx, pa, ma, mpa, pb, mb, mpb, block, k, WS_KNN_PART_A, ab_i, ab_d)));
+    LGR_TRY((knn_sweep<NB, TAIL>(ctx, pa, ma, mpa, pb, mb, mpb, block, k, WS_KNN_PART_A, ab_i, ab_d, ratio_thr)));
     // the other direction sweeps the same packed operands with the roles exchanged
     if (both) LGR_TRY((knn_sweep<NB, TAIL>(ctx, pb, mb, mpb, pa, ma, mpa, block, k, WS_KNN_PART_B, ba_i, ba_d)));
     return LGR_OK;
@@ -214,15 +233,50 @@ __global__ void vote_matches_kernel(const int32_t* __restrict__ cand, const floa
     dist[q] = best >= 0 ? cd[best] : 0.f;
 }
 
+// One thread per query: the ratio test on its row of a caller's mq x k table (list order, then -1 / 0.f: a list shorter than k ends in -1)
+__global__ void ratio_test_kernel(const int32_t* __restrict__ kidx, const float* __restrict__ kdist, int mq, int k, float thr,
+                                  int32_t* __restrict__ idx, float* __restrict__ dist) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= mq) return;
+    const int32_t first = kidx[(size_t) q * k];
+    const float d_first = kdist[(size_t) q * k];
+    const bool keep = first >= 0 && kidx[(size_t) q * k + k - 1] >= 0 && ratio_passes(d_first, kdist[(size_t) q * k + k - 1], thr);
+    idx[q] = keep ? first : -1;
+    dist[q] = keep ? d_first : 0.f;
+}
+
+int knn_dispatch(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block, int k,
+                 int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d, const float* ratio_thr) {
+    if (row_len == 352) return knn_match<22, 0>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    if (row_len == 135) return knn_match<8, 7>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    if (row_len == 33) return knn_match<2, 1>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    return lgr_fail(ctx, LGR_ERR_UNSUPPORTED, "row_len == 33 || row_len == 135 || row_len == 352", __FILE__, __LINE__);
+}
+
 }  // namespace
 
 int lgr_match_knn_core(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block, int k,
                        int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
     LGR_CHECK(ctx, k >= 1 && k <= KMAX, LGR_ERR_UNSUPPORTED);
-    if (row_len == 352) return knn_match<22, 0>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d);
-    if (row_len == 135) return knn_match<8, 7>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d);
-    if (row_len == 33) return knn_match<2, 1>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d);
-    return lgr_fail(ctx, LGR_ERR_UNSUPPORTED, "row_len == 33 || row_len == 135 || row_len == 352", __FILE__, __LINE__);
+    return knn_dispatch(ctx, row_len, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, nullptr);
+}
+
+// the k-nearest sweep of one direction with the ratio test where its lists are decoded: d_idx / d_dist hold mq entries
+int lgr_match_ratio_core(lgr_ctx* ctx, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, float threshold,
+                         int32_t* d_idx, float* d_dist) {
+    LGR_CHECK(ctx, k >= 2 && k <= KMAX, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, std::isfinite(threshold) && threshold > 0.f, LGR_ERR_INVALID_ARG);
+    return knn_dispatch(ctx, row_len, d_q, mq, d_t, mt, block, k, d_idx, d_dist, nullptr, nullptr, &threshold);
+}
+
+int lgr_ratio_test_core(lgr_ctx* ctx, const int32_t* d_knn_idx, const float* d_knn_dist, int mq, int k, float threshold, int32_t* d_idx, float* d_dist) {
+    LGR_CHECK(ctx, k >= 2 && k <= KMAX, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, mq >= 0 && std::isfinite(threshold) && threshold > 0.f && ((d_knn_idx && d_knn_dist && d_idx && d_dist) || mq == 0), LGR_ERR_INVALID_ARG);
+    if (mq == 0) return LGR_OK;
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    ratio_test_kernel<<<cdiv(mq, 256), 256, 0, ctx->stream>>>(d_knn_idx, d_knn_dist, mq, k, threshold, d_idx, d_dist);
+    LGR_HIP(ctx, hipGetLastError());
+    return LGR_OK;
 }
 
 int lgr_vote_matches_core(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
@@ -305,6 +359,64 @@ extern "C" int lgr_vote_matches(lgr_ctx* ctx, const int32_t* cand_idx, const flo
     LGR_HIP(ctx, hipMemcpyAsync(dcd, cand_dist, (size_t) mq * width * 4, hipMemcpyHostToDevice, ctx->stream));
     if (mt) LGR_HIP(ctx, hipMemcpyAsync(dp, train_pts, (size_t) mt * 12 * 4, hipMemcpyHostToDevice, ctx->stream));
     LGR_TRY(lgr_vote_matches_core(ctx, dc, dcd, mq, width, dp, mt, iss_radius, di, dd));
+    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LGR_OK;
+}
+
+extern "C" int lgr_ratio_test_dev(lgr_ctx* ctx, const int32_t* d_knn_idx, const float* d_knn_dist, int mq, int k, float threshold, int32_t* d_idx, float* d_dist) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    return lgr_ratio_test_core(ctx, d_knn_idx, d_knn_dist, mq, k, threshold, d_idx, d_dist);
+}
+
+extern "C" int lgr_ratio_test(lgr_ctx* ctx, const int32_t* knn_idx, const float* knn_dist, int mq, int k, float threshold, int32_t* idx, float* dist) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, k >= 2 && k <= KMAX, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, mq >= 0 && std::isfinite(threshold) && threshold > 0.f && ((knn_idx && knn_dist && idx && dist) || mq == 0), LGR_ERR_INVALID_ARG);
+    if (mq == 0) return LGR_OK;
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    int32_t *dki, *di;
+    float *dkd, *dd;
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * k, &dki));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mq * k, &dkd));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq, &di));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq, &dd));
+    LGR_HIP(ctx, hipMemcpyAsync(dki, knn_idx, (size_t) mq * k * 4, hipMemcpyHostToDevice, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(dkd, knn_dist, (size_t) mq * k * 4, hipMemcpyHostToDevice, ctx->stream));
+    LGR_TRY(lgr_ratio_test_core(ctx, dki, dkd, mq, k, threshold, di, dd));
+    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LGR_OK;
+}
+
+extern "C" int lgr_match_ratio_dev(lgr_ctx* ctx, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, float threshold,
+                                   int32_t* d_idx, float* d_dist) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    return lgr_match_ratio_core(ctx, row_len, d_q, mq, d_t, mt, block, k, threshold, d_idx, d_dist);
+}
+
+extern "C" int lgr_match_ratio(lgr_ctx* ctx, int row_len, const float* q, int mq, const float* t, int mt, int block, int k, float threshold,
+                               int32_t* idx, float* dist) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, k >= 2 && k <= KMAX && (row_len == 33 || row_len == 135 || row_len == 352), LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, (q || mq == 0) && (t || mt == 0) && (idx || mq == 0) && (dist || mq == 0) && mq >= 0 && mt >= 0 && block > 0, LGR_ERR_INVALID_ARG);
+    if (mq == 0) return LGR_OK;
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    float *dq, *dt, *dd;
+    int32_t* di;
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * row_len + 1, &dq));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * row_len + 1, &dt));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq + 1, &di));
+    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq + 1, &dd));
+    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) mq * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dt, t, (size_t) mt * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
+    LGR_TRY(lgr_match_ratio_core(ctx, row_len, dq, mq, dt, mt, block, k, threshold, di, dd));
     LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -198,7 +198,8 @@ inline lgr_params to_abi(const AlignmentParameters& p) {
     // detectKeyPoints (src/common.cpp:657-691): "iss" -> ISS, anything else -> every point (with a warning there)
     a.keypoint_id = p.keypoint_id == "iss" ? LGR_KEYPOINT_ISS : LGR_KEYPOINT_ANY;
     a.iss_radius_src = p.iss_radius_src; a.iss_radius_tgt = p.iss_radius_tgt;
-    a.matching_id = p.matching_id == "cluster" ? LGR_MATCH_CLUSTER : (p.matching_id == "one_sided" ? LGR_MATCH_ONE_SIDED : LGR_MATCH_LR);
+    a.matching_id = p.matching_id == "cluster" ? LGR_MATCH_CLUSTER : (p.matching_id == "one_sided" ? LGR_MATCH_ONE_SIDED :
+                    (p.matching_id == "ratio" ? LGR_MATCH_RATIO : LGR_MATCH_LR));   // ratio: ratio_k travels in lgr_feature_params (to_feature_abi)
     a.metric_id = p.metric_id == "uniformity" ? LGR_METRIC_UNIFORMITY : p.metric_id == "closest_plane" ? LGR_METRIC_CLOSEST_PLANE
                   : p.metric_id == "combination" ? LGR_METRIC_COMBINATION
                   : p.metric_id == "weighted_closest_plane" ? LGR_METRIC_WEIGHTED_CLOSEST_PLANE : LGR_METRIC_CORRESPONDENCES;
@@ -453,6 +454,7 @@ inline Matrix4f chooseBestHypothesis(const PointNCloud::ConstPtr& src, const Poi
 inline lgr_feature_params to_feature_abi(const AlignmentParameters& parameters_) {
     lgr_feature_params f;
     lgr_default_feature_params(&f);
+    f.ratio_k = parameters_.ratio_k;   // read under matching_id "ratio" only (include/common.h:146)
     if (parameters_.descriptor_id == "shot") {
         f.descriptor_id = LGR_DESCRIPTOR_SHOT;
         if (!lrf_is_default(parameters_.lrf_id)) f.lrf_id = LGR_LRF_GRAVITY;

@@ -17,7 +17,8 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # LGR_HIP_LIB: another build of the same sources (A/B experiments of tools/: e.g. a library built with `make EXP=-D...`); never a fallback
 LIB_PATH = os.environ.get("LGR_HIP_LIB") or os.path.join(_CSRC, "liblgr_hip.so")
 
-MATCH_LR, MATCH_ONE_SIDED, MATCH_CLUSTER = 0, 1, 2
+MATCH_LR, MATCH_ONE_SIDED, MATCH_CLUSTER, MATCH_RATIO = 0, 1, 2, 3
+MATCHING_RATIO_THRESHOLD = 1.1     # LGR_MATCHING_RATIO_THRESHOLD: what the pipeline uses under MATCH_RATIO
 METRIC_CORRESPONDENCES, METRIC_UNIFORMITY, METRIC_CLOSEST_PLANE, METRIC_COMBINATION, METRIC_WEIGHTED_CLOSEST_PLANE = 0, 1, 2, 3, 4
 WEIGHT_CONSTANT, WEIGHT_EXP_CURVATURE, WEIGHT_CURVEDNESS, WEIGHT_HARRIS, WEIGHT_TOMASI, WEIGHT_CURVATURE, WEIGHT_NSS = 0, 1, 2, 3, 4, 5, 6
 WEIGHT_IDS = {"constant": 0, "exp_curvature": 1, "curvedness": 2, "harris": 3, "tomasi": 4, "curvature": 5, "nss": 6}
@@ -84,19 +85,21 @@ FORMAT_AUTO, FORMAT_F32, FORMAT_F16, FORMAT_F16R = -1, 0, 1, 2
 
 
 class FeatureParams(C.Structure):
-    """lgr_feature_params: the descriptor of the correspondence search (AlignmentParameters.descriptor_id / lrf_id)."""
-    _fields_ = [("descriptor_id", C.c_int32), ("lrf_id", C.c_int32), ("reserved", C.c_int32 * 6)]
+    """lgr_feature_params: the descriptor of the correspondence search (AlignmentParameters.descriptor_id / lrf_id) and ratio_k."""
+    _fields_ = [("descriptor_id", C.c_int32), ("lrf_id", C.c_int32), ("ratio_k", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
-def feature_params(descriptor="fpfh", lrf_id=None):
+def feature_params(descriptor="fpfh", lrf_id=None, ratio_k=None):
     """descriptor: 'fpfh' / 'shot' / 'rops' (or the LGR_DESCRIPTOR_* value).  lrf_id None: the frames built for the descriptor
-    (LRF_GRAVITY for RoPS, LRF_DEFAULT otherwise)."""
+    (LRF_GRAVITY for RoPS, LRF_DEFAULT otherwise).  ratio_k (MATCH_RATIO only): the list length of the ratio test, None = 2."""
     f = FeatureParams()
     _lib.lgr_default_feature_params(C.byref(f))
     f.descriptor_id = {"fpfh": DESCRIPTOR_FPFH, "shot": DESCRIPTOR_SHOT, "rops": DESCRIPTOR_ROPS}.get(descriptor, descriptor)
     if lrf_id is None:
         lrf_id = LRF_GRAVITY if f.descriptor_id == DESCRIPTOR_ROPS else LRF_DEFAULT
     f.lrf_id = int(lrf_id)
+    if ratio_k is not None:
+        f.ratio_k = int(ratio_k)
     return f
 
 
@@ -673,6 +676,38 @@ class Context:
         q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
         idx = np.zeros((q.shape[0], max(int(k), 0)), np.int32); dist = np.zeros((q.shape[0], max(int(k), 0)), np.float32)
         self.check(_lib.lgr_match_knn(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    # ---- the ratio test on a query's k-nearest list (MATCH_RATIO): on a table, and fused into the sweep ------------------------------
+    def ratio_test(self, knn_idx, knn_dist, threshold=MATCHING_RATIO_THRESHOLD):
+        """cuda int32 / float32 [mq, k] lists of match_knn -> (idx int32 [mq], dist float32 [mq]): a list's first entry iff the list
+        has k entries and dist[0] * threshold < dist[k - 1] (f32, strict), else -1 / 0."""
+        torch = self.torch
+        ki = knn_idx.contiguous(); kd = knn_dist.contiguous()
+        idx = self.empty((ki.shape[0],), torch.int32); dist = self.empty((ki.shape[0],), torch.float32)
+        self.check(_lib.lgr_ratio_test_dev(self.h, _ptr(ki), _ptr(kd), ki.shape[0], int(ki.shape[1]), C.c_float(threshold), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def ratio_test_host(self, knn_idx, knn_dist, threshold=MATCHING_RATIO_THRESHOLD):
+        ki = np.ascontiguousarray(knn_idx, np.int32); kd = np.ascontiguousarray(knn_dist, np.float32)
+        idx = np.zeros(ki.shape[0], np.int32); dist = np.zeros(ki.shape[0], np.float32)
+        self.check(_lib.lgr_ratio_test(self.h, _ptr(ki), _ptr(kd), ki.shape[0], int(ki.shape[1]), C.c_float(threshold), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match_ratio(self, q, t, block=10000, k=2, threshold=MATCHING_RATIO_THRESHOLD):
+        """match_knn and ratio_test in one sweep (the [mq, k] table is never written): (idx int32 [mq], dist float32 [mq])"""
+        torch = self.torch
+        q = q.contiguous(); t = t.contiguous()
+        idx = self.empty((q.shape[0],), torch.int32); dist = self.empty((q.shape[0],), torch.float32)
+        self.check(_lib.lgr_match_ratio_dev(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), int(k), C.c_float(threshold),
+                                            _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match_ratio_host(self, q, t, block=10000, k=2, threshold=MATCHING_RATIO_THRESHOLD):
+        q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
+        idx = np.zeros(q.shape[0], np.int32); dist = np.zeros(q.shape[0], np.float32)
+        self.check(_lib.lgr_match_ratio(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), int(k), C.c_float(threshold),
+                                        _ptr(idx), _ptr(dist)))
         return idx, dist
 
     def vote_matches(self, cand_idx, cand_dist, train_pts, iss_radius):

@@ -259,10 +259,19 @@ def read_correspondences(csv_path):
     return np.array(rows, dtype=[("index_query", "<i4"), ("index_match", "<i4"), ("distance", "<f4"), ("threshold", "<f4")])
 
 
-def results_row(**kw):
+def matching_name(matching, ratio_k=2):
+    """the matching id as file names and results.csv carry it (constructName src/common.cpp:1195-1196, operator<< src/analysis.cpp:304-305):
+    'ratio' is followed by ratio_k, every other id stands as it is"""
+    return matching + str(int(ratio_k)) if matching == "ratio" else matching
+
+
+def results_row(ratio_k=2, **kw):
     """One row of results.csv in the column order of printAnalysisHeader (src/analysis.cpp:295-328); missing columns
-    stay empty (as feature_radius does in the reference when unset)."""
+    stay empty (as feature_radius does in the reference when unset).  ratio_k is no column: matching_type 'ratio' is written
+    as matching_name does."""
     cols = RESULTS_HEADER.split(",")
+    if isinstance(kw.get("matching_type"), str):
+        kw["matching_type"] = matching_name(kw["matching_type"], ratio_k)
     unknown = set(kw) - set(cols)
     if unknown:
         raise KeyError(sorted(unknown))

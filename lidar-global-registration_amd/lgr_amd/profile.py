@@ -14,7 +14,7 @@ default_params(**kw) with the same field names, which is what lets a parity test
 """
 import numpy as np
 
-MATCHING = {"lr": 0, "one_sided": 1, "cluster": 2}
+MATCHING = {"lr": 0, "one_sided": 1, "cluster": 2, "ratio": 3}
 METRIC = {"correspondences": 0, "uniformity": 1, "closest_plane": 2, "combination": 3, "weighted_closest_plane": 4}
 WEIGHT = {"constant": 0, "exp_curvature": 1, "curvedness": 2, "harris": 3, "tomasi": 4, "curvature": 5, "nss": 6}   # weighted_closest_plane: capi.metric_params(weight)
 SCORE = {"constant": 0, "mae": 1, "mse": 2, "exp": 3}

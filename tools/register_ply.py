@@ -41,6 +41,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lidar-global-registration_amd"))
 
 
+def _descriptor(capi, a, lrf, as_struct=False):
+    """the descriptor argument of the Context calls: the plain name for FPFH, else the feature-parameter struct (which carries ratio_k)"""
+    if a.descriptor == "fpfh" and a.matching != "ratio" and not as_struct:
+        return a.descriptor
+    return capi.feature_params(a.descriptor, lrf_id=lrf, ratio_k=a.ratio_k if a.matching == "ratio" else None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("source"); ap.add_argument("target")
@@ -49,7 +56,9 @@ def main():
                                                                     "weighted_closest_plane"])
     ap.add_argument("--weight", default="constant", choices=["constant", "exp_curvature", "curvedness", "curvature", "nss"],
                     help="point weights of weighted_closest_plane (src/weights.cpp)")
-    ap.add_argument("--matching", default="cluster", choices=["lr", "one_sided", "cluster"])
+    ap.add_argument("--matching", default="cluster", choices=["lr", "one_sided", "cluster", "ratio"])
+    ap.add_argument("--ratio-k", type=int, default=2, metavar="K",
+                    help="--matching ratio: the test compares a key point's nearest row with its K-th nearest, 2 .. 8 (threshold 1.1)")
     ap.add_argument("--alignment", default="ransac", choices=["ransac", "gror"])
     ap.add_argument("--randomness", type=int, default=1, metavar="K",
                     help="matches kept per key point and level before the proximity vote, 1 .. 8 (include/matching.h:612-625, :327-352)")
@@ -79,6 +88,10 @@ def main():
         ap.error("--measure takes 1 .. 64 runs")
     if not 1 <= a.randomness <= 8:
         ap.error("--randomness takes 1 .. 8")
+    if not 2 <= a.ratio_k <= 8:
+        ap.error("--ratio-k takes 2 .. 8")
+    if a.matching == "ratio" and a.randomness != 1:
+        ap.error("--matching ratio needs --randomness 1")
     if not 0 <= a.refine <= 1024:
         ap.error("--refine takes 0 .. 1024 steps")
     if a.metrics_csv and not a.ground_truth:
@@ -105,9 +118,9 @@ def main():
     t = time.perf_counter()
     lrf = {"default": capi.LRF_DEFAULT, "gravity": capi.LRF_GRAVITY}[a.lrf]
     if a.metric == "weighted_closest_plane":
-        res = ctx.align_ex2(clouds[0], clouds[1], p, descriptor=capi.feature_params(a.descriptor, lrf_id=lrf), mparams=capi.metric_params(a.weight))
+        res = ctx.align_ex2(clouds[0], clouds[1], p, descriptor=_descriptor(capi, a, lrf, True), mparams=capi.metric_params(a.weight))
     else:
-        res = ctx.align(clouds[0], clouds[1], p, descriptor=a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf))
+        res = ctx.align(clouds[0], clouds[1], p, descriptor=_descriptor(capi, a, lrf))
     dt = time.perf_counter() - t
     T = res.matrix()
     print(f"aligned in {1e3 * dt:.1f} ms: converged={res.converged} correspondences={res.n_correspondences} inliers={res.n_inliers} "
@@ -136,7 +149,7 @@ def measure(ctx, capi, formats, a, p, clouds, name, lrf):
     mp = capi.metric_params(a.weight) if a.metric == "weighted_closest_plane" else None
     t = time.perf_counter()
     m, runs = ctx.measure(clouds[0], clouds[1], p, T_gt, n_times=a.measure, seeds=[s0 + i for i in range(a.measure)],
-                          descriptor=capi.feature_params(a.descriptor, lrf_id=lrf), mparams=mp)
+                          descriptor=_descriptor(capi, a, lrf, True), mparams=mp)
     dt = time.perf_counter() - t
     deg = 180.0 / np.pi
     print(f"\nmeasured {m.n_times} runs in {1e3 * dt:.1f} ms (one correspondence search: {1e3 * runs[0].result.time_cs:.1f} ms):")
@@ -180,7 +193,7 @@ def refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
 def hypotheses(ctx, capi, formats, a, p, clouds, lrf):
     """the set of distinct hypotheses of the same correspondences (lgr_ransac_multi), and with --debug-dir compareOverlaps over its members"""
     src, tgt = clouds
-    desc = a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf)
+    desc = _descriptor(capi, a, lrf)
     corr = ctx.correspondences(src, tgt, p, descriptor=desc)
     t = time.perf_counter()
     res, hyps, best = ctx.ransac_multi(src, tgt, corr, p, max_set=a.hypotheses)
@@ -222,7 +235,7 @@ def debug_files(ctx, capi, formats, a, p, clouds, T, lrf):
     maps = {"temperature": ctx.temperature_maps(src, tgt, T, p.distance_thr)}
     if T_gt is not None:
         maps["temperature_gt"] = ctx.temperature_maps(src, tgt, T_gt, p.distance_thr)
-    desc = a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf)
+    desc = _descriptor(capi, a, lrf)
     corr = ctx.correspondences(src, tgt, p, descriptor=desc).cpu().numpy().view(capi.CORR_DTYPE).reshape(-1)
     # metric_estimator->buildInliers(tn, inliers, error, rand) in the estimator's dense form
     if a.metric in ("closest_plane", "weighted_closest_plane"):
@@ -264,7 +277,7 @@ def analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
     from lgr_amd import profile
     T_gt = formats.get_transformation(a.ground_truth[0], a.ground_truth[1])
     score = {v: k for k, v in profile.SCORE.items()}[p.score_id]
-    desc = a.descriptor if a.descriptor == "fpfh" else capi.feature_params(a.descriptor, lrf_id=lrf)
+    desc = _descriptor(capi, a, lrf)
     # the alignment's own correspondences: lgr_align hands none back, so the search (deterministic) runs once more here
     corr = ctx.correspondences(clouds[0], clouds[1], p, descriptor=desc)
     # metric, rmse, inliers and correct inliers of the final transformation under the run's metric, in the estimator's dense form (start:
@@ -295,7 +308,7 @@ def analyse(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
         version="lgr_amd", descriptor=a.descriptor, testname=name, metric=metric, rmse=rmse, correspondences=e.n_correspondences,
         correct_correspondences=e.n_correct_correspondences, inliers=n_inl, correct_inliers=m.n_correct_inliers,
         nr_points=p.feature_nr_points, distance_thr=p.distance_thr, edge_thr=p.edge_thr_coef, iteration=res.iterations,
-        matching_type=a.matching, randomness=p.randomness, r_err=e.r_err, t_err=e.t_err, pcd_err=e.pcd_err, normal_diff=e.normal_diff,
+        matching_type=a.matching, ratio_k=a.ratio_k, randomness=p.randomness, r_err=e.r_err, t_err=e.t_err, pcd_err=e.pcd_err, normal_diff=e.normal_diff,
         corr_uniformity=e.corr_uniformity, lrf_type=a.lrf, metric_type=a.metric, overlap_rmse=e.overlap_rmse, alignment_type=a.alignment,
         keypoint_type=a.keypoint, time_cs=res.time_cs, time_te=res.time_te, score_type=score, iss_radius_src=p.iss_radius_src,
         iss_radius_tgt=p.iss_radius_tgt, normal_nr_points=p.normal_nr_points, reestimate=0,   # (the device path has no frame re-estimation)
