@@ -614,6 +614,21 @@ int lgr_ransac_multi_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tg
                          const lgr_params*, int max_set, lgr_result* res, lgr_hypothesis* out /* host, max_set */, int* n_out, int* best_index);
 int lgr_ransac_multi(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
                      const lgr_params*, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index);
+/* lgr_ransac_multi* for all five metrics, with the metric parameters of weighted_closest_plane where lgr_ransac_ex* takes them (NULL: the
+ * defaults; read under that metric only, harris and tomasi LGR_ERR_UNSUPPORTED before any work; host weights for the host entry, device
+ * weights for the _dev one).  uniformity / correspondences: lgr_ransac_multi*'s bytes.  Under a plane metric the fields of a member mean
+ * what lgr_result's mean after lgr_ransac_ex*: n_inliers = plane inliers (closest_plane, weighted_closest_plane) or correspondence inliers
+ * (combination), loop_metric / metric = the estimator's metric; an item of the fold is an iteration that survives prerejection with >=
+ * MIN_NR_INLIERS of those inliers, scored on the sparse subset its iteration keys (never abandoned part-way: the second pass runs without
+ * the loop's gate), the guess is scored under counter 0xFFFFFFFD, and the final block of a member is lgr_ransac_ex_dev's (counters
+ * 0xFFFFFFFE / 0xFFFFFFFF, the refit over the plane pairs in ascending source index or, combination, over the correspondence inliers),
+ * run on the device for every member with one read-back for all.  lgr_ransac_last_plane_gate reports the loop's numbers.  alignment_id =
+ * gror stays LGR_ERR_UNSUPPORTED. */
+int lgr_ransac_multi_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                            const lgr_params*, const lgr_metric_params*, int max_set, lgr_result* res, lgr_hypothesis* out /* host, max_set */,
+                            int* n_out, int* best_index);
+int lgr_ransac_multi_ex(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                        const lgr_params*, const lgr_metric_params*, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index);
 
 /* ---- include/analysis.h:36-98 AlignmentAnalysis::start(transformation_gt, testname) (src/analysis.cpp:218-246): a transformation judged
  *      against a known ground truth.  What the reference leaves unordered (OpenMP reductions, kd-tree ties) has the declared orders of

@@ -129,7 +129,7 @@ enum {
     WS_GT_MISC, WS_GT_TERMS, WS_GT_ALIGNED, WS_GT_OVERLAP, WS_GT_FLAGS, WS_GT_KNN, WS_GT_DENS, WS_GT_CORR,   // lgr_analysis.hip
     WS_PD_TERMS, WS_PD_MISC, WS_PD_INLIERS, WS_PD_MASK,   // lgr_plane_dense.hip
     WS_DBG_MISC, WS_DBG_MOVED, WS_DBG_FLAGS, WS_DBG_OVERLAP, WS_DBG_DENS, WS_DBG_SORT, WS_DBG_HOST_A, WS_DBG_HOST_B,   // lgr_debug.hip
-    WS_HYP_SET, WS_HYP_ITEMS, WS_HYP_FINAL,   // lgr_hypotheses.hip, lgr_ransac_multi_dev
+    WS_HYP_SET, WS_HYP_ITEMS, WS_HYP_FINAL, WS_HYP_PLANE,   // lgr_hypotheses.hip, lgr_ransac_multi*_dev
     WS_RF_STATE, WS_RF_TERMS, WS_RF_PAIRS, WS_RF_TRACE,   // lgr_refine.hip
     WS_KNN_PART_A, WS_KNN_PART_B, WS_KNN_FLAG, WS_KNN_CAND_IJ, WS_KNN_CAND_JI,   // lgr_match_knn.hip; the pipeline's candidate lists
     WS_GTB_MISC, WS_GTB_FOOT, WS_GTB_TERMS,   // lgr_analysis.hip: lgr_evaluate_gt_batch_dev

@@ -12,7 +12,8 @@
 // Float sequences restate the oracle op for op (oracle/src/orc_ransac.cpp); compiled with -ffp-contract=off.
 // The loop itself runs from the device for all five metrics (RState, ransac_device_schedule below; rounds 4-5).  Uniformity / correspondences:
 // the host enqueues two rounds and the final block blind and reads one record -- one synchronisation per alignment.  The plane metrics: the
-// same rounds with the plane evaluation in them (a hypothesis's sparse subset is keyed by its iteration), then a host-driven final block.
+// same rounds with the plane evaluation in them (a hypothesis's sparse subset is keyed by its iteration), then a host-driven final block
+// (lgr_ransac_ex_dev) -- or, for the set of distinct hypotheses (lgr_ransac_multi_ex_dev), a final block per member that stays on the device.
 // This file is the host side; the kernels are in lgr_ransac_common.cuh (sampling, hypotheses), lgr_ransac_count.cuh (packing, phase 1),
 // lgr_ransac_metric.cuh (phase 2, refit) and lgr_ransac_schedule.cuh (the device-driven loop), all one translation unit.
 #include <algorithm>
@@ -385,8 +386,10 @@ static int metric_candidates(lgr_ctx* ctx, const LoopBuffers& L, const Packed& p
 
 // The front of a round, behind whatever set the round's range and gate in the RState (rs_begin in the loop, mh_begin in the second pass):
 // hypotheses -> inlier counts -> candidates -> their metric in b.metric / b.ninl.  nb_up: an upper bound of the round's iterations.
+// gated = false (the second pass of lgr_ransac_multi_ex_dev): the plane evaluation runs every subset to its end -- the values of an abandoned
+// hypothesis are partial and timing dependent, and an item of the fold must be exact; dS->final_metric / dS->largest are not read then.
 static int enqueue_round_front(lgr_ctx* ctx, const LoopBuffers& L, const Packed& pk, int c, const lgr_params* p, uint64_t seed, int nb_up,
-                               const lgr_plane_dev* plane) {
+                               const lgr_plane_dev* plane, bool gated = true) {
     const BatchBuffers& b = L.b;
     RState* const dS = L.dS;
     const bool closest = plane && (p->metric_id == LGR_METRIC_CLOSEST_PLANE || p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE);
@@ -395,8 +398,8 @@ static int enqueue_round_front(lgr_ctx* ctx, const LoopBuffers& L, const Packed&
     count_list_kernel<<<L.g_count, CB, 0, ctx->stream>>>(b.Ts, b.list, &dS->n_ok, pk.PP, pk.pstats, c, b.counts, L.maskT, L.mask_cap);
     if (closest) {
         // every survivor on its sparse subset; its plane inliers are "the inliers" (gate: the loop's best metric and record so far)
-        const lgr_plane_dyn dyn{&dS->n_ok, &dS->round_first, &dS->final_metric, &dS->largest, &dS->n_gated};
-        LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list, nb_up, 0u, p->score_id, L.pl_cnt, L.pl_cp, nullptr, nullptr, nullptr, 0.f, 0, nullptr, &dyn));
+        const lgr_plane_dyn dyn{&dS->n_ok, &dS->round_first, gated ? &dS->final_metric : nullptr, gated ? &dS->largest : nullptr, gated ? &dS->n_gated : nullptr};
+        LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list, nb_up, 0u, p->score_id, L.pl_cnt, L.pl_cp, nullptr, nullptr, nullptr, 0.f, gated ? 0 : 0x7fffffff, nullptr, &dyn));
         rs_plane_counts_kernel<<<64, 256, 0, ctx->stream>>>(dS, L.pl_cnt, b.counts);
     }
     rs_cand_kernel<<<64, 1024, 0, ctx->stream>>>(dS, b.counts, b.list, b.list2, b.hpos);
@@ -404,8 +407,8 @@ static int enqueue_round_front(lgr_ctx* ctx, const LoopBuffers& L, const Packed&
         rs_plane_pick_kernel<<<64, 256, 0, ctx->stream>>>(dS, b.hpos, L.pl_cnt, L.pl_cp, b.metric, b.ninl);
     } else if (plane) {   // combination: correspondences metric with the constant score (include/metric.h:191-192) x plane metric of the candidates
         LGR_TRY(metric_candidates(ctx, L, pk, c, LGR_METRIC_CORRESPONDENCES, LGR_SCORE_CONSTANT));
-        const lgr_plane_dyn dyn{&dS->n_cand, &dS->round_first, &dS->final_metric, &dS->int_max, &dS->n_gated};   // (records are correspondence counts here: only the metric gates)
-        LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list2, nb_up, 0u, p->score_id, L.pl_cnt, L.pl_cp, nullptr, nullptr, nullptr, 0.f, 0x7fffffff, b.metric, &dyn));
+        const lgr_plane_dyn dyn{&dS->n_cand, &dS->round_first, gated ? &dS->final_metric : nullptr, gated ? &dS->int_max : nullptr, gated ? &dS->n_gated : nullptr};   // (records are correspondence counts here: only the metric gates)
+        LGR_TRY(lgr_plane_eval(ctx, *plane, b.Ts, b.list2, nb_up, 0u, p->score_id, L.pl_cnt, L.pl_cp, nullptr, nullptr, nullptr, 0.f, 0x7fffffff, gated ? b.metric : nullptr, &dyn));
         rs_plane_mul_kernel<<<64, 256, 0, ctx->stream>>>(dS, b.metric, L.pl_cp);
     } else {
         LGR_TRY(metric_candidates(ctx, L, pk, c, p->metric_id, p->score_id));
@@ -819,13 +822,42 @@ extern "C" int lgr_choose_best_hypothesis(lgr_ctx* ctx, const float* src, int ns
     return lgr_choose_best_hypothesis_dev(ctx, ds, ns, dt, nt, dc, c, tns16, n, T_out16, best_index, uniformities);
 }
 
+// The scratch of the single-transform evaluations under a plane metric that stay on the device (the hypothesis set's guess and final
+// blocks): a slot of its own, WS_PLANE_OUT being the loop's at another size (loop_buffers).
+struct PlaneScratch {
+    int* pl;            // the plane test's outputs: inlier count, metric, rmse, number of pairs
+    float* guess;       // the guess's evaluation record (metric, inliers, rmse) and a word that stays 0
+    int2* pairs;        // the plane pairs in arrival order, n_sp
+    float4 *P0, *P1;    // ... and their points in ascending source index, n_sp each
+};
+static int plane_scratch(lgr_ctx* ctx, const lgr_plane_dev& plane, PlaneScratch* s) {
+    const size_t n1 = (size_t) std::max(plane.n_sp, 1);
+    float4* base;
+    LGR_TRY(lgr_ws_t(ctx, WS_HYP_PLANE, 2 + (n1 + 1) / 2 + 2 * n1, &base));
+    s->pl = (int*) base; s->guess = (float*) (base + 1); s->pairs = (int2*) (base + 2);
+    s->P0 = base + 2 + (n1 + 1) / 2; s->P1 = s->P0 + n1;
+    return LGR_OK;
+}
+// evaluate_one_plane without a read-back: (metric, n_inl bits, rmse) -> d_out3; the plane pairs stay in s.pairs, their number in s.pl[3]
+static int evaluate_one_plane_dev(lgr_ctx* ctx, const float* d_T, const Packed& pk, int c, int metric_id, int score_id, uint8_t* d_mask,
+                                  const lgr_plane_dev& plane, unsigned counter, bool want_pairs, const PlaneScratch& s, float* d_scratch3, float* d_out3) {
+    LGR_TRY(lgr_plane_eval(ctx, plane, d_T, nullptr, 1, counter, score_id, s.pl, (float*) (s.pl + 1), (float*) (s.pl + 2), want_pairs ? s.pairs : nullptr, s.pl + 3));
+    const bool combination = metric_id == LGR_METRIC_COMBINATION;
+    if (combination) LGR_TRY(evaluate_one_dev(ctx, d_T, pk, c, LGR_METRIC_CORRESPONDENCES, LGR_SCORE_CONSTANT, d_mask, d_scratch3, d_out3));
+    mh_plane_store_kernel<<<1, 64, 0, ctx->stream>>>(s.pl, d_out3, combination ? 1 : 0);
+    LGR_HIP(ctx, hipGetLastError());
+    return LGR_OK;
+}
+
 // the set of distinct hypotheses: the loop, then a second pass over its iterations (the mh_* kernels, lgr_ransac_schedule.cuh) and the fold
-extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
-                                    const lgr_params* p, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index) {
-    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
-    if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_TRY(check_params(ctx, p));
-    LGR_CHECK(ctx, p->metric_id == LGR_METRIC_UNIFORMITY || p->metric_id == LGR_METRIC_CORRESPONDENCES, LGR_ERR_UNSUPPORTED);
+static int ransac_multi_impl(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                             const lgr_params* p, const lgr_metric_params* mp, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out,
+                             int* best_index) {
+    const bool weighted = p->metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE;
+    if (weighted && mp && !mp->weights) {   // refused before any work, as lgr_ransac_ex_dev does
+        LGR_CHECK(ctx, mp->weight_id >= LGR_WEIGHT_CONSTANT && mp->weight_id <= LGR_WEIGHT_NSS, LGR_ERR_INVALID_ARG);
+        LGR_CHECK(ctx, mp->weight_id != LGR_WEIGHT_HARRIS && mp->weight_id != LGR_WEIGHT_TOMASI, LGR_ERR_UNSUPPORTED);
+    }
     LGR_CHECK(ctx, p->alignment_id == LGR_ALIGN_RANSAC, LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, max_set >= 1 && max_set <= LGR_HYPOTHESES_MAX, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, d_src && d_tgt && (d_corr || c == 0) && res && out && n_out && best_index && c >= 0 && ns > 0 && nt > 0, LGR_ERR_INVALID_ARG);
@@ -843,21 +875,47 @@ extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, co
     const int batch = std::max(1, p->ransac_batch);
     uint8_t* d_mask;
     LGR_TRY(lgr_ws_t(ctx, WS_RANSAC_MASK, (size_t) c + 16, &d_mask));
+    RansacMisc* M;
+    LGR_TRY(ransac_misc(ctx, &M));
+    const bool closest = p->metric_id == LGR_METRIC_CLOSEST_PLANE || weighted;   // (the plane pairs feed the refit)
+    const bool planar = closest || p->metric_id == LGR_METRIC_COMBINATION;
+    lgr_plane_dev plane;
+    PlaneScratch ps{};
     // the hypothesis set is always built on the launch chain (as the plane metrics are); the loop's final block is enqueued and unused
     RState loop;
-    LGR_TRY(ransac_device_schedule(ctx, d_src, d_tgt, d_corr, c, pk, p, seed, max_iterations, batch, LGR_RANSAC_SCHEDULE_CHAIN, nullptr, 0.f, d_mask, &loop));
+    if (planar) {
+        // as lgr_ransac_ex_dev: the estimator's set-up, the guess's evaluation (it is the metric to beat, and the first item below), the loop
+        ctx->plane_gate[0] = ctx->plane_gate[1] = 0;
+        LGR_TRY(lgr_plane_setup(ctx, d_src, ns, d_tgt, nt, seed, &plane));
+        if (weighted) LGR_TRY(lgr_weights_prepare(ctx, d_src, ns, mp, &plane.w, &plane.w_sum, &plane.w_gate));
+        LGR_TRY(plane_scratch(ctx, plane, &ps));
+        LGR_HIP(ctx, hipMemsetAsync(ps.pl, 0, 32, ctx->stream));
+        float guess_metric = 0.f;
+        if (p->has_guess) {
+            LGR_HIP(ctx, hipMemcpyAsync(M->T, p->guess, 64, hipMemcpyHostToDevice, ctx->stream));
+            LGR_TRY(evaluate_one_plane_dev(ctx, M->T, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFDu, false, ps, M->ev, ps.guess));
+            float* hg;
+            LGR_TRY(lgr_pinned(ctx, 64, (void**) &hg));
+            LGR_HIP(ctx, hipMemcpyAsync(hg, ps.guess, 4, hipMemcpyDeviceToHost, ctx->stream));
+            LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            guess_metric = hg[0];
+        }
+        LGR_TRY(ransac_device_schedule(ctx, d_src, d_tgt, d_corr, c, pk, p, seed, max_iterations, batch, LGR_RANSAC_SCHEDULE_CHAIN, &plane, guess_metric, nullptr, &loop));
+        ctx->plane_gate[0] = (unsigned) (closest ? loop.tot_ok : loop.tot_cand);   // the loop's numbers: the second pass is ungated and adds nothing
+        ctx->plane_gate[1] = (unsigned) loop.n_gated;
+    } else {
+        LGR_TRY(ransac_device_schedule(ctx, d_src, d_tgt, d_corr, c, pk, p, seed, max_iterations, batch, LGR_RANSAC_SCHEDULE_CHAIN, nullptr, 0.f, d_mask, &loop));
+    }
     fill_result(res, loop, nullptr, false, 0, 0.f);
     const int iterations = loop.done;
     const float m_star = loop.final_metric;
 
     // ---- second pass: the loop's own working set, the items of a round, the set
     LoopBuffers L;
-    LGR_TRY(loop_buffers(ctx, p, c, max_iterations, batch, nullptr, &L));
+    LGR_TRY(loop_buffers(ctx, p, c, max_iterations, batch, planar ? &plane : nullptr, &L));
     const BatchBuffers& b = L.b;
     const int nb_max = L.nb_max;
     RState* const dS = L.dS;
-    RansacMisc* M;
-    LGR_TRY(ransac_misc(ctx, &M));
     float* item_T;
     LGR_TRY(lgr_ws_t(ctx, WS_HYP_ITEMS, (size_t) nb_max * 19 + 16, &item_T));
     float* item_m = item_T + (size_t) nb_max * 16;
@@ -866,7 +924,10 @@ extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, co
     int* d_n_items = kslot + nb_max;
     lgr_fold_set set;
     LGR_TRY(lgr_fold_begin(ctx, max_set, &set));
-    if (p->has_guess) {
+    if (p->has_guess && planar) {
+        // :139-143 the guess is the first item, with the metric of its evaluation in front of the loop (counter 0xFFFFFFFD), no inlier gate
+        LGR_TRY(lgr_fold_launch(ctx, set, M->T, ps.guess, nullptr, -1, 1, nullptr, p->distance_thr));
+    } else if (p->has_guess) {
         // :139-143 the guess is the first item: the metric `evaluate` gives it, no inlier gate
         LGR_HIP(ctx, hipMemcpyAsync(M->T, p->guess, 64, hipMemcpyHostToDevice, ctx->stream));
         LGR_TRY(evaluate_one_dev(ctx, M->T, pk, c, p->metric_id, p->score_id, d_mask, L.d_ev, L.d_ev + 4));
@@ -877,7 +938,7 @@ extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, co
         const int nb = std::min(nb_max, iterations - first);
         mh_begin_kernel<<<1, 64, 0, ctx->stream>>>(dS, first, nb, gate_metric, p->metric_id, c);
         LGR_HIP(ctx, hipMemsetAsync(kslot, 0xff, (size_t) nb * 4, ctx->stream));
-        LGR_TRY(enqueue_round_front(ctx, L, pk, c, p, seed, nb, nullptr));
+        LGR_TRY(enqueue_round_front(ctx, L, pk, c, p, seed, nb, planar ? &plane : nullptr, false));
         mh_keep_kernel<<<64, 256, 0, ctx->stream>>>(dS, b.list2, b.metric, m_star, kslot);
         mh_order_kernel<<<1, 1024, 0, ctx->stream>>>(dS, kslot, b.Ts, b.metric, item_T, item_m, item_it, d_n_items);
         LGR_HIP(ctx, hipGetLastError());
@@ -918,7 +979,22 @@ extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, co
         LGR_HIP(ctx, hipMemcpyAsync(d_loopT + (size_t) k * 16, out[k].loop_transformation, 64, hipMemcpyHostToDevice, ctx->stream));
         float* f = fin + (size_t) k * 12;
         float* Tn = d_Tn + (size_t) k * 16;
-        LGR_TRY(enqueue_final_block(ctx, pk, c, p, d_loopT + (size_t) k * 16, d_mask, Tn, f, f + 4));
+        if (planar) {
+            // evaluation under counter 0xFFFFFFFE, refit, evaluation under 0xFFFFFFFF, as lgr_ransac_ex_dev's final block -- without its host
+            const float* Tl = d_loopT + (size_t) k * 16;
+            LGR_TRY(evaluate_one_plane_dev(ctx, Tl, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFEu, closest, ps, L.d_ev, f));
+            if (closest) {
+                // estimateOptimalRigidTransformation over the plane pairs in ascending source index, their number read on the device
+                mh_plane_rank_pack_kernel<<<std::max(1, cdiv(plane.n_sp, 256)), 256, 0, ctx->stream>>>(d_src, d_tgt, ps.pairs, ps.pl + 3, ps.P0, ps.P1);
+                refit_kernel<<<1, 256, 0, ctx->stream>>>(ps.P0, ps.P1, 0, Tn, ps.pl + 3, (const int*) (ps.guess + 3));
+                LGR_HIP(ctx, hipGetLastError());
+            } else {
+                LGR_TRY(refit_launch(ctx, pk, c, d_mask, Tn));
+            }
+            LGR_TRY(evaluate_one_plane_dev(ctx, Tn, pk, c, p->metric_id, p->score_id, d_mask, plane, 0xFFFFFFFFu, false, ps, L.d_ev, f + 4));
+        } else {
+            LGR_TRY(enqueue_final_block(ctx, pk, c, p, d_loopT + (size_t) k * 16, d_mask, Tn, f, f + 4));
+        }
         LGR_TRY(evaluate_one_dev(ctx, Tn, pk, c, LGR_METRIC_UNIFORMITY, LGR_SCORE_MSE, d_mask, L.d_ev, f + 8));
     }
     if (n_set) {
@@ -949,6 +1025,24 @@ extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, co
     return LGR_OK;
 }
 
+// the two metrics lgr_ransac_multi* has always taken; the _ex entries take all five
+extern "C" int lgr_ransac_multi_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                                    const lgr_params* p, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_TRY(check_params(ctx, p));
+    LGR_CHECK(ctx, p->metric_id == LGR_METRIC_UNIFORMITY || p->metric_id == LGR_METRIC_CORRESPONDENCES, LGR_ERR_UNSUPPORTED);
+    return ransac_multi_impl(ctx, d_src, ns, d_tgt, nt, d_corr, c, p, nullptr, max_set, res, out, n_out, best_index);
+}
+extern "C" int lgr_ransac_multi_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c,
+                                       const lgr_params* p, const lgr_metric_params* mp, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out,
+                                       int* best_index) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_TRY(check_params(ctx, p));
+    return ransac_multi_impl(ctx, d_src, ns, d_tgt, nt, d_corr, c, p, mp, max_set, res, out, n_out, best_index);
+}
+
 extern "C" int lgr_ransac_multi(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
                                 const lgr_params* p, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out, int* best_index) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
@@ -959,4 +1053,18 @@ extern "C" int lgr_ransac_multi(lgr_ctx* ctx, const float* src, int ns, const fl
     lgr_corr* dc;
     LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
     return lgr_ransac_multi_dev(ctx, ds, ns, dt, nt, dc, c, p, max_set, res, out, n_out, best_index);
+}
+extern "C" int lgr_ransac_multi_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
+                                   const lgr_params* p, const lgr_metric_params* mp, int max_set, lgr_result* res, lgr_hypothesis* out, int* n_out,
+                                   int* best_index) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, max_set >= 1 && max_set <= LGR_HYPOTHESES_MAX, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, src && tgt && (corr || c == 0) && res && ns > 0 && nt > 0 && c >= 0, LGR_ERR_INVALID_ARG);
+    float *ds, *dt;
+    lgr_corr* dc;
+    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
+    lgr_metric_params mpd;
+    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
+    return lgr_ransac_multi_ex_dev(ctx, ds, ns, dt, nt, dc, c, p, mp, max_set, res, out, n_out, best_index);
 }

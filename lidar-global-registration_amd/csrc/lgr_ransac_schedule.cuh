@@ -1,6 +1,6 @@
 // lgr_ransac_schedule.cuh -- the loop of the prerejective RANSAC driven from the device: its state (RState), the bodies and kernels of a
 // round's phases (rs_begin, rs_hyp, rs_cand, rs_replay), the resident kernel that runs them behind grid barriers, the plane metrics'
-// rs_plane_* kernels and the second pass' mh_* kernels (the set of distinct hypotheses).
+// rs_plane_* kernels and the second pass' mh_* kernels (the set of distinct hypotheses; mh_plane_*: its final block under a plane metric).
 // Part of lgr_ransac.hip's one translation unit; see its header for the schedule and DESIGN.md section 5.
 #pragma once
 #include <climits>
@@ -419,5 +419,48 @@ __global__ __launch_bounds__(1024) void mh_order_kernel(const RState* __restrict
         total += tot;
     }
     if (tid == 0) n_items[0] = total;
+}
+
+// The final block of a member under closest_plane / weighted_closest_plane refits over the plane pairs (source point, nearest target point) in
+// ASCENDING SOURCE INDEX; plane_kernel appends them with an atomic.  Source indices within a subset are distinct, so the place of a pair is
+// the number of pairs with a smaller source index: every thread ranks one pair against all n keys, which the workgroup stages through LDS
+// MH_RANK_TILE at a time (every lane reads the same word: a broadcast, no bank conflict), and writes the two points of its pair where
+// plane_pack_kernel would have put them after a sort.  n = *n_pairs lives on the device; the grid covers its upper bound (the subset's
+// size) and workgroups behind n return at once.  O(n^2 / 256) per workgroup, n <= 0.01 |src|: DESIGN.md section 3.1g has the measured cost.
+constexpr int MH_RANK_TILE = 2048;
+__global__ __launch_bounds__(256) void mh_plane_rank_pack_kernel(const float* __restrict__ src, const float* __restrict__ tgt, const int2* __restrict__ pairs,
+                                                                  const int* __restrict__ n_pairs, float4* __restrict__ P0, float4* __restrict__ P1) {
+    __shared__ __align__(16) int keys[MH_RANK_TILE];
+    const int n = *n_pairs, tid = threadIdx.x;
+    const int i = blockIdx.x * 256 + tid;
+    if (blockIdx.x * 256 >= n) return;   // (the whole workgroup)
+    const int2 mine = i < n ? pairs[i] : make_int2(INT_MAX, 0);
+    int rank = 0;
+    for (int t0 = 0; t0 < n; t0 += MH_RANK_TILE) {
+        const int m = min(MH_RANK_TILE, n - t0);
+        __syncthreads();
+        for (int t = tid; t < m; t += 256) keys[t] = pairs[t0 + t].x;
+        __syncthreads();
+        int k = 0;
+        for (; k + 4 <= m; k += 4) {
+            const int4 q = *reinterpret_cast<const int4*>(&keys[k]);
+            rank += (q.x < mine.x) + (q.y < mine.x) + (q.z < mine.x) + (q.w < mine.x);
+        }
+        for (; k < m; ++k) rank += keys[k] < mine.x;
+    }
+    if (i >= n) return;
+    const float* s = src + (size_t) mine.x * 12;
+    const float* t = tgt + (size_t) mine.y * 12;
+    P0[rank] = make_float4(s[0], s[1], s[2], 0.f);
+    P1[rank] = make_float4(t[0], t[1], t[2], 0.f);
+}
+// the record of a single transform's evaluation under a plane metric, from the plane test's outputs pl = (count, metric, rmse):
+// closest_plane / weighted_closest_plane: the plane test's own figures; combination: dst3 holds the correspondences evaluation
+// (metric, inliers, rmse) and its metric takes the plane metric as a factor, in f32 (metric_cs * metric_cp, src/metric.cpp:248)
+__global__ void mh_plane_store_kernel(const int* __restrict__ pl, float* __restrict__ dst3, int combination) {
+    if (threadIdx.x != 0) return;
+    const float cp = __int_as_float(pl[1]);
+    if (combination) { dst3[0] = dst3[0] * cp; return; }
+    dst3[0] = cp; dst3[1] = __int_as_float(pl[0]); dst3[2] = __int_as_float(pl[2]);
 }
 }  // namespace

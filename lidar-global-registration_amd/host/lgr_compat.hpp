@@ -517,9 +517,10 @@ public:
         hypotheses_.assign(LGR_SAVE_MULTIPLE_HYPOTHESES_MAX, lgr_hypothesis{});
         int n = 0;
         best_hypothesis_ = -1;
-        const int rc = lgr_ransac_multi(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(),
-                                        reinterpret_cast<const lgr_corr*>(correspondences_->data()), (int) correspondences_->size(), &a,
-                                        LGR_SAVE_MULTIPLE_HYPOTHESES_MAX, &r, hypotheses_.data(), &n, &best_hypothesis_);
+        lgr_metric_params m = to_metric_abi(parameters_);   // (every metric_id; weight_id is read under weighted_closest_plane)
+        const int rc = lgr_ransac_multi_ex(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(),
+                                           reinterpret_cast<const lgr_corr*>(correspondences_->data()), (int) correspondences_->size(), &a, &m,
+                                           LGR_SAVE_MULTIPLE_HYPOTHESES_MAX, &r, hypotheses_.data(), &n, &best_hypothesis_);
         hypotheses_.resize(rc == LGR_OK ? n : 0);
         check(rc, "SampleConsensusPrerejectiveOMP::align (multiple hypotheses)");
 #else

@@ -952,6 +952,30 @@ class Context:
                                          C.byref(params), int(max_set), C.byref(res), out, C.byref(n), C.byref(bi)))
         return res, [out[i] for i in range(n.value)], bi.value
 
+    def ransac_multi_ex(self, src, tgt, corr, params, max_set=64, metric_params=None):
+        """lgr_ransac_multi_ex_dev: ransac_multi for all five metrics (metric_params: a MetricParams with device weights, None = the
+        defaults; read under weighted_closest_plane only)."""
+        corr = self._corr_dev(corr)
+        res = Result()
+        out = (Hypothesis * max(int(max_set), 1))()
+        n, bi = C.c_int(0), C.c_int(-1)
+        self.check(_lib.lgr_ransac_multi_ex_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), corr.shape[0],
+                                                C.byref(params), C.byref(metric_params) if metric_params is not None else None, int(max_set),
+                                                C.byref(res), out, C.byref(n), C.byref(bi)))
+        return res, [out[i] for i in range(n.value)], bi.value
+
+    def ransac_multi_ex_host(self, src, tgt, corr, params, max_set=64, metric_params=None):
+        """lgr_ransac_multi_ex: clouds, correspondences and (metric_params) weights in host memory."""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        corr = np.ascontiguousarray(corr)
+        res = Result()
+        out = (Hypothesis * max(int(max_set), 1))()
+        n, bi = C.c_int(0), C.c_int(-1)
+        self.check(_lib.lgr_ransac_multi_ex(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr), corr.shape[0],
+                                            C.byref(params), C.byref(metric_params) if metric_params is not None else None, int(max_set),
+                                            C.byref(res), out, C.byref(n), C.byref(bi)))
+        return res, [out[i] for i in range(n.value)], bi.value
+
     def fold_hypotheses(self, tns, metrics, distance_thr, max_set):
         """lgr_fold_hypotheses_dev: updateHypotheses folded over the items in order.  tns: cuda float32 [n, 16] (column-major 4x4 rows),
         metrics: cuda float32 [n] -> (set transforms [m, 16], set metrics [m], source indices [m]) as numpy arrays."""

@@ -4,7 +4,7 @@
     python tools/register_ply.py source.ply target.ply [--keypoint iss|any] [--metric uniformity|combination|...]
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
-                                 [--debug-dir DIR] [--hypotheses N] [--refine N]
+                                 [--debug-dir DIR] [--hypotheses N [--hypotheses-plane]] [--refine N]
                                  [--measure N [--measure-seed S0] [--measurements test_measurements.csv]]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
@@ -22,6 +22,8 @@ transformation; with a ground truth the same six as temperature_gt_* and compare
 With --hypotheses N (ransac, metrics uniformity and correspondences): the loop once more in the reference's SAVE_MULTIPLE_HYPOTHESES mode
 (src/sac_prerejective_omp.cpp:11) through lgr_ransac_multi -- the set of up to N distinct hypotheses, one line per member (id, iteration,
 loop metric, metric after the refit, inliers, uniformity, chosen); with --debug-dir the members also go through compareOverlaps.
+With --hypotheses-plane as well the set is built through lgr_ransac_multi_ex, which takes every metric: closest_plane, combination and
+weighted_closest_plane (with --weight); without it --hypotheses refuses those metrics as it always has.
 With --refine N: after everything above, the found transformation goes through up to N dense closest-plane steps (lgr_refine_plane: inliers,
 refit, evaluation, while the metric rises) under the run's score -- and the run's weights under weighted_closest_plane; the evaluation before
 and after is printed, the refined transformation is appended to --out as a second row named <name>_refined, and with --ground-truth it is
@@ -76,6 +78,8 @@ def main():
     ap.add_argument("--debug-dir", default=None, help="write the files of generateDebugFiles / compareHypotheses (src/main.cpp:207-284) there")
     ap.add_argument("--hypotheses", type=int, default=0, metavar="N",
                     help="also keep the set of up to N distinct hypotheses (ransac with uniformity / correspondences) and list its members")
+    ap.add_argument("--hypotheses-plane", action="store_true",
+                    help="with --hypotheses: build the set through lgr_ransac_multi_ex, which also takes closest_plane, combination and weighted_closest_plane")
     ap.add_argument("--refine", type=int, default=0, metavar="N", help="refine the result by up to N dense closest-plane steps (lgr_refine_plane)")
     ap.add_argument("--measure", type=int, default=0, metavar="N",
                     help="the measure test type: N seeded runs judged against --ground-truth, and their test_measurements.csv row")
@@ -96,8 +100,10 @@ def main():
         ap.error("--refine takes 0 .. 1024 steps")
     if a.metrics_csv and not a.ground_truth:
         ap.error("--metrics-csv needs --ground-truth")
-    if a.hypotheses and (a.alignment != "ransac" or a.metric not in ("uniformity", "correspondences")):
-        ap.error("--hypotheses needs --alignment ransac and --metric uniformity or correspondences")
+    if a.hypotheses_plane and not a.hypotheses:
+        ap.error("--hypotheses-plane needs --hypotheses")
+    if a.hypotheses and (a.alignment != "ransac" or (a.metric not in ("uniformity", "correspondences") and not a.hypotheses_plane)):
+        ap.error("--hypotheses needs --alignment ransac and --metric uniformity or correspondences (any other metric: add --hypotheses-plane)")
 
     import numpy as np
     from lgr_amd import capi, formats, profile
@@ -196,7 +202,11 @@ def hypotheses(ctx, capi, formats, a, p, clouds, lrf):
     desc = _descriptor(capi, a, lrf)
     corr = ctx.correspondences(src, tgt, p, descriptor=desc)
     t = time.perf_counter()
-    res, hyps, best = ctx.ransac_multi(src, tgt, corr, p, max_set=a.hypotheses)
+    if a.hypotheses_plane:
+        mp = capi.metric_params(a.weight) if a.metric == "weighted_closest_plane" else None
+        res, hyps, best = ctx.ransac_multi_ex(src, tgt, corr, p, max_set=a.hypotheses, metric_params=mp)
+    else:
+        res, hyps, best = ctx.ransac_multi(src, tgt, corr, p, max_set=a.hypotheses)
     print(f"{len(hyps)} distinct hypotheses in {1e3 * (time.perf_counter() - t):.1f} ms (iterations={res.iterations} converged={res.converged}):")
     print("\tid\titeration\tloop_metric\tmetric\tinliers\tuniformity\tchosen")
     for k, h in enumerate(hyps):
