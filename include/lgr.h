@@ -375,6 +375,28 @@ int lgr_match_local(lgr_ctx*, const float* query_pts, int mq, const float* train
                     const float guess16[16], float match_search_radius, int32_t* idx, float* dist);
 int lgr_match_local_dev(lgr_ctx*, const float* d_query_pts, int mq, const float* d_train_pts, int mt, const float* d_q33, const float* d_t33,
                         const float guess16[16] /* host */, float match_search_radius, int32_t* d_idx, float* d_dist);
+/* ---- matchLocal<FeatureT> with parameters.randomness = k (:637-678, KNNResult :44-94) on rows of row_len 33 (FPFH), 135 (RoPS135) or
+ *      352 (SHOT: the descriptor floats without the frame, as lgr_match_shot takes them); other lengths and k outside
+ *      1..LGR_RANDOMNESS_MAX: LGR_ERR_UNSUPPORTED.  The moved query point is x*c0 + (y*c1 + (z*c2 + c3)) per coordinate.  A query row is
+ *      valid when all row_len floats are finite; a non-finite moved point has no candidates; a candidate is a finite train point whose
+ *      s = ((dx*dx + dy*dy) + dz*dz) to the moved point satisfies strict s < r*r and whose row is all finite.  Descriptor distance:
+ *      pcl::L2_Norm -- sum = 0; for j ascending: d = q[j] - t[j]; sum += d*d (no contraction); sqrtf.  idx / dist are mq x k: row i
+ *      holds the first k candidates in ascending (distance, s, train index), then -1 / 0.f (KNNResult puts a later equal distance
+ *      behind an earlier one, radiusSearch visits by ascending spatial distance, the index stands for FLANN's unspecified order).
+ *      A radius whose square is not finite (FLT_MAX): every finite train point with a finite s; radius 0: no candidate.  NULL pointers
+ *      with non-zero counts, negative counts, a negative or NaN radius: LGR_ERR_INVALID_ARG, before any work.  mq = 0 writes nothing,
+ *      mt = 0 fills -1 / 0.f.  (row_len 33, k 1) equals lgr_match_local* bit for bit.  guess16: column-major, host. ---- */
+int lgr_match_local_knn(lgr_ctx*, int row_len, const float* query_pts, int mq, const float* train_pts, int mt, const float* q, const float* t,
+                        const float guess16[16], float match_search_radius, int k, int32_t* idx /* mq x k */, float* dist /* mq x k */);
+int lgr_match_local_knn_dev(lgr_ctx*, int row_len, const float* d_query_pts, int mq, const float* d_train_pts, int mt, const float* d_q, const float* d_t,
+                            const float guess16[16] /* host */, float match_search_radius, int k, int32_t* d_idx, float* d_dist);
+/* ---- matchFLANN<FeatureT>, randomness 1 (:562-592), on rows of row_len 33, 135 or 352 (others: LGR_ERR_UNSUPPORTED): lgr_match_flann's
+ *      declared choice for every row length.  idx[i] = the row lgr_match_bf / lgr_match_rops / lgr_match_shot finds with a single train
+ *      block (the argmin under OpenCV's lane order, the lowest index at equal distance); dist[i] = sqrtf of the sequential sum above
+ *      (FLANN's L2_Simple); -1 / 0.f for an invalid query.  mq = 0 writes nothing, mt = 0 fills -1 / 0.f.  (33) equals lgr_match_flann*
+ *      bit for bit.  randomness > 1 under FLANN is not built: the reference leaves its tie order unspecified. ---- */
+int lgr_match_flann_rows(lgr_ctx*, int row_len, const float* q, int mq, const float* t, int mt, int32_t* idx, float* dist);
+int lgr_match_flann_rows_dev(lgr_ctx*, int row_len, const float* d_q, int mq, const float* d_t, int mt, int32_t* d_idx, float* d_dist);
 
 /* diagnostics of the context's last match call (stand-alone or inside lgr_align*), kept in the context:
  * [items_ab, dense_ab, items_ba, dense_ba, sub_cols, rg_rows] and the duration of

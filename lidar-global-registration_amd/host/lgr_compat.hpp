@@ -342,18 +342,42 @@ inline std::vector<MultivaluedCorrespondence> matchBF(const typename Cloud<Featu
     return out;
 }
 
+namespace detail {
+template <class FeatureT>
+constexpr int row_len() { return sizeof(FeatureT) == 540 ? 135 : sizeof(FeatureT) == 1444 ? 352 : 33; }
+// SHOT352: the 352 descriptor floats of every row, without the frame (as matchBF strips them); empty for the other descriptors
+template <class FeatureT>
+inline std::vector<float> shot_rows(const Cloud<FeatureT>& c) {
+    std::vector<float> r(sizeof(FeatureT) == 1444 ? c.size() * 352 : 0);
+    if (sizeof(FeatureT) == 1444)
+        for (std::size_t i = 0; i < c.size(); ++i) std::memcpy(r.data() + i * 352, &c.points[i], 352 * sizeof(float));
+    return r;
+}
+// the rows an entry point reads: the stripped copy for SHOT, the cloud's own (contiguous) rows otherwise
+template <class FeatureT>
+inline const float* rows(const Cloud<FeatureT>& c, const std::vector<float>& stripped) {
+    return sizeof(FeatureT) == 1444 ? stripped.data() : reinterpret_cast<const float*>(c.points.data());
+}
+}  // namespace detail
+
 // ---- include/matching.h:367-370 (randomness = 1; exact search, so the rows matchBF finds -- tests/flann_bf_matcher.h:82-83)
 template <class FeatureT>
 inline std::vector<MultivaluedCorrespondence> matchFLANN(const typename Cloud<FeatureT>::ConstPtr& query_features,
                                                          const typename Cloud<FeatureT>::ConstPtr& train_features,
                                                          const AlignmentParameters& parameters) {
-    static_assert(sizeof(FeatureT) == 132, "only FPFH is built on this path");
-    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness > 1 is built for matchBF only");
+    static_assert(sizeof(FeatureT) == 132 || sizeof(FeatureT) == 1444 || sizeof(FeatureT) == 540, "only FPFH, SHOT and RoPS135 are built on this path");
+    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness > 1 is not built for matchFLANN (the reference leaves its tie order unspecified)");
     int mq = (int) query_features->size(), mt = (int) train_features->size();
     std::vector<int32_t> idx(mq);
     std::vector<float> dist(mq);
-    check(lgr_match_flann(context(), reinterpret_cast<const float*>(query_features->points.data()), mq,
-                          reinterpret_cast<const float*>(train_features->points.data()), mt, idx.data(), dist.data()), "matchFLANN");
+    if constexpr (sizeof(FeatureT) == 132) {
+        check(lgr_match_flann(context(), reinterpret_cast<const float*>(query_features->points.data()), mq,
+                              reinterpret_cast<const float*>(train_features->points.data()), mt, idx.data(), dist.data()), "matchFLANN");
+    } else {
+        const std::vector<float> q352 = detail::shot_rows(*query_features), t352 = detail::shot_rows(*train_features);
+        check(lgr_match_flann_rows(context(), detail::row_len<FeatureT>(), detail::rows(*query_features, q352), mq, detail::rows(*train_features, t352), mt,
+                                   idx.data(), dist.data()), "matchFLANN");
+    }
     std::vector<MultivaluedCorrespondence> out(mq);
     for (int i = 0; i < mq; ++i)
         if (idx[i] >= 0) { out[i].match_indices.push_back(idx[i]); out[i].distances.push_back(dist[i]); }
@@ -366,18 +390,29 @@ inline std::vector<MultivaluedCorrespondence> matchLocal(const PointNCloud::Cons
                                                          const typename Cloud<FeatureT>::ConstPtr& query_features,
                                                          const typename Cloud<FeatureT>::ConstPtr& train_features,
                                                          const AlignmentParameters& parameters, const Matrix4f& guess) {
-    static_assert(sizeof(FeatureT) == 132, "only FPFH is built on this path");
-    if (parameters.randomness != 1) throw std::runtime_error("lgr: randomness > 1 is built for matchBF only");
+    static_assert(sizeof(FeatureT) == 132 || sizeof(FeatureT) == 1444 || sizeof(FeatureT) == 540, "only FPFH, SHOT and RoPS135 are built on this path");
+    const int k = parameters.randomness;
+    if (k < 1 || k > LGR_RANDOMNESS_MAX) throw std::runtime_error("lgr: randomness outside 1..LGR_RANDOMNESS_MAX is not supported");
     int mq = (int) query_features->size(), mt = (int) train_features->size();
     if ((int) query_pcd->size() != mq || (int) train_pcd->size() != mt) throw std::runtime_error("lgr: matchLocal: clouds and feature clouds differ in size");
-    std::vector<int32_t> idx(mq);
-    std::vector<float> dist(mq);
-    check(lgr_match_local(context(), raw(*query_pcd), mq, raw(*train_pcd), mt, reinterpret_cast<const float*>(query_features->points.data()),
-                          reinterpret_cast<const float*>(train_features->points.data()), guess.data(), parameters.match_search_radius,
-                          idx.data(), dist.data()), "matchLocal");
+    std::vector<int32_t> idx((std::size_t) mq * k);
+    std::vector<float> dist((std::size_t) mq * k);
+    if (sizeof(FeatureT) == 132 && k == 1) {
+        check(lgr_match_local(context(), raw(*query_pcd), mq, raw(*train_pcd), mt, reinterpret_cast<const float*>(query_features->points.data()),
+                              reinterpret_cast<const float*>(train_features->points.data()), guess.data(), parameters.match_search_radius,
+                              idx.data(), dist.data()), "matchLocal");
+    } else {
+        const std::vector<float> q352 = detail::shot_rows(*query_features), t352 = detail::shot_rows(*train_features);
+        check(lgr_match_local_knn(context(), detail::row_len<FeatureT>(), raw(*query_pcd), mq, raw(*train_pcd), mt, detail::rows(*query_features, q352),
+                                  detail::rows(*train_features, t352), guess.data(), parameters.match_search_radius, k, idx.data(), dist.data()), "matchLocal");
+    }
     std::vector<MultivaluedCorrespondence> out(mq);
     for (int i = 0; i < mq; ++i)
-        if (idx[i] >= 0) { out[i].match_indices.push_back(idx[i]); out[i].distances.push_back(dist[i]); }
+        for (int e = 0; e < k; ++e)
+            if (idx[(std::size_t) i * k + e] >= 0) {
+                out[i].match_indices.push_back(idx[(std::size_t) i * k + e]);
+                out[i].distances.push_back(dist[(std::size_t) i * k + e]);
+            }
     return out;
 }
 

@@ -419,6 +419,43 @@ class Context:
                                             g, C.c_float(radius), _ptr(idx), _ptr(dist)))
         return idx, dist
 
+    # ---- matchLocal with a k-list and matchFLANN on FPFH / RoPS135 / SHOT rows (the row length is the descriptors' second dimension) ----
+    def match_local_knn(self, qpts, tpts, qf, tf, guess, radius, k=1):
+        """matchLocal<FeatureT> with randomness = k: cuda points [m, 12], descriptors [m, 33 | 135 | 352]; guess 4x4 (numpy).
+        (idx int32 [mq, k], dist float32 [mq, k]): a query's candidates in ascending (distance, spatial distance, index), then -1 / 0."""
+        torch = self.torch
+        g = (C.c_float * 16)(*np.asarray(guess, np.float32).T.reshape(16).tolist())
+        qpts = qpts.contiguous(); tpts = tpts.contiguous(); qf = qf.contiguous(); tf = tf.contiguous()
+        idx = self.empty((qf.shape[0], max(int(k), 0)), torch.int32)
+        dist = self.empty((qf.shape[0], max(int(k), 0)), torch.float32)
+        self.check(_lib.lgr_match_local_knn_dev(self.h, int(qf.shape[1]), _ptr(qpts), qf.shape[0], _ptr(tpts), tf.shape[0], _ptr(qf), _ptr(tf),
+                                                g, C.c_float(radius), int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match_local_knn_host(self, qpts, tpts, qf, tf, guess, radius, k=1):
+        g = (C.c_float * 16)(*np.asarray(guess, np.float32).T.reshape(16).tolist())
+        qpts = np.ascontiguousarray(qpts, np.float32); tpts = np.ascontiguousarray(tpts, np.float32)
+        qf = np.ascontiguousarray(qf, np.float32); tf = np.ascontiguousarray(tf, np.float32)
+        idx = np.zeros((qf.shape[0], max(int(k), 0)), np.int32); dist = np.zeros((qf.shape[0], max(int(k), 0)), np.float32)
+        self.check(_lib.lgr_match_local_knn(self.h, int(qf.shape[1]), _ptr(qpts), qf.shape[0], _ptr(tpts), tf.shape[0], _ptr(qf), _ptr(tf),
+                                            g, C.c_float(radius), int(k), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match_flann_rows(self, q, t):
+        """matchFLANN<FeatureT>, randomness 1: cuda float32 [m, 33 | 135 | 352] -> (idx int32 [mq], dist float32 [mq]); the row the
+        brute-force matcher finds with one train block, the distance in FLANN's sequential order."""
+        torch = self.torch
+        q = q.contiguous(); t = t.contiguous()
+        idx = self.empty((q.shape[0],), torch.int32); dist = self.empty((q.shape[0],), torch.float32)
+        self.check(_lib.lgr_match_flann_rows_dev(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def match_flann_rows_host(self, q, t):
+        q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
+        idx = np.zeros(q.shape[0], np.int32); dist = np.zeros(q.shape[0], np.float32)
+        self.check(_lib.lgr_match_flann_rows(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], _ptr(idx), _ptr(dist)))
+        return idx, dist
+
     def match_bf_host(self, q, t, block=10000):
         q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
         idx = np.zeros(q.shape[0], np.int32); dist = np.zeros(q.shape[0], np.float32)
