@@ -232,8 +232,13 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // more than 2 DA apart and, for "swap", the larger is below 1 - DA.  Anything else -- a value
 // inside a band, a degenerate pair (coincident points, d parallel to the normal), rho below 1e-2, a NaN anywhere (every test is written
 // so that NaN fails it) -- is NOT decided here: the caller evaluates that pair with the canonical sequence.  On the 1M bench pair
-// about one pair in 10^4 is; the rows are bit-identical to the oracle's (tests/test_gpu_parity_1m.py::test_fpfh_1m_full compares all
-// 2 x 33 M values), and -DLGR_SPFH_CHECK builds a kernel that evaluates BOTH for every pair and counts disagreements (tools/exp_spfh_check.py).
+// 1.9e-4 .. 2.1e-4 of the pairs are (seeds 566 and 567, both clouds: 32 866 .. 34 914 of 1.6e8 .. 1.7e8); the rows are bit-identical to the
+// oracle's (tests/test_gpu_parity_1m.py::test_fpfh_1m_full compares all 2 x 33 M values), and -DLGR_SPFH_CHECK builds a kernel that
+// evaluates BOTH for every pair and counts disagreements (tools/exp_spfh_check.py: 0 decided-but-wrong of 6.7e8 pairs).  One undecided
+// lane sends its whole 64-pair batch through the canonical sequence, so the fraction is what a change of this arithmetic has to hold.
+// Tried and taken out: six of the seven dot products, rho^2 and the polynomial fused, fract / med3 / one compare
+// in bin_decided -- the same undecided fraction (1.9e-4 .. 2.1e-4: 32 856 .. 34 888 pairs), 0 decided-but-wrong, 142 -> 116 vector
+// instructions per pair batch, and no time (FPFH stage 4.43 .. 4.55 ms against 4.45 .. 4.51 without it).
 __device__ __forceinline__ float lgr_atan2f_fast(float y, float x) {   // lgr_atan2f's polynomial on v_rcp_f32 quotients
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = (ax > ay) ? ax : ay;
@@ -361,8 +366,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LGR_SPFH_WAV
             const int cx = min(max(lgr_cellc(x, g.ox, g.h), 0), g.dx - 1), cy = min(max(lgr_cellc(y, g.oy, g.h), 0), g.dy - 1), cz = min(max(lgr_cellc(z, g.oz, g.h), 0), g.dz - 1);
             cell = (cz * g.dy + cy) * g.dx + cx;
         }
-        kcnt[l] = 0;
     }
+    int kc = 0;   // neighbour count k of tile point l, the point itself included (lanes 0..15; to kcnt[] once, in front of the rows)
     for (int q = l; q < 2 * ST * SHP; q += 64) (&hist[0][0][0])[q] = 0;
     __syncthreads();
     const float r2box = r2 * 1.0001f + 1e-30f;
@@ -432,13 +437,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LGR_SPFH_WAV
             float4 Q = make_float4(0.f, 0.f, 0.f, 0.f);
             if (l < n_c) Q = cp[l];
             for (int i = p0; i < p0 + n_run; ++i) {
-                const float4 P_i = tp[i];
-                const float d2 = lgr_dist2(P_i.x, P_i.y, P_i.z, Q.x, Q.y, Q.z);
+                // tile point i from lane i's registers (i is wave-uniform): no LDS read to wait for per (tile point, candidate block)
+                const float Pix = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), i)), Piy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y), i));
+                const float Piz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(z), i));
+                const int Pipos = __builtin_amdgcn_readlane(pos, i);
+                const float d2 = lgr_dist2(Pix, Piy, Piz, Q.x, Q.y, Q.z);
                 const bool acc = l < n_c && d2 < r2;
                 const unsigned long long am = __ballot(acc);
                 if (am == 0ull) continue;
-                if (l == 0) kcnt[i] += __popcll(am);
-                const bool enq = acc && __float_as_int(Q.w) != __float_as_int(P_i.w);   // if (s == t) return: the point itself
+                kc += (l == i) ? (int) __popcll(am) : 0;
+                const bool enq = acc && __float_as_int(Q.w) != Pipos;   // if (s == t) return: the point itself
                 const unsigned long long em = __ballot(enq);
                 if (enq) {
                     const int rank = __builtin_amdgcn_mbcnt_hi((unsigned) (em >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) em, 0u));
@@ -491,6 +499,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LGR_SPFH_WAV
             }
         if (n_buf > 0) test_block(n_buf);
     }
+    if (l < ST) kcnt[l] = kc;
     __syncthreads();
     // rows: bin value = sequential float sum of `count` copies of 100 / (k - 1) (lgr_seqsum: the loop's result without the loop); zero
     // padding up to the pitch
@@ -664,10 +673,16 @@ __global__ __launch_bounds__(64) void fpfh_mfma_kernel(GridDev g, const float* _
             }
             head += 4 * G;
         };
+        // Whole rounds only while the run streams: what a chunk leaves below 16 candidates stays in the ring for the next chunk's round (FRING
+        // holds 15 + 64).  `head` advances by 4 per group from 0 either way, so the group boundaries, the candidate order and every
+        // accumulator's MFMA sequence are those of consuming each chunk to the last whole group -- which sent a quarter of all groups (1..3 per
+        // chunk of ~40 live candidates) through the one-group path below, a dependent ring read -> SPFH load -> MFMA round trip each.
+        auto consume_rounds = [&]() {
+            while (tail - head >= 16) round(std::integral_constant<int, 4>{});
+        };
+        // the end of a run: n_groups <= 3 single groups (and the padded one)
         auto consume = [&](int n_groups) {
-            int gq = 0;
-            for (; gq + 4 <= n_groups; gq += 4) round(std::integral_constant<int, 4>{});
-            for (; gq < n_groups; ++gq, head += 4) {
+            for (int gq = 0; gq < n_groups; ++gq, head += 4) {
                 const float4 e = ring[(head + k) & (FRING - 1)];
                 const float d2 = lgr_dist2(x, y, z, e.x, e.y, e.z);
                 const bool in = active & (d2 < r2);
@@ -705,12 +720,19 @@ __global__ __launch_bounds__(64) void fpfh_mfma_kernel(GridDev g, const float* _
                         ring[(tail + rank) & (FRING - 1)] = make_float4(P.x, P.y, P.z, __uint_as_float((unsigned) t * (unsigned) HP));   // .w: element offset of the SPFH row
                     }
                     tail += __popcll(lm);
+                    if (tail - head < 16) continue;   // (no read yet: the next chunk's stores go behind these, tail - head <= 15 + 64 <= FRING)
                     __syncthreads();   // one wave per workgroup: orders the LDS stores before the reads below
-                    consume((tail - head) >> 2);
+                    consume_rounds();
                     __syncthreads();   // ... and those reads before the next chunk's stores
                 }
             }
-        // the last 1..3 candidates of the run: pad the group with the all-zero SPFH row (position g.n) far away
+        // what the run left in the ring (< 16 candidates): single groups, then the last 1..3 candidates padded to a group with the
+        // all-zero SPFH row (position g.n) far away
+        if (tail - head >= 4) {
+            __syncthreads();
+            consume((tail - head) >> 2);
+            __syncthreads();
+        }
         if (tail > head) {
             if (l < 4 - (tail - head)) ring[(tail + l) & (FRING - 1)] = make_float4(3.0e38f, 3.0e38f, 3.0e38f, __uint_as_float((unsigned) g.n * (unsigned) HP));
             __syncthreads();
