@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-/* ABI revision.  Still 5 with the ratio matcher: lgr_feature_params.ratio_k takes the first of that struct's reserved words (a host that
+/* ABI revision.  Still 5 with the prepared clouds: lgr_cloud, struct lgr_cloud_info, lgr_cloud_level_info, lgr_cloud_prepare*, lgr_cloud_destroy,
+ * lgr_cloud_info, lgr_cloud_keypoints*, lgr_cloud_level*, lgr_correspondences_prepared*, lgr_align_prepared and the host twin lgr_nearest are
+ * additions; no struct or entry point that existed changed.  Still 5 with the ratio matcher: lgr_feature_params.ratio_k takes the first of that struct's reserved words (a host that
  * zeroes them gets k = 2, MATCHING_RATIO_K, and the word is read under LGR_MATCH_RATIO only), LGR_MATCH_RATIO and the lgr_ratio_test* /
  * lgr_match_ratio* entry points are additions.  5 (round 5): lgr_ctx_options.arithmetic / pcl_neighbour_cap and lgr_match_options.auto_dense / irregular_rows (former reserved words: a host that zeroes
  * them keeps the default arithmetic and switches auto_dense and the irregular-row lane off), lgr_match_last_lbstats, lgr_match_last_irregular, lgr_selfcheck_philox,
@@ -731,6 +733,60 @@ int lgr_measure_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, in
 float lgr_measure_mean(const float* x, int n);
 float lgr_measure_deviation(const float* x, int n, float mean);
 
+/* ---- prepared clouds: include/matching.h:132-146 Storage, filled once per cloud by FeatureBasedMatcherImpl::initialize (:164-262) ----
+ * The correspondence search does everything up to the matcher per cloud: key points, the down-sampling chain, normals, descriptor rows
+ * (one level under feature_radius > 0, the pruned level range otherwise) and the match filter's per-cloud tables.  lgr_cloud_prepare*
+ * runs those stages once into an object that owns its device memory (hipMalloc; nothing of it lives in the context's workspace, so it
+ * outlives any number of calls and may be used from any context of its device); lgr_correspondences_prepared* / lgr_align_prepared
+ * start at the matcher.  A host that registers N scans pairwise prepares each scan once.
+ *   - side (0 / 1) selects which of vp_* / has_vp_* / iss_radius_* of lgr_params the cloud is prepared with; the rest is read as in a pair
+ *     call, and lgr_params is checked as lgr_correspondences_ex_dev checks it, with the same codes.
+ *   - the object records what its state depends on: feature_nr_points, normal_nr_points, feature_radius (every value <= 0 counts as
+ *     "unset"), scale_factor, normals_available, keypoint_id, the side's view point and ISS radius, cluster_k under LGR_MATCH_CLUSTER
+ *     (0 otherwise: the other filters read the densities only), descriptor_id, lrf_id and the context's arithmetic; floats by their
+ *     bits.  A pair call whose lgr_params (source-side fields for src, target-side fields for tgt) differ from that record returns
+ *     LGR_ERR_INVALID_ARG; so do clouds of another device than the context's.  A cloud prepared as side 0 serves as a target when the
+ *     fields agree.
+ *   - the pair calls never write to a cloud: one cloud may appear in any number of pairs, on both sides, and as both arguments of a call.
+ *   - lgr_correspondences_prepared* returns the bytes lgr_correspondences_ex* returns for the same clouds and parameters, and
+ *     lgr_align_prepared the lgr_result of lgr_align_ex2* apart from the time fields; stage_ms[0..2] are 0 in a prepared call.  Whatever
+ *     the unprepared entry points refuse is refused with the same code by lgr_cloud_prepare* or by the pair call.
+ *   - a cloud of fewer than 2 points is a valid object: pairs with it have no correspondences, lgr_align_prepared gives the identity, not
+ *     converged.
+ * Getters: lgr_cloud_keypoints* gives the key points as indices into the cloud, lgr_cloud_level* one level's key-point list (indices into
+ * the key points) and descriptor rows (rows x row_len).  The _dev forms hand out the object's own pointers, read-only and valid until
+ * lgr_cloud_destroy; a NULL list means 0..count-1 (keypoint any; the one level of the single-scale form).  The host forms copy into caller
+ * arrays (either may be NULL) and synchronise. */
+typedef struct lgr_cloud lgr_cloud;
+struct lgr_cloud_info {           /* a tag, not a typedef: the getter carries the same name (as stat(2) does) */
+    int32_t  n, keypoints, row_len;
+    int32_t  levels;              /* levels that hold rows: 1 in the single-scale form, 0 without key points or without two points */
+    int32_t  first_log2_radius;   /* log2_radius of level 0 (levels follow in steps of 1) */
+    int32_t  multiscale;          /* 1: prepared with feature_radius unset */
+    uint64_t bytes;               /* device memory the object holds */
+    int32_t  reserved[4];         /* 0 */
+};
+typedef struct {
+    int32_t log2_radius;
+    float   radius, voxel;        /* powf(scale_factor, log2_radius) and the voxel of include/matching.h:230-231 */
+    int32_t rows, surface;        /* key points of the level; size of the level's down-sampled surface */
+    int32_t reserved[3];          /* 0 */
+} lgr_cloud_level_info;
+int lgr_cloud_prepare(lgr_ctx*, const float* pts, int n, int side, const lgr_params*, const lgr_feature_params* /* or NULL */, lgr_cloud** out);
+int lgr_cloud_prepare_dev(lgr_ctx*, const float* d_pts, int n, int side, const lgr_params*, const lgr_feature_params* /* or NULL */, lgr_cloud** out);
+int lgr_cloud_destroy(lgr_cloud*);   /* NULL: LGR_OK */
+int lgr_cloud_info(const lgr_cloud*, struct lgr_cloud_info* out);
+int lgr_cloud_keypoints(const lgr_cloud*, int32_t* out_or_null /* keypoints */, int* m);
+int lgr_cloud_keypoints_dev(const lgr_cloud*, const int32_t** d_idx /* NULL: 0..n-1 */, int* m);
+int lgr_cloud_level(const lgr_cloud*, int level, lgr_cloud_level_info* info_or_null, int32_t* list_out_or_null, float* rows_out_or_null);
+int lgr_cloud_level_dev(const lgr_cloud*, int level, lgr_cloud_level_info* info_or_null, const int32_t** d_list_or_null, const float** d_rows_or_null);
+int lgr_correspondences_prepared(lgr_ctx*, const lgr_cloud* src, const lgr_cloud* tgt, const lgr_params*, const lgr_feature_params* /* or NULL */,
+                                 lgr_corr* out, int* n_out);
+int lgr_correspondences_prepared_dev(lgr_ctx*, const lgr_cloud* src, const lgr_cloud* tgt, const lgr_params*, const lgr_feature_params* /* or NULL */,
+                                     lgr_corr* d_out, int* n_out /* host */);
+int lgr_align_prepared(lgr_ctx*, const lgr_cloud* src, const lgr_cloud* tgt, const lgr_params*, const lgr_feature_params* /* or NULL */,
+                       const lgr_metric_params* /* or NULL; weights: a DEVICE array */, lgr_result*);
+
 /* src/analysis.cpp:45-88 calculateOverlapRmse (and :30-43 calculatePointCloudRmse, computed by the same pass; pcd_err may be NULL).
  * d_idx (optional, ns ints): the target point whose tangent plane source point i was measured against, -1 where the point was skipped. */
 int lgr_overlap_rmse_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T16[16] /* host */, const float Tgt16[16] /* host */,
@@ -864,6 +920,7 @@ int lgr_compare_overlaps(lgr_ctx*, const float* src, int ns, const float* tgt, i
  * with k = 1 (squared distance, then index), at a cost that does not depend on how far a query lies from the cloud.  -1 / +inf where the
  * query is not finite or the cloud has no finite point. */
 int lgr_nearest_dev(lgr_ctx*, const float* d_q, int nq, const float* d_pts, int n, int32_t* d_idx, float* d_d2_or_null);
+int lgr_nearest(lgr_ctx*, const float* q, int nq, const float* pts, int n, int32_t* idx, float* d2_or_null);   /* host twin */
 /* src/common.cpp:818-835 getColor(v, vmin, vmax) per value */
 int lgr_color_map_dev(lgr_ctx*, const float* d_values, int n, float vmin, float vmax, int32_t* d_colors);
 int lgr_color_map(lgr_ctx*, const float* values, int n, float vmin, float vmax, int32_t* colors);   /* host twin */

@@ -3,6 +3,7 @@
 //   include/matching.h:395-411, 428-453, 492-550  -> lgr_filter_dev
 //   src/correspondence_search.cpp:4-15 + include/matching.h:148-262 (keypoint 'any', single scale) -> lgr_correspondences*
 //   src/alignment.cpp:72-109 (RANSAC branch; CSV side effects dropped)                          -> lgr_align*
+//   include/matching.h:132-146, 164-262 (one Storage per cloud, filled once)                    -> lgr_cloud_fill, lgr_*_prepared*
 #include <rocprim/device/device_scan.hpp>
 
 #include <chrono>
@@ -10,7 +11,7 @@
 
 #include <climits>
 
-#include "lgr_internal.h"
+#include "lgr_cloud.h"
 #include "lgr_pointpass.cuh"
 
 namespace {
@@ -245,6 +246,8 @@ struct CorrCall {
     const float *clouds[2], *kclouds[2];     // the clouds; the key-point clouds (the clouds themselves, or the ISS detections
     int sizes[2], ksizes[2];                 // with their index lists)
     int32_t* kidx[2] = {nullptr, nullptr};
+    lgr_cloud* own[2] = {nullptr, nullptr};  // lgr_cloud_prepare*: the object that side's results go into (NULL: workspace)
+    MsSide mss[2];                           // multi-scale: initialize() of both clouds
     lgr_corr* d_out;
     int* n_out;
     bool empty = false;                      // a cloud without two points: nothing to match
@@ -273,6 +276,9 @@ struct CorrCall {
     float iss_radius(int side) const { return side == 0 ? p->iss_radius_src : p->iss_radius_tgt; }
     bool ratio() const { return p->matching_id == LGR_MATCH_RATIO; }
     bool both_dirs() const { return p->matching_id != LGR_MATCH_ONE_SIDED && !ratio(); }
+    // a per-cloud result whose size a stage finds out itself: the side's object, or the workspace slot of the existing entry points
+    template <class T>
+    int result(int side, int slot, size_t count, T** out) const { return own[side] ? lgr_cloud_alloc_t(ctx, own[side], count, out) : lgr_ws_t(ctx, slot, count, out); }
 };
 
 // One level of one cloud (include/matching.h:234-248; the single-scale search has one level): down-sample `in` into `surf`, normals,
@@ -298,25 +304,14 @@ static int level_features(lgr_ctx* cx, const CorrCall& c, int side, const float*
 }
 
 // ---- multi-scale matching (feature_radius unset): include/matching.h:176-262 (initialize) and :264-352
-// (match_multiscale).  The heavy stages (5-NN, down-sampling chain, normals, descriptors, brute-force matching per level) run on
-// the device; the per-key-point level assignment (log2f/sqrtf of the reference's host arithmetic, level pruning) and
-// the proximity vote over the <= nr_scales matches of a key point run on the host between them.
-struct MsSide {
-    float iss_radius = 0.f;
-    int min_l2 = INT_MAX, max_l2 = INT_MIN;
-    std::vector<std::vector<int>> lists;   // per scale: key-point indices
-    std::vector<size_t> feat_off;          // per scale: row offset into the feature buffer
-    float* feat = nullptr;                 // device, sum(rows) x D (D = the descriptor's row length)
-    int32_t* d_lists = nullptr;            // device copy of the lists, concatenated like feat_off
-    std::vector<float> xyz;                // host copy of the key points (3 floats each) for the vote
-};
-
+// (match_multiscale).  The heavy stages (5-NN, down-sampling chain, normals, descriptors, brute-force matching per level, the merge
+// of the levels' matches and the proximity vote) run on the device; the per-key-point level assignment (log2f/sqrtf of the
+// reference's host arithmetic, level pruning) runs on the host in initialize.
 static int ms_initialize(CorrCall& c, int side, MsSide& st) {
     lgr_ctx* ctx = c.ctx;
     const lgr_params* p = c.p;
     const int D = c.d->len, n = c.sizes[side], n_kps = c.ksizes[side];
     const float *d_pcd = c.clouds[side], *d_kps = c.kclouds[side];
-    st.iss_radius = c.iss_radius(side);
     const int k = 5;
     LGR_CHECK(ctx, n >= k, LGR_ERR_INVALID_ARG);
     // :180-188 density of every key point = distance to its 4th neighbour in the full cloud
@@ -326,12 +321,8 @@ static int ms_initialize(CorrCall& c, int side, MsSide& st) {
     LGR_TRY(lgr_ws_t(ctx, WS_MS_KNN_D, (size_t) n_kps * k, &d_d2));
     LGR_TRY(lgr_knn_dev(ctx, d_kps, n_kps, d_pcd, n, k, d_nn, d_d2));
     std::vector<float> d2((size_t) n_kps * k);
-    std::vector<float> kp((size_t) n_kps * 12);
     LGR_HIP(ctx, hipMemcpyAsync(d2.data(), d_d2, d2.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(kp.data(), d_kps, kp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    st.xyz.resize((size_t) n_kps * 3);
-    for (int i = 0; i < n_kps; ++i) for (int a = 0; a < 3; ++a) st.xyz[3 * (size_t) i + a] = kp[12 * (size_t) i + a];
     std::vector<int> level(n_kps);
     for (int i = 0; i < n_kps; ++i) {
         float density = sqrtf(d2[(size_t) i * k + (k - 1)]);
@@ -350,17 +341,25 @@ static int ms_initialize(CorrCall& c, int side, MsSide& st) {
     while (1000 * count[back - 1] < max_nr) { --back; st.max_l2--; }
     for (int& v : level) v = std::min(std::max(v, st.min_l2), st.max_l2);
     const int nr_scales = st.max_l2 - st.min_l2 + 1;
-    st.lists.assign(nr_scales, {});
+    std::vector<std::vector<int>> lists(nr_scales);   // per scale: key-point indices
     for (int i = 0; i < n_kps; ++i)
-        for (int j = level[i]; j <= st.max_l2; ++j) st.lists[j - st.min_l2].push_back(i);
-    st.feat_off.assign(nr_scales + 1, 0);
-    for (int i = 0; i < nr_scales; ++i) st.feat_off[i + 1] = st.feat_off[i] + st.lists[i].size();
-    const size_t rows = st.feat_off[nr_scales];
-    LGR_TRY(lgr_ws_t(ctx, side == 0 ? WS_MS_FEAT_S : WS_MS_FEAT_T, rows * D + 1, &st.feat));
-    LGR_TRY(lgr_ws_t(ctx, side == 0 ? WS_MS_LIST_S : WS_MS_LIST_T, rows + 1, &st.d_lists));
+        for (int j = level[i]; j <= st.max_l2; ++j) lists[j - st.min_l2].push_back(i);
+    st.levels.assign(nr_scales, lgr_cloud_lvl{});
+    size_t rows = 0;
+    for (int i = 0; i < nr_scales; ++i) {
+        lgr_cloud_lvl& l = st.levels[i];
+        l.log2_radius = st.min_l2 + i;
+        l.radius = powf(p->scale_factor, (float) l.log2_radius);
+        l.voxel = sqrtf(M_PI * l.radius * l.radius / (float) p->feature_nr_points);
+        l.rows = (int) lists[i].size();
+        l.off = rows;
+        rows += lists[i].size();
+    }
+    LGR_TRY(c.result(side, side == 0 ? WS_MS_FEAT_S : WS_MS_FEAT_T, rows * D + 1, &st.feat));
+    LGR_TRY(c.result(side, side == 0 ? WS_MS_LIST_S : WS_MS_LIST_T, rows + 1, &st.d_lists));
     for (int i = 0; i < nr_scales; ++i)
-        if (!st.lists[i].empty())
-            LGR_HIP(ctx, hipMemcpyAsync(st.d_lists + st.feat_off[i], st.lists[i].data(), st.lists[i].size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!lists[i].empty())
+            LGR_HIP(ctx, hipMemcpyAsync(st.d_lists + st.levels[i].off, lists[i].data(), lists[i].size() * 4, hipMemcpyHostToDevice, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // :228-261 per scale: down-sample the previous level's cloud, normals, descriptors of the level's key points
     float *bufA, *bufB, *sub;
@@ -370,40 +369,12 @@ static int ms_initialize(CorrCall& c, int side, MsSide& st) {
     const float* in = d_pcd;
     int n_in = n;
     for (int i = 0; i < nr_scales; ++i) {
-        float search_radius = powf(p->scale_factor, (float) (st.min_l2 + i));
-        float voxel = sqrtf(M_PI * search_radius * search_radius / (float) p->feature_nr_points);
+        lgr_cloud_lvl& l = st.levels[i];
         float* out = (i & 1) ? bufB : bufA;
-        int nd;
-        LGR_TRY(level_features(ctx, c, side, in, n_in, voxel, search_radius, out, d_kps, (int) st.lists[i].size(), st.d_lists + st.feat_off[i], sub,
-                               st.feat + st.feat_off[i] * D, c.ms, &nd));
-        in = out; n_in = nd;
+        LGR_TRY(level_features(ctx, c, side, in, n_in, l.voxel, l.radius, out, d_kps, l.rows, st.d_lists + l.off, sub, st.feat + l.off * D, c.ms, &l.surface));
+        in = out; n_in = l.surface;
     }
     return LGR_OK;
-}
-
-// :316-349 one match per query: the candidate (one per level) with the largest proximity-weighted support among the
-// candidates, ties by the smaller descriptor distance
-static void ms_vote(const MsSide& tr, const std::vector<std::vector<int>>& mi, const std::vector<std::vector<float>>& md,
-                    std::vector<int32_t>& out_idx, std::vector<float>& out_dist) {
-    const int nq = (int) mi.size();
-    for (int i = 0; i < nq; ++i) {
-        const std::vector<int>& m = mi[i];
-        float best_c = 0.f, best_d = 0.f;
-        int best = -1;
-        for (size_t m1 = 0; m1 < m.size(); ++m1) {
-            float cnt = 0.f;
-            for (size_t m2 = m1; m2 < m.size(); ++m2) {
-                const float* a = tr.xyz.data() + 3 * (size_t) m[m1];
-                const float* b = tr.xyz.data() + 3 * (size_t) m[m2];
-                float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-                float dist_l2 = std::sqrt((dx * dx + dy * dy) + dz * dz);
-                if (dist_l2 < 32 * tr.iss_radius) cnt += tr.iss_radius / std::max(dist_l2, tr.iss_radius);
-            }
-            if (cnt > best_c || (cnt == best_c && md[i][m1] < best_d)) { best_c = cnt; best_d = md[i][m1]; best = (int) m1; }
-        }
-        out_idx[i] = best >= 0 ? m[best] : -1;
-        out_dist[i] = best >= 0 ? md[i][best] : 0.f;
-    }
 }
 
 // inverse of a column-major 4x4 by Gauss-Jordan with partial pivoting in double, rounded to float: the canonical stand-in for
@@ -474,70 +445,95 @@ static int match_ratio(const CorrCall& c, const float* fa, int ma, const float* 
     return lgr_match_ratio_core(c.ctx, c.d->len, fa, ma, fb, mb, c.p->bf_block_size, c.ratio_k, LGR_MATCHING_RATIO_THRESHOLD, ab_i, ab_d);
 }
 
-static int ms_match_tables(CorrCall& c) {
+// A level's matches into the per-key-point candidate tables (include/matching.h:300-315): one thread per (row, slot) of the level's
+// result arrays, both directions in one launch.  Row i of direction a -> b is key point la[i]; its slot e lands at column
+// col0 + e of that key point's table row, so the levels' order is the slot order; a match lb[.] is a key-point index too.  Unmatched
+// slots (-1) keep the table's -1 fill.
+__global__ void ms_merge_kernel(int ma, int mb, int kr, int width, int col0, const int32_t* __restrict__ la, const int32_t* __restrict__ lb,
+                                const int32_t* __restrict__ ab_i, const float* __restrict__ ab_d, const int32_t* __restrict__ ba_i, const float* __restrict__ ba_d,
+                                int32_t* __restrict__ cij, float* __restrict__ dij, int32_t* __restrict__ cji, float* __restrict__ dji) {
+    const long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    const long long na = (long long) ma * kr, nb = cji ? (long long) mb * kr : 0;
+    if (e < na) {
+        const int v = ab_i[e];
+        if (v >= 0 && v < mb) {
+            const size_t at = (size_t) la[e / kr] * width + col0 + (int) (e % kr);
+            cij[at] = lb[v]; dij[at] = ab_d[e];
+        }
+    } else if (e < na + nb) {
+        const long long f = e - na;
+        const int v = ba_i[f];
+        if (v >= 0 && v < ma) {
+            const size_t at = (size_t) lb[f / kr] * width + col0 + (int) (f % kr);
+            cji[at] = la[v]; dji[at] = ba_d[f];
+        }
+    }
+}
+
+// match_multiscale over two initialized clouds: per common level the matcher, the level's matches into the candidate tables, then the
+// vote per direction -- ij on the target key points with their radius, ji on the source key points.  Nothing is read back.
+static int ms_match(CorrCall& c) {
     lgr_ctx* ctx = c.ctx;
     const int D = c.d->len;
-    MsSide st[2];
-    for (int s = 0; s < 2; ++s) LGR_TRY(ms_initialize(c, s, st[s]));
-    tick(ctx, 4);
+    const MsSide* st = c.mss;
     const bool need_ji = c.both_dirs();
     const int ns = c.ksizes[0], nt = c.ksizes[1], kr = c.p->randomness;
-    std::vector<std::vector<int>> mi_ij(ns), mi_ji(need_ji ? nt : 0);
-    std::vector<std::vector<float>> md_ij(ns), md_ji(need_ji ? nt : 0);
     const int lo = std::max(st[0].min_l2, st[1].min_l2), hi = std::min(st[0].max_l2, st[1].max_l2);
+    if (lo > hi) {   // no level in common: no key point has a candidate
+        LGR_HIP(ctx, hipMemsetAsync(c.ij, 0xff, (size_t) ns * 4, ctx->stream));
+        LGR_HIP(ctx, hipMemsetAsync(c.dij, 0, (size_t) ns * 4, ctx->stream));
+        if (need_ji) {
+            LGR_HIP(ctx, hipMemsetAsync(c.ji, 0xff, (size_t) nt * 4, ctx->stream));
+            LGR_HIP(ctx, hipMemsetAsync(c.dji, 0, (size_t) nt * 4, ctx->stream));
+        }
+        return LGR_OK;
+    }
+    const int width = (hi - lo + 1) * kr;
+    int32_t *cij, *cji = nullptr;
+    LGR_TRY(lgr_ws_t(ctx, WS_KNN_CAND_IJ, (size_t) 2 * ns * width, &cij));
+    if (need_ji) LGR_TRY(lgr_ws_t(ctx, WS_KNN_CAND_JI, (size_t) 2 * nt * width, &cji));
+    float *dij = (float*) (cij + (size_t) ns * width), *dji = need_ji ? (float*) (cji + (size_t) nt * width) : nullptr;
+    LGR_HIP(ctx, hipMemsetAsync(cij, 0xff, (size_t) ns * width * 4, ctx->stream));
+    if (need_ji) LGR_HIP(ctx, hipMemsetAsync(cji, 0xff, (size_t) nt * width * 4, ctx->stream));
+    // the level buffers at the size of the largest level (a key point takes part in every level from its own up): growing one would
+    // wait for the stream
+    int32_t* r;
+    float* sub = nullptr;
+    const lgr_cloud_lvl &top_a = st[0].levels[hi - st[0].min_l2], &top_b = st[1].levels[hi - st[1].min_l2];
+    LGR_TRY(lgr_ws_t(ctx, WS_MS_RES, (size_t) 2 * (top_a.rows + top_b.rows) * kr + 4, &r));
+    if (c.p->has_guess) LGR_TRY(lgr_ws_t(ctx, WS_MS_SUB, (size_t) (top_a.rows + top_b.rows) * 12 + 4, &sub));
     for (int level = lo; level <= hi; ++level) {
-        const int ia = level - st[0].min_l2, ib = level - st[1].min_l2;
-        const std::vector<int>& la = st[0].lists[ia];
-        const std::vector<int>& lb = st[1].lists[ib];
-        const int ma = (int) la.size(), mb = (int) lb.size();
+        const lgr_cloud_lvl &a = st[0].levels[level - st[0].min_l2], &b = st[1].levels[level - st[1].min_l2];
+        const int ma = a.rows, mb = b.rows;
         if (ma == 0 || mb == 0) continue;
-        int32_t* r;
-        LGR_TRY(lgr_ws_t(ctx, WS_MS_RES, (size_t) 2 * (ma + mb) * kr + 4, &r));
         int32_t *ab_i = r, *ba_i = r + (size_t) ma * kr;
         float *ab_d = (float*) (r + (size_t) (ma + mb) * kr), *ba_d = ab_d + (size_t) ma * kr;
-        const float* fa = st[0].feat + st[0].feat_off[ia] * D;
-        const float* fb = st[1].feat + st[1].feat_off[ib] * D;
+        const float* fa = st[0].feat + a.off * D;
+        const float* fb = st[1].feat + b.off * D;
+        const int32_t *la = st[0].d_lists + a.off, *lb = st[1].d_lists + b.off;
         const float *pa = nullptr, *pb = nullptr;
         if (c.p->has_guess) {   // matchLocal works on the level's key-point sub-clouds (kps_multiscale, include/matching.h:243)
-            float* sub;
-            LGR_TRY(lgr_ws_t(ctx, WS_MS_SUB, (size_t) (ma + mb) * 12 + 4, &sub));
-            gather_rows12(ctx, c.kclouds[0], st[0].d_lists + st[0].feat_off[ia], ma, sub);
-            gather_rows12(ctx, c.kclouds[1], st[1].d_lists + st[1].feat_off[ib], mb, sub + (size_t) ma * 12);
+            gather_rows12(ctx, c.kclouds[0], la, ma, sub);
+            gather_rows12(ctx, c.kclouds[1], lb, mb, sub + (size_t) ma * 12);
             pa = sub; pb = sub + (size_t) ma * 12;
         }
         // randomness > 1: the level's kr matches per key point, in list order (checked on entry: brute force, no guess)
         if (c.ratio()) LGR_TRY(match_ratio(c, fa, ma, fb, mb, ab_i, ab_d));   // (checked on entry: kr = 1, brute force, no guess)
         else if (kr > 1) LGR_TRY(lgr_match_knn_core(ctx, D, fa, ma, fb, mb, c.p->bf_block_size, kr, ab_i, ab_d, need_ji ? ba_i : nullptr, need_ji ? ba_d : nullptr));
         else LGR_TRY(match_dispatch(c, pa, fa, ma, pb, fb, mb, ab_i, ab_d, ba_i, ba_d));
-        std::vector<int32_t> h((size_t) 2 * (ma + mb) * kr);
-        LGR_HIP(ctx, hipMemcpyAsync(h.data(), r, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const int32_t *h_ab = h.data(), *h_ba = h.data() + (size_t) ma * kr;
-        const float *h_abd = (const float*) (h.data() + (size_t) (ma + mb) * kr), *h_bad = h_abd + (size_t) ma * kr;
-        for (int i = 0; i < ma; ++i)
-            for (int e = 0; e < kr; ++e) {
-                const size_t at = (size_t) i * kr + e;
-                if (h_ab[at] >= 0) { mi_ij[la[i]].push_back(lb[h_ab[at]]); md_ij[la[i]].push_back(h_abd[at]); }
-            }
-        if (need_ji)
-            for (int j = 0; j < mb; ++j)
-                for (int e = 0; e < kr; ++e) {
-                    const size_t at = (size_t) j * kr + e;
-                    if (h_ba[at] >= 0) { mi_ji[lb[j]].push_back(la[h_ba[at]]); md_ji[lb[j]].push_back(h_bad[at]); }
-                }
+        const long long items = (long long) (ma + (need_ji ? mb : 0)) * kr;
+        ms_merge_kernel<<<cdiv(items, 256), 256, 0, ctx->stream>>>(ma, mb, kr, width, (level - lo) * kr, la, lb, ab_i, ab_d, ba_i, ba_d, cij, dij, cji, dji);
     }
-    std::vector<int32_t> ij(ns), ji(need_ji ? nt : 0);
-    std::vector<float> dij(ns), dji(need_ji ? nt : 0);
-    ms_vote(st[1], mi_ij, md_ij, ij, dij);
-    if (need_ji) ms_vote(st[0], mi_ji, md_ji, ji, dji);
-    LGR_HIP(ctx, hipMemcpyAsync(c.ij, ij.data(), (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(c.dij, dij.data(), (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (need_ji) {
-        LGR_HIP(ctx, hipMemcpyAsync(c.ji, ji.data(), (size_t) nt * 4, hipMemcpyHostToDevice, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(c.dji, dji.data(), (size_t) nt * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host staging vectors go out of scope
+    LGR_HIP(ctx, hipGetLastError());
+    LGR_TRY(lgr_vote_matches_launch(ctx, cij, dij, ns, width, c.kclouds[1], nt, c.p->iss_radius_tgt, c.ij, c.dij));
+    if (need_ji) LGR_TRY(lgr_vote_matches_launch(ctx, cji, dji, nt, width, c.kclouds[0], ns, c.p->iss_radius_src, c.ji, c.dji));
     return LGR_OK;
+}
+
+static int ms_match_tables(CorrCall& c) {
+    for (int s = 0; s < 2; ++s) LGR_TRY(ms_initialize(c, s, c.mss[s]));
+    tick(c.ctx, 4);
+    return ms_match(c);
 }
 
 // ---- the stages of lgr_correspondences_ex_dev, in the order they run
@@ -575,19 +571,33 @@ static int check(CorrCall& c, const lgr_feature_params* fp) {
 // key points (src/correspondence_search.cpp:8-11): every point, or the ISS detections.  kps = pcd[kps_indices]
 // (include/matching.h:167); every later stage works on the key-point clouds and the indices are mapped back at the
 // end (finalize, include/matching.h:150-160).
-static int keypoints(CorrCall& c) {
+static int keypoints(CorrCall& c, int s) {
     lgr_ctx* ctx = c.ctx;
     if (c.p->keypoint_id != LGR_KEYPOINT_ISS) return LGR_OK;
-    for (int s = 0; s < 2; ++s) {
-        float* kp;
-        LGR_TRY(lgr_ws_t(ctx, s == 0 ? WS_PIPE_KIDX_S : WS_PIPE_KIDX_T, (size_t) c.sizes[s] + 1, &c.kidx[s]));
-        int m = 0;
-        LGR_TRY(lgr_iss_keypoints_dev(ctx, c.clouds[s], c.sizes[s], c.iss_radius(s), 0.975f, 0.975f, 4, c.kidx[s], &m));
-        LGR_TRY(lgr_ws_t(ctx, s == 0 ? WS_PIPE_KPS_S : WS_PIPE_KPS_T, (size_t) std::max(m, 1) * 12, &kp));
-        if (m) gather_rows12(ctx, c.clouds[s], c.kidx[s], m, kp);
-        c.kclouds[s] = kp; c.ksizes[s] = m;
+    float* kp;
+    LGR_TRY(lgr_ws_t(ctx, s == 0 ? WS_PIPE_KIDX_S : WS_PIPE_KIDX_T, (size_t) c.sizes[s] + 1, &c.kidx[s]));
+    int m = 0;
+    LGR_TRY(lgr_iss_keypoints_dev(ctx, c.clouds[s], c.sizes[s], c.iss_radius(s), 0.975f, 0.975f, 4, c.kidx[s], &m));
+    if (c.own[s]) {   // the detector writes into a list as long as the cloud: the object keeps the m indices it found
+        int32_t* kept;
+        LGR_TRY(lgr_cloud_alloc_t(ctx, c.own[s], (size_t) std::max(m, 1), &kept));
+        LGR_HIP(ctx, hipMemcpyAsync(kept, c.kidx[s], (size_t) m * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        c.kidx[s] = kept;
     }
+    LGR_TRY(c.result(s, s == 0 ? WS_PIPE_KPS_S : WS_PIPE_KPS_T, (size_t) std::max(m, 1) * 12, &kp));
+    if (m) gather_rows12(ctx, c.clouds[s], c.kidx[s], m, kp);
+    c.kclouds[s] = kp; c.ksizes[s] = m;
     return LGR_OK;
+}
+
+// the matches of both directions (the pair's own buffers)
+static int alloc_matches(CorrCall& c) {
+    lgr_ctx* ctx = c.ctx;
+    const int ns = c.ksizes[0], nt = c.ksizes[1];
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_IJ, (size_t) ns, &c.ij));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_JI, (size_t) nt, &c.ji));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_DIJ, (size_t) ns, &c.dij));
+    return lgr_ws_t(ctx, WS_PIPE_DJI, (size_t) nt, &c.dji);
 }
 
 static int alloc(CorrCall& c) {
@@ -597,10 +607,7 @@ static int alloc(CorrCall& c) {
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_FEAT_T, (size_t) nt * c.d->len, &c.feat[1]));
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_S, (size_t) c.sizes[0] * 12, &c.surf[0]));
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_SURF_T, (size_t) c.sizes[1] * 12, &c.surf[1]));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_IJ, (size_t) ns, &c.ij));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_JI, (size_t) nt, &c.ji));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_DIJ, (size_t) ns, &c.dij));
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_DJI, (size_t) nt, &c.dji));
+    LGR_TRY(alloc_matches(c));
     LGR_TRY(filter_tables_alloc(ctx, c.p->matching_id, ns, nt, c.p->cluster_k, &c.ftab));
     return lgr_ctx_aux2(ctx);
 }
@@ -622,6 +629,22 @@ static int start_tables(CorrCall& c) {
     return LGR_OK;
 }
 
+// include/matching.h:172,230-231: radius quantised to a power of scale_factor; voxel from feature_nr_points
+static lgr_cloud_lvl single_level(const lgr_params* p) {
+    lgr_cloud_lvl l{};
+    l.log2_radius = (int) std::floor(std::log2(p->feature_radius) / std::log2(p->scale_factor));
+    l.radius = powf(p->scale_factor, (float) l.log2_radius);
+    l.voxel = sqrtf(M_PI * l.radius * l.radius / (float) p->feature_nr_points);
+    return l;
+}
+
+// the matcher of the single-scale search on both clouds' rows
+static int match_single(CorrCall& c) {
+    if (c.ratio()) return match_ratio(c, c.feat[0], c.ksizes[0], c.feat[1], c.ksizes[1], c.ij, c.dij);   // one level: the vote is the identity
+    if (c.p->randomness > 1) return match_knn_vote(c);
+    return match_dispatch(c, c.kclouds[0], c.feat[0], c.ksizes[0], c.kclouds[1], c.feat[1], c.ksizes[1], c.ij, c.dij, c.ji, c.dji);
+}
+
 // The two clouds' feature stages are independent until the matcher: the source cloud runs on this context, the target cloud
 // on a second context (own stream and workspace) driven by a second host thread, so that the ~20 host read-backs per cloud
 // (voxel counts, grid extents) and the short sort / scan launches of one cloud hide behind the other cloud's kernels.
@@ -629,14 +652,11 @@ static int start_tables(CorrCall& c) {
 static int features_and_match_single(CorrCall& c) {
     lgr_ctx* ctx = c.ctx;
     const lgr_params* p = c.p;
-    // include/matching.h:172,230-231: radius quantised to a power of scale_factor; voxel from feature_nr_points
-    const int log2_radius = (int) std::floor(std::log2(p->feature_radius) / std::log2(p->scale_factor));
-    const float search_radius = powf(p->scale_factor, (float) log2_radius);
-    const float voxel = sqrtf(M_PI * search_radius * search_radius / (float) p->feature_nr_points);
+    const lgr_cloud_lvl l = single_level(p);
     auto cloud_features = [&](lgr_ctx* cx, int s, float* ms) -> int {
         LGR_HIP(cx, hipSetDevice(cx->device));
         int nd;
-        return level_features(cx, c, s, c.clouds[s], c.sizes[s], voxel, search_radius, c.surf[s], c.kclouds[s], c.ksizes[s], nullptr, nullptr, c.feat[s], ms, &nd);
+        return level_features(cx, c, s, c.clouds[s], c.sizes[s], l.voxel, l.radius, c.surf[s], c.kclouds[s], c.ksizes[s], nullptr, nullptr, c.feat[s], ms, &nd);
     };
     float ms_t[3] = {0, 0, 0};
     const auto t_feat0 = std::chrono::steady_clock::now();
@@ -656,9 +676,7 @@ static int features_and_match_single(CorrCall& c) {
     for (int s = 0; s < 3; ++s) { c.ms[s] += ms_t[s]; sum += c.ms[s]; }
     if (sum > 0.f) for (int s = 0; s < 3; ++s) c.ms[s] *= wall / sum;
     tick(ctx, 4);
-    if (c.ratio()) return match_ratio(c, c.feat[0], c.ksizes[0], c.feat[1], c.ksizes[1], c.ij, c.dij);   // one level: the vote is the identity
-    if (p->randomness > 1) return match_knn_vote(c);
-    return match_dispatch(c, c.kclouds[0], c.feat[0], c.ksizes[0], c.kclouds[1], c.feat[1], c.ksizes[1], c.ij, c.dij, c.ji, c.dji);
+    return match_single(c);
 }
 
 // wait for the tables, filter, map key-point indices back (finalize), stage times
@@ -694,7 +712,7 @@ extern "C" int lgr_correspondences_ex_dev(lgr_ctx* ctx, const float* d_src, int 
     CorrCall c(ctx, d_src, ns, d_tgt, nt, p, d_out, n_out);   // its guards act on every return below
     LGR_TRY(check(c, fp));
     if (c.empty) return LGR_OK;
-    LGR_TRY(keypoints(c));
+    for (int s = 0; s < 2; ++s) LGR_TRY(keypoints(c, s));
     if (c.ksizes[0] == 0 || c.ksizes[1] == 0) return LGR_OK;   // ISS found nothing on a side: no job has been posted yet
     LGR_TRY(alloc(c));
     LGR_TRY(start_tables(c));                                  // aux2, under everything up to finish
@@ -727,6 +745,105 @@ extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, co
 }
 
 
+// ---- prepared clouds (lgr_cloud.h): the per-cloud stages above, run once per cloud into an object; a pair call starts at the matcher
+static uint32_t float_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+
+int lgr_cloud_key_of(lgr_ctx* ctx, const lgr_params* p, const lgr_feature_params* fp, int side, lgr_cloud_key* out) {
+    lgr_cloud_key k;
+    memset(&k, 0, sizeof k);
+    k.feature_nr_points = p->feature_nr_points; k.normal_nr_points = p->normal_nr_points; k.normals_available = p->normals_available;
+    k.keypoint_id = p->keypoint_id;
+    k.has_vp = side == 0 ? p->has_vp_src : p->has_vp_tgt;
+    k.cluster_k = p->matching_id == LGR_MATCH_CLUSTER ? p->cluster_k : 0;   // the other filters read the densities only
+    k.descriptor_id = fp ? fp->descriptor_id : (int) LGR_DESCRIPTOR_FPFH;
+    k.lrf_id = fp ? fp->lrf_id : (int) LGR_LRF_DEFAULT;
+    k.arithmetic = ctx->opt.arithmetic;
+    k.feature_radius = p->feature_radius > 0.f ? float_bits(p->feature_radius) : 0u;   // unset, however it is written: multi-scale
+    k.scale_factor = float_bits(p->scale_factor);
+    k.iss_radius = float_bits(side == 0 ? p->iss_radius_src : p->iss_radius_tgt);
+    if (k.has_vp) for (int a = 0; a < 3; ++a) k.vp[a] = float_bits((side == 0 ? p->vp_src : p->vp_tgt)[a]);
+    *out = k;
+    return LGR_OK;
+}
+
+int lgr_cloud_fill(lgr_ctx* ctx, lgr_cloud* cl, int side, const lgr_params* p, const lgr_feature_params* fp) {
+    int n0 = 0;
+    lgr_corr none;   // check only asks for an output pointer; nothing is written through it
+    CorrCall c(ctx, cl->pts, cl->n, cl->pts, cl->n, p, &none, &n0);
+    LGR_TRY(check(c, fp));
+    LGR_TRY(lgr_cloud_key_of(ctx, p, fp, side, &cl->key));
+    cl->row_len = c.d->len;
+    cl->multiscale = !(p->feature_radius > 0.f);
+    cl->kps = cl->pts; cl->m = cl->n;
+    if (c.empty) { cl->empty = true; return LGR_OK; }
+    c.own[side] = cl;
+    LGR_TRY(keypoints(c, side));
+    cl->kps = c.kclouds[side]; cl->m = c.ksizes[side]; cl->kidx = c.kidx[side];
+    if (cl->m == 0) return LGR_OK;   // ISS found nothing: a pair with this cloud has no correspondences
+    if (!cl->multiscale) {
+        float* surf;
+        cl->single = single_level(p);
+        cl->single.rows = cl->m;
+        LGR_TRY(lgr_cloud_alloc_t(ctx, cl, (size_t) cl->m * cl->row_len, &cl->feat));
+        LGR_TRY(lgr_ws_t(ctx, side == 0 ? WS_PIPE_SURF_S : WS_PIPE_SURF_T, (size_t) cl->n * 12, &surf));
+        LGR_TRY(level_features(ctx, c, side, cl->pts, cl->n, cl->single.voxel, cl->single.radius, surf, cl->kps, cl->m, nullptr, nullptr, cl->feat, c.ms, &cl->single.surface));
+    } else {
+        LGR_TRY(ms_initialize(c, side, cl->ms));
+    }
+    LGR_TRY(lgr_cloud_alloc_t(ctx, cl, (size_t) cl->m + 16, &cl->thr));
+    if (cl->key.cluster_k) LGR_TRY(lgr_cloud_alloc_t(ctx, cl, (size_t) cl->m * cl->key.cluster_k, &cl->knn));
+    LGR_TRY(filter_cloud_tables(ctx, cl->kps, cl->m, cl->key.cluster_k, cl->thr, cl->knn));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LGR_OK;
+}
+
+extern "C" int lgr_correspondences_prepared_dev(lgr_ctx* ctx, const lgr_cloud* src, const lgr_cloud* tgt, const lgr_params* p, const lgr_feature_params* fp,
+                                                lgr_corr* d_out, int* n_out) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, src && tgt && p && n_out, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, src->device == ctx->device && tgt->device == ctx->device, LGR_ERR_INVALID_ARG);
+    const lgr_cloud* cl[2] = {src, tgt};
+    CorrCall c(ctx, src->pts, src->n, tgt->pts, tgt->n, p, d_out, n_out);
+    LGR_TRY(check(c, fp));
+    for (int s = 0; s < 2; ++s) {
+        lgr_cloud_key k;
+        LGR_TRY(lgr_cloud_key_of(ctx, p, fp, s, &k));
+        LGR_CHECK(ctx, memcmp(&k, &cl[s]->key, sizeof k) == 0 /* the cloud was prepared for other parameters */, LGR_ERR_INVALID_ARG);
+    }
+    for (int s = 0; s < 3; ++s) ctx->stage_ms[s] = 0.f;
+    if (c.empty) return LGR_OK;
+    for (int s = 0; s < 2; ++s) {
+        c.kclouds[s] = cl[s]->kps; c.ksizes[s] = cl[s]->m; c.kidx[s] = cl[s]->kidx;
+        c.feat[s] = cl[s]->feat; c.mss[s] = cl[s]->ms;
+    }
+    if (c.ksizes[0] == 0 || c.ksizes[1] == 0) return LGR_OK;
+    c.ftab.thr_s = src->thr; c.ftab.knn_s = src->knn;
+    c.ftab.thr_t = tgt->thr; c.ftab.knn_t = tgt->knn;
+    LGR_TRY(alloc_matches(c));
+    tick(ctx, 4);
+    LGR_TRY(src->multiscale ? ms_match(c) : match_single(c));
+    return finish(c);
+}
+
+extern "C" int lgr_correspondences_prepared(lgr_ctx* ctx, const lgr_cloud* src, const lgr_cloud* tgt, const lgr_params* p, const lgr_feature_params* fp,
+                                            lgr_corr* out, int* n_out) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, src && tgt && p && n_out, LGR_ERR_INVALID_ARG);
+    lgr_corr* dc = nullptr;
+    if (src->n >= 2 && tgt->n >= 2) {
+        LGR_CHECK(ctx, out != nullptr, LGR_ERR_INVALID_ARG);
+        LGR_HIP(ctx, hipSetDevice(ctx->device));
+        LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) src->n + 1, &dc));
+    }
+    LGR_TRY(lgr_correspondences_prepared_dev(ctx, src, tgt, p, fp, dc, n_out));
+    if (*n_out) LGR_HIP(ctx, hipMemcpyAsync(out, dc, (size_t) *n_out * 16, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LGR_OK;
+}
+
+
 extern "C" int lgr_align_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, lgr_result* res) {
     return lgr_align_ex_dev(ctx, d_src, ns, d_tgt, nt, p, nullptr, res);
 }
@@ -736,29 +853,59 @@ extern "C" int lgr_align_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const 
     return lgr_align_ex2_dev(ctx, d_src, ns, d_tgt, nt, p, fp, nullptr, res);
 }
 
+static int align_estimate(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, const lgr_metric_params* mp,
+                          const lgr_corr* dc, int c, std::chrono::steady_clock::time_point t0, lgr_result* res);
+// what lgr_align* checks before the search, and its answer for a cloud without two points
+static int align_check(lgr_ctx* ctx, const lgr_params* p, const lgr_feature_params* fp) {
+    // alignTeaser throws in the reference (src/alignment.cpp:40)
+    LGR_CHECK(ctx, p->alignment_id == LGR_ALIGN_RANSAC || p->alignment_id == LGR_ALIGN_GROR, LGR_ERR_UNSUPPORTED);
+    LGR_CHECK(ctx, p->n_samples >= 3 && p->n_samples <= 8, LGR_ERR_UNSUPPORTED);   // (lgr_ransac.hip instantiates its kernels for 3..8)
+    const Descriptor* descriptor;
+    return feature_descriptor(ctx, p, fp, &descriptor);
+}
+static void align_identity(lgr_result* res) {
+    // a cloud without two points gives no correspondences; the reference then leaves the identity, not converged
+    // (selectCorrespondences refuses fewer than n_samples, src/sac_prerejective_omp.cpp:36-42)
+    memset(res, 0, sizeof(*res));
+    for (int i = 0; i < 16; ++i) res->transformation[i] = (i % 5 == 0) ? 1.f : 0.f;
+}
+
+extern "C" int lgr_align_prepared(lgr_ctx* ctx, const lgr_cloud* src, const lgr_cloud* tgt, const lgr_params* p, const lgr_feature_params* fp,
+                                  const lgr_metric_params* mp, lgr_result* res) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, src && tgt && p && res, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, src->device == ctx->device && tgt->device == ctx->device, LGR_ERR_INVALID_ARG);
+    LGR_TRY(align_check(ctx, p, fp));
+    if (src->n < 2 || tgt->n < 2) { align_identity(res); return LGR_OK; }
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    auto t0 = std::chrono::steady_clock::now();
+    lgr_corr* dc;
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) src->n + 1, &dc));
+    int c = 0;
+    LGR_TRY(lgr_correspondences_prepared_dev(ctx, src, tgt, p, fp, dc, &c));
+    return align_estimate(ctx, src->pts, src->n, tgt->pts, tgt->n, p, mp, dc, c, t0, res);
+}
+
 extern "C" int lgr_align_ex2_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
                                  const lgr_metric_params* mp, lgr_result* res) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (d_src || ns == 0) && (d_tgt || nt == 0) && p && res && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
-    // alignTeaser throws in the reference (src/alignment.cpp:40)
-    LGR_CHECK(ctx, p->alignment_id == LGR_ALIGN_RANSAC || p->alignment_id == LGR_ALIGN_GROR, LGR_ERR_UNSUPPORTED);
-    LGR_CHECK(ctx, p->n_samples >= 3 && p->n_samples <= 8, LGR_ERR_UNSUPPORTED);   // (lgr_ransac.hip instantiates its kernels for 3..8)
-    const Descriptor* descriptor;
-    LGR_TRY(feature_descriptor(ctx, p, fp, &descriptor));
-    if (ns < 2 || nt < 2) {
-        // a cloud without two points gives no correspondences; the reference then leaves the identity, not converged
-        // (selectCorrespondences refuses fewer than n_samples, src/sac_prerejective_omp.cpp:36-42)
-        memset(res, 0, sizeof(*res));
-        for (int i = 0; i < 16; ++i) res->transformation[i] = (i % 5 == 0) ? 1.f : 0.f;
-        return LGR_OK;
-    }
+    LGR_TRY(align_check(ctx, p, fp));
+    if (ns < 2 || nt < 2) { align_identity(res); return LGR_OK; }
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     auto t0 = std::chrono::steady_clock::now();
     lgr_corr* dc;
     LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));
     int c = 0;
     LGR_TRY(lgr_correspondences_ex_dev(ctx, d_src, ns, d_tgt, nt, p, fp, dc, &c));
+    return align_estimate(ctx, d_src, ns, d_tgt, nt, p, mp, dc, c, t0, res);
+}
+
+// the transform estimation behind a finished search (src/alignment.cpp:72-109), for lgr_align_ex2_dev and lgr_align_prepared
+static int align_estimate(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_params* p, const lgr_metric_params* mp,
+                          const lgr_corr* dc, int c, std::chrono::steady_clock::time_point t0, lgr_result* res) {
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     double time_cs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     tick(ctx, 7);

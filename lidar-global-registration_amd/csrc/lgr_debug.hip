@@ -282,6 +282,27 @@ extern "C" int lgr_nearest_dev(lgr_ctx* ctx, const float* d_q, int nq, const flo
     return LGR_OK;
 }
 
+extern "C" int lgr_nearest(lgr_ctx* ctx, const float* q, int nq, const float* pts, int n, int32_t* idx, float* d2) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, nq >= 0 && n >= 0 && (q || nq == 0) && (pts || n == 0) && (idx || nq == 0), LGR_ERR_INVALID_ARG);
+    if (nq == 0) return LGR_OK;
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    float *dq, *dp, *dd;
+    int32_t* di;
+    LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_A, (size_t) nq * 12, &dq));
+    LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_B, (size_t) n * 12, &dp));
+    LGR_TRY(lgr_ws_t(ctx, WS_DBG_MISC, (size_t) 2 * nq, &di));
+    dd = (float*) (di + nq);
+    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) nq * 48, hipMemcpyHostToDevice, ctx->stream));
+    if (n) LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    LGR_TRY(lgr_nearest_dev(ctx, dq, nq, dp, n, di, dd));
+    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (d2) LGR_HIP(ctx, hipMemcpyAsync(d2, dd, (size_t) nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return LGR_OK;
+}
+
 extern "C" int lgr_compare_overlaps_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* tns16, int n, float distance_thr,
                                         int32_t* counts, float* weighted_counts, int32_t* counts2, uint8_t* d_mask_src, uint8_t* d_mask_tgt) {
     lgr_turn turn__(ctx);

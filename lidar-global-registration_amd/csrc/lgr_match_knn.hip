@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "lgr_match_dense.cuh"
+#include "lgr_cloud.h"
 
 namespace {
 
@@ -279,6 +280,18 @@ int lgr_ratio_test_core(lgr_ctx* ctx, const int32_t* d_knn_idx, const float* d_k
     return LGR_OK;
 }
 
+// the multi-scale path's vote (lgr_cloud.h): the width and radius the caller has -- the width bound and the radius check belong to the
+// public entry points --, candidates that are the pipeline's own, so the flag is not read back
+int lgr_vote_matches_launch(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
+                            float iss_radius, int32_t* d_idx, float* d_dist) {
+    if (mq == 0) return LGR_OK;
+    int* bad;
+    LGR_TRY(lgr_ws_t(ctx, WS_KNN_FLAG, 1, &bad));
+    vote_matches_kernel<<<cdiv(mq, 256), 256, 0, ctx->stream>>>(d_cand_idx, d_cand_dist, mq, width, d_train_pts, mt, iss_radius, d_idx, d_dist, bad);
+    LGR_HIP(ctx, hipGetLastError());
+    return LGR_OK;
+}
+
 int lgr_vote_matches_core(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
                           float iss_radius, int32_t* d_idx, float* d_dist) {
     LGR_CHECK(ctx, mq >= 0 && mt >= 0 && width >= 1 && width <= 64 && std::isfinite(iss_radius) && iss_radius > 0.f, LGR_ERR_INVALID_ARG);
@@ -288,8 +301,7 @@ int lgr_vote_matches_core(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* 
     int* bad;
     LGR_TRY(lgr_ws_t(ctx, WS_KNN_FLAG, 1, &bad));
     LGR_HIP(ctx, hipMemsetAsync(bad, 0, 4, ctx->stream));
-    vote_matches_kernel<<<cdiv(mq, 256), 256, 0, ctx->stream>>>(d_cand_idx, d_cand_dist, mq, width, d_train_pts, mt, iss_radius, d_idx, d_dist, bad);
-    LGR_HIP(ctx, hipGetLastError());
+    LGR_TRY(lgr_vote_matches_launch(ctx, d_cand_idx, d_cand_dist, mq, width, d_train_pts, mt, iss_radius, d_idx, d_dist));
     int h_bad = 0;
     LGR_HIP(ctx, hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -510,6 +510,26 @@ public:
     virtual CorrespondencesPtr calculateCorrespondences() = 0;
     virtual ~CorrespondenceSearch() = default;
 };
+// one lgr_cloud for the duration of a scope (include/lgr.h: prepared clouds), the reference's per-cloud Storage (include/matching.h:132-146)
+class PreparedCloud {
+public:
+    PreparedCloud(const PointNCloud& cloud, int side, const lgr_params& a, const lgr_feature_params& f) {
+        check(lgr_cloud_prepare(context(), reinterpret_cast<const float*>(cloud.points.data()), (int) cloud.size(), side, &a, &f, &cloud_), "lgr_cloud_prepare");
+    }
+    ~PreparedCloud() { lgr_cloud_destroy(cloud_); }
+    PreparedCloud(const PreparedCloud&) = delete;
+    PreparedCloud& operator=(const PreparedCloud&) = delete;
+    const lgr_cloud* get() const { return cloud_; }
+private:
+    lgr_cloud* cloud_ = nullptr;
+};
+// AlignmentParameters::save_features: the writer of one level's descriptor table lives with the other file formats in lgr_io.hpp
+// (saveFeatures, include/feature_analysis.h:11-27), which registers it here when it is included; a caller that never sets save_features
+// needs neither.
+using FeatureSaver = void (*)(const AlignmentParameters& parameters, bool is_source, const std::optional<int>& log2_radius, const float* rows, std::size_t n,
+                              std::size_t row_len);
+inline FeatureSaver& feature_saver() { static FeatureSaver saver = nullptr; return saver; }
+
 class FeatureBasedCorrespondenceSearch : CorrespondenceSearch {
 public:
     FeatureBasedCorrespondenceSearch() = delete;
@@ -523,12 +543,35 @@ public:
         lgr_params a = to_abi(parameters_);
         auto out = std::make_shared<Correspondences>(src_->size());
         int n = 0;
-        check(lgr_correspondences_ex(context(), raw(*src_), (int) src_->size(), raw(*tgt_), (int) tgt_->size(), &a, &f,
-                                     reinterpret_cast<lgr_corr*>(out->data()), &n), "calculateCorrespondences");
+        // initialize() per cloud (include/matching.h:164-262), then the pair: the bytes lgr_correspondences_ex returns
+        PreparedCloud src(*src_, 0, a, f), tgt(*tgt_, 1, a, f);
+        check(lgr_correspondences_prepared(context(), src.get(), tgt.get(), &a, &f, reinterpret_cast<lgr_corr*>(out->data()), &n), "calculateCorrespondences");
         out->resize(n);
+        if (parameters_.save_features) saveFeatures(src.get(), tgt.get());
         return out;
     }
 protected:
+    // include/matching.h:273-279: the tables of every level the two clouds share, source -> target only (!inverse_tn)
+    void saveFeatures(const lgr_cloud* src, const lgr_cloud* tgt) const {
+        if (!feature_saver()) throw std::runtime_error("lgr: save_features needs lgr_io.hpp (saveFeatures) in the program");
+        const lgr_cloud* clouds[2] = {src, tgt};
+        struct lgr_cloud_info info[2];
+        for (int s = 0; s < 2; ++s) check(lgr_cloud_info(clouds[s], &info[s]), "lgr_cloud_info");
+        if (!info[0].levels || !info[1].levels) return;
+        const int lo = std::max(info[0].first_log2_radius, info[1].first_log2_radius);
+        const int hi = std::min(info[0].first_log2_radius + info[0].levels, info[1].first_log2_radius + info[1].levels) - 1;
+        std::vector<float> rows;
+        for (int log2_radius = lo; log2_radius <= hi; ++log2_radius)
+            for (int s = 0; s < 2; ++s) {
+                lgr_cloud_level_info li;
+                const int level = log2_radius - info[s].first_log2_radius;
+                check(lgr_cloud_level(clouds[s], level, &li, nullptr, nullptr), "lgr_cloud_level");
+                rows.resize((std::size_t) li.rows * (std::size_t) info[s].row_len);
+                check(lgr_cloud_level(clouds[s], level, nullptr, nullptr, rows.data()), "lgr_cloud_level");
+                feature_saver()(parameters_, s == 0, info[s].multiscale ? std::optional<int>(log2_radius) : std::nullopt, rows.data(), (std::size_t) li.rows,
+                                (std::size_t) info[s].row_len);
+            }
+    }
     PointNCloud::ConstPtr src_, tgt_;
     AlignmentParameters parameters_;
 };

@@ -286,6 +286,72 @@ inline void saveVector(const std::vector<T>& vs, const std::string& filepath) {
     fout.close();
 }
 
+// include/feature_analysis.h:11-27 saveFeatures, on a row table (n rows of row_len floats) and the file it goes to: one line
+// `index,v0,...,vD-1` per row, no header; the index is the row number unless `indices` names it (the reference passes none).  The file
+// names of include/matching.h:274-278 come from featuresPath.
+inline void saveFeatures(const float* rows, std::size_t n, std::size_t row_len, const std::vector<int>* indices, const std::string& filepath) {
+    std::ofstream fout(filepath);
+    if (!fout.is_open()) perror(("error while opening file " + filepath).c_str());
+    for (std::size_t i = 0; i < n; ++i) {
+        if (indices) fout << (*indices)[i]; else fout << i;
+        for (std::size_t j = 0; j < row_len; ++j) fout << "," << rows[i * row_len + j];
+        fout << "\n";
+    }
+    fout.close();
+}
+// histograms_src / histograms_tgt with a fixed feature radius, histograms<log2_radius>_src / _tgt per level without one
+inline std::string featuresStem(bool is_source, const std::optional<int>& log2_radius = std::nullopt) {
+    return "histograms" + (log2_radius.has_value() ? std::to_string(log2_radius.value()) : std::string()) + (is_source ? "_src" : "_tgt");
+}
+
+// the writer FeatureBasedCorrespondenceSearch uses under AlignmentParameters::save_features (lgr_compat.hpp: feature_saver): the file is
+// parameters.dir_path / <featuresStem>.csv
+namespace io_detail {
+inline void save_level_features(const AlignmentParameters& parameters, bool is_source, const std::optional<int>& log2_radius, const float* rows, std::size_t n,
+                                std::size_t row_len) {
+    saveFeatures(rows, n, row_len, nullptr, (std::filesystem::path(parameters.dir_path) / (featuresStem(is_source, log2_radius) + ".csv")).string());
+}
+inline const bool feature_saver_registered = (feature_saver() = &save_level_features, true);
+}  // namespace io_detail
+
+// src/feature_analysis.cpp:20-56 saveExtractedPointIds for points already in memory: the nearest source point, the source moved by the
+// ground truth, and the nearest target point of every extracted point (two lgr_nearest calls), written to `filepath`
+inline void saveExtractedPointIds(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& transformation_gt,
+                                  const PointNCloud::ConstPtr& extracted_points, const std::string& filepath);
+
+// src/feature_analysis.cpp:46-54, the file of saveExtractedPointIds: the ids and, per axis, the coordinate of the moved source point and of
+// the target point they name
+inline void saveExtractedPointIds(const std::vector<int>& src_ids, const std::vector<int>& tgt_ids, const PointNCloud& src_aligned_gt, const PointNCloud& tgt,
+                                  const std::string& filepath) {
+    std::ofstream fout(filepath);
+    if (!fout.is_open()) perror(("error while opening file " + filepath).c_str());
+    fout << "id_src,id_tgt,x_src,x_tgt,y_src,y_tgt,z_src,z_tgt\n";
+    for (std::size_t i = 0; i < src_ids.size(); ++i) {
+        const PointN &s = src_aligned_gt.points[(std::size_t) src_ids[i]], &t = tgt.points[(std::size_t) tgt_ids[i]];
+        fout << src_ids[i] << "," << tgt_ids[i] << ",";
+        fout << s.x << "," << t.x << ",";
+        fout << s.y << "," << t.y << ",";
+        fout << s.z << "," << t.z << "\n";
+    }
+    fout.close();
+}
+
+inline void saveExtractedPointIds(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& transformation_gt,
+                                  const PointNCloud::ConstPtr& extracted_points, const std::string& filepath) {
+    PointNCloud src_aligned_gt;
+    transformPointCloudWithNormals(*src, src_aligned_gt, transformation_gt);
+    const int n = (int) extracted_points->size();
+    std::vector<std::int32_t> ids[2];
+    const PointNCloud* all[2] = {&src_aligned_gt, tgt.get()};
+    for (int s = 0; s < 2; ++s) {
+        ids[s].assign((std::size_t) n + 1, 0);
+        check(lgr_nearest(context(), reinterpret_cast<const float*>(extracted_points->points.data()), n, reinterpret_cast<const float*>(all[s]->points.data()),
+                          (int) all[s]->size(), ids[s].data(), nullptr), "saveExtractedPointIds");
+        ids[s].resize((std::size_t) n);
+    }
+    saveExtractedPointIds(std::vector<int>(ids[0].begin(), ids[0].end()), std::vector<int>(ids[1].begin(), ids[1].end()), src_aligned_gt, *tgt, filepath);
+}
+
 // ---- the files of generateDebugFiles / compareHypotheses (src/main.cpp:207-284).  A file is parameters.dir_path / <stem>.<extension>, the stem
 //      being the reference's `name` argument (its constructPath adds the test name and version in front).  The histogram PNGs are not
 //      written: plots.py is no part of this project.

@@ -226,6 +226,18 @@ class Measurement(C.Structure):
                 ("reserved", C.c_int32 * 5)]
 
 
+class CloudInfo(C.Structure):
+    """struct lgr_cloud_info (include/lgr.h)."""
+    _fields_ = [("n", C.c_int32), ("keypoints", C.c_int32), ("row_len", C.c_int32), ("levels", C.c_int32), ("first_log2_radius", C.c_int32),
+                ("multiscale", C.c_int32), ("bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+class CloudLevelInfo(C.Structure):
+    """lgr_cloud_level_info (include/lgr.h)."""
+    _fields_ = [("log2_radius", C.c_int32), ("radius", C.c_float), ("voxel", C.c_float), ("rows", C.c_int32), ("surface", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class LgrError(RuntimeError):
     pass
 
@@ -247,6 +259,10 @@ _lib.lgr_measure_mean.restype = C.c_float
 _lib.lgr_measure_mean.argtypes = [C.c_void_p, C.c_int]
 _lib.lgr_measure_deviation.restype = C.c_float
 _lib.lgr_measure_deviation.argtypes = [C.c_void_p, C.c_int, C.c_float]
+_lib.lgr_cloud_destroy.argtypes = [C.c_void_p]
+_lib.lgr_cloud_info.argtypes = [C.c_void_p, C.c_void_p]
+_lib.lgr_cloud_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.lgr_cloud_level.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
 if _lib.lgr_version() != ABI_VERSION:     # a stale liblgr_hip.so would read lgr_params / call lgr_match_last_* with another layout
     raise ImportError(f"{LIB_PATH} has ABI revision {_lib.lgr_version()}, this binding needs {ABI_VERSION}: rebuild it (make -C {_CSRC})")
 
@@ -278,6 +294,66 @@ def _ptr(t):
     if isinstance(t, np.ndarray):
         return t.ctypes.data_as(C.c_void_p)
     return C.c_void_p(t.data_ptr())
+
+
+class PreparedCloud:
+    """One lgr_cloud (Context.prepare_cloud): key points, per-level descriptor rows and the filter's tables of one cloud, in device
+    memory of its own.  Read-only for every pair call; close() (or the with block) frees it."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def close(self):
+        if self.h:
+            _lib.lgr_cloud_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _ok(rc):
+        if rc != 0:
+            raise LgrError(f"rc={rc}")
+
+    def info(self):
+        out = CloudInfo()
+        self._ok(_lib.lgr_cloud_info(self.h, C.byref(out)))
+        return out
+
+    def keypoints(self):
+        """indices of the key points into the cloud, int32 [m]"""
+        out = np.empty(self.info().keypoints, np.int32)
+        m = C.c_int(0)
+        self._ok(_lib.lgr_cloud_keypoints(self.h, _ptr(out), C.byref(m)))
+        return out[: m.value]
+
+    def levels(self):
+        """the CloudLevelInfo of every level"""
+        out = []
+        for i in range(self.info().levels):
+            li = CloudLevelInfo()
+            self._ok(_lib.lgr_cloud_level(self.h, i, C.byref(li), None, None))
+            out.append(li)
+        return out
+
+    def level(self, i):
+        """(CloudLevelInfo, list int32 [rows] of indices into the key points, rows float32 [rows, row_len])"""
+        li = CloudLevelInfo()
+        self._ok(_lib.lgr_cloud_level(self.h, int(i), C.byref(li), None, None))
+        lst = np.empty(li.rows, np.int32)
+        rows = np.empty((li.rows, self.info().row_len), np.float32)
+        self._ok(_lib.lgr_cloud_level(self.h, int(i), C.byref(li), _ptr(lst), _ptr(rows)))
+        return li, lst, rows
 
 
 class Context:
@@ -843,6 +919,37 @@ class Context:
             self.check(_lib.lgr_correspondences_ex_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], C.byref(params),
                                                        C.byref(f), _ptr(out), C.byref(n)))
         return out[: n.value]
+
+    # ---- prepared clouds (lgr_cloud: the per-cloud half of the search, run once) ----------------------------
+    def _prepare_cloud(self, fn, pts, params, side, descriptor):
+        f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+        h = C.c_void_p()
+        self.check(fn(self.h, _ptr(pts), pts.shape[0], int(side), C.byref(params), C.byref(f), C.byref(h)))
+        return PreparedCloud(self, h)
+
+    def prepare_cloud(self, pts, params, side=0, descriptor="fpfh"):
+        """lgr_cloud_prepare_dev: pts a cuda float32 [n,12] (copied: the object owns its memory).  side 0 / 1: which of the vp_* /
+        iss_radius_* fields of params the cloud is prepared with."""
+        return self._prepare_cloud(_lib.lgr_cloud_prepare_dev, pts, params, side, descriptor)
+
+    def prepare_cloud_host(self, pts, params, side=0, descriptor="fpfh"):
+        return self._prepare_cloud(_lib.lgr_cloud_prepare, np.ascontiguousarray(pts, np.float32), params, side, descriptor)
+
+    def correspondences_prepared(self, a, b, params, descriptor="fpfh"):
+        """lgr_correspondences_prepared_dev on two PreparedCloud: what correspondences() returns for their clouds."""
+        out = self.empty((max(a.info().n, 1), 4), self.torch.int32)
+        n = C.c_int(0)
+        f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+        self.check(_lib.lgr_correspondences_prepared_dev(self.h, a.h, b.h, C.byref(params), C.byref(f), _ptr(out), C.byref(n)))
+        return out[: n.value]
+
+    def align_prepared(self, a, b, params, descriptor="fpfh", metric_params=None):
+        """lgr_align_prepared: what align_ex2() returns for the two clouds, apart from the time fields."""
+        res = Result()
+        f = descriptor if isinstance(descriptor, FeatureParams) else feature_params(descriptor)
+        self.check(_lib.lgr_align_prepared(self.h, a.h, b.h, C.byref(params), C.byref(f),
+                                           C.byref(metric_params) if metric_params is not None else None, C.byref(res)))
+        return res
 
     def stage_ms(self):
         out = (C.c_float * 12)()
@@ -1483,6 +1590,20 @@ class Context:
         self.check(_lib.lgr_nearest_dev(self.h, _ptr(q), q.shape[0], _ptr(pts), pts.shape[0], _ptr(idx), _ptr(d2)))
         self._join()
         return idx[: q.shape[0]], d2[: q.shape[0]]
+
+    def extracted_point_ids(self, src, tgt, T_gt, extracted):
+        """saveExtractedPointIds (src/feature_analysis.cpp:20-56): for every extracted point the nearest source point, the source moved by
+        the ground truth, and the nearest target point (two lgr_nearest_dev calls).  src, tgt, extracted: cuda float32 [n, 12]; the source
+        is moved on the host in the order the library moves a cloud, x c0 + (y c1 + (z c2 + c3)).  Returns numpy id_src / id_tgt int32 [n]
+        and the two points' coordinates xyz_src / xyz_tgt float32 [n, 3] (formats.write_extracted_ids writes them)."""
+        T = np.asarray(T_gt, np.float32)
+        moved = src.cpu().numpy().copy()
+        x, y, z = moved[:, 0].copy(), moved[:, 1].copy(), moved[:, 2].copy()
+        for a in range(3):
+            moved[:, a] = T[a, 0] * x + (T[a, 1] * y + (T[a, 2] * z + T[a, 3]))
+        id_src = self.nearest(extracted, self.torch.from_numpy(moved).to(self._dev()))[0].cpu().numpy()
+        id_tgt = self.nearest(extracted, tgt)[0].cpu().numpy()
+        return dict(id_src=id_src, id_tgt=id_tgt, xyz_src=moved[id_src, :3], xyz_tgt=tgt.cpu().numpy()[id_tgt, :3])
 
     def color_map(self, values, vmin=None, vmax=None):
         """getColor per value of a cuda float32 vector -> numpy int32 colours.  Without a range: saveColorizedWeights' 0.01 / 0.99 quantiles

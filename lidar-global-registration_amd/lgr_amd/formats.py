@@ -204,6 +204,40 @@ def save_vector(path, values):
             f.write(_g(v) + "\n")
 
 
+def _gf(v):
+    """_g for a float that may be a NaN with the sign bit set: `ostream << float` prints that one as -nan"""
+    v = float(v)
+    return "-nan" if v != v and np.signbit(v) else _g(v)
+
+
+def histograms_name(log2_radius=None, is_source=True):
+    """the file stem of saveFeatures as match_multiscale calls it (include/matching.h:274-278): histograms_src / histograms_tgt with a
+    fixed feature radius, histograms<log2_radius>_src / _tgt per level without one"""
+    return "histograms" + ("" if log2_radius is None else str(int(log2_radius))) + ("_src" if is_source else "_tgt")
+
+
+def write_histograms(path, rows, indices=None):
+    """saveFeatures (include/feature_analysis.h:11-27): one line `index,v0,...,vD-1` per descriptor row, no header; the index is the
+    row number unless `indices` names it (the reference passes none)."""
+    rows = np.asarray(rows, np.float32)
+    with open(path, "w") as f:
+        for i, r in enumerate(rows):
+            f.write(str(int(indices[i]) if indices is not None else i) + "".join("," + _gf(v) for v in r) + "\n")
+
+
+EXTRACTED_IDS_HEADER = "id_src,id_tgt,x_src,x_tgt,y_src,y_tgt,z_src,z_tgt"
+
+
+def write_extracted_ids(path, ids):
+    """saveExtractedPointIds (src/feature_analysis.cpp:46-54).  ids: what Context.extracted_point_ids returns -- id_src / id_tgt [n],
+    xyz_src (the source points moved by the ground truth, at id_src) and xyz_tgt (the target points at id_tgt), [n, 3] each."""
+    with open(path, "w") as f:
+        f.write(EXTRACTED_IDS_HEADER + "\n")
+        for i in range(len(ids["id_src"])):
+            f.write("%d,%d," % (int(ids["id_src"][i]), int(ids["id_tgt"][i]))
+                    + ",".join(_gf(ids["xyz_src"][i][a]) + "," + _gf(ids["xyz_tgt"][i][a]) for a in range(3)) + "\n")
+
+
 def save_transformation(csv_path, name, T):
     """saveTransformation (src/common.cpp:127-153): append one row, header on creation."""
     exists = os.path.exists(csv_path)

@@ -5,7 +5,7 @@
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
                                  [--debug-dir DIR] [--hypotheses N [--hypotheses-plane]] [--refine N]
-                                 [--measure N [--measure-seed S0] [--measurements test_measurements.csv]]
+                                 [--measure N [--measure-seed S0] [--measurements test_measurements.csv]] [--save-features DIR]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
@@ -33,6 +33,9 @@ N alignments that differ in the RANSAC seed only (S0, S0 + 1, ...; S0 defaults t
 them, all judged against the ground truth in one batch; one line per run, then the aggregate row, appended to --measurements when given
 (with the header when the file is new).  With --hypotheses N and --ground-truth the members of the set are judged the same way
 (lgr_evaluate_gt_batch) and their rotation, translation and overlap error are listed.
+With --save-features DIR or --measure N the two clouds are prepared once (lgr_cloud_prepare) and the alignment runs on the prepared clouds
+(lgr_align_prepared; lgr_measure itself searches once for all its runs, as before).  --save-features is the reference's save_features: DIR receives the descriptor tables of the levels the clouds share, named as include/matching.h:274-278
+names them, plus ids.csv (saveExtractedPointIds for the target cloud) with --ground-truth.
 """
 import argparse
 import os
@@ -85,6 +88,8 @@ def main():
                     help="the measure test type: N seeded runs judged against --ground-truth, and their test_measurements.csv row")
     ap.add_argument("--measure-seed", type=int, default=None, metavar="S0", help="seed of the first run (default: the profile's seed); run i uses S0 + i")
     ap.add_argument("--measurements", default=None, metavar="PATH", help="test_measurements.csv the aggregate row is appended to (with --measure)")
+    ap.add_argument("--save-features", default=None, metavar="DIR",
+                    help="save_features: prepare the two clouds once, align through them and write the levels' descriptor tables (and ids.csv with --ground-truth) to DIR")
     a = ap.parse_args()
     if a.measure and not a.ground_truth:
         ap.error("--measure needs --ground-truth")
@@ -123,7 +128,9 @@ def main():
                                 normals_available=ld["normals_available"], randomness=a.randomness)
     t = time.perf_counter()
     lrf = {"default": capi.LRF_DEFAULT, "gravity": capi.LRF_GRAVITY}[a.lrf]
-    if a.metric == "weighted_closest_plane":
+    if a.save_features or a.measure:
+        res = align_prepared(ctx, capi, formats, a, p, clouds, lrf)
+    elif a.metric == "weighted_closest_plane":
         res = ctx.align_ex2(clouds[0], clouds[1], p, descriptor=_descriptor(capi, a, lrf, True), mparams=capi.metric_params(a.weight))
     else:
         res = ctx.align(clouds[0], clouds[1], p, descriptor=_descriptor(capi, a, lrf))
@@ -145,6 +152,33 @@ def main():
         refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
     if a.measure:
         measure(ctx, capi, formats, a, p, clouds, name, lrf)
+
+
+def align_prepared(ctx, capi, formats, a, p, clouds, lrf):
+    """--save-features / --measure: both clouds are prepared once (lgr_cloud_prepare) and the alignment runs on the prepared clouds.
+    AlignmentParameters::save_features: the descriptor tables of the levels the two clouds share are written as match_multiscale does for
+    source -> target (include/matching.h:273-279): histograms_src.csv / histograms_tgt.csv with a fixed radius,
+    histograms<log2_radius>_src.csv / _tgt.csv per level without one.  With --ground-truth also ids.csv for the target cloud
+    (saveExtractedPointIds, src/main.cpp:342-344)."""
+    f = _descriptor(capi, a, lrf, True)
+    t = time.perf_counter()
+    with ctx.prepare_cloud(clouds[0], p, 0, f) as src, ctx.prepare_cloud(clouds[1], p, 1, f) as tgt:
+        print(f"prepared both clouds in {1e3 * (time.perf_counter() - t):.1f} ms ({src.info().bytes + tgt.info().bytes} bytes held)")
+        res = ctx.align_prepared(src, tgt, p, descriptor=f, metric_params=capi.metric_params(a.weight) if a.metric == "weighted_closest_plane" else None)
+        if not a.save_features:
+            return res
+        os.makedirs(a.save_features, exist_ok=True)
+        levels = [{li.log2_radius: i for i, li in enumerate(c.levels())} for c in (src, tgt)]
+        for log2_radius in sorted(set(levels[0]) & set(levels[1])):
+            for c, lv, is_source in ((src, levels[0], True), (tgt, levels[1], False)):
+                stem = formats.histograms_name(None if a.feature_radius > 0 else log2_radius, is_source)
+                formats.write_histograms(os.path.join(a.save_features, stem + ".csv"), c.level(lv[log2_radius])[2])
+                print(f"wrote {stem}.csv")
+    if a.ground_truth:
+        T_gt = formats.get_transformation(a.ground_truth[0], a.ground_truth[1])
+        formats.write_extracted_ids(os.path.join(a.save_features, "ids.csv"), ctx.extracted_point_ids(clouds[0], clouds[1], T_gt, clouds[1]))
+        print("wrote ids.csv")
+    return res
 
 
 def measure(ctx, capi, formats, a, p, clouds, name, lrf):
