@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-/* ABI revision.  Still 5 with the prepared clouds: lgr_cloud, struct lgr_cloud_info, lgr_cloud_level_info, lgr_cloud_prepare*, lgr_cloud_destroy,
+/* ABI revision.  Still 5 with the reference point order on the device: lgr_hash_order_dev, lgr_downsample_order_dev, lgr_dedupe_order_dev,
+ * lgr_preprocess_order_dev and lgr_selfcheck_hash_order are additions; no struct or entry point that existed changed.  Still 5 with the prepared clouds: lgr_cloud, struct lgr_cloud_info, lgr_cloud_level_info, lgr_cloud_prepare*, lgr_cloud_destroy,
  * lgr_cloud_info, lgr_cloud_keypoints*, lgr_cloud_level*, lgr_correspondences_prepared*, lgr_align_prepared and the host twin lgr_nearest are
  * additions; no struct or entry point that existed changed.  Still 5 with the ratio matcher: lgr_feature_params.ratio_k takes the first of that struct's reserved words (a host that
  * zeroes them gets k = 2, MATCHING_RATIO_K, and the word is read under LGR_MATCH_RATIO only), LGR_MATCH_RATIO and the lgr_ratio_test* /
@@ -231,7 +232,8 @@ int lgr_bbox_dev(lgr_ctx*, const float* d_pts, int n, float* d_min3_max3 /* 6 fl
 /* ---- loader preprocessing: the steps of loadPointClouds (src/common.cpp:429-470) after the PLY reader:
  *      filterDuplicatePoints (:417-427), intensity = 1, voxel grid at 2 x calculatePointCloudDensity (:453-456,
  *      include/common.h:288), estimateNormalsPoints(30).  out holds n points, out != pts.  vp3 NULL -> origin.
- *      order (host entry): LGR_ORDER_REFERENCE reproduces the libstdc++ unordered_set / unordered_map output order. ---- */
+ *      order (host entry): LGR_ORDER_REFERENCE reproduces the libstdc++ unordered_set / unordered_map output order
+ *      (lgr_preprocess_order_dev below). ---- */
 int lgr_preprocess(lgr_ctx*, const float* pts, int n, const float* vp3, int normals_available, int order, float* out, int* n_out, float* voxel_out);
 int lgr_preprocess_dev(lgr_ctx*, const float* d_pts, int n, const float* vp3 /* host */, int normals_available, float* d_out, int* n_out /* host */,
                        float* voxel_out /* host, or NULL */);
@@ -251,10 +253,38 @@ int lgr_iss_keypoints_dev(lgr_ctx*, const float* d_pts, int n, float radius, flo
 
 /* ---- include/downsample.h:32 downsamplePointCloud(pcd, pcd_down, voxel_size)  (src/downsample.cpp:5-41) ----
  * out may alias the input (the reference passes the same cloud, src/common.cpp:455-456).  n_out <= n.
- * order: LGR_ORDER_REFERENCE reproduces the libstdc++ unordered_map iteration order (host post-pass),
+ * order: LGR_ORDER_REFERENCE reproduces the libstdc++ unordered_map iteration order (on the device: lgr_downsample_order_dev),
  *        LGR_ORDER_CANONICAL = voxels sorted by (iz,iy,ix). */
 int lgr_downsample(lgr_ctx*, const float* pts, int n, float voxel, int order, float* out, int* n_out);
 int lgr_downsample_dev(lgr_ctx*, const float* d_pts, int n, float voxel, float* d_out, int* n_out /* host */);
+
+/* ---- the reference's point ORDER on the device ----
+ * The reference numbers its points by the iteration order of two libstdc++ hash containers: the std::unordered_set of
+ * filterDuplicatePoints (src/common.cpp:417-427, after reserve(n)) and the std::unordered_map of downsamplePointCloud
+ * (src/downsample.cpp:20,32-34); every index it writes afterwards (correspondence CSVs, extracted point ids, inlier lists) is in that
+ * order.  csrc/lgr_stdhash.h states the rule (bucket schedule from the runtime's rehash policy object, per bucket count one sort by
+ * (earliest time of the bucket descending, time descending)) and the two hashes; csrc/lgr_hash_order.hip runs it as kernels.
+ *
+ * lgr_hash_order_dev: the elements of a container are its distinct keys, numbered 0..n-1 by first insertion, d_hash[e] the hash code of
+ * element e; d_order (n entries) receives the element ids in iteration order.  reserve: 0 (the container grew by itself) or the argument
+ * of a reserve() before the first insertion, >= n; anything else is LGR_ERR_INVALID_ARG.  n == 0: LGR_OK, nothing written.  Asynchronous,
+ * no host synchronisation, no allocation beyond the context's workspace. */
+int lgr_hash_order_dev(lgr_ctx*, const uint64_t* d_hash, int n, long long reserve, int32_t* d_order);
+/* lgr_downsample_dev with the output order as an argument: LGR_ORDER_CANONICAL gives its bytes, LGR_ORDER_REFERENCE the voxels in the map's
+ * iteration order (elements = the voxels by first input index; invalid points are skipped as there).  d_out may alias d_pts. */
+int lgr_downsample_order_dev(lgr_ctx*, const float* d_pts, int n, float voxel, int order, float* d_out, int* n_out /* host */);
+/* lgr_dedupe_dev likewise: LGR_ORDER_REFERENCE is the set's iteration order under reserve(n) (points with a NaN coordinate never compare
+ * equal and are all kept; the first occurrence's payload is kept, intensity := 1).  d_out != d_pts. */
+int lgr_dedupe_order_dev(lgr_ctx*, const float* d_pts, int n, int order, float* d_out, int* n_out /* host */);
+/* lgr_preprocess_dev likewise, the whole loader chain on the device: duplicates out in set order, density, the voxel grid over THAT order
+ * (so every voxel accumulates in it), map order, normals.  What lgr_preprocess (host entry) runs. */
+int lgr_preprocess_order_dev(lgr_ctx*, const float* d_pts, int n, const float* vp3 /* host */, int normals_available, int order, float* d_out,
+                             int* n_out /* host */, float* voxel_out /* host, or NULL */);
+/* Guard for a host whose libstdc++ orders differently: n voxel keys drawn on the host (coordinates in [0, spread), generator seeded with
+ * seed) go through a real std::unordered_map (reserve(reserve) first when reserve > 0; 0 or >= n) and through lgr_hash_order_dev;
+ * *mismatches = positions at which the device order, or the host restatement of the rule, differs from the container's iteration order,
+ * plus elements whose restated hash differs from the library's.  Must be 0. */
+int lgr_selfcheck_hash_order(lgr_ctx*, int n, int spread, uint64_t seed, long long reserve, long long* mismatches);
 
 /* ---- src/common.cpp:644-655 estimateNormalsPoints(k, pcd, surface, vp, normals_available) ----
  * writes normal_x/y/z + curvature of pts in place; surf NULL -> pts is its own surface; vp NULL -> origin */

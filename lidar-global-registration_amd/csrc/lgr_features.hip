@@ -11,7 +11,6 @@
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
 
 #include "lgr_grid.cuh"
@@ -1002,22 +1001,12 @@ __global__ void fine_keys(GridDev g, const float* __restrict__ pts, int stride, 
     keys[i] = k; vals[i] = i;
 }
 
-struct Key3 { int x, y, z; bool operator==(const Key3& o) const { return x == o.x && y == o.y && z == o.z; } };
-// include/common.h:212-223 HashEigen<Eigen::Vector3i> (std::hash<int> is the identity)
-struct HashKey3 {
-    std::size_t operator()(const Key3& k) const {
-        std::size_t seed = 0;
-        const int e[3] = {k.x, k.y, k.z};
-        for (int i = 0; i < 3; ++i) seed ^= std::hash<int>()(e[i]) + 0x9e3779b9 + (seed << 6) + (seed >> 2);
-        return seed;
-    }
-};
-
 }  // namespace
 
-// device pipeline; n_out on host.  keys_first (optional, host vectors) receive per-voxel key and first input index.
+// device pipeline; n_out on host.  d_keys / d_first (optional): every voxel's key and first input index, in output order, left on the
+// device (WS_DS_MISC) for the reference order (lgr_hash_order.hip).
 static int downsample_core(lgr_ctx* ctx, const float* d_pts, int n, float voxel, float* d_out, int* n_out,
-                           std::vector<unsigned long long>* h_keys, std::vector<int>* h_first) {
+                           const unsigned long long** d_keys, const int** d_first) {
     LGR_CHECK(ctx, voxel > 0.f, LGR_ERR_INVALID_ARG);   // reference only prints an error; a non-positive voxel is meaningless
     *n_out = 0;
     if (n == 0) return LGR_OK;
@@ -1068,7 +1057,7 @@ static int downsample_core(lgr_ctx* ctx, const float* d_pts, int n, float voxel,
     if (h[2]) return lgr_fail(ctx, LGR_ERR_VOXEL_TOO_SMALL, "voxel index exceeds 21 bits per axis", __FILE__, __LINE__);
     unsigned long long* okeys = nullptr;
     int* ofirst = nullptr;
-    if (h_keys) {
+    if (d_keys) {
         LGR_TRY(lgr_ws_t(ctx, WS_DS_MISC, (size_t) nv * 3 + 4, (int**) &ofirst));
         okeys = (unsigned long long*) (ofirst + ((nv + 1) & ~1));
     }
@@ -1078,12 +1067,7 @@ static int downsample_core(lgr_ctx* ctx, const float* d_pts, int n, float voxel,
     if (alias) LGR_TRY(lgr_ws_t(ctx, WS_HOST_F, (size_t) nv * 12 + 4, &stage));
     voxel_accumulate<<<cdiv(n, 256), 256, 0, ctx->stream>>>(d_pts, keys2, vals2, flags, rank, n, stage, okeys, ofirst);
     if (alias) LGR_HIP(ctx, hipMemcpyAsync(d_out, stage, (size_t) nv * 48, hipMemcpyDeviceToDevice, ctx->stream));
-    if (h_keys) {
-        h_keys->resize(nv); h_first->resize(nv);
-        LGR_HIP(ctx, hipMemcpyAsync(h_keys->data(), okeys, (size_t) nv * 8, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(h_first->data(), ofirst, (size_t) nv * 4, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (d_keys) { *d_keys = okeys; *d_first = ofirst; }
     LGR_HIP(ctx, hipGetLastError());
     *n_out = nv;
     return LGR_OK;
@@ -1095,6 +1079,11 @@ extern "C" int lgr_downsample_dev(lgr_ctx* ctx, const float* d_pts, int n, float
     LGR_CHECK(ctx, (d_pts || n == 0) && (d_out || n == 0) && n_out && n >= 0, LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     return downsample_core(ctx, d_pts, n, voxel, d_out, n_out, nullptr, nullptr);
+}
+
+int lgr_downsample_keys(lgr_ctx* ctx, const float* d_pts, int n, float voxel, float* d_out, int* n_out, const unsigned long long** d_keys,
+                        const int** d_first) {
+    return downsample_core(ctx, d_pts, n, voxel, d_out, n_out, d_keys, d_first);
 }
 
 extern "C" int lgr_downsample(lgr_ctx* ctx, const float* pts, int n, float voxel, int order, float* out, int* n_out) {
@@ -1109,32 +1098,12 @@ extern "C" int lgr_downsample(lgr_ctx* ctx, const float* pts, int n, float voxel
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n * 12, &dp));
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n * 12, &dout));
     LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<unsigned long long> keys;
-    std::vector<int> first;
     int nv = 0;
-    LGR_TRY(downsample_core(ctx, dp, n, voxel, dout, &nv, order == LGR_ORDER_REFERENCE ? &keys : nullptr, &first));
-    if (order == LGR_ORDER_CANONICAL) {
-        LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) nv * 48, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    } else {
-        // reference order = iteration order of std::unordered_map<Vector3i, AccumulatedPoint, HashEigen>
-        // (src/downsample.cpp:20,32-34).  Replay the insertion sequence (voxels by first input index) through
-        // the very same container and walk it; the values were computed on the device.
-        std::vector<float> tmp((size_t) nv * 12);
-        LGR_HIP(ctx, hipMemcpyAsync(tmp.data(), dout, (size_t) nv * 48, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<int> by_first(nv);
-        for (int i = 0; i < nv; ++i) by_first[i] = i;
-        std::sort(by_first.begin(), by_first.end(), [&](int a, int b) { return first[a] < first[b]; });
-        std::unordered_map<Key3, int, HashKey3> m;
-        for (int v : by_first) {
-            unsigned long long k = keys[v];
-            Key3 k3{(int) (k & 0x1fffff), (int) ((k >> 21) & 0x1fffff), (int) ((k >> 42) & 0x1fffff)};
-            m[k3] = v;
-        }
-        size_t o = 0;
-        for (const auto& kv : m) { memcpy(out + 12 * o, tmp.data() + 12 * (size_t) kv.second, 48); ++o; }
-    }
+    // reference order = iteration order of std::unordered_map<Vector3i, AccumulatedPoint, HashEigen> (src/downsample.cpp:20,32-34),
+    // computed on the device (lgr_hash_order.hip)
+    LGR_TRY(lgr_downsample_order_dev(ctx, dp, n, voxel, order, dout, &nv));
+    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) nv * 48, hipMemcpyDeviceToHost, ctx->stream));
+    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = nv;
     return LGR_OK;
 }

@@ -134,6 +134,7 @@ enum {
     WS_KNN_PART_A, WS_KNN_PART_B, WS_KNN_FLAG, WS_KNN_CAND_IJ, WS_KNN_CAND_JI,   // lgr_match_knn.hip; the pipeline's candidate lists
     WS_GTB_MISC, WS_GTB_FOOT, WS_GTB_TERMS,   // lgr_analysis.hip: lgr_evaluate_gt_batch_dev
     WS_MEASURE_MASKS, WS_MEASURE_W,           // lgr_align.hip: lgr_measure_dev
+    WS_HO_WORK, WS_HO_ACT, WS_HO_HASH, WS_HO_STAGE,   // lgr_hash_order.hip: sort keys / bucket table / callers' hash codes and lists / unordered points
     WS_COUNT
 };
 static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");
@@ -245,6 +246,14 @@ int lgr_check_corr(lgr_ctx* ctx, const lgr_corr* d_corr, int c, int ns, int nt);
 int lgr_sort_pairs_u32(lgr_ctx* ctx, const unsigned* kin, unsigned* kout, const int* vin, int* vout, size_t n, int begin_bit, int end_bit);
 int lgr_sort_pairs_u64(lgr_ctx* ctx, const unsigned long long* kin, unsigned long long* kout, const int* vin, int* vout, size_t n,
                        const int* shifts, const int* widths, int n_ranges);
+// lgr_hash_order.hip: lgr_hash_order_dev without the turn (n > 0 elements, reserve 0 or >= n; d_order: n entries), on ctx->stream, no read-back;
+// d_out[pos] = d_in[d_via ? d_via[d_order[pos]] : d_order[pos]] over 12-float points (d_out apart from d_in)
+int lgr_hash_order_launch(lgr_ctx* ctx, const unsigned long long* d_hash, int n, long long reserve, int32_t* d_order);
+int lgr_gather_points_launch(lgr_ctx* ctx, const float* d_in, const int32_t* d_order, const int* d_via, int n, float* d_out);
+// lgr_features.hip: lgr_downsample_dev that also leaves every voxel's key ((iz, iy, ix) in 21-bit fields) and first input index on the
+// device, in output order (WS_DS_MISC: valid until the next downsample of this context)
+int lgr_downsample_keys(lgr_ctx* ctx, const float* d_pts, int n, float voxel, float* d_out, int* n_out, const unsigned long long** d_keys,
+                        const int** d_first);
 // lgr_match.hip: the query-side half of a coming brute-force match (clustering + assignment / sort / placement of d_a33), run ahead
 // of the call while the train side's descriptors are still being computed; consumed by the next lgr_match_bf*_dev on the same
 // (d_a33, ma, mb, both directions) or dropped by lgr_match_prepare_cancel.

@@ -7,14 +7,12 @@
 // Device: three stable radix sorts (z, y, x bit patterns; -0 folded into +0, points with a NaN coordinate never equal)
 // give the duplicate runs with their lowest index first; flags -> scan -> compaction in input order.  The quantile is
 // element k of the radix-sorted densities.  The reference's std::unordered_set / unordered_map output ORDER is
-// reproduced on request by the host entry point (replay through the same containers), like lgr_downsample does.
+// reproduced on request on the device (lgr_hash_order.hip): the *_order_dev entry points, which the host entry point goes through.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include <functional>
-#include <unordered_set>
-
 #include "lgr_internal.h"
+#include "lgr_stdhash.h"
 
 namespace {
 
@@ -110,17 +108,30 @@ int cloud_density_dev(lgr_ctx* ctx, const float* d_pts, int n, float quantile, f
     return LGR_OK;
 }
 
-struct HPt { float v[12]; };
-struct HPtHash {   // include/common.h:202-210 + include/utils.h:28-32
-    size_t operator()(const HPt& p) const {
-        size_t seed = 0;
-        for (int a = 0; a < 3; ++a) seed ^= std::hash<float>()(p.v[a]) + 0x9e3779b9 + (seed << 6) + (seed >> 2);
-        return seed;
-    }
-};
-struct HPtEq {
-    bool operator()(const HPt& a, const HPt& b) const { return a.v[0] == b.v[0] && a.v[1] == b.v[1] && a.v[2] == b.v[2]; }
-};
+// PointHash of the kept points (include/common.h:202-210): element e of the set = point e of the input-order result
+__global__ void dd_hash_kernel(const float* __restrict__ pts, int m, unsigned long long* __restrict__ hash) {
+    int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m) return;
+    const float* p = pts + (size_t) e * 12;
+    hash[e] = lgr_hash_point_bits(__float_as_uint(p[0]), __float_as_uint(p[1]), __float_as_uint(p[2]));
+}
+
+// the set's iteration order after reserve(n) and the n insertions: the kept points of dedupe_dev permuted by lgr_hash_order
+int dedupe_order_dev(lgr_ctx* ctx, const float* d_pts, int n, int order, float* d_out, int* n_out) {
+    if (order == LGR_ORDER_CANONICAL) return dedupe_dev(ctx, d_pts, n, d_out, n_out);
+    float* stage;
+    LGR_TRY(lgr_ws_t(ctx, WS_HO_STAGE, (size_t) n * 12 + 4, &stage));
+    int m = 0;
+    LGR_TRY(dedupe_dev(ctx, d_pts, n, stage, &m));
+    unsigned long long* hash;
+    LGR_TRY(lgr_ws_t(ctx, WS_HO_HASH, (size_t) m * 2 + 2, &hash));
+    int32_t* ord = (int32_t*) (hash + m);
+    dd_hash_kernel<<<cdiv(m, 256), 256, 0, ctx->stream>>>(stage, m, hash);
+    LGR_TRY(lgr_hash_order_launch(ctx, hash, m, n, ord));
+    LGR_TRY(lgr_gather_points_launch(ctx, stage, ord, nullptr, m, d_out));
+    *n_out = m;
+    return LGR_OK;
+}
 
 }  // namespace
 
@@ -142,24 +153,41 @@ extern "C" int lgr_dedupe_dev(lgr_ctx* ctx, const float* d_pts, int n, float* d_
     return dedupe_dev(ctx, d_pts, n, d_out, n_out);
 }
 
-extern "C" int lgr_preprocess_dev(lgr_ctx* ctx, const float* d_pts, int n, const float* vp3, int normals_available, float* d_out, int* n_out,
-                                  float* voxel_out) {
+extern "C" int lgr_dedupe_order_dev(lgr_ctx* ctx, const float* d_pts, int n, int order, float* d_out, int* n_out) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, (d_pts || n == 0) && (d_out || n == 0) && n_out && n >= 0 && d_pts != d_out, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, order == LGR_ORDER_REFERENCE || order == LGR_ORDER_CANONICAL, LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    *n_out = 0;
+    if (n == 0) return LGR_OK;
+    return dedupe_order_dev(ctx, d_pts, n, order, d_out, n_out);
+}
+
+extern "C" int lgr_preprocess_order_dev(lgr_ctx* ctx, const float* d_pts, int n, const float* vp3, int normals_available, int order, float* d_out,
+                                        int* n_out, float* voxel_out) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, d_pts && d_out && n_out && n > 1 && d_pts != d_out, LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, order == LGR_ORDER_REFERENCE || order == LGR_ORDER_CANONICAL, LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float* u;
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) n * 12, &u));
     int m = 0;
-    LGR_TRY(dedupe_dev(ctx, d_pts, n, u, &m));
+    LGR_TRY(dedupe_order_dev(ctx, d_pts, n, order, u, &m));   // set order: the voxel grid below accumulates every voxel in that order
     LGR_CHECK(ctx, m > 1, LGR_ERR_INVALID_ARG);
     float density = 0.f;
     LGR_TRY(cloud_density_dev(ctx, u, m, 0.8f, &density));
     const float voxel = 2 * density;   // FINE_VOXEL_SIZE_COEFFICIENT, include/common.h:59
-    LGR_TRY(lgr_downsample_dev(ctx, u, m, voxel, d_out, n_out));
+    LGR_TRY(lgr_downsample_order_dev(ctx, u, m, voxel, order, d_out, n_out));
     LGR_TRY(lgr_normals_knn_dev(ctx, d_out, *n_out, nullptr, 0, 30, vp3, normals_available));
     if (voxel_out) *voxel_out = voxel;
     return LGR_OK;
+}
+
+extern "C" int lgr_preprocess_dev(lgr_ctx* ctx, const float* d_pts, int n, const float* vp3, int normals_available, float* d_out, int* n_out,
+                                  float* voxel_out) {
+    return lgr_preprocess_order_dev(ctx, d_pts, n, vp3, normals_available, LGR_ORDER_CANONICAL, d_out, n_out, voxel_out);
 }
 
 extern "C" int lgr_preprocess(lgr_ctx* ctx, const float* pts, int n, const float* vp3, int normals_available, int order, float* out, int* n_out,
@@ -172,42 +200,11 @@ extern "C" int lgr_preprocess(lgr_ctx* ctx, const float* pts, int n, const float
     float *dp, *dout;
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) n * 12, &dp));
     LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) n * 12, &dout));
-    if (order == LGR_ORDER_CANONICAL) {
-        LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
-        LGR_TRY(lgr_preprocess_dev(ctx, dp, n, vp3, normals_available, dout, n_out, voxel_out));
-        LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) *n_out * 48, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return LGR_OK;
-    }
-    // reference order: the set's iteration order after inserting the points in input order (filterDuplicatePoints), then
-    // the unordered_map order of the voxel grid (lgr_downsample with LGR_ORDER_REFERENCE)
-    std::vector<float> u;
-    {
-        std::unordered_set<HPt, HPtHash, HPtEq> set;
-        set.reserve(n);
-        for (int i = 0; i < n; ++i) {
-            HPt p;
-            memcpy(p.v, pts + 12 * (size_t) i, 48);
-            set.insert(p);
-        }
-        u.resize(set.size() * 12);
-        size_t o = 0;
-        for (const HPt& p : set) { memcpy(u.data() + 12 * o, p.v, 48); u[12 * o + 8] = 1.f; ++o; }
-    }
-    const int m = (int) (u.size() / 12);
-    LGR_CHECK(ctx, m > 1, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipMemcpyAsync(dp, u.data(), (size_t) m * 48, hipMemcpyHostToDevice, ctx->stream));
-    float density = 0.f;
-    LGR_TRY(cloud_density_dev(ctx, dp, m, 0.8f, &density));
-    const float voxel = 2 * density;
-    std::vector<float> ds((size_t) m * 12);
-    int nd = 0;
-    LGR_TRY(lgr_downsample(ctx, u.data(), m, voxel, LGR_ORDER_REFERENCE, ds.data(), &nd));
-    LGR_HIP(ctx, hipMemcpyAsync(dout, ds.data(), (size_t) nd * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_TRY(lgr_normals_knn_dev(ctx, dout, nd, nullptr, 0, 30, vp3, normals_available));
-    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) nd * 48, hipMemcpyDeviceToHost, ctx->stream));
+    // reference order: the set's iteration order after inserting the points in input order (filterDuplicatePoints), then the
+    // unordered_map order of the voxel grid -- both on the device (lgr_preprocess_order_dev)
+    LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    LGR_TRY(lgr_preprocess_order_dev(ctx, dp, n, vp3, normals_available, order, dout, n_out, voxel_out));
+    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) *n_out * 48, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *n_out = nd;
-    if (voxel_out) *voxel_out = voxel;
     return LGR_OK;
 }

@@ -658,12 +658,31 @@ class Context:
         self.check(_lib.lgr_smoothed_densities_dev(self.h, _ptr(pts), pts.shape[0], int(k), _ptr(out)))
         return out
 
-    def preprocess(self, pts, vp=None, normals_available=False):
+    def hash_order(self, hashes, reserve=0):
+        """iteration order of a libstdc++ hash container whose element e (numbered by first insertion) has hash code hashes[e] (cuda
+        uint64 / int64 tensor): int32 element ids.  reserve: 0, or the argument (>= n) of a reserve() before the first insertion."""
+        n = int(hashes.shape[0])
+        out = self.empty((n,), self.torch.int32)
+        self.check(_lib.lgr_hash_order_dev(self.h, _ptr(hashes) if n else None, n, C.c_longlong(int(reserve)), _ptr(out) if n else None))
+        return out
+
+    def selfcheck_hash_order(self, n, spread=2000, seed=1, reserve=0):
+        """mismatches (must be 0) between a real std::unordered_map of n drawn voxel keys and the device order (include/lgr.h)"""
+        out = C.c_longlong(-1)
+        self.check(_lib.lgr_selfcheck_hash_order(self.h, int(n), int(spread), C.c_uint64(int(seed)), C.c_longlong(int(reserve)), C.byref(out)))
+        return out.value
+
+    def preprocess(self, pts, vp=None, normals_available=False, order=ORDER_CANONICAL):
+        """order = ORDER_REFERENCE: the reference's unordered_set / unordered_map numbering (lgr_preprocess_order_dev)"""
         out = self.empty((pts.shape[0], 12), self.torch.float32)
         n = C.c_int(0)
         voxel = C.c_float(0)
         v = (C.c_float * 3)(*[float(x) for x in vp]) if vp is not None else None
-        self.check(_lib.lgr_preprocess_dev(self.h, _ptr(pts), pts.shape[0], v, int(normals_available), _ptr(out), C.byref(n), C.byref(voxel)))
+        if order == ORDER_CANONICAL:
+            self.check(_lib.lgr_preprocess_dev(self.h, _ptr(pts), pts.shape[0], v, int(normals_available), _ptr(out), C.byref(n), C.byref(voxel)))
+        else:
+            self.check(_lib.lgr_preprocess_order_dev(self.h, _ptr(pts), pts.shape[0], v, int(normals_available), int(order), _ptr(out), C.byref(n),
+                                                     C.byref(voxel)))
         return out[: n.value], voxel.value
 
     def preprocess_host(self, pts, vp=None, normals_available=False, order=ORDER_CANONICAL):
@@ -675,10 +694,13 @@ class Context:
         self.check(_lib.lgr_preprocess(self.h, _ptr(pts), pts.shape[0], v, int(normals_available), int(order), _ptr(out), C.byref(n), C.byref(voxel)))
         return out[: n.value].copy(), voxel.value
 
-    def dedupe(self, pts):
+    def dedupe(self, pts, order=ORDER_CANONICAL):
         out = self.empty((max(pts.shape[0], 1), 12), self.torch.float32)
         n = C.c_int(0)
-        self.check(_lib.lgr_dedupe_dev(self.h, _ptr(pts), pts.shape[0], _ptr(out), C.byref(n)))
+        if order == ORDER_CANONICAL:
+            self.check(_lib.lgr_dedupe_dev(self.h, _ptr(pts), pts.shape[0], _ptr(out), C.byref(n)))
+        else:
+            self.check(_lib.lgr_dedupe_order_dev(self.h, _ptr(pts), pts.shape[0], int(order), _ptr(out), C.byref(n)))
         return out[: n.value]
 
     def cloud_density(self, pts, quantile=0.8):
@@ -693,10 +715,15 @@ class Context:
                                               int(min_neighbors), _ptr(idx), C.byref(n)))
         return idx[: n.value]
 
-    def downsample(self, pts, voxel):
-        out = self.empty((pts.shape[0], 12), self.torch.float32)
+    def downsample(self, pts, voxel, order=ORDER_CANONICAL, out=None):
+        """order = ORDER_REFERENCE: the voxels in the reference's unordered_map order; out (optional) may be pts itself"""
+        if out is None:
+            out = self.empty((pts.shape[0], 12), self.torch.float32)
         n = C.c_int(0)
-        self.check(_lib.lgr_downsample_dev(self.h, _ptr(pts), pts.shape[0], C.c_float(voxel), _ptr(out), C.byref(n)))
+        if order == ORDER_CANONICAL:
+            self.check(_lib.lgr_downsample_dev(self.h, _ptr(pts), pts.shape[0], C.c_float(voxel), _ptr(out), C.byref(n)))
+        else:
+            self.check(_lib.lgr_downsample_order_dev(self.h, _ptr(pts), pts.shape[0], C.c_float(voxel), int(order), _ptr(out), C.byref(n)))
         return out[: n.value]
 
     def downsample_host(self, pts, voxel, order=ORDER_CANONICAL):

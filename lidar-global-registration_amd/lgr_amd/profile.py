@@ -52,11 +52,13 @@ def default_profile(mod, density_src, density_tgt, *, keypoint="iss", feature_ra
     return mod.default_params(**kw)
 
 
-def load_pair(ctx, src_path, tgt_path, vp_src=None, vp_tgt=None):
+def load_pair(ctx, src_path, tgt_path, vp_src=None, vp_tgt=None, order=None):
     """loadPointClouds (src/common.cpp:429-470) on the device: read both PLY files, filter duplicates, intensity = 1, voxel grid at
-    2 x density, normals (k = 30).  -> dict(src, tgt: cuda tensors [n x 12]; voxel_*, density_*, normals_available, raw_*)"""
+    2 x density, normals (k = 30).  -> dict(src, tgt: cuda tensors [n x 12]; voxel_*, density_*, normals_available, raw_*)
+    order: None / capi.ORDER_CANONICAL, or capi.ORDER_REFERENCE for the reference's own point numbering (lgr_preprocess_order_dev)"""
     import torch
-    from . import formats
+    from . import capi, formats
+    order = capi.ORDER_CANONICAL if order is None else order
     out = {}
     avail = True
     raw = {}
@@ -66,7 +68,7 @@ def load_pair(ctx, src_path, tgt_path, vp_src=None, vp_tgt=None):
         avail = avail and formats.has_normals(fields)
     out["normals_available"] = avail
     for side, vp in (("src", vp_src), ("tgt", vp_tgt)):
-        cloud, voxel = ctx.preprocess(torch.from_numpy(raw[side]).cuda(ctx.device), vp=vp, normals_available=avail)
+        cloud, voxel = ctx.preprocess(torch.from_numpy(raw[side]).cuda(ctx.device), vp=vp, normals_available=avail, order=order)
         out[side] = cloud.clone()
         out["voxel_" + side] = voxel
         out["density_" + side] = ctx.cloud_density(out[side])

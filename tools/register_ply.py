@@ -6,6 +6,7 @@
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
                                  [--debug-dir DIR] [--hypotheses N [--hypotheses-plane]] [--refine N]
                                  [--measure N [--measure-seed S0] [--measurements test_measurements.csv]] [--save-features DIR]
+                                 [--order canonical|reference]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
@@ -36,6 +37,8 @@ them, all judged against the ground truth in one batch; one line per run, then t
 With --save-features DIR or --measure N the two clouds are prepared once (lgr_cloud_prepare) and the alignment runs on the prepared clouds
 (lgr_align_prepared; lgr_measure itself searches once for all its runs, as before).  --save-features is the reference's save_features: DIR receives the descriptor tables of the levels the clouds share, named as include/matching.h:274-278
 names them, plus ids.csv (saveExtractedPointIds for the target cloud) with --ground-truth.
+With --order reference the loader numbers the points as the reference does (the iteration order of its unordered_set and unordered_map,
+lgr_preprocess_order_dev), so every index written afterwards is the reference's; the default, canonical, is the (iz,iy,ix) voxel order.
 """
 import argparse
 import os
@@ -90,6 +93,8 @@ def main():
     ap.add_argument("--measurements", default=None, metavar="PATH", help="test_measurements.csv the aggregate row is appended to (with --measure)")
     ap.add_argument("--save-features", default=None, metavar="DIR",
                     help="save_features: prepare the two clouds once, align through them and write the levels' descriptor tables (and ids.csv with --ground-truth) to DIR")
+    ap.add_argument("--order", default="canonical", choices=["canonical", "reference"],
+                    help="point numbering after the loader: (iz,iy,ix) voxel order, or the reference's hash-container order")
     a = ap.parse_args()
     if a.measure and not a.ground_truth:
         ap.error("--measure needs --ground-truth")
@@ -114,7 +119,8 @@ def main():
     from lgr_amd import capi, formats, profile
     ctx = capi.Context(0)
     t = time.perf_counter()
-    ld = profile.load_pair(ctx, a.source, a.target)        # loadPointClouds: duplicates, 2 x density voxel grid, normals
+    # loadPointClouds: duplicates, 2 x density voxel grid, normals
+    ld = profile.load_pair(ctx, a.source, a.target, order=capi.ORDER_REFERENCE if a.order == "reference" else capi.ORDER_CANONICAL)
     ctx.sync()
     for side, path in (("src", a.source), ("tgt", a.target)):
         print(f"{os.path.basename(path)}: {len(ld['raw_' + side])} points -> {ld[side].shape[0]} after preprocessing "
