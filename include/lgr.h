@@ -53,7 +53,8 @@ enum {
     LGR_ERR_NO_DEVICE = -2,
     LGR_ERR_OOM = -3,
     LGR_ERR_HIP = -4,          /* a HIP runtime call failed; see lgr_last_error */
-    LGR_ERR_UNSUPPORTED = -5,  /* e.g. n_samples outside 3..8, randomness outside 1..LGR_RANDOMNESS_MAX (or > 1 with FLANN / a guess), alignment teaser,
+    LGR_ERR_UNSUPPORTED = -5,  /* e.g. n_samples outside 3..8, randomness outside 1..LGR_RANDOMNESS_MAX (or > 1 with FLANN / a guess), alignment teaser
+                                  through lgr_align* (TEASER is the stand-alone lgr_teaser*), a k_select outside 3..LGR_TEASER_NODES_MAX,
                                   LGR_MATCH_RATIO with ratio_k outside 2..LGR_RANDOMNESS_MAX, randomness > 1, FLANN or a guess */
     LGR_ERR_VOXEL_TOO_SMALL = -6
 };
@@ -620,6 +621,48 @@ int lgr_gror_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int n
 /* node degrees of optimalSelectionBasedOnNodeReliability (include/gror/ia_gror.hpp:126-170), c int32 on the device */
 int lgr_gror_node_degree_dev(lgr_ctx*, const float* d_src, const float* d_tgt, const lgr_corr* d_corr, int c,
                              float resolution, int32_t* d_degree);
+
+/* ---- alignTeaser(src, tgt, correspondences, parameters) (src/alignment.cpp:37-69).  The reference throws ("Not implemented: support
+ *      TEASER", :40); its commented-out body (:41-69) fixes the estimator's parameters, and the statement computed here is this
+ *      project's own ("TEASER"): the k_select correspondences of highest GROR node degree, their compatibility
+ *      graph, its maximum core, a greedy clique in it, the rotation by GNC-TLS over the clique's open chain of TIMs, the shift by
+ *      per-axis TLS over the clique's members.  No scale estimation (:50).
+ *      lgr_params.alignment_id has no value for it: lgr_align* / lgr_measure* keep returning LGR_ERR_UNSUPPORTED for "teaser". ---- */
+enum { LGR_TEASER_NODES_MAX = 2048 };
+typedef struct {
+    float   noise_bound;               /* beta = distance_thr (:48); finite, in (0, 1e18], else LGR_ERR_INVALID_ARG (cbar2 = 1, :49) */
+    int32_t k_select;                  /* nodes kept: 0 = 1024, else 3..LGR_TEASER_NODES_MAX; anything else LGR_ERR_UNSUPPORTED */
+    int32_t rotation_max_iterations;   /* 100 (:53); 1..1000, else LGR_ERR_INVALID_ARG */
+    float   rotation_gnc_factor;       /* 1.4 (:54); finite and > 1, else LGR_ERR_INVALID_ARG */
+    float   rotation_cost_threshold;   /* 0.005 (:55); finite and >= 0, else LGR_ERR_INVALID_ARG */
+    int32_t reserved[3];
+} lgr_teaser_params;
+typedef struct {
+    int32_t valid;                     /* 1: a clique of >= 3 nodes was found and the transform is a solution */
+    int32_t n_nodes;                   /* K = min(c, k_select) */
+    int32_t max_core, n_core;          /* K* and |V*| */
+    int32_t n_clique;
+    int32_t rotation_iterations;       /* SVD solves */
+    int32_t n_rotation_inliers;        /* TIMs with weight >= 0.5 */
+    int32_t n_translation_inliers;     /* clique members inside all three axes' consensus sets */
+    float   rotation_cost;             /* the last GNC cost formed (0: the loop stopped at mu <= 0) */
+    float   translation_cost[3];       /* the TLS cost of each axis's shift */
+    int32_t reserved[4];
+} lgr_teaser_info;
+/* the reference's commented values (:48-55) with noise_bound = distance_thr */
+void lgr_default_teaser_params(lgr_teaser_params*, float distance_thr);
+/* Result: transformation (the identity without a solution), iterations = rotation_iterations, converged = valid, n_inliers = set bytes
+ * of the mask (|T_i - (R S_i + t)| <= beta on every axis, over all c), metric = n_clique, best_iteration = K*, estimated_iters = K,
+ * n_correspondences = c, time_te, stage_ms[0..5] = nodes, adjacency, clique, rotation, translation, mask.  c < 3: LGR_OK, no solution,
+ * nothing is read from the correspondences.  An index outside its cloud: LGR_ERR_INVALID_ARG (checked on the device, reported with
+ * the call's one read-back).  clique (optional): 2 * LGR_TEASER_NODES_MAX int32 -- [0, n_clique) the clique's correspondence indices
+ * in node order, [LGR_TEASER_NODES_MAX, + n_nodes) the nodes' (degree descending, index ascending), every other entry -1.
+ * inlier_mask (optional): c bytes. */
+int lgr_teaser(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const lgr_teaser_params*,
+               lgr_result* res, lgr_teaser_info* info /* or NULL */, int32_t* clique /* host, or NULL */, uint8_t* inlier_mask /* host, or NULL */);
+int lgr_teaser_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const lgr_corr* d_corr, int c, const lgr_teaser_params*,
+                   lgr_result* res /* host */, lgr_teaser_info* info /* host, or NULL */, int32_t* d_clique /* or NULL */,
+                   uint8_t* d_inlier_mask /* or NULL */);
 
 /* ---- include/hypotheses.h:10-16 (host bookkeeping; compiled out in the reference, SAVE_MULTIPLE_HYPOTHESES false) ---- */
 /* include/hypotheses.h:14-16 chooseBestHypothesis(src, tgt, correspondences, params, tns) (src/hypotheses.cpp:50-129), the

@@ -135,6 +135,7 @@ enum {
     WS_GTB_MISC, WS_GTB_FOOT, WS_GTB_TERMS,   // lgr_analysis.hip: lgr_evaluate_gt_batch_dev
     WS_MEASURE_MASKS, WS_MEASURE_W,           // lgr_align.hip: lgr_measure_dev
     WS_HO_WORK, WS_HO_ACT, WS_HO_HASH, WS_HO_STAGE,   // lgr_hash_order.hip: sort keys / bucket table / callers' hash codes and lists / unordered points
+    WS_TEASER_STATE, WS_TEASER_ADJ,   // lgr_teaser.hip: state words + clique positions + consensus flags / the K x K bit matrix
     WS_COUNT
 };
 static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");

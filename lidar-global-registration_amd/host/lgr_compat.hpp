@@ -645,8 +645,25 @@ inline AlignmentResult alignGror(const PointNCloud::ConstPtr& src, const PointNC
     out.iterations = 1; out.converged = true; out.time_te = r.time_te;
     return out;
 }
-inline AlignmentResult alignTeaser(const PointNCloud::ConstPtr&, const PointNCloud::ConstPtr&, const CorrespondencesPtr&, const AlignmentParameters&) {
-    throw std::runtime_error("Not implemented: support TEASER");   // src/alignment.cpp:40
+// src/alignment.cpp:37-69: the reference throws "Not implemented: support TEASER" (:40); its commented-out body (:41-69) names the
+// estimator and its parameters -- noise_bound = distance_thr, cbar2 = 1, no scale, GNC-TLS rotation with 100 iterations, factor 1.4 and cost
+// threshold 0.005 -- and reports iterations = 1.  Here it is carried out by lgr_teaser (include/lgr.h; the statement: DESIGN.md section 4).
+// converged = a solution was found (a clique of at least three correspondences); without one the transformation is the identity.
+inline AlignmentResult alignTeaser(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const CorrespondencesPtr& correspondences,
+                                   const AlignmentParameters& parameters, lgr_teaser_info* info_out = nullptr) {
+    lgr_teaser_params tp;
+    lgr_default_teaser_params(&tp, parameters.distance_thr);
+    lgr_result r;
+    lgr_teaser_info info;
+    check(lgr_teaser(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(),
+                     reinterpret_cast<const lgr_corr*>(correspondences->data()), (int) correspondences->size(), &tp, &r, &info, nullptr, nullptr),
+          "alignTeaser");
+    if (info_out) *info_out = info;
+    AlignmentResult out;
+    out.src = src; out.tgt = tgt; out.correspondences = correspondences;
+    std::memcpy(out.transformation.data(), r.transformation, 64);
+    out.iterations = 1; out.converged = info.valid != 0; out.time_te = r.time_te;
+    return out;
 }
 // src/alignment.cpp:72-109 without the two CSV side effects (correspondences csv, transformations.csv)
 inline AlignmentResult alignPointClouds(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const AlignmentParameters& params) {

@@ -62,6 +62,32 @@ class Result(C.Structure):
         return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
 
 
+TEASER_NODES_MAX = 2048   # LGR_TEASER_NODES_MAX
+
+
+class TeaserParams(C.Structure):
+    """lgr_teaser_params (include/lgr.h): the values of the reference's commented-out alignTeaser body (src/alignment.cpp:41-69)."""
+    _fields_ = [("noise_bound", C.c_float), ("k_select", C.c_int32), ("rotation_max_iterations", C.c_int32), ("rotation_gnc_factor", C.c_float),
+                ("rotation_cost_threshold", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class TeaserInfo(C.Structure):
+    """lgr_teaser_info (include/lgr.h)."""
+    _fields_ = [("valid", C.c_int32), ("n_nodes", C.c_int32), ("max_core", C.c_int32), ("n_core", C.c_int32), ("n_clique", C.c_int32),
+                ("rotation_iterations", C.c_int32), ("n_rotation_inliers", C.c_int32), ("n_translation_inliers", C.c_int32),
+                ("rotation_cost", C.c_float), ("translation_cost", C.c_float * 3), ("reserved", C.c_int32 * 4)]
+
+
+def default_teaser_params(distance_thr, **kw):
+    """lgr_default_teaser_params + overrides"""
+    p = TeaserParams()
+    _lib.lgr_default_teaser_params(C.byref(p), C.c_float(distance_thr))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
 class MatchOptions(C.Structure):
     """lgr_match_options (include/lgr.h): how the matcher runs, never what it returns."""
     _fields_ = [("prune", C.c_int32), ("leaves", C.c_int32), ("near", C.c_int32), ("operand_format", C.c_int32), ("box_bounds", C.c_int32),
@@ -1200,6 +1226,35 @@ class Context:
         self.check(_lib.lgr_gror_node_degree_dev(self.h, _ptr(src), _ptr(tgt), _ptr(corr), c, C.c_float(resolution), _ptr(deg)))
         self._join()
         return deg[:c].cpu().numpy()
+
+    def teaser(self, src, tgt, corr, params):
+        """lgr_teaser_dev.  src, tgt: cuda float32 [n, 12]; corr: numpy CORR_DTYPE or cuda int32 [c, 4]; params: TeaserParams (or a noise
+        bound: the defaults with it) -> (Result, TeaserInfo, clique [n_clique] and nodes [n_nodes] as correspondence indices, mask [c])."""
+        if not isinstance(params, TeaserParams):
+            params = default_teaser_params(float(params))
+        corr = self._corr_dev(corr)
+        c = corr.shape[0]
+        res, info = Result(), TeaserInfo()
+        lists = self.empty((2 * TEASER_NODES_MAX,), self.torch.int32)
+        mask = self.empty((max(c, 1),), self.torch.uint8)
+        self.check(_lib.lgr_teaser_dev(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr) if c else None, c, C.byref(params),
+                                       C.byref(res), C.byref(info), _ptr(lists), _ptr(mask)))
+        self._join()
+        self.sync()   # (c < 3 returns with the list fill still queued)
+        lists = lists.cpu().numpy()
+        return res, info, lists[: info.n_clique].copy(), lists[TEASER_NODES_MAX: TEASER_NODES_MAX + info.n_nodes].copy(), mask[:c].cpu().numpy()
+
+    def teaser_host(self, src, tgt, corr, params):
+        """lgr_teaser: numpy clouds and correspondences in, the same tuple out."""
+        if not isinstance(params, TeaserParams):
+            params = default_teaser_params(float(params))
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32); corr = np.ascontiguousarray(corr)
+        c = corr.shape[0]
+        res, info = Result(), TeaserInfo()
+        lists = np.zeros(2 * TEASER_NODES_MAX, np.int32); mask = np.zeros(max(c, 1), np.uint8)
+        self.check(_lib.lgr_teaser(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], _ptr(corr) if c else None, c, C.byref(params),
+                                   C.byref(res), C.byref(info), _ptr(lists), _ptr(mask)))
+        return res, info, lists[: info.n_clique].copy(), lists[TEASER_NODES_MAX: TEASER_NODES_MAX + info.n_nodes].copy(), mask[:c].copy()
 
     def refit(self, src, tgt, corr, mask=None):
         corr = self._corr_dev(corr)

@@ -6,7 +6,7 @@
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
                                  [--debug-dir DIR] [--hypotheses N [--hypotheses-plane]] [--refine N]
                                  [--measure N [--measure-seed S0] [--measurements test_measurements.csv]] [--save-features DIR]
-                                 [--order canonical|reference]
+                                 [--order canonical|reference] [--alignment ransac|gror|teaser]
 
 Steps: formats.read_ply (include/io.h) -> lgr_preprocess (duplicate filter, 2 x density voxel grid, normals;
 src/common.cpp:429-470) -> lgr_align (src/alignment.cpp:72-109) -> formats.save_transformation (src/common.cpp:127-153).
@@ -37,6 +37,10 @@ them, all judged against the ground truth in one batch; one line per run, then t
 With --save-features DIR or --measure N the two clouds are prepared once (lgr_cloud_prepare) and the alignment runs on the prepared clouds
 (lgr_align_prepared; lgr_measure itself searches once for all its runs, as before).  --save-features is the reference's save_features: DIR receives the descriptor tables of the levels the clouds share, named as include/matching.h:274-278
 names them, plus ids.csv (saveExtractedPointIds for the target cloud) with --ground-truth.
+With --alignment teaser the correspondence search runs on its own (lgr_correspondences) and its correspondences go through lgr_teaser with
+the reference's commented parameters (src/alignment.cpp:41-69; noise bound = distance_thr); the clique and the two inlier counts are
+printed, and --out, --ground-truth, --debug-dir and --refine then work on the found transformation as for the other alignments.  lgr_align
+and lgr_measure know no teaser, so --measure, --save-features and --hypotheses refuse it.
 With --order reference the loader numbers the points as the reference does (the iteration order of its unordered_set and unordered_map,
 lgr_preprocess_order_dev), so every index written afterwards is the reference's; the default, canonical, is the (iz,iy,ix) voxel order.
 """
@@ -67,7 +71,7 @@ def main():
     ap.add_argument("--matching", default="cluster", choices=["lr", "one_sided", "cluster", "ratio"])
     ap.add_argument("--ratio-k", type=int, default=2, metavar="K",
                     help="--matching ratio: the test compares a key point's nearest row with its K-th nearest, 2 .. 8 (threshold 1.1)")
-    ap.add_argument("--alignment", default="ransac", choices=["ransac", "gror"])
+    ap.add_argument("--alignment", default="ransac", choices=["ransac", "gror", "teaser"])
     ap.add_argument("--randomness", type=int, default=1, metavar="K",
                     help="matches kept per key point and level before the proximity vote, 1 .. 8 (include/matching.h:612-625, :327-352)")
     ap.add_argument("--descriptor", default="fpfh", choices=["fpfh", "shot", "rops"])
@@ -115,6 +119,9 @@ def main():
     if a.hypotheses and (a.alignment != "ransac" or (a.metric not in ("uniformity", "correspondences") and not a.hypotheses_plane)):
         ap.error("--hypotheses needs --alignment ransac and --metric uniformity or correspondences (any other metric: add --hypotheses-plane)")
 
+    if a.alignment == "teaser" and (a.measure or a.save_features):
+        ap.error("--alignment teaser runs through lgr_teaser: --measure and --save-features (lgr_measure, lgr_align_prepared) do not take it")
+
     import numpy as np
     from lgr_amd import capi, formats, profile
     ctx = capi.Context(0)
@@ -129,12 +136,14 @@ def main():
     clouds = [ld["src"], ld["tgt"]]
     # getParametersFromConfig with the keys left out: distance_thr = 4 x max density, iss_radius = 2 x density (src/common.cpp:266-271,325-333)
     p = profile.default_profile(capi, ld["density_src"], ld["density_tgt"], keypoint=a.keypoint, metric=a.metric, matching=a.matching,
-                                alignment=a.alignment, feature_radius=a.feature_radius if a.feature_radius > 0 else None,
+                                alignment="ransac" if a.alignment == "teaser" else a.alignment, feature_radius=a.feature_radius if a.feature_radius > 0 else None,
                                 distance_thr=a.distance_thr if a.distance_thr > 0 else None, iterations=a.iterations,
                                 normals_available=ld["normals_available"], randomness=a.randomness)
     t = time.perf_counter()
     lrf = {"default": capi.LRF_DEFAULT, "gravity": capi.LRF_GRAVITY}[a.lrf]
-    if a.save_features or a.measure:
+    if a.alignment == "teaser":
+        res = align_teaser(ctx, capi, a, p, clouds, lrf)
+    elif a.save_features or a.measure:
         res = align_prepared(ctx, capi, formats, a, p, clouds, lrf)
     elif a.metric == "weighted_closest_plane":
         res = ctx.align_ex2(clouds[0], clouds[1], p, descriptor=_descriptor(capi, a, lrf, True), mparams=capi.metric_params(a.weight))
@@ -158,6 +167,20 @@ def main():
         refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
     if a.measure:
         measure(ctx, capi, formats, a, p, clouds, name, lrf)
+
+
+def align_teaser(ctx, capi, a, p, clouds, lrf):
+    """alignPointClouds with alignment "teaser" (src/alignment.cpp:92-101): the search, then lgr_teaser on its correspondences"""
+    t = time.perf_counter()
+    corr = ctx.correspondences(clouds[0], clouds[1], p, descriptor=_descriptor(capi, a, lrf))
+    ctx.sync()
+    time_cs = time.perf_counter() - t
+    res, info, clique, nodes, mask = ctx.teaser(clouds[0], clouds[1], corr, capi.default_teaser_params(p.distance_thr))
+    res.time_cs = time_cs
+    print(f"teaser: valid={info.valid} nodes={info.n_nodes} max_core={info.max_core} core_nodes={info.n_core} clique={info.n_clique} "
+          f"rotation_iterations={info.rotation_iterations} rotation_inliers={info.n_rotation_inliers}/{max(info.n_clique - 1, 0)} "
+          f"translation_inliers={info.n_translation_inliers}/{info.n_clique}")
+    return res
 
 
 def align_prepared(ctx, capi, formats, a, p, clouds, lrf):
