@@ -469,6 +469,10 @@ int lgr_match_last_check(lgr_ctx*, double* out2);
  * side was waived (the exact minimum lies above the coarse rejection's U^2), entries with a row that counts as computed only through the
  * per-stage column criterion (columns; 0 for rows).  ~0 (-1) = not run: all eight, or a direction's four when it was not matched. */
 int lgr_match_last_check_cover(lgr_ctx*, unsigned long long* out8);
+/* the same option also packs the MFMA operands a second time with the reference packing kernel and compares on the device, bit for bit:
+ * out2[0] = pieces compared (16-byte pieces of fragments and norms, tile shells) over the call's packing launches, out2[1] = pieces that
+ * differed (any: the call fails).  ~0 (-1) = not run (self_check off, or the f32 operand format). */
+int lgr_match_last_pack_check(lgr_ctx*, unsigned long long* out2);
 /* ---- src/common.cpp:531-547 calculateSmoothedDensities(pcd, k) / :202-208 calculatePointCloudDensity ---- */
 int lgr_smoothed_densities(lgr_ctx*, const float* pts, int n, int k, float* out);
 int lgr_smoothed_densities_dev(lgr_ctx*, const float* d_pts, int n, int k, float* d_out);

@@ -68,6 +68,7 @@ struct lgr_ctx {
     double mcheck[2] = {-1, -1};
     unsigned plane_gate[2] = {0, 0};            // lgr_ransac_last_plane_gate: the last RANSAC call of THIS context
     unsigned long long mcover[8] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // lgr_match_last_check_cover
+    unsigned long long mpack[2] = {~0ull, ~0ull};   // lgr_match_last_pack_check
     bool internal = false;                      // an aux / aux2 context: works inside its owner's turn (lgr_turn)
     int turn_depth = 0;                         // public entry points call each other: only the outermost one takes the device's turn
     unsigned long long turn_id = 0;             // identity for the turn hand-over (never reused, unlike the address)

@@ -113,6 +113,14 @@ extern "C" int lgr_match_last_check(lgr_ctx* ctx, double* out2) {
     return LGR_OK;
 }
 
+// ... the packing kernel against its reference in the last call: 16-byte pieces of fragments and norms and tile shells compared / differing,
+// over the call's packing launches (rows, the 16 column sets, the leaf centres); both ~0 when the check did not run
+extern "C" int lgr_match_last_pack_check(lgr_ctx* ctx, unsigned long long* out2) {
+    if (!ctx || !out2) return LGR_ERR_INVALID_ARG;
+    out2[0] = ctx->mpack[0]; out2[1] = ctx->mpack[1];
+    return LGR_OK;
+}
+
 // ... and what it covered, rows [0..3] then columns [4..7]: entries checked, entries whose upper side was tested, entries whose upper side
 // was waived (coarse rejection), entries with a row guaranteed only through the per-stage column criterion (columns; 0 for rows);
 // all ~0 when the check did not run, a direction's four when that direction was not matched.
@@ -409,7 +417,7 @@ struct OperandScale {
 // r2 / drop2: the largest |x - c|^2 and the largest energy of the three coordinates the rotated 30-D format would drop, both sides
 // (assign_kernel, build_side); operand_format: lgr_match_options (< 0: plain forced, 2: rotated forced, otherwise by the data)
 static OperandScale operand_scale(bool f16, float r2, float drop2, int operand_format) {
-    OperandScale o{false, {1.f, 1.f, {1.f, 1.f, 1.f}}, {0.f, 0.f, 1.f}, 1.f, 1.f};
+    OperandScale o{false, {1.f, 1.f, {1.f, 1.f, 1.f}, {1.f, 1.f, 1.f}}, {0.f, 0.f, 1.f}, 1.f, 1.f};
     if (!f16) return o;
     F16Scale& sc = o.sc;
     EpsExtra& ex = o.ex;
@@ -430,6 +438,7 @@ static OperandScale operand_scale(bool f16, float r2, float drop2, int operand_f
     sc.a_norm[0] = (float) std::ldexp(1.0, e1);
     sc.a_norm[1] = (float) std::ldexp(1.0, std::max(0, e1 - 11));
     sc.a_norm[2] = (float) std::ldexp(1.0, std::max(0, e1 - 22));
+    for (int k = 0; k < 3; ++k) sc.inv_a_norm[k] = 1.f / sc.a_norm[k];   // exact: powers of two
     o.c_scale = (float) std::ldexp(1.0, 2 * sexp);
     o.out_scale = sc.inv_s2;
     // error terms of the split: elements whose second half would be an f16 subnormal may be flushed
@@ -593,6 +602,7 @@ struct MatchCall {
     PruneWs carve_prune_ws(char* base) const;
     int prepare_prune_ws();
     int pack_operands();
+    int check_pack16(const float* X, const int* perm, int n_pad, int role, const int* blkcl, const void* op, const float* nrm, const float2* shell_);
     int alloc_tables();
     int launch_mfma(const unsigned* mask, const CoarseArgs& ca, bool allow_split = true);
     int init_touched_tables();
@@ -753,8 +763,45 @@ int MatchCall::upload_group_tables() {
 
 static void launch_pack16(bool rot, hipStream_t s, const float* X, const int* perm, int n_pad, int role, const float* cen, const int* blkcl, const F16Scale& sc,
                           void* op, float* nrm, float2* shell) {
-    if (rot) pack16_kernel<true><<<cdiv(n_pad, 256), 256, 0, s>>>(X, perm, n_pad, role, cen, blkcl, sc, (_Float16*) op, nrm, shell);
-    else pack16_kernel<false><<<cdiv(n_pad, 256), 256, 0, s>>>(X, perm, n_pad, role, cen, blkcl, sc, (_Float16*) op, nrm, shell);
+    const dim3 grid(cdiv(n_pad, 256));
+    _Float16* P = (_Float16*) op;
+    if (role == 0) {
+        if (rot) pack16_kernel<true, false><<<grid, 256, 0, s>>>(X, perm, n_pad, cen, blkcl, sc, P, nrm, shell);
+        else pack16_kernel<false, false><<<grid, 256, 0, s>>>(X, perm, n_pad, cen, blkcl, sc, P, nrm, shell);
+    } else {
+        if (rot) pack16_kernel<true, true><<<grid, 256, 0, s>>>(X, perm, n_pad, cen, blkcl, sc, P, nrm, shell);
+        else pack16_kernel<false, true><<<grid, 256, 0, s>>>(X, perm, n_pad, cen, blkcl, sc, P, nrm, shell);
+    }
+}
+// lgr_match_options.self_check (tests): one packing launch again with the reference kernel, set by set into one set-sized scratch buffer (131 MB
+// at 1M rows instead of 2.1 GB), and every 16-byte piece of the fragments and norms and every tile shell compared on the device.  The counts
+// add up over the launches of a call (lgr_match_last_pack_check); a differing piece fails the call.
+int MatchCall::check_pack16(const float* X, const int* perm, int n_pad, int role, const int* blkcl, const void* op, const float* nrm, const float2* shell_) {
+    const int n_sets = role == 1 ? KCL : 1, tiles = n_pad / TILE;
+    const size_t frag16 = (size_t) tiles * NF * 64;   // 16-byte pieces of a set
+    Carve carve{0, nullptr};
+    const size_t o_frag = carve(frag16 * 16), o_nrm = carve((size_t) n_pad * 4), o_shell = carve((size_t) tiles * 8), o_cnt = carve(16);
+    char* scratch;
+    LGR_TRY(lgr_ws_t(ctx, WS_MATCH_DENSE, carve.off, &scratch));   // (the rerank's buffers are not live yet)
+    unsigned long long* d_cnt = (unsigned long long*) (scratch + o_cnt);
+    float* r_nrm = (float*) (scratch + o_nrm);
+    float2* r_shell = shell_ ? (float2*) (scratch + o_shell) : nullptr;
+    hipStream_t s = ctx->stream;
+    LGR_HIP(ctx, hipMemsetAsync(d_cnt, 0, 16, s));
+    for (int set = 0; set < n_sets; ++set) {
+        if (os.rot) pack16_ref_kernel<true><<<cdiv(n_pad, 256), 256, 0, s>>>(X, perm, n_pad, role, cen, blkcl, os.sc, set, set + 1, (_Float16*) (scratch + o_frag), r_nrm, r_shell);
+        else pack16_ref_kernel<false><<<cdiv(n_pad, 256), 256, 0, s>>>(X, perm, n_pad, role, cen, blkcl, os.sc, set, set + 1, (_Float16*) (scratch + o_frag), r_nrm, r_shell);
+        pack_compare_kernel<uint4><<<(unsigned) std::min<size_t>(cdiv(frag16, 256), 4096), 256, 0, s>>>((const uint4*) op + set * frag16, (const uint4*) (scratch + o_frag), frag16, d_cnt);
+        pack_compare_kernel<uint4><<<cdiv(n_pad / 4, 256), 256, 0, s>>>((const uint4*) (nrm + (size_t) set * n_pad), (const uint4*) r_nrm, (size_t) n_pad / 4, d_cnt);
+        if (shell_) pack_compare_kernel<uint2><<<cdiv(tiles, 256), 256, 0, s>>>((const uint2*) (shell_ + (size_t) set * tiles), (const uint2*) r_shell, (size_t) tiles, d_cnt);
+    }
+    unsigned long long h_cnt[2] = {0ull, 0ull};
+    LGR_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, 16, hipMemcpyDeviceToHost, s));
+    LGR_HIP(ctx, hipStreamSynchronize(s));
+    if (ctx->mpack[0] == ~0ull) ctx->mpack[0] = ctx->mpack[1] = 0ull;
+    ctx->mpack[0] += h_cnt[0]; ctx->mpack[1] += h_cnt[1];
+    if (h_cnt[1]) { ctx->err = "matcher self-check: pack16_kernel's operands differ from pack16_ref_kernel's"; return LGR_ERR_HIP; }
+    return LGR_OK;
 }
 
 // base == nullptr: the sizes only (PruneWs::bytes)
@@ -838,9 +885,17 @@ int MatchCall::pack_operands() {
         // 1 ms of HBM writes that everything up to pass 0 crawls beside -- started later, pass 0 starts later.  (Round 5
         // measured the alternatives: behind lb_mfma_kernel -- which then runs alone in 0.18 ms instead of 0.85 -- box_lb_kernel crawls beside the
         // packing instead (0.07 -> 0.92 ms); behind the near kernels, with pass 0's stage selection from assign_kernel's distances so that
-        // mask_kernel need not wait for the column norms: mask_kernel crawls (0.4 -> 1.04 ms) and pass 0 starts 0.1 ms later than with this order.)
+        // mask_kernel need not wait for the column norms: mask_kernel crawls (0.4 -> 1.04 ms) and pass 0 starts 0.1 ms later than with this order.
+        // Measured again with the streaming pack16_kernel, 0.5 ms instead of 0.8: behind lb_mfma_kernel pass 0 starts no earlier -- DESIGN.md 11.)
         LGR_TRY(sB.fork(ctx->ev3));
         launch_pack16(os.rot, sB.s, d_b, B.perm, mb_pad, 1, cen, nullptr, os.sc, Bop, nBp, shellB);
+        if (mo.self_check) {   // (tests) the three packing launches of the call against the reference kernel
+            LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            LGR_HIP(ctx, hipStreamSynchronize(sB.s));
+            LGR_TRY(check_pack16(d_a, A.perm, ma_pad, 0, A.blkcl, Aop, nAp, shellA));
+            LGR_TRY(check_pack16(d_b, B.perm, mb_pad, 1, nullptr, Bop, nBp, shellB));
+            if (prune) LGR_TRY(check_pack16(cen2, W.cperm, n_cpad, 1, nullptr, W.cop, W.cnrm, nullptr));
+        }
     }
     group_max_kernel<<<dim3(n_groups, KCL), 256, 0, sB.s>>>(nBp, mb_pad, 0, group_start, gmaxB);
     group_max_kernel<<<dim3(n_rg, 1), 256, 0, ctx->stream>>>(nAp, ma_pad, rg_rows, nullptr, gmaxA);
@@ -1213,6 +1268,7 @@ static int match_impl(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, 
     memset(&ctx->mstats, 0, sizeof ctx->mstats);
     ctx->mcheck[0] = ctx->mcheck[1] = -1;
     for (unsigned long long& c : ctx->mcover) c = ~0ull;
+    ctx->mpack[0] = ctx->mpack[1] = ~0ull;
     ctx->mfma_timed = 0;
     // default result: unmatched
     if (ma) { LGR_HIP(ctx, hipMemsetAsync(d_ab_idx, 0xff, (size_t) ma * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(d_ab_dist, 0, (size_t) ma * 4, ctx->stream)); }

@@ -95,8 +95,9 @@ template <> struct OpFmt<FMT_F16R> {
 };
 static_assert(OpFmt<FMT_F16R>::fa(0) == 0 && OpFmt<FMT_F16R>::fb(0) == 0 && OpFmt<FMT_F16R>::fa(1) == 1 && OpFmt<FMT_F16R>::fb(1) == 1,
               "the first two steps are the coarse d2~ (stored fragments 0 and 1 of both sides)");
-// 2^s, 2^-2s, the a-side norm-slot constants (plain format: three terms against a_norm[0..2]; rotated: two terms against a_norm[0])
-struct F16Scale { float s_mul; float inv_s2; float a_norm[3]; };
+// 2^s, 2^-2s, the a-side norm-slot constants (plain format: three terms against a_norm[0..2]; rotated: two terms against a_norm[0]) and
+// their reciprocals: the constants are powers of two (operand_scale), so x * inv_a_norm[k] is the correctly rounded x / a_norm[k]
+struct F16Scale { float s_mul; float inv_s2; float a_norm[3]; float inv_a_norm[3]; };
 
 // Coarse rejection (rotated format, passes that have upper bounds; DESIGN.md 3b "coarse rejection").  After the first two
 // MFMA steps of a 32 x 32 tile the accumulator holds  c = |a'|^2_lead + |b'|^2_lead - 2 a1.b1  (scaled by 2^2s): the

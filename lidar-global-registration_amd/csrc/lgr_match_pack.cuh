@@ -51,34 +51,40 @@ __global__ void pack_kernel(const float* __restrict__ X, const int* __restrict__
 // rows: h = split(-2 x' 2^s);  cols: h = split(x' 2^s).
 // Helmert coordinates of one 11-bin block: y_k = (x_0 + .. + x_{k-1} - k x_k) / sqrt(k (k + 1)), k = 1..10 (orthonormal, all
 // orthogonal to (1,..,1)); *u = (x_0 + .. + x_10) / sqrt(11) is the dropped coordinate.
-__device__ __forceinline__ void helmert11(const float* __restrict__ x, float* __restrict__ y, float* u) {
+__device__ __forceinline__ float helmert_rs(int k) {   // 1 / sqrt(k (k + 1)), k = 1..10
     const float rs[10] = {0.70710678118654752f, 0.40824829046386302f, 0.28867513459481288f, 0.22360679774997897f, 0.18257418583505537f,
                           0.15430334996209191f, 0.13363062095621219f, 0.11785113019775793f, 0.10540925533894598f, 0.09534625892455924f};
+    return rs[k - 1];
+}
+__device__ __forceinline__ void helmert11(const float* __restrict__ x, float* __restrict__ y, float* u) {
     float pre = x[0];
 #pragma unroll
     for (int k = 1; k <= 10; ++k) {
-        y[k - 1] = (pre - (float) k * x[k]) * rs[k - 1];
+        y[k - 1] = (pre - (float) k * x[k]) * helmert_rs(k);
         pre = pre + x[k];
     }
     *u = pre * 0.30151134457776363f;
 }
 
+// The reference packing kernel: the whole row in registers (x0, v, y and the 64 halves live at once: 113 VGPRs), IEEE divisions by the
+// norm constants, both shell roots in every lane.  pack16_kernel below writes the same bits; lgr_match_options.self_check packs with both
+// and compares on the device (check_pack16).  Sets [set_lo, set_hi) of role 1 (role 0: 0, 1); set `set` goes to slot set - set_lo of P / nrm / shell.
 template <bool ROT>
-__global__ __launch_bounds__(256) void pack16_kernel(const float* __restrict__ X, const int* __restrict__ perm, int n_pad, int role,
-                              const float* __restrict__ cen, const int* __restrict__ blkcl, F16Scale sc,
+__global__ __launch_bounds__(256) void pack16_ref_kernel(const float* __restrict__ X, const int* __restrict__ perm, int n_pad, int role,
+                              const float* __restrict__ cen, const int* __restrict__ blkcl, F16Scale sc, int set_lo, int set_hi,
                               _Float16* __restrict__ P, float* __restrict__ nrm, float2* __restrict__ shell /* [sets][n_pad / 32] or nullptr */) {
     int pos = blockIdx.x * blockDim.x + threadIdx.x;
     const bool in_range = pos < n_pad;
     if (!in_range) pos = n_pad - 1;           // (nothing is stored for these lanes)
     // the row is read once (a 132-byte gather) and packed for every set: 16 column sets, one per centre, or the row set
-    const int n_sets = role == 1 ? KCL : 1;
     const int o = perm[pos];
     float x0[33];
 #pragma unroll
     for (int k = 0; k < 33; ++k) x0[k] = o >= 0 ? X[(size_t) o * 33 + k] : 0.f;
 #pragma unroll 1
-    for (int set = 0; set < n_sets; ++set) {
+    for (int set = set_lo; set < set_hi; ++set) {
     const int c = role == 1 ? set : blkcl[pos / BLOCK_ROWS];
+    const size_t slot = (size_t) (set - set_lo);
     float v[33];
     float n2 = 0.f;
     if (o >= 0) {
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(256) void pack16_kernel(const float* __restrict__ X
         for (int k = 0; k < 33; ++k) v[k] = 0.f;
         n2 = __uint_as_float(0x7f800000u);
     }
-    if (in_range) nrm[(size_t) set * n_pad + pos] = n2;   // |x'|^2 in all 33 coordinates: the magnitude the error bounds are stated in
+    if (in_range) nrm[slot * n_pad + pos] = n2;   // |x'|^2 in all 33 coordinates: the magnitude the error bounds are stated in
     if (shell) {
         // radial shell of the 32-position tile about this centre: (min, max) of |x'| over its finite rows (min rounded down, max up; an
         // empty tile: (+inf, 0)) -- the 32 rows of a tile are the 32 lanes of a half wave (shell bound, lgr_match_rerank.cuh / match_mfma)
@@ -98,7 +104,7 @@ __global__ __launch_bounds__(256) void pack16_kernel(const float* __restrict__ X
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
         if (in_range && (pos & 31) == 0)
-            shell[(size_t) set * (n_pad / TILE) + (pos >> 5)] = make_float2(mn < FLT_BIG ? sqrtf(mn) * 0.9999998f : mn, sqrtf(mx) * 1.0000002f);
+            shell[slot * (n_pad / TILE) + (pos >> 5)] = make_float2(mn < FLT_BIG ? sqrtf(mn) * 0.9999998f : mn, sqrtf(mx) * 1.0000002f);
     }
     float y[30], u0, u1, u2;
     if (ROT) { helmert11(v, y, &u0); helmert11(v + 11, y + 10, &u1); helmert11(v + 22, y + 20, &u2); }
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(256) void pack16_kernel(const float* __restrict__ X
 #pragma unroll
         for (int cidx = 3 * nd + 6; cidx < nf * 16; ++cidx) put(cidx, (_Float16) 0.f);
     }
-    f16x8* base = reinterpret_cast<f16x8*>(P) + ((size_t) set * (n_pad / TILE) + tile) * nf * 64;
+    f16x8* base = reinterpret_cast<f16x8*>(P) + (slot * (n_pad / TILE) + tile) * nf * 64;
 #pragma unroll
     for (int piece = 0; piece < 2 * nf; ++piece) {
         f16x8 w;
@@ -181,6 +187,176 @@ __global__ __launch_bounds__(256) void pack16_kernel(const float* __restrict__ X
         base[(piece >> 1) * 64 + ((piece & 1) << 5) + r] = w;
     }
     }   // sets
+}
+
+// An f32 product on its way to an f16 conversion, hidden from the compiler: it would otherwise fuse the two into v_fma_mixlo_f16 (x mul + 0),
+// which turns a zero product into +0 whatever its sign, where the multiply and v_cvt_pk_f16_f32 keep -0 (rows: mul < 0).  Harmless to the
+// matcher, but the packing kernels are compared bit for bit.
+__device__ __forceinline__ float unfused(float x) { asm("" : "+v"(x)); return x; }
+
+// The packing kernel: the bits of pack16_ref_kernel, formed so that little is live at once.  A lane still owns a row and walks the sets, but
+// every 16-byte piece leaves as soon as its eight halves exist: the rotated format's coordinate k yields h1 for piece k / 8 and h2 for piece
+// 4 + k / 8 straight from the running Helmert prefix, so besides the row itself (x0, 33 registers) only two pieces, the prefix and the two
+// norm sums are carried.  The sums n2 (33 terms) and n2m (30) stay ONE chain each, in the reference's order; the norm terms are multiplied by
+// the reciprocals of the power-of-two constants (F16Scale::inv_a_norm: the same correctly rounded quotient, subnormals included); the
+// shell's roots are taken by the one lane per tile that stores them.  Precondition the reference does not have: X holds at least one row -- a
+// padding position (perm < 0) loads row 0 (one 132-byte gather per padding lane, unconditional so that the loads need no branches) and
+// uses none of it; match_impl returns before the packing when a side is empty, and the leaf centres always have rows.  COLS: role 1 (the 16 sets; the role is a template parameter so that the
+// columns' centre address is uniform and costs no vector registers), otherwise role 0.  (Non-temporal stores of the column fragments were
+// tried and bought nothing: DESIGN.md section 11.)
+template <bool ROT, bool COLS>
+__global__ __launch_bounds__(256, 6) void pack16_kernel(const float* __restrict__ X, const int* __restrict__ perm, int n_pad,
+                              const float* __restrict__ cen, const int* __restrict__ blkcl, F16Scale sc,
+                              _Float16* __restrict__ P, float* __restrict__ nrm, float2* __restrict__ shell /* [sets][n_pad / 32] or nullptr */) {
+    const int pos = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= n_pad) return;                 // (n_pad is a multiple of TILE: whole half waves leave, and the shell's shuffles stay inside a half wave)
+    constexpr int n_sets = COLS ? KCL : 1;
+    const int o = perm[pos];
+    const bool valid = o >= 0;
+    float x0[33];                             // (a padding position reads row 0, see above: its coordinates are never used)
+#pragma unroll
+    for (int k = 0; k < 33; ++k) x0[k] = X[(size_t) (valid ? o : 0) * 33 + k];
+    constexpr int nd = ROT ? 30 : 33, nf = ROT ? OpFmt<FMT_F16R>::NF : OpFmt<FMT_F16>::NF;
+    const int tile = pos >> 5, r = pos & 31;
+    constexpr bool rows = !COLS;
+    const float mul = rows ? -2.0f * sc.s_mul : sc.s_mul;
+    const float s2 = sc.s_mul * sc.s_mul;
+    const float inf = __uint_as_float(0x7f800000u);
+    const _Float16 c0 = (_Float16) sc.a_norm[0], c1 = (_Float16) sc.a_norm[1], c2 = (_Float16) sc.a_norm[2], z = (_Float16) 0.f;
+#pragma unroll 1
+    for (int set = 0; set < n_sets; ++set) {
+        // the centre is uniform -- the set's, or that of the 256-row block this workgroup is -- and comes through the scalar cache
+        static_assert(BLOCK_ROWS == 256, "a workgroup packs one row block");
+        const float* __restrict__ cc = cen + (COLS ? set : __builtin_amdgcn_readfirstlane(blkcl[pos / BLOCK_ROWS])) * 33;
+        f16x8* base = reinterpret_cast<f16x8*>(P) + ((size_t) set * (n_pad / TILE) + tile) * nf * 64 + r;
+        // piece (f, khalf) of row r sits at fragment (f * 64 + khalf * 32 + r)
+        auto store = [&](int piece, const f16x8& w) {
+            f16x8* q = base + (piece >> 1) * 64 + ((piece & 1) << 5);
+            *q = w;
+        };
+        float n2 = 0.f;
+        if constexpr (ROT) {
+            // stored K index: [0,30) h1, 30..31 norm slots, [32,62) h2, 62..63 norm slots (the layout comment above pack16_ref_kernel)
+            float n2m = 0.f;
+            f16x8 w1, w2;
+            if (valid) {
+#pragma unroll
+                for (int b = 0; b < 3; ++b) {
+                    float pre = 0.f;
+#pragma unroll
+                    for (int kk = 0; kk < 11; ++kk) {
+                        const float vk = x0[11 * b + kk] - cc[11 * b + kk];
+                        n2 = n2 + vk * vk;
+                        if (kk == 0) pre = vk;
+                        else {
+                            const int k = 10 * b + kk - 1;
+                            const float yk = (pre - (float) kk * vk) * helmert_rs(kk);
+                            pre = pre + vk;
+                            n2m = n2m + yk * yk;
+                            const float x = unfused(yk * mul);  // exact (power of two)
+                            const _Float16 h1 = (_Float16) x;
+                            w1[k & 7] = h1; w2[k & 7] = (_Float16) (x - (float) h1);
+                            if ((k & 7) == 7) {
+                                store(k >> 3, w1); store(4 + (k >> 3), w2);
+                                // keep the instruction scheduler from moving the two sum chains behind the pieces: it would then hold every
+                                // v and y of the row until the end of the set, which is what this order is there to avoid
+                                asm volatile("" : "+v"(n2), "+v"(n2m));
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
+                    }
+                }
+            } else {
+                // padding: x' = 0 (h1 = f16(0 * mul): -0 for rows), |x'|^2 = +inf
+                const _Float16 h0 = (_Float16) unfused(0.f * mul);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { w1[j] = h0; w2[j] = z; }
+#pragma unroll
+                for (int p3 = 0; p3 < 3; ++p3) { store(p3, w1); store(4 + p3, w2); }
+                n2 = inf; n2m = inf;
+            }
+            // two norm terms against c0; a padding position keeps n1 finite and puts +inf into n2 (pack16_ref_kernel)
+            const float N = n2m * s2, q1 = N * sc.inv_a_norm[0];
+            _Float16 n1 = (_Float16) 65504.f, nn2 = (_Float16) inf;
+            if (valid && q1 < 65504.f) {
+                n1 = (_Float16) q1;
+                const float r1 = __builtin_fmaf(-sc.a_norm[0], (float) n1, N);   // exact
+                nn2 = (_Float16) (r1 * sc.inv_a_norm[0]);
+            }
+            w1[6] = rows ? c0 : n1; w1[7] = rows ? n1 : c0;
+            w2[6] = rows ? z : nn2; w2[7] = rows ? nn2 : z;
+            store(3, w1); store(7, w2);
+        } else {
+            // concatenated K index: [0,nd) a1.b1, [nd,2nd) a1.b2, [2nd,3nd) a2.b1, six norm slots, zeros
+#pragma unroll
+            for (int k = 0; k < 33; ++k) { const float vk = x0[k] - cc[k]; n2 = n2 + vk * vk; }
+            if (!valid) n2 = inf;
+            const float N = n2 * s2;
+            _Float16 b1 = (_Float16) inf, b2 = z, b3 = z;   // padding: +inf
+            if (valid) {
+                b1 = (_Float16) (N * sc.inv_a_norm[0]);
+                const float r1 = __builtin_fmaf(-sc.a_norm[0], (float) b1, N);
+                b2 = (_Float16) (r1 * sc.inv_a_norm[1]);
+                const float r2 = __builtin_fmaf(-sc.a_norm[1], (float) b2, r1);
+                b3 = (_Float16) (r2 * sc.inv_a_norm[2]);
+            }
+#pragma unroll
+            for (int piece = 0; piece < 2 * nf; ++piece) {
+                f16x8 w;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int cidx = piece * 8 + j;
+                    _Float16 h = z;
+                    if (cidx < 3 * nd) {
+                        const int part = cidx / nd, k = cidx % nd;
+                        const float d = x0[k] - cc[k];
+                        const float dv = valid ? d : 0.f, x = unfused(dv * mul);
+                        // (the reference kernel converts its coordinates in pairs and the odd 33rd one through v_fma_mixlo_f16: its h1 is +0
+                        //  where the product is -0 -- a padding row, a row at its centre -- and is formed the same way here)
+                        const _Float16 h1 = k == 32 ? (_Float16) __builtin_fmaf(dv, mul, 0.f) : (_Float16) x;
+                        const bool second = rows ? part == 2 : part == 1;   // rows: h1 h1 h2, columns: h1 h2 h1
+                        h = second ? (_Float16) (x - (float) h1) : h1;
+                    } else if (cidx < 3 * nd + 3) {
+                        const int t = cidx - 3 * nd;
+                        h = rows ? (t == 0 ? c0 : t == 1 ? c1 : c2) : (t == 0 ? b1 : t == 1 ? b2 : b3);
+                    } else if (cidx < 3 * nd + 6) {
+                        const int t = cidx - 3 * nd - 3;
+                        h = rows ? (t == 0 ? b1 : t == 1 ? b2 : b3) : (t == 0 ? c0 : t == 1 ? c1 : c2);
+                    }
+                    w[j] = h;
+                }
+                store(piece, w);
+            }
+        }
+        nrm[(size_t) set * n_pad + pos] = n2;   // |x'|^2 in all 33 coordinates: the magnitude the error bounds are stated in
+        if (shell) {
+            // radial shell of the tile about this centre, as in pack16_ref_kernel; the roots only where they are stored
+            const bool fin = n2 < FLT_BIG;
+            float mn = fin ? n2 : inf, mx = fin ? n2 : 0.f;
+#pragma unroll
+            for (int d = 16; d > 0; d >>= 1) { mn = fminf(mn, __shfl_xor(mn, d)); mx = fmaxf(mx, __shfl_xor(mx, d)); }
+            if (r == 0)
+                shell[(size_t) set * (n_pad / TILE) + tile] = make_float2(mn < FLT_BIG ? sqrtf(mn) * 0.9999998f : mn, sqrtf(mx) * 1.0000002f);
+        }
+    }   // sets
+}
+
+// lgr_match_options.self_check: pieces (T = uint4: 16 bytes; uint2: a tile's shell) of two packings, bit for bit; counts[0] += pieces
+// compared, counts[1] += pieces differing
+__device__ __forceinline__ bool same_bits(const uint4& u, const uint4& v) { return u.x == v.x && u.y == v.y && u.z == v.z && u.w == v.w; }
+__device__ __forceinline__ bool same_bits(const uint2& u, const uint2& v) { return u.x == v.x && u.y == v.y; }
+template <class T>
+__global__ void pack_compare_kernel(const T* __restrict__ a, const T* __restrict__ b, size_t n, unsigned long long* __restrict__ counts) {
+    unsigned diff = 0u, seen = 0u;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
+        ++seen;
+        diff += same_bits(a[i], b[i]) ? 0u : 1u;
+    }
+    for (int d = 32; d > 0; d >>= 1) { diff += __shfl_xor(diff, d); seen += __shfl_xor(seen, d); }
+    if ((threadIdx.x & 63) == 0) {
+        if (seen) atomicAdd(&counts[0], (unsigned long long) seen);
+        if (diff) atomicAdd(&counts[1], (unsigned long long) diff);
+    }
 }
 
 // original rows in padded (cluster-sorted) order, contiguous, for the exact rerank (padding rows are never read)

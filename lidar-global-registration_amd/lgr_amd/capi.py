@@ -662,6 +662,13 @@ class Context:
         return {d: {k: (-1 if out[4 * j + n] == 0xFFFFFFFFFFFFFFFF else int(out[4 * j + n])) for n, k in enumerate(keys)}
                 for j, d in enumerate(("rows", "cols"))}
 
+    def match_pack_check(self):
+        """(compared, differing) pieces of the packing kernel's output against the reference packing kernel's in the last match call run
+        under set_match_options(self_check=...): 16-byte pieces of fragments and norms and tile shells; (-1, -1) when it did not run"""
+        out = (C.c_ulonglong * 2)()
+        self.check(_lib.lgr_match_last_pack_check(self.h, out))
+        return tuple(-1 if v == 0xFFFFFFFFFFFFFFFF else int(v) for v in out)
+
     def match_kernel_ms(self):
         ms = C.c_float(0)
         self.check(_lib.lgr_match_last_kernel_ms(self.h, C.byref(ms)))
