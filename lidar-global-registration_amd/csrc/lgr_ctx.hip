@@ -132,6 +132,7 @@ static int make_internal(lgr_ctx* ctx, lgr_ctx** out, hipEvent_t* ev) {
     LGR_CHECK(ctx, lgr_ctx_create(ctx->device, ctx->opt.helper_contexts ? LGR_STREAM_OWN : (void*) ctx->stream, out) == LGR_OK, LGR_ERR_HIP);
     (*out)->opt = ctx->opt;
     (*out)->mopt = ctx->mopt;
+    (*out)->knnf_mode = ctx->knnf_mode; (*out)->knnf_check = ctx->knnf_check;
     (*out)->internal = true;
     if (!*ev) LGR_HIP(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
     return LGR_OK;

@@ -43,7 +43,7 @@ struct lgr_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
-    lgr_buf ws[160];
+    lgr_buf ws[192];
     void* pinned = nullptr;  // small pinned host scratch for read-backs
     size_t pinned_cap = 0;
     hipEvent_t ev[32];       // 0..8 stage timers (lgr_align), 9.. pairs around the match_mfma passes
@@ -69,6 +69,9 @@ struct lgr_ctx {
     unsigned plane_gate[2] = {0, 0};            // lgr_ransac_last_plane_gate: the last RANSAC call of THIS context
     unsigned long long mcover[8] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // lgr_match_last_check_cover
     unsigned long long mpack[2] = {~0ull, ~0ull};   // lgr_match_last_pack_check
+    int knnf_mode = -1, knnf_check = 0;         // lgr_ctx_set_knn_filter: how 33-float rows are swept by the k-nearest matcher
+    unsigned long long knnf_last[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0};   // lgr_match_knn_last: the last k-nearest call of THIS context
+    double knnf_worst = -1;                     // lgr_match_knn_last_check
     bool internal = false;                      // an aux / aux2 context: works inside its owner's turn (lgr_turn)
     int turn_depth = 0;                         // public entry points call each other: only the outermost one takes the device's turn
     unsigned long long turn_id = 0;             // identity for the turn hand-over (never reused, unlike the address)
@@ -137,9 +140,13 @@ enum {
     WS_MEASURE_MASKS, WS_MEASURE_W,           // lgr_align.hip: lgr_measure_dev
     WS_HO_WORK, WS_HO_ACT, WS_HO_HASH, WS_HO_STAGE,   // lgr_hash_order.hip: sort keys / bucket table / callers' hash codes and lists / unordered points
     WS_TEASER_STATE, WS_TEASER_ADJ,   // lgr_teaser.hip: state words + clique positions + consensus flags / the K x K bit matrix
+    // lgr_match_knn_mfma.cuh: the centre; per side the two operand forms, norms / norm bounds / tile bounds, irregular rows; per direction the group
+    // values, widened bounds, candidate counts and lists, fallback list and flags, counters, the fallback rows and their results
+    WS_KNNF_OPS_A, WS_KNNF_OPS_B, WS_KNNF_MISC_A, WS_KNNF_MISC_B, WS_KNNF_IRR_A, WS_KNNF_IRR_B, WS_KNNF_PART, WS_KNNF_UW, WS_KNNF_CNT, WS_KNNF_CAND,
+    WS_KNNF_FB, WS_KNNF_ISFB, WS_KNNF_DEV, WS_KNNF_FBROWS, WS_KNNF_FBIDX, WS_KNNF_FBDIST, WS_KNNF_CENTRE,
     WS_COUNT
 };
-static_assert(WS_COUNT <= 160, "grow lgr_ctx::ws");
+static_assert(WS_COUNT <= 192, "grow lgr_ctx::ws");
 
 // returns device pointer of at least `bytes` (contents undefined unless kept); grows with 25% slack
 int lgr_ws(lgr_ctx* ctx, int slot, size_t bytes, void** out);

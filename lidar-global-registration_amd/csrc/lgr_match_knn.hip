@@ -246,11 +246,37 @@ __global__ void ratio_test_kernel(const int32_t* __restrict__ kidx, const float*
     dist[q] = keep ? d_first : 0.f;
 }
 
+}  // namespace
+
+#include "lgr_match_knn_mfma.cuh"
+
+namespace {
+
+// 33-float rows under lgr_ctx_set_knn_filter: the filtered path, or the exact scan below with the reason in knnf_last[7]
+int knn_match_33(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int k, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d,
+                 const float* ratio_thr) {
+    const unsigned long long fresh[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0};
+    memcpy(ctx->knnf_last, fresh, sizeof fresh);
+    ctx->knnf_worst = -1;
+    const bool args_ok = (d_a || ma == 0) && (d_b || mb == 0) && ma >= 0 && mb >= 0 && block > 0 && (ab_i || ma == 0) && (ab_d || ma == 0);
+    const bool want = ctx->knnf_mode == 1 || (ctx->knnf_mode == -1 && (long long) ma * mb >= KNNF_AUTO_MIN_PAIRS);
+    if (want && args_ok) {
+        if (ma > 0 && mb > 0) {
+            bool done = false;
+            LGR_TRY(knnf_match(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr, &done));
+            if (done) return LGR_OK;
+        } else ctx->knnf_last[7] = KNNF_REASON_EMPTY;
+    }
+    const int rc = knn_match<2, 1>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    if (rc == LGR_OK && args_ok) { ctx->knnf_last[1] = (unsigned long long) ma * mb * (ba_i ? 2 : 1); ctx->knnf_last[3] = (unsigned long long) ma + (ba_i ? mb : 0); }
+    return rc;
+}
+
 int knn_dispatch(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block, int k,
                  int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d, const float* ratio_thr) {
     if (row_len == 352) return knn_match<22, 0>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
     if (row_len == 135) return knn_match<8, 7>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
-    if (row_len == 33) return knn_match<2, 1>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    if (row_len == 33) return knn_match_33(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
     return lgr_fail(ctx, LGR_ERR_UNSUPPORTED, "row_len == 33 || row_len == 135 || row_len == 352", __FILE__, __LINE__);
 }
 
@@ -306,6 +332,37 @@ int lgr_vote_matches_core(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* 
     LGR_HIP(ctx, hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     LGR_CHECK(ctx, h_bad == 0 /* a candidate >= mt */, LGR_ERR_INVALID_ARG);
+    return LGR_OK;
+}
+
+static void knnf_propagate(lgr_ctx* ctx, int mode, int self_check) {
+    ctx->knnf_mode = mode; ctx->knnf_check = self_check;
+    if (ctx->aux) knnf_propagate(ctx->aux, mode, self_check);
+    if (ctx->aux2) knnf_propagate(ctx->aux2, mode, self_check);
+}
+
+extern "C" int lgr_ctx_set_knn_filter(lgr_ctx* ctx, int mode, int self_check) {
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, mode >= -1 && mode <= 1 && (self_check == 0 || self_check == 1), LGR_ERR_INVALID_ARG);
+    knnf_propagate(ctx, mode, self_check);
+    return LGR_OK;
+}
+
+extern "C" int lgr_ctx_get_knn_filter(lgr_ctx* ctx, int* mode, int* self_check) {
+    if (!ctx || !mode || !self_check) return LGR_ERR_INVALID_ARG;
+    *mode = ctx->knnf_mode; *self_check = ctx->knnf_check;
+    return LGR_OK;
+}
+
+extern "C" int lgr_match_knn_last(lgr_ctx* ctx, unsigned long long* out8) {
+    if (!ctx || !out8) return LGR_ERR_INVALID_ARG;
+    memcpy(out8, ctx->knnf_last, sizeof ctx->knnf_last);
+    return LGR_OK;
+}
+
+extern "C" int lgr_match_knn_last_check(lgr_ctx* ctx, double* worst_ratio) {
+    if (!ctx || !worst_ratio) return LGR_ERR_INVALID_ARG;
+    *worst_ratio = ctx->knnf_worst;
     return LGR_OK;
 }
 

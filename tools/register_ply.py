@@ -99,6 +99,8 @@ def main():
                     help="save_features: prepare the two clouds once, align through them and write the levels' descriptor tables (and ids.csv with --ground-truth) to DIR")
     ap.add_argument("--order", default="canonical", choices=["canonical", "reference"],
                     help="point numbering after the loader: (iz,iy,ix) voxel order, or the reference's hash-container order")
+    ap.add_argument("--knn-filter", default="auto", choices=["auto", "on", "off"],
+                    help="how --randomness > 1 / --matching ratio sweep FPFH rows (never what they return): the MFMA filter from the crossover size, always, never")
     a = ap.parse_args()
     if a.measure and not a.ground_truth:
         ap.error("--measure needs --ground-truth")
@@ -125,6 +127,7 @@ def main():
     import numpy as np
     from lgr_amd import capi, formats, profile
     ctx = capi.Context(0)
+    ctx.set_knn_filter({"auto": -1, "on": 1, "off": 0}[a.knn_filter])
     t = time.perf_counter()
     # loadPointClouds: duplicates, 2 x density voxel grid, normals
     ld = profile.load_pair(ctx, a.source, a.target, order=capi.ORDER_REFERENCE if a.order == "reference" else capi.ORDER_CANONICAL)
