@@ -12,7 +12,7 @@
 #include <climits>
 
 #include "lgr_cloud.h"
-#include "lgr_pointpass.cuh"
+#include "lgr_host.h"
 
 namespace {
 
@@ -725,7 +725,7 @@ extern "C" int lgr_correspondences(lgr_ctx* ctx, const float* src, int ns, const
     return lgr_correspondences_ex(ctx, src, ns, tgt, nt, p, nullptr, out, n_out);
 }
 
-// (the host entry points stage both clouds with stage_clouds, lgr_pointpass.cuh: WS_HOST_A / WS_HOST_B on ctx->stream)
+// (the host entry points stage their arrays through lgr_host_call, lgr_host.h, on ctx->stream)
 extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_params* p, const lgr_feature_params* fp,
                                       lgr_corr* out, int* n_out) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
@@ -736,12 +736,12 @@ extern "C" int lgr_correspondences_ex(lgr_ctx* ctx, const float* src, int ns, co
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
     lgr_corr* dc;
-    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(lgr_ws_t(ctx, WS_PIPE_CORR, (size_t) ns + 1, &dc));   // the pipeline's own slot, as in lgr_measure_dev: not a staged array
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
     LGR_TRY(lgr_correspondences_ex_dev(ctx, ds, ns, dt, nt, p, fp, dc, n_out));
-    if (*n_out) LGR_HIP(ctx, hipMemcpyAsync(out, dc, (size_t) *n_out * 16, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out, dc, (size_t) *n_out));
+    return hc.finish();
 }
 
 
@@ -944,11 +944,11 @@ extern "C" int lgr_align_ex2(lgr_ctx* ctx, const float* src, int ns, const float
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (src || ns == 0) && (tgt || nt == 0) && p && res && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
     if (ns < 2 || nt < 2) return lgr_align_ex2_dev(ctx, nullptr, 0, nullptr, 0, p, fp, mp, res);   // identity, not converged
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     lgr_metric_params mpd;
-    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.weights(ns, &mp, &mpd));
     return lgr_align_ex2_dev(ctx, ds, ns, dt, nt, p, fp, mp, res);
 }
 
@@ -1087,10 +1087,10 @@ extern "C" int lgr_measure(lgr_ctx* ctx, const float* src, int ns, const float* 
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (src || ns == 0) && (tgt || nt == 0) && p && ns >= 0 && nt >= 0, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     lgr_metric_params mpd;
-    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.weights(ns, &mp, &mpd));
     return lgr_measure_dev(ctx, ds, ns, dt, nt, p, fp, mp, Tgt16, seeds, n_times, runs, out);
 }

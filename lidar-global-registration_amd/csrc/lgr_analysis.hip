@@ -23,6 +23,7 @@
 #include "lgr_grid.cuh"
 #include "lgr_internal.h"
 #include "lgr_libm.cuh"
+#include "lgr_host.h"
 #include "lgr_pointpass.cuh"
 
 namespace {
@@ -655,7 +656,7 @@ extern "C" int lgr_evaluate_gt_batch_dev(lgr_ctx* ctx, const float* d_src, int n
 }
 
 namespace {
-// (stage_clouds and stage_problem, host clouds and correspondences -> the WS_HOST_A / B / C slots, are in lgr_pointpass.cuh)
+// (the host twins stage their arrays through lgr_host_call, lgr_host.h; two masks of one call share a staged buffer)
 #define GT_CHECK_HOST_CLOUDS(ctx) LGR_CHECK(ctx, ns >= 0 && nt >= 0 && (src || ns == 0) && (tgt || nt == 0), LGR_ERR_INVALID_ARG)
 }  // namespace
 
@@ -666,12 +667,12 @@ extern "C" int lgr_overlap_rmse(lgr_ctx* ctx, const float* src, int ns, const fl
     GT_CHECK_HOST_CLOUDS(ctx);
     float *ds, *dt;
     int32_t* di = nullptr;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
-    if (idx && ns) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) ns + 4, &di));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    if (idx && ns) LGR_TRY(hc.out((size_t) ns, &di, 4));   // (slack kept from before; no reader past ns is known)
     LGR_TRY(lgr_overlap_rmse_dev(ctx, ds, ns, dt, nt, T16, Tgt16, distance_thr, overlap_rmse, overlap_size, pcd_err, di));
-    if (di) LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) ns * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    if (di) LGR_TRY(hc.fetch(idx, di, (size_t) ns));
+    return hc.finish();
 }
 
 extern "C" int lgr_merge_overlaps(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float Tgt16[16], float distance_thr,
@@ -681,13 +682,13 @@ extern "C" int lgr_merge_overlaps(lgr_ctx* ctx, const float* src, int ns, const 
     GT_CHECK_HOST_CLOUDS(ctx);
     float *ds, *dt;
     uint8_t* dm;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) ns + (size_t) nt + 16, &dm));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.out((size_t) ns + (size_t) nt, &dm, LGR_PAD_MASK));   // both masks in one buffer
     LGR_TRY(lgr_merge_overlaps_dev(ctx, ds, ns, dt, nt, Tgt16, distance_thr, dm, dm + ns, n_overlap2, overlap, overlap_area));
-    if (mask_src && ns) LGR_HIP(ctx, hipMemcpyAsync(mask_src, dm, (size_t) ns, hipMemcpyDeviceToHost, ctx->stream));
-    if (mask_tgt && nt) LGR_HIP(ctx, hipMemcpyAsync(mask_tgt, dm + ns, (size_t) nt, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(mask_src, dm, (size_t) ns));
+    LGR_TRY(hc.fetch(mask_tgt, dm + ns, (size_t) nt));
+    return hc.finish();
 }
 
 extern "C" int lgr_normal_difference(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float Tgt16[16], float distance_thr,
@@ -696,7 +697,8 @@ extern "C" int lgr_normal_difference(lgr_ctx* ctx, const float* src, int ns, con
     if (!ctx) return LGR_ERR_INVALID_ARG;
     GT_CHECK_HOST_CLOUDS(ctx);
     float *ds, *dt;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
     return lgr_normal_difference_dev(ctx, ds, ns, dt, nt, Tgt16, distance_thr, normal_diff, n_normal_overlap);
 }
 
@@ -709,14 +711,14 @@ extern "C" int lgr_correct_correspondences(lgr_ctx* ctx, const float* src, int n
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) 2 * c + 16, &dm));
-    if (c && inlier_mask) LGR_HIP(ctx, hipMemcpyAsync(dm, inlier_mask, (size_t) c, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    LGR_TRY(hc.in(inlier_mask, (size_t) c, &dm, (size_t) c + LGR_PAD_MASK));   // the inlier mask, then the correct mask
     LGR_TRY(lgr_correct_correspondences_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, Tgt16, (c && inlier_mask) ? dm : nullptr,
                                             (c && correct_mask) ? dm + c : nullptr, n3));
-    if (c && correct_mask) LGR_HIP(ctx, hipMemcpyAsync(correct_mask, dm + c, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(correct_mask, dm + c, (size_t) c));
+    return hc.finish();
 }
 
 extern "C" int lgr_evaluate_gt_batch(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float* T16s, int n,
@@ -729,15 +731,16 @@ extern "C" int lgr_evaluate_gt_batch(lgr_ctx* ctx, const float* src, int ns, con
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm;   // the correct mask, then the n inlier masks
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) (n + 1) * c + 16, &dm));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    LGR_TRY(hc.out((size_t) (n + 1) * c, &dm, LGR_PAD_MASK));
     const bool masks = c && n && inlier_masks;
-    if (masks) LGR_HIP(ctx, hipMemcpyAsync(dm + c, inlier_masks, (size_t) n * c, hipMemcpyHostToDevice, ctx->stream));
+    if (masks) LGR_HIP(ctx, hipMemcpyAsync(dm + c, inlier_masks, (size_t) n * c, hipMemcpyHostToDevice, ctx->stream));   // behind the correct mask
     LGR_TRY(lgr_evaluate_gt_batch_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, T16s, n, Tgt16, distance_thr, converged, masks ? dm + c : nullptr, out,
                                       (c && correct_mask) ? dm : nullptr));
-    if (c && n && correct_mask) LGR_HIP(ctx, hipMemcpyAsync(correct_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    if (n) LGR_TRY(hc.fetch(correct_mask, dm, (size_t) c));
+    return hc.finish();
 }
 
 extern "C" int lgr_evaluate_gt(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float T16[16],
@@ -749,12 +752,12 @@ extern "C" int lgr_evaluate_gt(lgr_ctx* ctx, const float* src, int ns, const flo
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) 2 * c + 16, &dm));
-    if (c && inlier_mask) LGR_HIP(ctx, hipMemcpyAsync(dm, inlier_mask, (size_t) c, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    LGR_TRY(hc.in(inlier_mask, (size_t) c, &dm, (size_t) c + LGR_PAD_MASK));   // the inlier mask, then the correct mask
     LGR_TRY(lgr_evaluate_gt_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, T16, Tgt16, distance_thr, converged,
                                 (c && inlier_mask) ? dm : nullptr, out, (c && correct_mask) ? dm + c : nullptr));
-    if (c && correct_mask) LGR_HIP(ctx, hipMemcpyAsync(correct_mask, dm + c, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(correct_mask, dm + c, (size_t) c));
+    return hc.finish();
 }

@@ -22,6 +22,7 @@
 #include "lgr_grid.cuh"
 #include "lgr_internal.h"
 #include "lgr_libm.cuh"
+#include "lgr_host.h"
 #include "lgr_pointpass.cuh"
 #include "lgr_weights_math.h"
 
@@ -198,27 +199,26 @@ int upload(lgr_ctx* ctx, float* d, const float* h, size_t n_floats) {
     return LGR_OK;
 }
 
-// host twin plumbing for a lgr_temperature_out: device arrays of n entries each in one slot, copied back where the caller asked
-struct TempStage { lgr_temperature_out dev; };
-int temp_stage(lgr_ctx* ctx, int slot, const lgr_temperature_out* host, int n, TempStage* st) {
-    st->dev = lgr_temperature_out{nullptr, nullptr, nullptr, nullptr, nullptr};
+// host twin plumbing for a lgr_temperature_out: the arrays the caller asked for, n entries each, in one staged buffer; copied back afterwards
+int temp_out_dev(lgr_host_call& hc, const lgr_temperature_out* host, int n, lgr_temperature_out* dev) {
+    *dev = lgr_temperature_out{nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!host || n == 0) return LGR_OK;
     int32_t* d;
-    LGR_TRY(lgr_ws_t(ctx, slot, (size_t) 5 * n + 16, &d));
-    if (host->temp_distance) st->dev.temp_distance = (float*) d;
-    if (host->temp_normal) st->dev.temp_normal = (float*) d + n;
-    if (host->color_distance) st->dev.color_distance = d + 2 * (size_t) n;
-    if (host->color_normal) st->dev.color_normal = d + 3 * (size_t) n;
-    if (host->nn) st->dev.nn = d + 4 * (size_t) n;
+    LGR_TRY(hc.out((size_t) 5 * n, &d, 16));   // (slack kept from before; no reader past 5 n is known)
+    if (host->temp_distance) dev->temp_distance = (float*) d;
+    if (host->temp_normal) dev->temp_normal = (float*) d + n;
+    if (host->color_distance) dev->color_distance = d + 2 * (size_t) n;
+    if (host->color_normal) dev->color_normal = d + 3 * (size_t) n;
+    if (host->nn) dev->nn = d + 4 * (size_t) n;
     return LGR_OK;
 }
-int temp_unstage(lgr_ctx* ctx, const lgr_temperature_out* host, int n, const TempStage& st) {
+int temp_out_fetch(lgr_host_call& hc, const lgr_temperature_out* host, int n, const lgr_temperature_out& dev) {
     if (!host || n == 0) return LGR_OK;
-    const void* src[5] = {st.dev.temp_distance, st.dev.temp_normal, st.dev.color_distance, st.dev.color_normal, st.dev.nn};
-    void* dst[5] = {host->temp_distance, host->temp_normal, host->color_distance, host->color_normal, host->nn};
-    for (int k = 0; k < 5; ++k)
-        if (dst[k]) LGR_HIP(ctx, hipMemcpyAsync(dst[k], src[k], (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(host->temp_distance, dev.temp_distance, (size_t) n));
+    LGR_TRY(hc.fetch(host->temp_normal, dev.temp_normal, (size_t) n));
+    LGR_TRY(hc.fetch(host->color_distance, dev.color_distance, (size_t) n));
+    LGR_TRY(hc.fetch(host->color_normal, dev.color_normal, (size_t) n));
+    return hc.fetch(host->nn, dev.nn, (size_t) n);
 }
 
 }  // namespace
@@ -287,20 +287,17 @@ extern "C" int lgr_nearest(lgr_ctx* ctx, const float* q, int nq, const float* pt
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, nq >= 0 && n >= 0 && (q || nq == 0) && (pts || n == 0) && (idx || nq == 0), LGR_ERR_INVALID_ARG);
     if (nq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dq, *dp, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_A, (size_t) nq * 12, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_B, (size_t) n * 12, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_DBG_MISC, (size_t) 2 * nq, &di));
-    dd = (float*) (di + nq);
-    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) nq * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q, (size_t) nq * 12, &dq));
+    LGR_TRY(hc.in(pts, (size_t) n * 12, &dp));
+    LGR_TRY(hc.out((size_t) nq, &di));
+    LGR_TRY(hc.out((size_t) nq, &dd));
     LGR_TRY(lgr_nearest_dev(ctx, dq, nq, dp, n, di, dd));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (d2) LGR_HIP(ctx, hipMemcpyAsync(d2, dd, (size_t) nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) nq));
+    LGR_TRY(hc.fetch(d2, dd, (size_t) nq));
+    return hc.finish();
 }
 
 extern "C" int lgr_compare_overlaps_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* tns16, int n, float distance_thr,
@@ -429,13 +426,13 @@ extern "C" int lgr_temperature_map(lgr_ctx* ctx, const float* cmp, int n, const 
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, n >= 0 && nr >= 0 && (cmp || n == 0) && (ref || nr == 0), LGR_ERR_INVALID_ARG);
     float *dc, *dr;
-    TempStage st;
-    LGR_TRY(stage_clouds(ctx, cmp, n, ref, nr, &dc, &dr));
-    LGR_TRY(temp_stage(ctx, WS_DBG_HOST_A, out, nr ? n : 0, &st));
-    LGR_TRY(lgr_temperature_map_dev(ctx, dc, n, dr, nr, distance_max, out ? &st.dev : nullptr, n_below));
-    LGR_TRY(temp_unstage(ctx, out, nr ? n : 0, st));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    lgr_temperature_out st;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(cmp, n, ref, nr, &dc, &dr));
+    LGR_TRY(temp_out_dev(hc, out, nr ? n : 0, &st));
+    LGR_TRY(lgr_temperature_map_dev(ctx, dc, n, dr, nr, distance_max, out ? &st : nullptr, n_below));
+    LGR_TRY(temp_out_fetch(hc, out, nr ? n : 0, st));
+    return hc.finish();
 }
 
 extern "C" int lgr_temperature_maps(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T16[16], float distance_thr,
@@ -444,18 +441,18 @@ extern "C" int lgr_temperature_maps(lgr_ctx* ctx, const float* src, int ns, cons
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, ns >= 0 && nt >= 0 && (src || ns == 0) && (tgt || nt == 0), LGR_ERR_INVALID_ARG);
     float *ds, *dt, *dm = nullptr;
-    TempStage ss, tt;
+    lgr_temperature_out ss, tt;
     const bool any = ns > 0 && nt > 0;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
-    LGR_TRY(temp_stage(ctx, WS_DBG_HOST_A, src_out, any ? ns : 0, &ss));
-    LGR_TRY(temp_stage(ctx, WS_DBG_HOST_B, tgt_out, any ? nt : 0, &tt));
-    if (moved && any) LGR_TRY(lgr_ws_t(ctx, WS_DBG_MOVED, (size_t) 12 * ns + 16, &dm));
-    LGR_TRY(lgr_temperature_maps_dev(ctx, ds, ns, dt, nt, T16, distance_thr, src_out ? &ss.dev : nullptr, tgt_out ? &tt.dev : nullptr, dm, n_below2));
-    LGR_TRY(temp_unstage(ctx, src_out, any ? ns : 0, ss));
-    LGR_TRY(temp_unstage(ctx, tgt_out, any ? nt : 0, tt));
-    if (dm) LGR_HIP(ctx, hipMemcpyAsync(moved, dm, (size_t) ns * 48, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(temp_out_dev(hc, src_out, any ? ns : 0, &ss));
+    LGR_TRY(temp_out_dev(hc, tgt_out, any ? nt : 0, &tt));
+    if (moved && any) LGR_TRY(lgr_ws_t(ctx, WS_DBG_MOVED, (size_t) 12 * ns + 16, &dm));   // the twin's own slot for the moved source
+    LGR_TRY(lgr_temperature_maps_dev(ctx, ds, ns, dt, nt, T16, distance_thr, src_out ? &ss : nullptr, tgt_out ? &tt : nullptr, dm, n_below2));
+    LGR_TRY(temp_out_fetch(hc, src_out, any ? ns : 0, ss));
+    LGR_TRY(temp_out_fetch(hc, tgt_out, any ? nt : 0, tt));
+    if (dm) LGR_TRY(hc.fetch(moved, dm, (size_t) ns * 12));
+    return hc.finish();
 }
 
 extern "C" int lgr_compare_overlaps(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* tns16, int n, float distance_thr,
@@ -466,43 +463,42 @@ extern "C" int lgr_compare_overlaps(lgr_ctx* ctx, const float* src, int ns, cons
     float *ds, *dt;
     uint8_t *dms = nullptr, *dmt = nullptr;
     const bool any = ns > 0 && nt > 0 && n > 0;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
-    if (mask_src && any) LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_A, (size_t) n * ns + 16, &dms));
-    if (mask_tgt && any) LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_B, (size_t) n * nt + 16, &dmt));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    if (mask_src && any) LGR_TRY(hc.out((size_t) n * ns, &dms, LGR_PAD_MASK));
+    if (mask_tgt && any) LGR_TRY(hc.out((size_t) n * nt, &dmt, LGR_PAD_MASK));
     LGR_TRY(lgr_compare_overlaps_dev(ctx, ds, ns, dt, nt, tns16, n, distance_thr, counts, weighted_counts, counts2, dms, dmt));
-    if (dms) LGR_HIP(ctx, hipMemcpyAsync(mask_src, dms, (size_t) n * ns, hipMemcpyDeviceToHost, ctx->stream));
-    if (dmt) LGR_HIP(ctx, hipMemcpyAsync(mask_tgt, dmt, (size_t) n * nt, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    if (dms) LGR_TRY(hc.fetch(mask_src, dms, (size_t) n * ns));
+    if (dmt) LGR_TRY(hc.fetch(mask_tgt, dmt, (size_t) n * nt));
+    return hc.finish();
 }
 
 namespace {
-// n values up, n colours back, through the WS_DBG_HOST_A slot
+// n values up, n colours back
 template <class F>
-int color_host(lgr_ctx* ctx, const float* values, int n, int32_t* colors, F&& run) {
+int colors_of_values(lgr_ctx* ctx, const float* values, int n, int32_t* colors, F&& run) {
     LGR_CHECK(ctx, n >= 0 && ((values && colors) || n == 0), LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float* dv;
-    LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_A, 2 * (size_t) n + 16, &dv));
-    int32_t* dc = (int32_t*) (dv + n);
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(dv, values, (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
+    int32_t* dc;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(values, (size_t) n, &dv));
+    LGR_TRY(hc.out((size_t) n, &dc));
     LGR_TRY(run(dv, dc));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(colors, dc, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(colors, dc, (size_t) n));
+    return hc.finish();
 }
 }  // namespace
 
 extern "C" int lgr_color_map(lgr_ctx* ctx, const float* values, int n, float vmin, float vmax, int32_t* colors) {
     lgr_turn turn__(ctx);
     if (!ctx) return LGR_ERR_INVALID_ARG;
-    return color_host(ctx, values, n, colors, [&](const float* dv, int32_t* dc) { return lgr_color_map_dev(ctx, dv, n, vmin, vmax, dc); });
+    return colors_of_values(ctx, values, n, colors, [&](const float* dv, int32_t* dc) { return lgr_color_map_dev(ctx, dv, n, vmin, vmax, dc); });
 }
 
 extern "C" int lgr_color_weights(lgr_ctx* ctx, const float* weights, int n, int32_t* colors, float range2[2]) {
     lgr_turn turn__(ctx);
     if (!ctx) return LGR_ERR_INVALID_ARG;
-    return color_host(ctx, weights, n, colors, [&](const float* dv, int32_t* dc) { return lgr_color_weights_dev(ctx, dv, n, dc, range2); });
+    return colors_of_values(ctx, weights, n, colors, [&](const float* dv, int32_t* dc) { return lgr_color_weights_dev(ctx, dv, n, dc, range2); });
 }
 
 extern "C" int lgr_color_correspondences(lgr_ctx* ctx, int n, const int32_t* kp, int n_kp, const lgr_corr* corr, int c, const lgr_corr* correct, int n_correct,
@@ -511,20 +507,17 @@ extern "C" int lgr_color_correspondences(lgr_ctx* ctx, int n, const int32_t* kp,
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, n >= 0 && n_kp >= 0 && c >= 0 && n_correct >= 0 && n_inl >= 0 && (kp || n_kp == 0) && (corr || c == 0) && (correct || n_correct == 0) &&
                        (inl || n_inl == 0) && (colors || n == 0), LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
-    // [colours n | key points n_kp (+ 1 so that "key points given, none found" keeps a non-null pointer)] and the three lists
-    int32_t* d;
-    lgr_corr* dl;
-    LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_A, (size_t) n + n_kp + 16, &d));
-    LGR_TRY(lgr_ws_t(ctx, WS_DBG_HOST_B, (size_t) c + n_correct + n_inl + 1, &dl));
-    int32_t* dkp = kp ? d + n : nullptr;
-    if (n_kp) LGR_HIP(ctx, hipMemcpyAsync(dkp, kp, (size_t) n_kp * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (c) LGR_HIP(ctx, hipMemcpyAsync(dl, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
-    if (n_correct) LGR_HIP(ctx, hipMemcpyAsync(dl + c, correct, (size_t) n_correct * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
-    if (n_inl) LGR_HIP(ctx, hipMemcpyAsync(dl + c + n_correct, inl, (size_t) n_inl * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
-    LGR_TRY(lgr_color_correspondences_dev(ctx, n, dkp, n_kp, c ? dl : nullptr, c, n_correct ? dl + c : nullptr, n_correct, n_inl ? dl + c + n_correct : nullptr,
+    int32_t *d, *dkp;
+    lgr_corr *dc, *dok, *di;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.out((size_t) n, &d));
+    LGR_TRY(hc.in(kp, (size_t) n_kp, &dkp));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    LGR_TRY(hc.in(correct, (size_t) n_correct, &dok));
+    LGR_TRY(hc.in(inl, (size_t) n_inl, &di));
+    // key points given, none found: the twin still gets a pointer (it colours by "were key points given"); the lists are null when empty
+    LGR_TRY(lgr_color_correspondences_dev(ctx, n, kp ? dkp : nullptr, n_kp, c ? dc : nullptr, c, n_correct ? dok : nullptr, n_correct, n_inl ? di : nullptr,
                                           n_inl, is_source, d));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(colors, d, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(colors, d, (size_t) n));
+    return hc.finish();
 }

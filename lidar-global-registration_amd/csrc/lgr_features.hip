@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_knn_wave.cuh"
 #include "lgr_seqsum.h"
 #include "lgr_math.cuh"
@@ -1064,7 +1065,7 @@ static int downsample_core(lgr_ctx* ctx, const float* d_pts, int n, float voxel,
     // out may alias the input: accumulate into a staging buffer first when it does
     float* stage = d_out;
     bool alias = d_out == d_pts;
-    if (alias) LGR_TRY(lgr_ws_t(ctx, WS_HOST_F, (size_t) nv * 12 + 4, &stage));
+    if (alias) LGR_TRY(lgr_ws_t(ctx, WS_SELF_COPY, (size_t) nv * 12 + 4, &stage));
     voxel_accumulate<<<cdiv(n, 256), 256, 0, ctx->stream>>>(d_pts, keys2, vals2, flags, rank, n, stage, okeys, ofirst);
     if (alias) LGR_HIP(ctx, hipMemcpyAsync(d_out, stage, (size_t) nv * 48, hipMemcpyDeviceToDevice, ctx->stream));
     if (d_keys) { *d_keys = okeys; *d_first = ofirst; }
@@ -1091,19 +1092,18 @@ extern "C" int lgr_downsample(lgr_ctx* ctx, const float* pts, int n, float voxel
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (pts || n == 0) && out && n_out && n >= 0, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, order == LGR_ORDER_REFERENCE || order == LGR_ORDER_CANONICAL, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     *n_out = 0;
     if (n == 0) return LGR_OK;
     float *dp, *dout;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n * 12, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n * 12, &dout));
-    LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(pts, (size_t) n * 12, &dp));
+    LGR_TRY(hc.out((size_t) n * 12, &dout));
     int nv = 0;
     // reference order = iteration order of std::unordered_map<Vector3i, AccumulatedPoint, HashEigen> (src/downsample.cpp:20,32-34),
     // computed on the device (lgr_hash_order.hip)
     LGR_TRY(lgr_downsample_order_dev(ctx, dp, n, voxel, order, dout, &nv));
-    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) nv * 48, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    LGR_TRY(hc.fetch(out, dout, (size_t) nv * 12));
+    LGR_TRY(hc.finish());
     *n_out = nv;
     return LGR_OK;
 }
@@ -1113,15 +1113,14 @@ extern "C" int lgr_selfcheck_rcp(lgr_ctx* ctx, unsigned lo_bits, unsigned hi_bit
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, out2 && lo_bits <= hi_bits, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     unsigned long long* d;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) 2, &d));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.out((size_t) 2, &d));
     LGR_HIP(ctx, hipMemsetAsync(d, 0, 16, ctx->stream));
     rcp_check_kernel<<<8 * ctx->n_cu, 256, 0, ctx->stream>>>(lo_bits, hi_bits, d);
     LGR_HIP(ctx, hipGetLastError());
-    LGR_HIP(ctx, hipMemcpyAsync(out2, d, 16, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out2, d, (size_t) 2));
+    return hc.finish();
 }
 
 // lgr.h: lgr_libm.cuh element-wise on the device (fn 0 acosf(a), 1 atanf(a), 2 atan2f(a, b), 3 sinf(a), 4 cosf(a)); host arrays
@@ -1144,19 +1143,16 @@ extern "C" int lgr_selfcheck_libm(lgr_ctx* ctx, int fn, const float* a, const fl
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, fn >= 0 && fn <= 6 && a && out && n >= 0 && (fn != 2 || b), LGR_ERR_INVALID_ARG);
     if (n == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *da, *db, *dout;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n, &da));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n, &db));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) n, &dout));
-    LGR_HIP(ctx, hipMemcpyAsync(da, a, (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (fn == 2) LGR_HIP(ctx, hipMemcpyAsync(db, b, (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(a, (size_t) n, &da));
+    LGR_TRY(hc.in(fn == 2 ? b : nullptr, (size_t) n, &db));   // only atan2f reads its second array
+    LGR_TRY(hc.out((size_t) n, &dout));
     if (fn >= 5) LGR_TRY(lgr_weights_libm_launch(ctx, fn, da, n, dout));   // expf / logf of the point weights (lgr_weights.hip)
     else libm_eval_kernel<<<8 * ctx->n_cu, 256, 0, ctx->stream>>>(fn, da, db, n, dout);
     LGR_HIP(ctx, hipGetLastError());
-    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out, dout, (size_t) n));
+    return hc.finish();
 }
 
 #ifdef LGR_SPFH_CHECK
@@ -1180,7 +1176,7 @@ extern "C" int lgr_normals_knn_dev(lgr_ctx* ctx, float* d_pts, int n, const floa
     if (!S) {
         // surface = the cloud itself: normals are written in place, so query a snapshot
         float* snap;
-        LGR_TRY(lgr_ws_t(ctx, WS_HOST_F, (size_t) n * 12, &snap));
+        LGR_TRY(lgr_ws_t(ctx, WS_SELF_COPY, (size_t) n * 12, &snap));
         LGR_HIP(ctx, hipMemcpyAsync(snap, d_pts, (size_t) n * 48, hipMemcpyDeviceToDevice, ctx->stream));
         S = snap; ns = n;
     }
@@ -1223,18 +1219,13 @@ extern "C" int lgr_normals_knn(lgr_ctx* ctx, float* pts, int n, const float* sur
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (pts || n == 0) && n >= 0, LGR_ERR_INVALID_ARG);
     if (n == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dp, *ds = nullptr;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n * 12, &dp));
-    LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (surf) {
-        LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) ns * 12 + 4, &ds));
-        LGR_HIP(ctx, hipMemcpyAsync(ds, surf, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    }
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in((const float*) pts, (size_t) n * 12, &dp));
+    if (surf) LGR_TRY(hc.in(surf, (size_t) ns * 12, &ds, LGR_PAD_CLOUD));   // (no surface stays null: the twin then takes the cloud itself)
     LGR_TRY(lgr_normals_knn_dev(ctx, dp, n, ds, ns, k, vp3, normals_available));
-    LGR_HIP(ctx, hipMemcpyAsync(pts, dp, (size_t) n * 48, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(pts, dp, (size_t) n * 12));
+    return hc.finish();
 }
 
 extern "C" int lgr_fpfh_dev(lgr_ctx* ctx, const float* d_kps, int m, const float* d_surf, int n, float radius, float* d_out) {
@@ -1293,15 +1284,12 @@ extern "C" int lgr_fpfh(lgr_ctx* ctx, const float* kps, int m, const float* surf
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (kps || m == 0) && (surf || n == 0) && (out || m == 0) && m >= 0 && n >= 0, LGR_ERR_INVALID_ARG);
     if (m == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dk, *ds, *dout;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) m * 12, &dk));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n * 12 + 4, &ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) m * 33, &dout));
-    LGR_HIP(ctx, hipMemcpyAsync(dk, kps, (size_t) m * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(ds, surf, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(kps, (size_t) m * 12, &dk));
+    LGR_TRY(hc.in(surf, (size_t) n * 12, &ds, LGR_PAD_CLOUD));
+    LGR_TRY(hc.out((size_t) m * 33, &dout));
     LGR_TRY(lgr_fpfh_dev(ctx, dk, m, ds, n, radius, dout));
-    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) m * 132, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out, dout, (size_t) m * 33));
+    return hc.finish();
 }

@@ -11,6 +11,7 @@
 
 #include "lgr_grid.cuh"
 #include "lgr_grid_rule.h"
+#include "lgr_host.h"
 #include "lgr_knn_wave.cuh"
 
 namespace {
@@ -459,13 +460,11 @@ extern "C" int lgr_smoothed_densities(lgr_ctx* ctx, const float* pts, int n, int
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, pts && out && n > 1, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dp, *dout;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n * 12, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) n, &dout));
-    LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(pts, (size_t) n * 12, &dp));
+    LGR_TRY(hc.out((size_t) n, &dout));
     LGR_TRY(lgr_smoothed_densities_dev(ctx, dp, n, k, dout));
-    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out, dout, (size_t) n));
+    return hc.finish();
 }

@@ -19,6 +19,7 @@
 
 #include <rocprim/device/device_scan.hpp>
 
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
 #include "lgr_pointpass.cuh"
@@ -394,12 +395,14 @@ extern "C" int lgr_gror(lgr_ctx* ctx, const float* src, int ns, const float* tgt
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm = nullptr;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
-    if (inlier_mask) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) c + 1, &dm));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    if (inlier_mask) LGR_TRY(hc.out((size_t) c, &dm));
     LGR_TRY(lgr_gror_dev(ctx, ds, ns, dt, nt, dc, c, resolution, k_optimal, res, dm));
     if (inlier_mask && c) {
-        LGR_HIP(ctx, hipMemcpyAsync(inlier_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        LGR_TRY(hc.fetch(inlier_mask, dm, (size_t) c));
+        LGR_TRY(hc.finish());
     }
     return LGR_OK;
 }

@@ -22,6 +22,7 @@
 #include <cmath>
 #include <vector>
 
+#include "lgr_host.h"
 #include "lgr_internal.h"
 
 namespace {
@@ -229,23 +230,20 @@ extern "C" int lgr_fold_hypotheses(lgr_ctx* ctx, const float* tns16, const float
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, max_set >= 1 && max_set <= LGR_HYPOTHESES_MAX, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, n >= 0 && ((tns16 && metrics) || n == 0) && set_tns16 && set_metrics && set_index && n_out, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
-    float *dT, *dM, *dO;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) std::max(n, 1) * 16, &dT));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) std::max(n, 1), &dM));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) max_set * 18, &dO));
-    float* dOm = dO + (size_t) max_set * 16;
-    int32_t* dOi = (int32_t*) (dOm + max_set);
-    if (n) {
-        LGR_HIP(ctx, hipMemcpyAsync(dT, tns16, (size_t) n * 64, hipMemcpyHostToDevice, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(dM, metrics, (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
+    float *dT, *dM, *dO, *dOm;
+    int32_t* dOi;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(tns16, (size_t) n * 16, &dT));
+    LGR_TRY(hc.in(metrics, (size_t) n, &dM));
+    LGR_TRY(hc.out((size_t) max_set * 16, &dO));
+    LGR_TRY(hc.out((size_t) max_set, &dOm));
+    LGR_TRY(hc.out((size_t) max_set, &dOi));
     LGR_TRY(lgr_fold_hypotheses_dev(ctx, dT, dM, n, distance_thr, max_set, dO, dOm, dOi, n_out));
     if (*n_out) {
-        LGR_HIP(ctx, hipMemcpyAsync(set_tns16, dO, (size_t) *n_out * 64, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(set_metrics, dOm, (size_t) *n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(set_index, dOi, (size_t) *n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        LGR_TRY(hc.fetch(set_tns16, dO, (size_t) *n_out * 16));
+        LGR_TRY(hc.fetch(set_metrics, dOm, (size_t) *n_out));
+        LGR_TRY(hc.fetch(set_index, dOi, (size_t) *n_out));
+        LGR_TRY(hc.finish());
     }
     return LGR_OK;
 }

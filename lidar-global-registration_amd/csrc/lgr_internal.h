@@ -126,13 +126,15 @@ enum {
     WS_PIPE_SURF_S, WS_PIPE_SURF_T, WS_PIPE_FEAT_S, WS_PIPE_FEAT_T, WS_PIPE_IJ, WS_PIPE_JI, WS_PIPE_DIJ, WS_PIPE_DJI,
     WS_PIPE_CORR, WS_PIPE_KNN_S, WS_PIPE_KNN_T, WS_PIPE_FLAGS, WS_PIPE_MISC, WS_PIPE_KIDX_S, WS_PIPE_KIDX_T, WS_PIPE_KPS_S, WS_PIPE_KPS_T,
     WS_MS_KNN_I, WS_MS_KNN_D, WS_MS_LIST_S, WS_MS_LIST_T, WS_MS_SUB, WS_MS_FEAT_S, WS_MS_FEAT_T, WS_MS_SURF2, WS_MS_RES, WS_PLANE_VISITED, WS_PLANE_CLAIMED, WS_PLANE_OUT, WS_LOCAL_G, WS_SORT_TMP, WS_MATCH_BOX, WS_RANSAC_GHIST,
-    WS_HOST_A, WS_HOST_B, WS_HOST_C, WS_HOST_D, WS_HOST_E, WS_HOST_F,
+    WS_HOST_0, WS_HOST_7 = WS_HOST_0 + 7,   // staged arrays of the host entry points, taken in order by lgr_host_call (lgr_host.h) and by nothing else
+    WS_SELF_COPY,      // lgr_features.hip: a _dev function's copy of a cloud it writes in place (the self-surface snapshot of lgr_normals_knn_dev, the aliased output of the voxel grid)
+    WS_PRE_UNORDERED,  // lgr_preprocess.hip: lgr_preprocess_order_dev's intermediate, the deduplicated cloud before the voxel grid
     WS_DENSE_PACK_A, WS_DENSE_PACK_B, WS_DENSE_KEYS,
     WS_ROPS_MASKED, WS_ROPS_LRF, WS_ROPS_KPS,
-    WS_WEIGHTS, WS_WEIGHTS_KNN, WS_WEIGHTS_TMP, WS_WEIGHTS_VALS, WS_WEIGHTS_SUM, WS_WEIGHTS_HOST,
+    WS_WEIGHTS, WS_WEIGHTS_KNN, WS_WEIGHTS_TMP, WS_WEIGHTS_VALS, WS_WEIGHTS_SUM,
     WS_GT_MISC, WS_GT_TERMS, WS_GT_ALIGNED, WS_GT_OVERLAP, WS_GT_FLAGS, WS_GT_KNN, WS_GT_DENS, WS_GT_CORR,   // lgr_analysis.hip
     WS_PD_TERMS, WS_PD_MISC, WS_PD_INLIERS, WS_PD_MASK,   // lgr_plane_dense.hip
-    WS_DBG_MISC, WS_DBG_MOVED, WS_DBG_FLAGS, WS_DBG_OVERLAP, WS_DBG_DENS, WS_DBG_SORT, WS_DBG_HOST_A, WS_DBG_HOST_B,   // lgr_debug.hip
+    WS_DBG_MISC, WS_DBG_MOVED, WS_DBG_FLAGS, WS_DBG_OVERLAP, WS_DBG_DENS, WS_DBG_SORT,   // lgr_debug.hip
     WS_HYP_SET, WS_HYP_ITEMS, WS_HYP_FINAL, WS_HYP_PLANE,   // lgr_hypotheses.hip, lgr_ransac_multi*_dev
     WS_RF_STATE, WS_RF_TERMS, WS_RF_PAIRS, WS_RF_TRACE,   // lgr_refine.hip
     WS_KNN_PART_A, WS_KNN_PART_B, WS_KNN_FLAG, WS_KNN_CAND_IJ, WS_KNN_CAND_JI,   // lgr_match_knn.hip; the pipeline's candidate lists
@@ -280,16 +282,6 @@ int lgr_ratio_test_core(lgr_ctx* ctx, const int32_t* d_knn_idx, const float* d_k
 // lgr_match_dense.hip: the exact dense matcher of the long descriptors, row_len 352 (SHOT) or 135 (RoPS), else LGR_ERR_UNSUPPORTED
 int lgr_match_dense(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block,
                     int32_t* ab_i, float* ab_d, int32_t* ba_i /* NULL: one direction */, float* ba_d);
-// host weights of a metric (lgr_align_ex2, lgr_ransac_ex) -> device copy on ctx->stream; *mp then points at the patched copy `staged`
-static inline int lgr_stage_host_weights(lgr_ctx* ctx, int ns, const lgr_metric_params** mp, lgr_metric_params* staged) {
-    if (!*mp || !(*mp)->weights) return LGR_OK;
-    float* dw;
-    LGR_TRY(lgr_ws_t(ctx, WS_WEIGHTS_HOST, (size_t) ns + 1, &dw));
-    LGR_HIP(ctx, hipMemcpyAsync(dw, (*mp)->weights, (size_t) ns * 4, hipMemcpyHostToDevice, ctx->stream));
-    *staged = **mp; staged->weights = dw; *mp = staged;
-    return LGR_OK;
-}
-
 // ---- the refit over flagged pairs, device-resident (lgr_ransac.hip; lgr_refine.hip's step) ----
 // estimateOptimalRigidTransformation over the pairs (P0[i], P1[i]) whose flag is set (0 / 1 ints), in ascending i, into d_Tout (16 floats):
 // lgr_refit_svd_dev's compaction and refit_kernel, on ctx->stream, nothing read back.  The kernel takes the number of pairs from

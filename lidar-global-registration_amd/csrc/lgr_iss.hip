@@ -13,6 +13,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
 
@@ -116,14 +117,12 @@ extern "C" int lgr_iss_keypoints(lgr_ctx* ctx, const float* pts, int n, float ra
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (pts || n == 0) && (idx || n == 0) && n_out && n >= 0, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float* dp;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n * 12 + 1, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) n + 1, &di));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(pts, (size_t) n * 12, &dp));
+    LGR_TRY(hc.out((size_t) n, &di));
     LGR_TRY(lgr_iss_keypoints_dev(ctx, dp, n, radius, gamma21, gamma32, min_neighbors, di, n_out));
-    if (*n_out) LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) *n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) *n_out));
+    return hc.finish();
 }

@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "lgr_host.h"
 #include "lgr_internal.h"
 
 #include "lgr_match_common.cuh"
@@ -1328,20 +1329,15 @@ extern "C" int lgr_match_bf(lgr_ctx* ctx, const float* q33, int mq, const float*
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (q33 || mq == 0) && (t33 || mt == 0) && (idx || mq == 0) && (dist || mq == 0) && mq >= 0 && mt >= 0, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * 33 + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * 33 + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq + 1, &dd));
-    if (mq) LGR_HIP(ctx, hipMemcpyAsync(dq, q33, (size_t) mq * 132, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dt, t33, (size_t) mt * 132, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q33, (size_t) mq * 33, &dq));
+    LGR_TRY(hc.in(t33, (size_t) mt * 33, &dt));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_match_bf_dev(ctx, dq, mq, dt, mt, block, di, dd));
-    if (mq) {
-        LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }

@@ -6,6 +6,7 @@
 // depend on scheduling.  The 33-d FPFH matcher is lgr_match.hip.
 #include <cfloat>
 
+#include "lgr_host.h"
 #include "lgr_match_dense.cuh"
 
 namespace {
@@ -113,20 +114,17 @@ int match_host(lgr_ctx* ctx, int row_len, const float* q, int mq, const float* t
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (q || mq == 0) && (t || mt == 0) && (idx || mq == 0) && (dist || mq == 0) && mq >= 0 && mt >= 0, LGR_ERR_INVALID_ARG);
     if (mq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * row_len + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * row_len + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq + 1, &dd));
-    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) mq * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dt, t, (size_t) mt * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q, (size_t) mq * row_len, &dq));
+    LGR_TRY(hc.in(t, (size_t) mt * row_len, &dt));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_match_dense(ctx, row_len, dq, mq, dt, mt, block, di, dd, nullptr, nullptr));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }
 
 }  // namespace

@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "lgr_host.h"
 #include "lgr_match_dense.cuh"
 #include "lgr_cloud.h"
 
@@ -386,20 +387,17 @@ extern "C" int lgr_match_knn(lgr_ctx* ctx, int row_len, const float* q, int mq, 
     LGR_CHECK(ctx, k >= 1 && k <= KMAX && (row_len == 33 || row_len == 135 || row_len == 352), LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, (q || mq == 0) && (t || mt == 0) && (idx || mq == 0) && (dist || mq == 0) && mq >= 0 && mt >= 0 && block > 0, LGR_ERR_INVALID_ARG);
     if (mq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * row_len + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * row_len + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq * k + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq * k + 1, &dd));
-    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) mq * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dt, t, (size_t) mt * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q, (size_t) mq * row_len, &dq));
+    LGR_TRY(hc.in(t, (size_t) mt * row_len, &dt));
+    LGR_TRY(hc.out((size_t) mq * k, &di));
+    LGR_TRY(hc.out((size_t) mq * k, &dd));
     LGR_TRY(lgr_match_knn_core(ctx, row_len, dq, mq, dt, mt, block, k, di, dd, nullptr, nullptr));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq * k));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq * k));
+    return hc.finish();
 }
 
 extern "C" int lgr_vote_matches_dev(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* d_cand_dist, int mq, int width, const float* d_train_pts, int mt,
@@ -416,22 +414,18 @@ extern "C" int lgr_vote_matches(lgr_ctx* ctx, const int32_t* cand_idx, const flo
     LGR_CHECK(ctx, mq >= 0 && mt >= 0 && width >= 1 && width <= 64 && std::isfinite(iss_radius) && iss_radius > 0.f, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, ((cand_idx && cand_dist && idx && dist) || mq == 0) && (train_pts || mt == 0), LGR_ERR_INVALID_ARG);
     if (mq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     int32_t *dc, *di;
     float *dcd, *dp, *dd;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * width, &dc));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mq * width, &dcd));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mt * 12 + 1, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) mq, &dd));
-    LGR_HIP(ctx, hipMemcpyAsync(dc, cand_idx, (size_t) mq * width * 4, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dcd, cand_dist, (size_t) mq * width * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dp, train_pts, (size_t) mt * 12 * 4, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(cand_idx, (size_t) mq * width, &dc));
+    LGR_TRY(hc.in(cand_dist, (size_t) mq * width, &dcd));
+    LGR_TRY(hc.in(train_pts, (size_t) mt * 12, &dp));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_vote_matches_core(ctx, dc, dcd, mq, width, dp, mt, iss_radius, di, dd));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }
 
 extern "C" int lgr_ratio_test_dev(lgr_ctx* ctx, const int32_t* d_knn_idx, const float* d_knn_dist, int mq, int k, float threshold, int32_t* d_idx, float* d_dist) {
@@ -446,20 +440,17 @@ extern "C" int lgr_ratio_test(lgr_ctx* ctx, const int32_t* knn_idx, const float*
     LGR_CHECK(ctx, k >= 2 && k <= KMAX, LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, mq >= 0 && std::isfinite(threshold) && threshold > 0.f && ((knn_idx && knn_dist && idx && dist) || mq == 0), LGR_ERR_INVALID_ARG);
     if (mq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     int32_t *dki, *di;
     float *dkd, *dd;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * k, &dki));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mq * k, &dkd));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq, &dd));
-    LGR_HIP(ctx, hipMemcpyAsync(dki, knn_idx, (size_t) mq * k * 4, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dkd, knn_dist, (size_t) mq * k * 4, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(knn_idx, (size_t) mq * k, &dki));
+    LGR_TRY(hc.in(knn_dist, (size_t) mq * k, &dkd));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_ratio_test_core(ctx, dki, dkd, mq, k, threshold, di, dd));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }
 
 extern "C" int lgr_match_ratio_dev(lgr_ctx* ctx, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, float threshold,
@@ -476,18 +467,15 @@ extern "C" int lgr_match_ratio(lgr_ctx* ctx, int row_len, const float* q, int mq
     LGR_CHECK(ctx, k >= 2 && k <= KMAX && (row_len == 33 || row_len == 135 || row_len == 352), LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, (q || mq == 0) && (t || mt == 0) && (idx || mq == 0) && (dist || mq == 0) && mq >= 0 && mt >= 0 && block > 0, LGR_ERR_INVALID_ARG);
     if (mq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * row_len + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * row_len + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq + 1, &dd));
-    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) mq * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dt, t, (size_t) mt * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q, (size_t) mq * row_len, &dq));
+    LGR_TRY(hc.in(t, (size_t) mt * row_len, &dt));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_match_ratio_core(ctx, row_len, dq, mq, dt, mt, block, k, threshold, di, dd));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "lgr_host.h"
 #include "lgr_internal.h"
 
 namespace {
@@ -59,22 +60,17 @@ extern "C" int lgr_match_flann(lgr_ctx* ctx, const float* q33, int mq, const flo
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (q33 || mq == 0) && (t33 || mt == 0) && (idx || mq == 0) && (dist || mq == 0) && mq >= 0 && mt >= 0, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * 33 + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * 33 + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq + 1, &dd));
-    if (mq) LGR_HIP(ctx, hipMemcpyAsync(dq, q33, (size_t) mq * 132, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dt, t33, (size_t) mt * 132, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q33, (size_t) mq * 33, &dq));
+    LGR_TRY(hc.in(t33, (size_t) mt * 33, &dt));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_match_flann_dev(ctx, dq, mq, dt, mt, di, dd));
-    if (mq) {
-        LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }
 
 extern "C" int lgr_match_local(lgr_ctx* ctx, const float* qpts, int mq, const float* tpts, int mt, const float* q33, const float* t33,
@@ -83,28 +79,17 @@ extern "C" int lgr_match_local(lgr_ctx* ctx, const float* qpts, int mq, const fl
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (qpts || mq == 0) && (tpts || mt == 0) && (q33 || mq == 0) && (t33 || mt == 0) && (idx || mq == 0) && (dist || mq == 0) &&
                    guess16 && mq >= 0 && mt >= 0, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dqp, *dtp, *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * 33 + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * 33 + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq + 1, &dd));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) mq * 12 + 1, &dqp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_F, (size_t) mt * 12 + 1, &dtp));
-    if (mq) {
-        LGR_HIP(ctx, hipMemcpyAsync(dq, q33, (size_t) mq * 132, hipMemcpyHostToDevice, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(dqp, qpts, (size_t) mq * 48, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (mt) {
-        LGR_HIP(ctx, hipMemcpyAsync(dt, t33, (size_t) mt * 132, hipMemcpyHostToDevice, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(dtp, tpts, (size_t) mt * 48, hipMemcpyHostToDevice, ctx->stream));
-    }
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q33, (size_t) mq * 33, &dq));
+    LGR_TRY(hc.in(t33, (size_t) mt * 33, &dt));
+    LGR_TRY(hc.in(qpts, (size_t) mq * 12, &dqp));
+    LGR_TRY(hc.in(tpts, (size_t) mt * 12, &dtp));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_match_local_dev(ctx, dqp, mq, dtp, mt, dq, dt, guess16, radius, di, dd));
-    if (mq) {
-        LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }

@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_internal.h"
 
 namespace {
@@ -344,26 +345,19 @@ extern "C" int lgr_match_local_knn(lgr_ctx* ctx, int row_len, const float* qpts,
     LGR_CHECK(ctx, mq >= 0 && mt >= 0 && (qpts || mq == 0) && (tpts || mt == 0) && (q || mq == 0) && (t || mt == 0) && (idx || mq == 0) && (dist || mq == 0) &&
                    guess16 && radius >= 0.f, LGR_ERR_INVALID_ARG);
     if (mq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dqp, *dtp, *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * row_len + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * row_len + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq * k + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq * k + 1, &dd));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) mq * 12 + 1, &dqp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_F, (size_t) mt * 12 + 1, &dtp));
-    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) mq * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dqp, qpts, (size_t) mq * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) {
-        LGR_HIP(ctx, hipMemcpyAsync(dt, t, (size_t) mt * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
-        LGR_HIP(ctx, hipMemcpyAsync(dtp, tpts, (size_t) mt * 48, hipMemcpyHostToDevice, ctx->stream));
-    }
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q, (size_t) mq * row_len, &dq));
+    LGR_TRY(hc.in(t, (size_t) mt * row_len, &dt));
+    LGR_TRY(hc.in(qpts, (size_t) mq * 12, &dqp));
+    LGR_TRY(hc.in(tpts, (size_t) mt * 12, &dtp));
+    LGR_TRY(hc.out((size_t) mq * k, &di));
+    LGR_TRY(hc.out((size_t) mq * k, &dd));
     LGR_TRY(lgr_match_local_knn_dev(ctx, row_len, dqp, mq, dtp, mt, dq, dt, guess16, radius, k, di, dd));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq * k));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq * k));
+    return hc.finish();
 }
 
 extern "C" int lgr_match_flann_rows(lgr_ctx* ctx, int row_len, const float* q, int mq, const float* t, int mt, int32_t* idx, float* dist) {
@@ -372,18 +366,15 @@ extern "C" int lgr_match_flann_rows(lgr_ctx* ctx, int row_len, const float* q, i
     LGR_CHECK(ctx, row_len_built(row_len), LGR_ERR_UNSUPPORTED);
     LGR_CHECK(ctx, mq >= 0 && mt >= 0 && (q || mq == 0) && (t || mt == 0) && (idx || mq == 0) && (dist || mq == 0), LGR_ERR_INVALID_ARG);
     if (mq == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dq, *dt, *dd;
     int32_t* di;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) mq * row_len + 1, &dq));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) mt * row_len + 1, &dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) mq + 1, &di));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) mq + 1, &dd));
-    LGR_HIP(ctx, hipMemcpyAsync(dq, q, (size_t) mq * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mt) LGR_HIP(ctx, hipMemcpyAsync(dt, t, (size_t) mt * row_len * 4, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(q, (size_t) mq * row_len, &dq));
+    LGR_TRY(hc.in(t, (size_t) mt * row_len, &dt));
+    LGR_TRY(hc.out((size_t) mq, &di));
+    LGR_TRY(hc.out((size_t) mq, &dd));
     LGR_TRY(lgr_match_flann_rows_dev(ctx, row_len, dq, mq, dt, mt, di, dd));
-    LGR_HIP(ctx, hipMemcpyAsync(idx, di, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dist, dd, (size_t) mq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(idx, di, (size_t) mq));
+    LGR_TRY(hc.fetch(dist, dd, (size_t) mq));
+    return hc.finish();
 }

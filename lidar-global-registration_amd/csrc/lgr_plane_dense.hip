@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
 #include "lgr_plane_point.cuh"
@@ -173,20 +174,19 @@ extern "C" int lgr_evaluate_plane_dense(lgr_ctx* ctx, const float* src, int ns, 
     lgr_turn turn__(ctx);
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, src && tgt && out && ns > 0 && nt > 1, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *ds, *dt;
     lgr_corr* di = nullptr;
     int32_t* dn = nullptr;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     lgr_metric_params staged;
-    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &staged));
-    if (inliers) LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) ns + 1, &di));
-    if (nn) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) ns + 4, &dn));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.weights(ns, &mp, &staged));
+    if (inliers) LGR_TRY(hc.out((size_t) ns, &di));
+    if (nn) LGR_TRY(hc.out((size_t) ns, &dn, 4));   // (slack kept from before; no reader past ns is known)
     LGR_TRY(lgr_evaluate_plane_dense_dev(ctx, ds, ns, dt, nt, T16, score_id, mp, inlier_threshold, out, di, dn));
-    if (di && out->n_inliers) LGR_HIP(ctx, hipMemcpyAsync(inliers, di, (size_t) out->n_inliers * sizeof(lgr_corr), hipMemcpyDeviceToHost, ctx->stream));
-    if (dn) LGR_HIP(ctx, hipMemcpyAsync(nn, dn, (size_t) ns * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(inliers, di, (size_t) out->n_inliers));
+    LGR_TRY(hc.fetch(nn, dn, (size_t) ns));
+    return hc.finish();
 }
 
 extern "C" int lgr_analysis_metric(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, const float T16[16],
@@ -195,19 +195,19 @@ extern "C" int lgr_analysis_metric(lgr_ctx* ctx, const float* src, int ns, const
     lgr_turn turn__(ctx);
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, src && tgt && out && ns > 0 && nt > 0 && c >= 0 && (corr || c == 0), LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     const bool plane = metric_id == LGR_METRIC_CLOSEST_PLANE || metric_id == LGR_METRIC_WEIGHTED_CLOSEST_PLANE;
     float *ds, *dt;
     lgr_corr *dc, *di = nullptr;
     uint8_t* dm = nullptr;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
     lgr_metric_params staged;
-    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &staged));
-    if (inlier_mask && !plane && c) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) c + 16, &dm));
-    if (inliers && plane) LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) ns + 1, &di));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    LGR_TRY(hc.weights(ns, &mp, &staged));
+    if (inlier_mask && !plane && c) LGR_TRY(hc.out((size_t) c, &dm, LGR_PAD_MASK));
+    if (inliers && plane) LGR_TRY(hc.out((size_t) ns, &di));
     LGR_TRY(lgr_analysis_metric_dev(ctx, ds, ns, dt, nt, c ? dc : nullptr, c, T16, Tgt16, metric_id, score_id, mp, out, dm, di));
-    if (dm) LGR_HIP(ctx, hipMemcpyAsync(inlier_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
-    if (di && out->n_inliers) LGR_HIP(ctx, hipMemcpyAsync(inliers, di, (size_t) out->n_inliers * sizeof(lgr_corr), hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    if (dm) LGR_TRY(hc.fetch(inlier_mask, dm, (size_t) c));
+    if (di) LGR_TRY(hc.fetch(inliers, di, (size_t) out->n_inliers));
+    return hc.finish();
 }

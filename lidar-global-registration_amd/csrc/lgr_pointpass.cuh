@@ -1,7 +1,8 @@
 // lgr_pointpass.cuh -- what the thread-per-point passes of lgr_analysis.hip, lgr_plane_dense.hip and lgr_debug.hip share: PCL's point
 // moves, the wave-aggregated counter, the sequential f32 sum jobs, the move of a whole cloud and
-// the compaction of an overlap cloud (flags, their exclusive scan, the kept rows).  Its host helpers -- the staging of host clouds and
-// correspondences (stage_clouds, stage_problem) and the scan of 0 / 1 flags (pp_scan_flags) -- also serve lgr_ransac.hip, lgr_gror.hip and lgr_align.hip.  Everything here sits in an unnamed namespace: each translation unit gets its own copy of the kernels.
+// the compaction of an overlap cloud (flags, their exclusive scan, the kept rows).  Its host helpers are the read-back of a few words
+// (read_words) and the scan of 0 / 1 flags (pp_scan_flags); host arrays are staged by lgr_host.h, not here.  Everything here sits in an
+// unnamed namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <rocprim/device/device_scan.hpp>
 
@@ -119,26 +120,6 @@ inline int read_words(lgr_ctx* ctx, const void* d, int n, void* out) {
     LGR_HIP(ctx, hipMemcpyAsync(h, d, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
     LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(out, h, (size_t) n * 4);
-    return LGR_OK;
-}
-
-// host clouds -> the WS_HOST_A / WS_HOST_B slots (nullptr for an empty cloud); the copies are ordered on the context's stream
-inline int stage_clouds(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, float** ds, float** dt) {
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) ns * 12 + 4, ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) nt * 12 + 4, dt));
-    if (ns) LGR_HIP(ctx, hipMemcpyAsync(*ds, src, (size_t) ns * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (nt) LGR_HIP(ctx, hipMemcpyAsync(*dt, tgt, (size_t) nt * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (!ns) *ds = nullptr;
-    if (!nt) *dt = nullptr;
-    return LGR_OK;
-}
-
-// ... and the correspondences of a registration problem -> the WS_HOST_C slot
-inline int stage_problem(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c, float** ds, float** dt, lgr_corr** dc) {
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, ds, dt));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) c + 1, dc));
-    if (c) LGR_HIP(ctx, hipMemcpyAsync(*dc, corr, (size_t) c * sizeof(lgr_corr), hipMemcpyHostToDevice, ctx->stream));
     return LGR_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_stdhash.h"
 
@@ -172,7 +173,7 @@ extern "C" int lgr_preprocess_order_dev(lgr_ctx* ctx, const float* d_pts, int n,
     LGR_CHECK(ctx, order == LGR_ORDER_REFERENCE || order == LGR_ORDER_CANONICAL, LGR_ERR_INVALID_ARG);
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     float* u;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) n * 12, &u));
+    LGR_TRY(lgr_ws_t(ctx, WS_PRE_UNORDERED, (size_t) n * 12, &u));
     int m = 0;
     LGR_TRY(dedupe_order_dev(ctx, d_pts, n, order, u, &m));   // set order: the voxel grid below accumulates every voxel in that order
     LGR_CHECK(ctx, m > 1, LGR_ERR_INVALID_ARG);
@@ -196,15 +197,13 @@ extern "C" int lgr_preprocess(lgr_ctx* ctx, const float* pts, int n, const float
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, pts && out && n_out && n > 1, LGR_ERR_INVALID_ARG);
     LGR_CHECK(ctx, order == LGR_ORDER_REFERENCE || order == LGR_ORDER_CANONICAL, LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dp, *dout;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) n * 12, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) n * 12, &dout));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(pts, (size_t) n * 12, &dp));
+    LGR_TRY(hc.out((size_t) n * 12, &dout));
     // reference order: the set's iteration order after inserting the points in input order (filterDuplicatePoints), then the
     // unordered_map order of the voxel grid -- both on the device (lgr_preprocess_order_dev)
-    LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
     LGR_TRY(lgr_preprocess_order_dev(ctx, dp, n, vp3, normals_available, order, dout, n_out, voxel_out));
-    LGR_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) *n_out * 48, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out, dout, (size_t) *n_out * 12));
+    return hc.finish();
 }

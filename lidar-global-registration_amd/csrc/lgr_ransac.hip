@@ -22,6 +22,7 @@
 #include <cmath>
 #include <vector>
 
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_pointpass.cuh"
 #include "lgr_ransac_schedule.cuh"
@@ -736,14 +737,16 @@ extern "C" int lgr_ransac_ex(lgr_ctx* ctx, const float* src, int ns, const float
     float *ds, *dt;
     lgr_corr* dc;
     uint8_t* dm;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) c + 16, &dm));
     lgr_metric_params mpd;
-    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    LGR_TRY(hc.out((size_t) c, &dm, LGR_PAD_MASK));
+    LGR_TRY(hc.weights(ns, &mp, &mpd));
     LGR_TRY(lgr_ransac_ex_dev(ctx, ds, ns, dt, nt, dc, c, p, mp, res, dm));
     if (final_mask && c >= p->n_samples) {
-        LGR_HIP(ctx, hipMemcpyAsync(final_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
-        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        LGR_TRY(hc.fetch(final_mask, dm, (size_t) c));
+        LGR_TRY(hc.finish());
     } else if (final_mask && c > 0) memset(final_mask, 0, c);
     return LGR_OK;
 }
@@ -776,7 +779,9 @@ extern "C" int lgr_refit_svd(lgr_ctx* ctx, const float* src, const float* tgt, i
     LGR_CHECK(ctx, src && tgt && (inliers || n == 0) && T16 && ns > 0 && nt > 0 && n >= 0, LGR_ERR_INVALID_ARG);
     float *ds, *dt;
     lgr_corr* dc;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, inliers, n, &ds, &dt, &dc));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(inliers, (size_t) n, &dc));
     LGR_TRY(lgr_check_corr(ctx, dc, n, ns, nt));   // the _dev form mirrors estimateOptimalRigidTransformation(src, tgt, inliers, T) and has no sizes to check against
     return lgr_refit_svd_dev(ctx, ds, dt, dc, n, nullptr, T16);
 }
@@ -818,7 +823,9 @@ extern "C" int lgr_choose_best_hypothesis(lgr_ctx* ctx, const float* src, int ns
     LGR_CHECK(ctx, src && tgt && (corr || c == 0) && (tns16 || n == 0) && T_out16 && n >= 0 && c >= 0 && ns > 0 && nt > 0, LGR_ERR_INVALID_ARG);
     float *ds, *dt;
     lgr_corr* dc;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
     return lgr_choose_best_hypothesis_dev(ctx, ds, ns, dt, nt, dc, c, tns16, n, T_out16, best_index, uniformities);
 }
 
@@ -1051,7 +1058,9 @@ extern "C" int lgr_ransac_multi(lgr_ctx* ctx, const float* src, int ns, const fl
     LGR_CHECK(ctx, src && tgt && (corr || c == 0) && res && ns > 0 && nt > 0 && c >= 0, LGR_ERR_INVALID_ARG);
     float *ds, *dt;
     lgr_corr* dc;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
     return lgr_ransac_multi_dev(ctx, ds, ns, dt, nt, dc, c, p, max_set, res, out, n_out, best_index);
 }
 extern "C" int lgr_ransac_multi_ex(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const lgr_corr* corr, int c,
@@ -1063,8 +1072,10 @@ extern "C" int lgr_ransac_multi_ex(lgr_ctx* ctx, const float* src, int ns, const
     LGR_CHECK(ctx, src && tgt && (corr || c == 0) && res && ns > 0 && nt > 0 && c >= 0, LGR_ERR_INVALID_ARG);
     float *ds, *dt;
     lgr_corr* dc;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
     lgr_metric_params mpd;
-    LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &mpd));
+    LGR_TRY(hc.weights(ns, &mp, &mpd));
     return lgr_ransac_multi_ex_dev(ctx, ds, ns, dt, nt, dc, c, p, mp, max_set, res, out, n_out, best_index);
 }

@@ -20,6 +20,7 @@
 #include <cfloat>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
 #include "lgr_plane_point.cuh"
@@ -226,8 +227,9 @@ extern "C" int lgr_refine_plane(lgr_ctx* ctx, const float* src, int ns, const fl
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, T0 && out && ns >= 0 && (src || ns == 0) && tgt && nt > 1 && params_ok(p) && (!trace || n_trace), LGR_ERR_INVALID_ARG);
     float *ds, *dt;
-    LGR_TRY(stage_clouds(ctx, src, ns, tgt, nt, &ds, &dt));
     lgr_metric_params staged;
-    if (ns) LGR_TRY(lgr_stage_host_weights(ctx, ns, &mp, &staged));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    if (ns) LGR_TRY(hc.weights(ns, &mp, &staged));   // (an empty source: the parameters go on as they came)
     return lgr_refine_plane_dev(ctx, ds, ns, dt, nt, T0, p, mp, out, trace, n_trace);
 }

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_libm.cuh"
 #include "lgr_rops_math.h"
 
@@ -249,17 +250,14 @@ extern "C" int lgr_gravity_lrf(lgr_ctx* ctx, const float* kps, int m, const floa
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (kps || m == 0) && (surf || n == 0) && (out9 || m == 0) && m >= 0 && n >= 0, LGR_ERR_INVALID_ARG);
     if (m == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dk, *ds, *dl;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) m * 12, &dk));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n * 12 + 4, &ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) m * 9, &dl));
-    LGR_HIP(ctx, hipMemcpyAsync(dk, kps, (size_t) m * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(ds, surf, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(kps, (size_t) m * 12, &dk));
+    LGR_TRY(hc.in(surf, (size_t) n * 12, &ds, LGR_PAD_CLOUD));
+    LGR_TRY(hc.out((size_t) m * 9, &dl));
     LGR_TRY(gravity_frames(ctx, dk, m, ds, n, radius, dl));
-    LGR_HIP(ctx, hipMemcpyAsync(out9, dl, (size_t) m * 36, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out9, dl, (size_t) m * 9));
+    return hc.finish();
 }
 
 extern "C" int lgr_rops(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, const float* lrf, float* out135) {
@@ -267,17 +265,13 @@ extern "C" int lgr_rops(lgr_ctx* ctx, const float* kps, int m, const float* surf
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, (kps || m == 0) && (surf || n == 0) && (lrf || m == 0) && (out135 || m == 0) && m >= 0 && n >= 0, LGR_ERR_INVALID_ARG);
     if (m == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dk, *ds, *dl, *dout;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) m * 12, &dk));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n * 12 + 4, &ds));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) m * ROPS_LEN, &dout));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) m * 9, &dl));
-    LGR_HIP(ctx, hipMemcpyAsync(dk, kps, (size_t) m * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(ds, surf, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(dl, lrf, (size_t) m * 36, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(kps, (size_t) m * 12, &dk));
+    LGR_TRY(hc.in(surf, (size_t) n * 12, &ds, LGR_PAD_CLOUD));
+    LGR_TRY(hc.in(lrf, (size_t) m * 9, &dl));
+    LGR_TRY(hc.out((size_t) m * ROPS_LEN, &dout));
     LGR_TRY(rops_rows(ctx, dk, m, ds, n, radius, dl, dout));
-    LGR_HIP(ctx, hipMemcpyAsync(out135, dout, (size_t) m * ROPS_LEN * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out135, dout, (size_t) m * ROPS_LEN));
+    return hc.finish();
 }

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_shot_math.h"
 
 namespace {
@@ -359,38 +360,32 @@ extern "C" int lgr_shot_dev(lgr_ctx* ctx, const float* d_kps, int m, const float
 }
 
 // host entry points: upload, run the device path, download
-static int shot_host(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, const float* lrf, float* out352, float* out_lrf) {
+static int shot_staged(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, const float* lrf, float* out352, float* out_lrf) {
     LGR_CHECK(ctx, (kps || m == 0) && (surf || n == 0) && m >= 0 && n >= 0, LGR_ERR_INVALID_ARG);
     if (m == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dk, *ds, *dl = nullptr, *dout = nullptr, *dlo = nullptr;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) m * 12, &dk));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n * 12 + 4, &ds));
-    if (out352) LGR_TRY(lgr_ws_t(ctx, WS_HOST_C, (size_t) m * SHOT_LEN, &dout));
-    if (out_lrf) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) m * 9, &dlo));
-    LGR_HIP(ctx, hipMemcpyAsync(dk, kps, (size_t) m * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (n) LGR_HIP(ctx, hipMemcpyAsync(ds, surf, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
-    if (lrf) {
-        LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) m * 9, &dl));
-        LGR_HIP(ctx, hipMemcpyAsync(dl, lrf, (size_t) m * 36, hipMemcpyHostToDevice, ctx->stream));
-    }
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(kps, (size_t) m * 12, &dk));
+    LGR_TRY(hc.in(surf, (size_t) n * 12, &ds, LGR_PAD_CLOUD));
+    if (lrf) LGR_TRY(hc.in(lrf, (size_t) m * 9, &dl));   // (no frames stay null: they are then estimated)
+    if (out352) LGR_TRY(hc.out((size_t) m * SHOT_LEN, &dout));
+    if (out_lrf) LGR_TRY(hc.out((size_t) m * 9, &dlo));
     LGR_TRY(shot_features(ctx, dk, m, ds, n, radius, dl, dout, dlo));
-    if (out352) LGR_HIP(ctx, hipMemcpyAsync(out352, dout, (size_t) m * SHOT_LEN * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_lrf) LGR_HIP(ctx, hipMemcpyAsync(out_lrf, dlo, (size_t) m * 36, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out352, dout, (size_t) m * SHOT_LEN));
+    LGR_TRY(hc.fetch(out_lrf, dlo, (size_t) m * 9));
+    return hc.finish();
 }
 
 extern "C" int lgr_shot_lrf(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, float* out9) {
     lgr_turn turn__(ctx);
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, out9 || m == 0, LGR_ERR_INVALID_ARG);
-    return shot_host(ctx, kps, m, surf, n, radius, nullptr, nullptr, out9);
+    return shot_staged(ctx, kps, m, surf, n, radius, nullptr, nullptr, out9);
 }
 
 extern "C" int lgr_shot(lgr_ctx* ctx, const float* kps, int m, const float* surf, int n, float radius, const float* lrf, float* out352, float* out_lrf) {
     lgr_turn turn__(ctx);
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, out352 || m == 0, LGR_ERR_INVALID_ARG);
-    return shot_host(ctx, kps, m, surf, n, radius, lrf, out352, out_lrf);
+    return shot_staged(ctx, kps, m, surf, n, radius, lrf, out352, out_lrf);
 }

@@ -15,9 +15,9 @@
 #include <chrono>
 #include <cmath>
 
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_math.cuh"
-#include "lgr_pointpass.cuh"
 #include "lgr_gror_nodes.cuh"
 #include "lgr_teaser_math.h"
 
@@ -520,12 +520,13 @@ extern "C" int lgr_teaser(lgr_ctx* ctx, const float* src, int ns, const float* t
     lgr_corr* dc;
     uint8_t* dm = nullptr;
     int32_t* dq = nullptr;
-    LGR_TRY(stage_problem(ctx, src, ns, tgt, nt, corr, c, &ds, &dt, &dc));
-    if (inlier_mask) LGR_TRY(lgr_ws_t(ctx, WS_HOST_D, (size_t) c + 1, &dm));
-    if (clique) LGR_TRY(lgr_ws_t(ctx, WS_HOST_E, (size_t) 2 * LGR_TEASER_NODES_MAX, &dq));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    LGR_TRY(hc.in(corr, (size_t) c, &dc));
+    if (inlier_mask) LGR_TRY(hc.out((size_t) c, &dm));
+    if (clique) LGR_TRY(hc.out((size_t) 2 * LGR_TEASER_NODES_MAX, &dq));
     LGR_TRY(lgr_teaser_dev(ctx, ds, ns, dt, nt, dc, c, params, res, info, dq, dm));
-    if (inlier_mask && c) LGR_HIP(ctx, hipMemcpyAsync(inlier_mask, dm, (size_t) c, hipMemcpyDeviceToHost, ctx->stream));
-    if (clique) LGR_HIP(ctx, hipMemcpyAsync(clique, dq, (size_t) 2 * LGR_TEASER_NODES_MAX * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(inlier_mask, dm, (size_t) c));
+    LGR_TRY(hc.fetch(clique, dq, (size_t) 2 * LGR_TEASER_NODES_MAX));
+    return hc.finish();
 }

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "lgr_grid.cuh"
+#include "lgr_host.h"
 #include "lgr_internal.h"
 #include "lgr_libm.cuh"
 #include "lgr_seqsum.h"
@@ -310,16 +311,15 @@ extern "C" int lgr_principal_curvatures(lgr_ctx* ctx, const float* pts, int n, i
     if (!ctx) return LGR_ERR_INVALID_ARG;
     LGR_CHECK(ctx, n >= 0 && (pts || n == 0) && (pc1 || n == 0) && (pc2 || n == 0), LGR_ERR_INVALID_ARG);
     if (n == 0) return LGR_OK;
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
-    float *dp, *d1;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n * 12, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n * 2, &d1));
-    LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
-    LGR_TRY(lgr_principal_curvatures_dev(ctx, dp, n, k, d1, d1 + n));
-    LGR_HIP(ctx, hipMemcpyAsync(pc1, d1, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipMemcpyAsync(pc2, d1 + n, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    float *dp, *d1, *d2;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(pts, (size_t) n * 12, &dp));
+    LGR_TRY(hc.out((size_t) n, &d1));
+    LGR_TRY(hc.out((size_t) n, &d2));
+    LGR_TRY(lgr_principal_curvatures_dev(ctx, dp, n, k, d1, d2));
+    LGR_TRY(hc.fetch(pc1, d1, (size_t) n));
+    LGR_TRY(hc.fetch(pc2, d2, (size_t) n));
+    return hc.finish();
 }
 
 extern "C" int lgr_weights_dev(lgr_ctx* ctx, const float* d_pts, int n, int weight_id, int nr_points, float* d_out, float* weights_sum) {
@@ -351,15 +351,13 @@ extern "C" int lgr_weights(lgr_ctx* ctx, const float* pts, int n, int weight_id,
         if (weights_sum) *weights_sum = 0.f;
         return LGR_OK;
     }
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     float *dp, *dw;
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_A, (size_t) n * 12, &dp));
-    LGR_TRY(lgr_ws_t(ctx, WS_HOST_B, (size_t) n, &dw));
-    LGR_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t) n * 48, hipMemcpyHostToDevice, ctx->stream));
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(pts, (size_t) n * 12, &dp));
+    LGR_TRY(hc.out((size_t) n, &dw));
     LGR_TRY(lgr_weights_dev(ctx, dp, n, weight_id, nr_points, dw, weights_sum));
-    LGR_HIP(ctx, hipMemcpyAsync(out, dw, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return LGR_OK;
+    LGR_TRY(hc.fetch(out, dw, (size_t) n));
+    return hc.finish();
 }
 
 // lgr.h: the expf / logf restatements element-wise on the device (lgr_selfcheck_libm fn 5 / 6)
