@@ -348,7 +348,8 @@ int lgr_match_bf2_dev(lgr_ctx*, const float* d_a33, int ma, const float* d_b33, 
                       int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
 /* ---- include/matching.h:373-376 matchBF<SHOT>(query, train, params): the contract of lgr_match_bf on M x 352 rows (OpenCV 4.5.1's
  *      normL2Sqr lane order for n = 352: 22 blocks of 16, no tail; ties: the later bf block, then the lower index; NaN rows never
- *      match).  An exact dense scan: every (query, train) distance is the canonical one. ---- */
+ *      match).  The result is defined by the exact dense scan on the canonical distances; lgr_ctx_set_dense_filter chooses between that
+ *      scan and an MFMA filter that runs the same selection on a proven superset of the rows it depends on: the same bytes either way. ---- */
 int lgr_match_shot(lgr_ctx*, const float* q352, int mq, const float* t352, int mt, int block, int32_t* idx, float* dist);
 int lgr_match_shot_dev(lgr_ctx*, const float* d_q352, int mq, const float* d_t352, int mt, int block, int32_t* d_idx, float* d_dist);
 /* both directions from one pass over the (a, b) distances */
@@ -360,6 +361,21 @@ int lgr_match_rops(lgr_ctx*, const float* q135, int mq, const float* t135, int m
 int lgr_match_rops_dev(lgr_ctx*, const float* d_q135, int mq, const float* d_t135, int mt, int block, int32_t* d_idx, float* d_dist);
 int lgr_match2_rops_dev(lgr_ctx*, const float* d_a135, int ma, const float* d_b135, int mb, int block,
                         int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
+/* How the six entry points above, and SHOT / RoPS matching at randomness 1 inside lgr_correspondences* / lgr_align* / prepared and
+ * multi-scale calls, sweep their rows; never what they return.  mode: -1 auto (filtered from the measured crossover size), 0 exact scan,
+ * 1 filtered at any size.  self_check: 0 / 1 (test sizes): on the device, every pair of regular rows against the proven bound of the
+ * filter and every query's candidates against an exact scan; a violation fails the call with LGR_ERR_HIP.  Values outside these:
+ * LGR_ERR_INVALID_ARG, the setting unchanged.  lgr_ctx_set_knn_filter and the k-nearest / ratio paths are independent of this switch.
+ * ABI: additions only (these four entry points); no struct changed, lgr_version() stays 5. */
+int lgr_ctx_set_dense_filter(lgr_ctx*, int mode, int self_check);
+int lgr_ctx_get_dense_filter(lgr_ctx*, int* mode, int* self_check);
+/* last one-match call of this context on 135 / 352-float rows: the slots of lgr_match_knn_last -- [0] 1 filtered / 0 exact scan, [1] (query,
+ * train) pairs whose canonical distance was computed, [2] query rows answered from candidates, [3] query rows answered by the exact scan,
+ * [4] train rows offered to every query, [5] per-row candidate capacity, [6] self-check violations (~0 = not run), [7] reason code when
+ * [0] == 0 under mode 1 (1: more than 1024 finite rows the operands cannot carry, 2: more than half of a direction's rows on the fallback
+ * scan, 3: an empty side) */
+int lgr_match_dense_last(lgr_ctx*, unsigned long long* out8);
+int lgr_match_dense_last_check(lgr_ctx*, double* worst_ratio /* max |f - d2| / e over checked pairs, -1 = not run */);
 /* ---- include/matching.h:612-625 matchBF with randomness = k > 1, on rows of row_len 33 (FPFH), 135 (RoPS135) or 352 (SHOT), other
  *      lengths and k outside 1..LGR_RANDOMNESS_MAX: LGR_ERR_UNSUPPORTED.  idx / dist are m x k: row i holds query i's matches in list
  *      order, then -1 / 0.f.  The distances are those of lgr_match_bf / lgr_match_rops / lgr_match_shot.  Per bf block

@@ -133,6 +133,7 @@ static int make_internal(lgr_ctx* ctx, lgr_ctx** out, hipEvent_t* ev) {
     (*out)->opt = ctx->opt;
     (*out)->mopt = ctx->mopt;
     (*out)->knnf_mode = ctx->knnf_mode; (*out)->knnf_check = ctx->knnf_check;
+    (*out)->densef_mode = ctx->densef_mode; (*out)->densef_check = ctx->densef_check;
     (*out)->internal = true;
     if (!*ev) LGR_HIP(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
     return LGR_OK;

@@ -72,6 +72,9 @@ struct lgr_ctx {
     int knnf_mode = -1, knnf_check = 0;         // lgr_ctx_set_knn_filter: how 33-float rows are swept by the k-nearest matcher
     unsigned long long knnf_last[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0};   // lgr_match_knn_last: the last k-nearest call of THIS context
     double knnf_worst = -1;                     // lgr_match_knn_last_check
+    int densef_mode = -1, densef_check = 0;     // lgr_ctx_set_dense_filter: how 135 / 352-float rows are swept by the one-match matcher
+    unsigned long long densef_last[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0};   // lgr_match_dense_last: the last one-match call of THIS context on long rows
+    double densef_worst = -1;                   // lgr_match_dense_last_check
     bool internal = false;                      // an aux / aux2 context: works inside its owner's turn (lgr_turn)
     int turn_depth = 0;                         // public entry points call each other: only the outermost one takes the device's turn
     unsigned long long turn_id = 0;             // identity for the turn hand-over (never reused, unlike the address)
@@ -146,6 +149,10 @@ enum {
     // values, widened bounds, candidate counts and lists, fallback list and flags, counters, the fallback rows and their results
     WS_KNNF_OPS_A, WS_KNNF_OPS_B, WS_KNNF_MISC_A, WS_KNNF_MISC_B, WS_KNNF_IRR_A, WS_KNNF_IRR_B, WS_KNNF_PART, WS_KNNF_UW, WS_KNNF_CNT, WS_KNNF_CAND,
     WS_KNNF_FB, WS_KNNF_ISFB, WS_KNNF_DEV, WS_KNNF_FBROWS, WS_KNNF_FBIDX, WS_KNNF_FBDIST, WS_KNNF_CENTRE,
+    // lgr_match_dense_mfma.cuh: the centre and scale; per side the [h1 | h2] operands, norms / norm bounds / tile bounds, irregular rows; per
+    // direction the upper bounds, candidate counts and lists, fallback list and flags, counters, the fallback rows and their results
+    WS_DENSEF_OPS_A, WS_DENSEF_OPS_B, WS_DENSEF_MISC_A, WS_DENSEF_MISC_B, WS_DENSEF_IRR_A, WS_DENSEF_IRR_B, WS_DENSEF_U, WS_DENSEF_CNT, WS_DENSEF_CAND,
+    WS_DENSEF_FB, WS_DENSEF_ISFB, WS_DENSEF_DEV, WS_DENSEF_FBROWS, WS_DENSEF_FBIDX, WS_DENSEF_FBDIST, WS_DENSEF_CENTRE,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 192, "grow lgr_ctx::ws");
@@ -279,7 +286,8 @@ int lgr_vote_matches_core(lgr_ctx* ctx, const int32_t* d_cand_idx, const float* 
 int lgr_match_ratio_core(lgr_ctx* ctx, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, float threshold,
                          int32_t* d_idx, float* d_dist);
 int lgr_ratio_test_core(lgr_ctx* ctx, const int32_t* d_knn_idx, const float* d_knn_dist, int mq, int k, float threshold, int32_t* d_idx, float* d_dist);
-// lgr_match_dense.hip: the exact dense matcher of the long descriptors, row_len 352 (SHOT) or 135 (RoPS), else LGR_ERR_UNSUPPORTED
+// lgr_match_dense.hip: the dense matcher of the long descriptors (exact scan, or the filter of lgr_ctx_set_dense_filter: the same bytes),
+// row_len 352 (SHOT) or 135 (RoPS), else LGR_ERR_UNSUPPORTED
 int lgr_match_dense(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block,
                     int32_t* ab_i, float* ab_d, int32_t* ba_i /* NULL: one direction */, float* ba_d);
 // ---- the refit over flagged pairs, device-resident (lgr_ransac.hip; lgr_refine.hip's step) ----

@@ -1,10 +1,12 @@
-// lgr_match_dense.hip -- the exact dense brute-force matcher of the long descriptors (SHOT352, RoPS135).
+// lgr_match_dense.hip -- the dense brute-force matcher of the long descriptors (SHOT352, RoPS135): the exact scan that defines the result,
+// and behind lgr_ctx_set_dense_filter the MFMA filter of lgr_match_dense_mfma.cuh, which returns the same bytes.
 //
 //   include/matching.h matchBF<SHOT> on M x 352 rows                               -> lgr_match_shot*, lgr_match2_shot_dev
 //   include/matching.h matchBF<RoPS135> on M x 135 rows                            -> lgr_match_rops*, lgr_match2_rops_dev
 // Every (query, train) pair is evaluated with OpenCV's own float sequence, so the result is the reference's bit for bit and does not
 // depend on scheduling.  The 33-d FPFH matcher is lgr_match.hip.
 #include <cfloat>
+#include <algorithm>
 
 #include "lgr_host.h"
 #include "lgr_match_dense.cuh"
@@ -69,17 +71,11 @@ __global__ void dense_match_decode(const unsigned long long* __restrict__ keys, 
     dist[i] = __uint_as_float((unsigned) (k >> 32));
 }
 
+// the exact scan on non-empty sides (ba_i == NULL: one direction): pack, one pass over the pair distances, decode
 template <int NB, int TAIL>
-int dense_match(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
+int dense_exact(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
     constexpr int LEN = 16 * NB + TAIL;
-    LGR_CHECK(ctx, (d_a || ma == 0) && (d_b || mb == 0) && ma >= 0 && mb >= 0 && block > 0 && (ab_i || ma == 0) && (ab_d || ma == 0), LGR_ERR_INVALID_ARG);
-    LGR_HIP(ctx, hipSetDevice(ctx->device));
     const bool both = ba_i != nullptr;
-    if (ma == 0 || mb == 0) {
-        if (ma) { LGR_HIP(ctx, hipMemsetAsync(ab_i, 0xff, (size_t) ma * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(ab_d, 0, (size_t) ma * 4, ctx->stream)); }
-        if (mb && both) { LGR_HIP(ctx, hipMemsetAsync(ba_i, 0xff, (size_t) mb * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(ba_d, 0, (size_t) mb * 4, ctx->stream)); }
-        return LGR_OK;
-    }
     const int mpa = cdiv(ma, MT) * MT, mpb = cdiv(mb, MT) * MT;
     float *pa, *pb;
     unsigned long long* keys;
@@ -96,6 +92,38 @@ int dense_match(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb
     dense_match_decode<<<cdiv(ma, 256), 256, 0, ctx->stream>>>(keys, ma, block, nb_b, ab_i, ab_d);
     if (both) dense_match_decode<<<cdiv(mb, 256), 256, 0, ctx->stream>>>(keys + mpa, mb, block, nb_a, ba_i, ba_d);
     LGR_HIP(ctx, hipGetLastError());
+    return LGR_OK;
+}
+
+}  // namespace
+
+#include "lgr_match_dense_mfma.cuh"
+
+namespace {
+
+// lgr_ctx_set_dense_filter: the filtered path, or the exact scan with the reason in densef_last[7]
+template <int NB, int TAIL>
+int dense_match(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d) {
+    const unsigned long long fresh[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0};
+    memcpy(ctx->densef_last, fresh, sizeof fresh);
+    ctx->densef_worst = -1;
+    LGR_CHECK(ctx, (d_a || ma == 0) && (d_b || mb == 0) && ma >= 0 && mb >= 0 && block > 0 && (ab_i || ma == 0) && (ab_d || ma == 0), LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    const bool both = ba_i != nullptr;
+    const bool want = ctx->densef_mode == 1 || (ctx->densef_mode == -1 && (long long) ma * mb >= DENSEF_AUTO_MIN_PAIRS);
+    if (ma == 0 || mb == 0) {
+        if (want) ctx->densef_last[7] = DENSEF_REASON_EMPTY;
+        if (ma) { LGR_HIP(ctx, hipMemsetAsync(ab_i, 0xff, (size_t) ma * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(ab_d, 0, (size_t) ma * 4, ctx->stream)); }
+        if (mb && both) { LGR_HIP(ctx, hipMemsetAsync(ba_i, 0xff, (size_t) mb * 4, ctx->stream)); LGR_HIP(ctx, hipMemsetAsync(ba_d, 0, (size_t) mb * 4, ctx->stream)); }
+        return LGR_OK;
+    }
+    if (want) {
+        bool done = false;
+        LGR_TRY((densef_match<NB, TAIL>(ctx, d_a, ma, d_b, mb, block, ab_i, ab_d, ba_i, ba_d, &done)));
+        if (done) return LGR_OK;
+    }
+    LGR_TRY((dense_exact<NB, TAIL>(ctx, d_a, ma, d_b, mb, block, ab_i, ab_d, ba_i, ba_d)));
+    ctx->densef_last[1] = (unsigned long long) ma * mb; ctx->densef_last[3] = (unsigned long long) ma + (both ? mb : 0);
     return LGR_OK;
 }
 
@@ -134,6 +162,37 @@ int lgr_match_dense(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const f
     if (row_len == 352) return dense_match<22, 0>(ctx, d_a, ma, d_b, mb, block, ab_i, ab_d, ba_i, ba_d);
     if (row_len == 135) return dense_match<8, 7>(ctx, d_a, ma, d_b, mb, block, ab_i, ab_d, ba_i, ba_d);
     return lgr_fail(ctx, LGR_ERR_UNSUPPORTED, "row_len == 352 || row_len == 135", __FILE__, __LINE__);
+}
+
+static void densef_propagate(lgr_ctx* ctx, int mode, int self_check) {
+    ctx->densef_mode = mode; ctx->densef_check = self_check;
+    if (ctx->aux) densef_propagate(ctx->aux, mode, self_check);
+    if (ctx->aux2) densef_propagate(ctx->aux2, mode, self_check);
+}
+
+extern "C" int lgr_ctx_set_dense_filter(lgr_ctx* ctx, int mode, int self_check) {
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, mode >= -1 && mode <= 1 && (self_check == 0 || self_check == 1), LGR_ERR_INVALID_ARG);
+    densef_propagate(ctx, mode, self_check);
+    return LGR_OK;
+}
+
+extern "C" int lgr_ctx_get_dense_filter(lgr_ctx* ctx, int* mode, int* self_check) {
+    if (!ctx || !mode || !self_check) return LGR_ERR_INVALID_ARG;
+    *mode = ctx->densef_mode; *self_check = ctx->densef_check;
+    return LGR_OK;
+}
+
+extern "C" int lgr_match_dense_last(lgr_ctx* ctx, unsigned long long* out8) {
+    if (!ctx || !out8) return LGR_ERR_INVALID_ARG;
+    memcpy(out8, ctx->densef_last, sizeof ctx->densef_last);
+    return LGR_OK;
+}
+
+extern "C" int lgr_match_dense_last_check(lgr_ctx* ctx, double* worst_ratio) {
+    if (!ctx || !worst_ratio) return LGR_ERR_INVALID_ARG;
+    *worst_ratio = ctx->densef_worst;
+    return LGR_OK;
 }
 
 extern "C" int lgr_match_shot_dev(lgr_ctx* ctx, const float* d_q, int mq, const float* d_t, int mt, int block, int32_t* d_idx, float* d_dist) {

@@ -868,6 +868,29 @@ class Context:
         self.check(_lib.lgr_match_knn_last_check(self.h, C.byref(out)))
         return out.value
 
+    # ---- how 135 / 352-float rows are swept by the one-match matcher (never what it returns) ---------------------------------------------
+    def set_dense_filter(self, mode=-1, self_check=0):
+        """mode -1 auto (filtered from the crossover size), 0 exact scan, 1 filtered at any size; self_check 0 / 1 (test sizes)"""
+        self.check(_lib.lgr_ctx_set_dense_filter(self.h, int(mode), int(self_check)))
+
+    def dense_filter(self):
+        """(mode, self_check) now in force"""
+        m, c = C.c_int(0), C.c_int(0)
+        self.check(_lib.lgr_ctx_get_dense_filter(self.h, C.byref(m), C.byref(c)))
+        return m.value, c.value
+
+    def match_dense_last(self):
+        """the eight counters of lgr_match_dense_last for the last one-match call on 135 / 352-float rows ([6]: -1 when the self-check did not run)"""
+        out = (C.c_ulonglong * 8)()
+        self.check(_lib.lgr_match_dense_last(self.h, out))
+        return [-1 if v == 0xFFFFFFFFFFFFFFFF else int(v) for v in out]
+
+    def match_dense_last_check(self):
+        """worst |filtered - canonical d2| / bound over the pairs the self-check of the last one-match call on long rows covered, or -1"""
+        out = C.c_double(-1)
+        self.check(_lib.lgr_match_dense_last_check(self.h, C.byref(out)))
+        return out.value
+
     def match_knn_host(self, q, t, block=10000, k=2):
         q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
         idx = np.zeros((q.shape[0], max(int(k), 0)), np.int32); dist = np.zeros((q.shape[0], max(int(k), 0)), np.float32)

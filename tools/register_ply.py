@@ -101,6 +101,8 @@ def main():
                     help="point numbering after the loader: (iz,iy,ix) voxel order, or the reference's hash-container order")
     ap.add_argument("--knn-filter", default="auto", choices=["auto", "on", "off"],
                     help="how --randomness > 1 / --matching ratio sweep FPFH rows (never what they return): the MFMA filter from the crossover size, always, never")
+    ap.add_argument("--dense-filter", default="auto", choices=["auto", "on", "off"],
+                    help="how SHOT / RoPS rows are matched at --randomness 1 (never what is returned): the MFMA filter from the crossover size, always, never")
     a = ap.parse_args()
     if a.measure and not a.ground_truth:
         ap.error("--measure needs --ground-truth")
@@ -128,6 +130,7 @@ def main():
     from lgr_amd import capi, formats, profile
     ctx = capi.Context(0)
     ctx.set_knn_filter({"auto": -1, "on": 1, "off": 0}[a.knn_filter])
+    ctx.set_dense_filter({"auto": -1, "on": 1, "off": 0}[a.dense_filter])
     t = time.perf_counter()
     # loadPointClouds: duplicates, 2 x density voxel grid, normals
     ld = profile.load_pair(ctx, a.source, a.target, order=capi.ORDER_REFERENCE if a.order == "reference" else capi.ORDER_CANONICAL)
