@@ -105,27 +105,49 @@ __device__ __forceinline__ void lgr_knn_scan(const GridDev& g, int b, int e, flo
     }
 }
 
+// The ring centre of lgr_knn_query along one axis: lgr_cellc's float expression, held to +-LGR_RING_CELL_MAX before the cast.  An axis has
+// fewer than 2^28 cells (the cell cap, lgr_grid_rule.h), so the last ring is below 2^29 + 2^28 and centre +- ring stays inside int for
+// every finite query (the quotient may be +-inf: the clamp takes that too).  A query in or near the box is far below the bound and keeps
+// its own cell.  A centre that the clamp moved lies between the query's true cell and the grid along that axis, so every grid cell is at
+// most as many cells from it as from the true cell: a cell the walk has not reached after ring s is MORE than s cells from the query's own
+// cell as well, and s h only underestimates the separation the termination rule needs.  The rule stays conservative (it stops later, never
+// earlier), and since the list is the minimum under a total order, the result is the brute-force one either way.
+constexpr float LGR_RING_CELL_MAX = 536870912.f;   // 2^29
+__device__ __forceinline__ int lgr_ring_cellc(float v, float o, float h) {
+    return (int) fminf(fmaxf(floorf((v - o) / h), -LGR_RING_CELL_MAX), LGR_RING_CELL_MAX);
+}
+
 // exact k-NN of (qx,qy,qz) in grid g: ring search with the same termination rule as the oracle
 // (after ring s every point closer than s*h has been seen).
+// Only cells that exist are walked.  The first ring is the Chebyshev gap between the centre and the grid's box of cells (0 for a query
+// inside it): no earlier ring holds a cell, so the list is empty until then and no earlier ring could have ended the search.  From that
+// ring on each of the three clamped ranges is non-empty, and a ring costs its in-grid cells: the z faces are whole rows; a z between them
+// has the two y edge rows (whole x runs) and, between those, only the two x end cells of a row -- rows whose end cells both lie outside
+// the grid are jumped over, and so is the whole stretch of z between the faces when it has neither.  Work per query: the in-grid cells of
+// the rings walked (each row visited holds at least one) plus a constant per ring, wherever the query lies.
 template <int BLOCK>
 __device__ __forceinline__ void lgr_knn_query(const GridDev& g, float qx, float qy, float qz, KnnList<BLOCK>& L) {
-    int c0x = lgr_cellc(qx, g.ox, g.h), c0y = lgr_cellc(qy, g.oy, g.h), c0z = lgr_cellc(qz, g.oz, g.h);
-    int maxring = max(max(max(c0x, g.dx - 1 - c0x), max(c0y, g.dy - 1 - c0y)), max(max(c0z, g.dz - 1 - c0z), 0));
-    for (int s = 0;; ++s) {
-        for (int z = c0z - s; z <= c0z + s; ++z) {
-            if (z < 0 || z >= g.dz) continue;
-            for (int y = c0y - s; y <= c0y + s; ++y) {
-                if (y < 0 || y >= g.dy) continue;
-                bool edge = (z == c0z - s) || (z == c0z + s) || (y == c0y - s) || (y == c0y + s);
+    const int c0x = lgr_ring_cellc(qx, g.ox, g.h), c0y = lgr_ring_cellc(qy, g.oy, g.h), c0z = lgr_ring_cellc(qz, g.oz, g.h);
+    const int maxring = max(max(max(c0x, g.dx - 1 - c0x), max(c0y, g.dy - 1 - c0y)), max(max(c0z, g.dz - 1 - c0z), 0));
+    const int s0 = max(max(max(-c0x, c0x - (g.dx - 1)), max(-c0y, c0y - (g.dy - 1))), max(max(-c0z, c0z - (g.dz - 1)), 0));
+    for (int s = s0;; ++s) {
+        const int zl = c0z - s, zr = c0z + s, yl = c0y - s, yr = c0y + s, xl = c0x - s, xr = c0x + s;
+        const int z0 = max(zl, 0), z1 = min(zr, g.dz - 1), y0 = max(yl, 0), y1 = min(yr, g.dy - 1), x0 = max(xl, 0), x1 = min(xr, g.dx - 1);
+        const bool x_ends = xl >= 0 || xr < g.dx, y_edges = yl >= 0 || yr < g.dy;   // (s >= s0: xl <= dx - 1 and xr >= 0, y alike)
+        for (int z = z0; z <= z1; ++z) {
+            const bool face = (z == zl) || (z == zr);
+            if (!face && !x_ends && !y_edges) { z = min(z1, zr - 1); continue; }   // nothing between the faces: on to zr, or out
+            for (int y = y0; y <= y1; ++y) {
+                const bool edge = face || (y == yl) || (y == yr);
+                if (!edge && !x_ends) { y = min(y1, yr - 1); continue; }            // no end cell in the grid: on to the yr edge, or out
                 const size_t row = ((size_t) z * g.dy + y) * g.dx;
-                if (edge || s == 0) {
+                if (edge) {
                     // the whole x run of this (z, y) row belongs to the shell: its cells are contiguous in memory
-                    int x0 = max(c0x - s, 0), x1 = min(c0x + s, g.dx - 1);
-                    if (x0 > x1) continue;
                     int b = g.cell_start[row + x0], e = g.cell_start[row + x1 + 1];
                     lgr_knn_scan(g, b, e, qx, qy, qz, L);
                 } else {
-                    for (int x = c0x - s; x <= c0x + s; x += 2 * s) {   // the two end cells of an interior row
+                    for (int end = 0; end < 2; ++end) {   // the two end cells of an interior row (s > 0 here: they differ)
+                        const int x = end ? xr : xl;
                         if (x < 0 || x >= g.dx) continue;
                         int b = g.cell_start[row + x], e = g.cell_start[row + x + 1];
                         lgr_knn_scan(g, b, e, qx, qy, qz, L);
@@ -186,8 +208,9 @@ __device__ __forceinline__ int nearest_within(const GridDev& g, float px, float 
 }
 
 // ---- exact nearest neighbour whose cost does not depend on where the query lies (lgr_debug.hip) ----
-// lgr_knn_query centres its rings on the query's own cell: right for a query inside the cloud, cubic in the separation (and an
-// out-of-range cell index) for one far outside it.  Here the search descends the grid itself.  cell_start is an exclusive prefix sum over
+// lgr_knn_query centres its rings on the query's own cell and walks the cells of each ring that lie in the grid: bounded wherever the
+// query is, but a query outside the cloud still pays for every in-grid cell of the rings between the first that touches the grid and the
+// one that ends the search, empty cells included.  Here the search descends the grid itself.  cell_start is an exclusive prefix sum over
 // the cells in (z, y, x) order, so the points of ANY contiguous cell range [lo, hi) are the contiguous sorted positions
 // [cell_start[lo], cell_start[hi]): two loads say how many points a node holds.  Nodes are such ranges of three kinds -- whole z-slabs
 // [z0, z1), rows [y0, y1) of one slab, cells [x0, x1) of one row -- each an axis-aligned box of cells.  A node is halved along its axis

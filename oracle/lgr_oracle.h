@@ -137,6 +137,9 @@ void orc_inverse4(const float* m16, float* out16);
 
 /* exact k-NN in 3-D, sorted by (d2, index); idx/d2 are n*k. Used by several stages and by tests. */
 int orc_knn(const float* qpts, int nq, const float* pts, int n, int k, int* idx, float* d2);
+/* the same lists with the cost of each query's ring walk: visits [nq][3] = iterations of the z and y loops, cells examined, rings walked;
+ * grid7 (may be NULL) = the cell, origin[3] and dim[3] of the grid searched */
+int orc_knn_visits(const float* qpts, int nq, const float* pts, int n, int k, int* idx, float* d2, long long* visits, float* grid7);
 
 /* src/common.cpp:531-547 */
 int orc_smoothed_densities(const float* pts, int n, int k, float* out);

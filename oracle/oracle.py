@@ -306,10 +306,18 @@ def inverse4(T):
     return np.array(out, np.float32).reshape(4, 4).T.copy()
 
 
-def knn(qpts, pts, k):
+def knn(qpts, pts, k, visits=False):
+    """visits=True: also the cost of each query's ring walk, int64 [nq, 3] = (iterations of the z and y loops, cells examined, rings
+    walked), and the grid searched as (h, origin[3], dim[3])"""
     qpts, pts = _pts(qpts), _pts(pts)
     idx = np.zeros((qpts.shape[0], k), np.int32)
     d2 = np.zeros((qpts.shape[0], k), np.float32)
+    if visits:
+        v = np.zeros((qpts.shape[0], 3), np.int64)
+        g = np.zeros(7, np.float32)
+        rc = lib().orc_knn_visits(_p(qpts), qpts.shape[0], _p(pts), pts.shape[0], k, _p(idx), _p(d2), _p(v), _p(g))
+        assert rc == 0
+        return idx, d2, v, (g[0], g[1:4].copy(), g[4:7].astype(np.int64))
     rc = lib().orc_knn(_p(qpts), qpts.shape[0], _p(pts), pts.shape[0], k, _p(idx), _p(d2))
     assert rc == 0
     return idx, d2

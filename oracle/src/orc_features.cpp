@@ -150,6 +150,26 @@ extern "C" int orc_knn(const float* qpts, int nq, const float* pts, int n, int k
     return 0;
 }
 
+// orc_knn with the cost of each query's walk: visits [nq][3] = loop iterations over z and y, cells examined, rings walked (Grid::knn);
+// grid7 (optional) = the grid the search ran on: h, origin[3], dim[3]
+extern "C" int orc_knn_visits(const float* qpts, int nq, const float* pts, int n, int k, int* idx, float* d2, long long* visits, float* grid7) {
+    Grid g;
+    g.build(pts, n, auto_cell(pts, n, 4.f));
+    if (grid7) {
+        grid7[0] = g.h;
+        for (int a = 0; a < 3; ++a) { grid7[1 + a] = g.origin[a]; grid7[4 + a] = (float) g.dim[a]; }
+    }
+    std::vector<Grid::Cand> c(k);
+    for (int i = 0; i < nq; ++i) {
+        int f = g.knn(qpts + 12 * (size_t) i, k, c.data(), visits + 3 * (size_t) i);
+        for (int j = 0; j < k; ++j) {
+            idx[(size_t) i * k + j] = j < f ? c[j].idx : -1;
+            d2[(size_t) i * k + j] = j < f ? c[j].d2 : INFINITY;
+        }
+    }
+    return 0;
+}
+
 // src/common.cpp:644-655 estimateNormalsPoints + :593-628 postprocessNormals, around pcl::NormalEstimationOMP with
 // setKSearch(k) [3P, PCL 1.12.1 features/impl/normal_3d_omp.hpp + common/impl/centroid.hpp]:
 //   neighbours = k nearest in the surface, sorted by (d2, index);

@@ -91,42 +91,75 @@ struct Grid {
     struct Cand { float d2; int idx; };
     static inline bool cand_less(const Cand& a, const Cand& b) { return a.d2 < b.d2 || (a.d2 == b.d2 && a.idx < b.idx); }
 
-    // exact k nearest by (d2, idx); out sorted ascending; returns count found (<= k)
-    int knn(const float* q, int k, Cand* out) const {
+    // The ring centre of knn along axis a: cellc's float expression, held to +-RING_CELL_MAX = 2^29 before the cast (the same float ops as
+    // lgr_ring_cellc on the device).  An axis has fewer than 2^28 cells, so centre +- ring stays inside int for every finite query.  A centre
+    // that the clamp moved lies between the query's true cell and the grid, so a cell not reached after ring s is more than s cells from the
+    // true cell too: s h only underestimates the separation, and the termination rule stays conservative.
+    static constexpr float RING_CELL_MAX = 536870912.f;
+    inline int ring_cellc(float v, int a) const {
+        return (int) std::fmin(std::fmax(std::floor((v - origin[a]) / h), -RING_CELL_MAX), RING_CELL_MAX);
+    }
+
+    // exact k nearest by (d2, idx); out sorted ascending; returns count found (<= k).
+    // Only cells that exist are walked, from the first ring that can touch the grid (the Chebyshev gap between the centre and the grid's
+    // box of cells) on; rows whose two end cells lie outside the grid are jumped over -- the walk of lgr_knn_query, loop for loop.
+    // visits (optional, [3]): the iterations of the z and y loops (the jumps included), the cells examined, the rings walked.
+    int knn(const float* q, int k, Cand* out, long long* visits = nullptr) const {
         std::vector<Cand> heap;  // max-heap on cand_less
         heap.reserve(k + 1);
+        long long n_iter = 0, n_cells = 0, n_rings = 0;
+        if (visits) visits[0] = visits[1] = visits[2] = 0;
         if (!finite3(q)) return 0;
-        int c0[3] = {cellc(q[0], 0), cellc(q[1], 1), cellc(q[2], 2)};
-        int maxring = 0;
-        for (int a = 0; a < 3; ++a) maxring = std::max(maxring, std::max(c0[a], dim[a] - 1 - c0[a]));
+        const int c0[3] = {ring_cellc(q[0], 0), ring_cellc(q[1], 1), ring_cellc(q[2], 2)};
+        int maxring = 0, s0 = 0;
+        for (int a = 0; a < 3; ++a) {
+            maxring = std::max(maxring, std::max(c0[a], dim[a] - 1 - c0[a]));
+            s0 = std::max(s0, std::max(-c0[a], c0[a] - (dim[a] - 1)));
+        }
         maxring = std::max(maxring, 0);
-        for (int s = 0;; ++s) {
+        auto scan_cell = [&](size_t c) {
+            ++n_cells;
+            for (int t = cell_start[c]; t < cell_start[c + 1]; ++t) {
+                int i = order[t];
+                Cand cd{dist2(q, pts + 12 * (size_t) i), i};
+                if ((int) heap.size() < k) {
+                    heap.push_back(cd);
+                    std::push_heap(heap.begin(), heap.end(), cand_less);
+                } else if (cand_less(cd, heap.front())) {
+                    std::pop_heap(heap.begin(), heap.end(), cand_less);
+                    heap.back() = cd;
+                    std::push_heap(heap.begin(), heap.end(), cand_less);
+                }
+            }
+        };
+        for (int s = s0;; ++s) {
             // scan shell at Chebyshev distance s
-            for (int z = c0[2] - s; z <= c0[2] + s; ++z) {
-                if (z < 0 || z >= dim[2]) continue;
-                for (int y = c0[1] - s; y <= c0[1] + s; ++y) {
-                    if (y < 0 || y >= dim[1]) continue;
-                    bool edge_zy = (z == c0[2] - s || z == c0[2] + s || y == c0[1] - s || y == c0[1] + s);
-                    int step = edge_zy ? 1 : 2 * s;
-                    if (step == 0) step = 1;
-                    for (int x = c0[0] - s; x <= c0[0] + s; x += step) {
-                        if (x < 0 || x >= dim[0]) continue;
-                        size_t c = ((size_t) z * dim[1] + y) * dim[0] + x;
-                        for (int t = cell_start[c]; t < cell_start[c + 1]; ++t) {
-                            int i = order[t];
-                            Cand cd{dist2(q, pts + 12 * (size_t) i), i};
-                            if ((int) heap.size() < k) {
-                                heap.push_back(cd);
-                                std::push_heap(heap.begin(), heap.end(), cand_less);
-                            } else if (cand_less(cd, heap.front())) {
-                                std::pop_heap(heap.begin(), heap.end(), cand_less);
-                                heap.back() = cd;
-                                std::push_heap(heap.begin(), heap.end(), cand_less);
-                            }
+            ++n_rings;
+            const int zl = c0[2] - s, zr = c0[2] + s, yl = c0[1] - s, yr = c0[1] + s, xl = c0[0] - s, xr = c0[0] + s;
+            const int z0 = std::max(zl, 0), z1 = std::min(zr, dim[2] - 1), y0 = std::max(yl, 0), y1 = std::min(yr, dim[1] - 1);
+            const int x0 = std::max(xl, 0), x1 = std::min(xr, dim[0] - 1);
+            const bool x_ends = xl >= 0 || xr < dim[0], y_edges = yl >= 0 || yr < dim[1];
+            for (int z = z0; z <= z1; ++z) {
+                ++n_iter;
+                const bool face = (z == zl) || (z == zr);
+                if (!face && !x_ends && !y_edges) { z = std::min(z1, zr - 1); continue; }
+                for (int y = y0; y <= y1; ++y) {
+                    ++n_iter;
+                    const bool edge = face || (y == yl) || (y == yr);
+                    if (!edge && !x_ends) { y = std::min(y1, yr - 1); continue; }
+                    const size_t row = ((size_t) z * dim[1] + y) * dim[0];
+                    if (edge) {
+                        for (int x = x0; x <= x1; ++x) scan_cell(row + x);
+                    } else {
+                        for (int end = 0; end < 2; ++end) {
+                            const int x = end ? xr : xl;
+                            if (x < 0 || x >= dim[0]) continue;
+                            scan_cell(row + x);
                         }
                     }
                 }
             }
+            if (visits) { visits[0] = n_iter; visits[1] = n_cells; visits[2] = n_rings; }
             if (s >= maxring) break;
             if ((int) heap.size() == k) {
                 float lim = (float) s * h * 0.999f;

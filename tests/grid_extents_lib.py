@@ -153,3 +153,124 @@ def knn_numpy(q, pts, k):
     d2 = d2_f32(q, pts)
     order = np.lexsort((np.broadcast_to(np.arange(d2.shape[1]), d2.shape), d2), axis=1)[:, :k]
     return order.astype(np.int32), np.take_along_axis(d2, order, 1)
+
+
+# ---- ring searches outside the cloud's box and on tiny clouds (the knn walk of orc_grid.h / lgr_grid.cuh) ------------------------------
+RING_CELL_MAX = 1 << 29        # the walk's centre is held to +-2^29 cells (lgr_ring_cellc / orc::Grid::ring_cellc)
+FAR_DISTANCES = (0.1, 1.0, 100.0, 1e5)
+
+
+def knn_padded(q, pts, k):
+    """knn_numpy with the slots a list cannot fill (k > n): index -1, d2 +inf"""
+    idx, d2 = knn_numpy(q, pts, k)
+    pad = k - idx.shape[1]
+    if pad > 0:
+        idx = np.concatenate([idx, np.full((len(idx), pad), -1, np.int32)], 1)
+        d2 = np.concatenate([d2, np.full((len(d2), pad), np.inf, F)], 1)
+    return idx, d2
+
+
+def auto_cell(xyz, target, device=False):
+    """the automatic cell of the k-NN grids restated in float32: sqrt(area * target / n) with area = the product of the two longest extents
+    (at least 1e-12), at least 1/1024 of the longest extent and 1e-6.  orc::auto_cell (oracle) answers 1 for fewer than two points;
+    lgr_grid_build (device=True) has no such case and arrives at sqrt(1e-12 * target)."""
+    xyz = np.asarray(xyz, F)[:, :3]
+    n = len(xyz)
+    if n < 2 and not device:
+        return F(1)
+    e = np.sort((xyz.max(0) - xyz.min(0)).astype(F))
+    area = max(F(e[2] * e[1]), F(1e-12))
+    h = np.sqrt(F(F(area * F(target)) / F(max(n, 1))))
+    return max(F(h), max(F(e[2] / F(1024)), F(1e-6)))
+
+
+def grid_of(xyz, target, device=False):
+    """(h, origin, dims) of the k-NN grid over xyz: the automatic cell, then the rule of DESIGN.md section 4"""
+    xyz = np.asarray(xyz, F)[:, :3]
+    h, d, _ = rule(xyz, auto_cell(xyz, target, device))
+    return h, xyz.min(0), d
+
+
+def outside_queries(b):
+    """80 queries on and outside the box of b: for each of the 26 sign directions of {-1, 0, 1}^3 the box centre plus the direction times
+    (half extent + delta), delta = 1e-4, 0.05 and 0.3 of the largest extent; then the box's min and max corners themselves"""
+    mn, mx = b[:, :3].min(0).astype(np.float64), b[:, :3].max(0).astype(np.float64)
+    c, half, ext = (mn + mx) / 2, (mx - mn) / 2, (mx - mn).max()
+    dirs = [np.array((i, j, k), np.float64) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1) if (i, j, k) != (0, 0, 0)]
+    q = [point(c + d * (half + delta * ext)) for d in dirs for delta in (1e-4, 0.05, 0.3)]
+    q += [point(b[:, :3].min(0)), point(b[:, :3].max(0))]
+    return np.stack(q).astype(F)
+
+
+def tiny_clouds():
+    """name -> n x 12: one point, two coincident, two distinct, three collinear along x, five coplanar, 70 coincident plus one other"""
+    p = (0.3, -0.2, 0.5)
+    return dict(
+        one=np.stack([point(p)]),
+        two_same=np.stack([point(p), point(p)]),
+        two=np.stack([point(p), point((0.31, -0.18, 0.505))]),
+        line3=np.stack([point((0.1, 0.2, 0.3)), point((0.6, 0.2, 0.3)), point((1.4, 0.2, 0.3))]),
+        plane5=np.stack([point((x, y, 0.25)) for x, y in ((0, 0), (1, 0), (0, 1), (1, 1), (0.4, 0.7))]),
+        same70=np.stack([point(p)] * 70 + [point((0.35, -0.1, 0.52))]),
+    )
+
+
+def tiny_queries(cloud, h):
+    """the cloud's own points, then its first and last point displaced along one, two and three axes, both ways, by 3 and by 200 cells h"""
+    q = [cloud]
+    for p in (cloud[0], cloud[-1]):
+        for m in (3, 200):
+            for axes in ((1, 0, 0), (1, 1, 0), (1, 1, 1), (0, 0, 1)):
+                for sign in (1, -1):
+                    q.append(point(p[:3].astype(np.float64) + sign * m * float(h) * np.array(axes, np.float64))[None])
+    return np.concatenate(q).astype(F)
+
+
+def far_queries(cloud):
+    """the cloud's first point displaced by 0.1, 1, 100 and 1e5 along all three axes at once (both ways) and along each axis alone; at the
+    one-point cloud's cell 1e5 is more than 2^31 cells"""
+    p = cloud[0, :3].astype(np.float64)
+    q = []
+    for d in FAR_DISTANCES:
+        for v in ((1, 1, 1), (-1, -1, -1), (1, 0, 0), (0, -1, 0), (0, 0, 1)):
+            q.append(point(p + d * np.array(v, np.float64)))
+    return np.stack(q).astype(F)
+
+
+def ring_walk(q, pts, k, h, origin, dims):
+    """What the ring walk may cost, from the grid and the query's cell alone.  Per query (first ring, last ring, in-grid cells of those rings):
+      centre c = clip(floor(fl(fl(q - o) / h)), +-2^29) per axis                       (the walk's own float expression)
+      first  = max over the axes of max(-c, c - (d - 1), 0)                             (Chebyshev gap between the centre and the cell box)
+      last   = the first ring s >= first after which k candidates are held and the k-th d2 <= fl(fl(fl(s) h) 0.999)^2, at most
+               max over the axes of max(c, d - 1 - c)                                   (the termination rule, restated)
+      cells  = B(last) - B(first - 1),  B(s) = prod over the axes of |[c - s, c + s] & [0, d - 1]|
+    A point is held after ring s when its (clamped) cell is at most s cells from c along every axis."""
+    q, pts = np.asarray(q, F)[:, :3], np.asarray(pts, F)[:, :3]
+    h, origin = F(h), np.asarray(origin, F)
+    d = [int(x) for x in dims]
+    pc = np.clip(np.floor((pts - origin) / h), 0, np.array(d, np.float64) - 1).astype(np.int64)
+    cq = np.clip(np.floor((q - origin) / h), -RING_CELL_MAX, RING_CELL_MAX).astype(np.int64)
+    d2 = d2_f32(q, pts)
+    out = []
+    for i in range(len(q)):
+        c = [int(x) for x in cq[i]]
+        first = max(max(-c[a], c[a] - (d[a] - 1), 0) for a in range(3))
+        maxring = max(max(c[a], d[a] - 1 - c[a]) for a in range(3))
+        last = maxring
+        if k <= len(pts):
+            ring = np.abs(pc - cq[i]).max(1)
+            for s in range(first, maxring):
+                held = d2[i][ring <= s]
+                if len(held) >= k:
+                    lim = F(F(F(s) * h) * F(0.999))
+                    if np.partition(held, k - 1)[k - 1] <= F(lim * lim):
+                        last = s
+                        break
+
+        def box(s):
+            n = 1
+            for a in range(3):
+                n *= max(min(c[a] + s, d[a] - 1) - max(c[a] - s, 0) + 1, 0)
+            return n
+        out.append((first, last, box(last) - (box(first - 1) if first > 0 else 0)))
+    return np.array(out, np.int64)

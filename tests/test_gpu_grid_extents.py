@@ -8,9 +8,12 @@ blob plus stray points that take the uniform grid to the cell cap, past it, and 
 3. no stray is anyone's neighbour, so every grid-independent result of a blob query equals the `room` result bit for bit.
 4. `thin`'s constructed pair -- within the radius, two cells apart at the cell the caller asked for -- is found.
 5. the ring searches (knn, normals_knn, smoothed_densities) against numpy's lexsort on (d2, index), k = 8 (heap kernel) and 40 (wave kernel),
-   on room, thin and flat ONLY, and with no query outside the cloud's box: lgr_knn_query walks rings from the query's own cell, cubic in
-   the separation (lgr_grid.cuh), so a stray that is far along three axes would cost one thread a walk of the order of 1e8 cells at
-   bench size.  That is a known cost, not the subject here, and a test that ran into a time limit would count as a hang.
+   on room, thin and flat, with queries that are points of the cloud.
+6. the ring searches away from there, k = 1, 2, 8 (heap kernel) and 16, 40 (wave kernel): queries on and outside the cloud's box (26
+   directions, three separations, the two corners), clouds of one to five points and of 70 coincident points plus one (k > n: the slots a
+   list cannot fill are -1 / +inf), and queries up to 1e5 -- more than 2^31 cells -- from a one-point cloud.  lgr_knn_query walks only the
+   cells of a ring that exist, from the first ring that touches the grid (lgr_grid.cuh), so none of these costs more than the grid's cells;
+   tests/test_oracle_grid_extents.py counts the visits of the same walk on the CPU.
 
 The module uses a context of its own: the cell tables of these scenes grow to about 1 GB, which the session's shared context should not
 carry into the other tests."""
@@ -261,3 +264,88 @@ def test_ring_searches_equal_numpy(ctx, oracle, world, name, r):
     got = ctx.normals_knn(cuda(cloud), 30).cpu().numpy()
     same(got, oracle.normals_knn(cloud, 30))
     assert np.isfinite(got[:n, 4:7]).all()
+
+
+# ---- 6. ring searches outside the box, on tiny clouds, far from them ---------------------------------------------------------------------
+RING_K = (1, 2, 8, 16, 40)                                            # below 16: knn_kernel (per-thread heaps); from 16: knn_wave_kernel
+TINY = ["one", "two_same", "two", "line3", "plane5", "same70"]
+
+
+def knn_target(k):
+    """points per cell lgr_knn_lists asks of the automatic cell: max(4, 0.35f k)"""
+    return max(F(4), F(F(0.35) * F(k)))
+
+
+def check_knn(ctx, q, cloud, k, want=None):
+    want_i, want_d = G.knn_padded(q, cloud, k) if want is None else (want[0][:, :k], want[1][:, :k])
+    idx, d2 = ctx.knn(cuda(q), cuda(cloud), k)
+    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
+    np.testing.assert_array_equal(bits(d2.cpu().numpy()), bits(want_d))
+    return want_i, want_d
+
+
+@pytest.fixture(scope="module")
+def outside(world):
+    """the 80 outside queries of the blob and their 40 nearest by numpy (a list of k is its first k columns: the order is total)"""
+    b = world["blob"]
+    q = G.outside_queries(b)
+    mn, mx = b[:, :3].min(0), b[:, :3].max(0)
+    assert len(q) == 80 and ((q[:78, :3] < mn) | (q[:78, :3] > mx)).any(1).all()
+    return dict(q=q, want=G.knn_padded(q, b, max(RING_K)))
+
+
+@pytest.mark.parametrize("k", RING_K)
+def test_knn_outside_the_box_equals_numpy(ctx, world, outside, k):
+    check_knn(ctx, outside["q"], world["blob"], k, outside["want"])
+
+
+@pytest.mark.parametrize("name", TINY)
+def test_knn_on_tiny_clouds_equals_numpy(ctx, name):
+    cloud = G.tiny_clouds()[name]
+    n = len(cloud)
+    for k in RING_K:
+        q = G.tiny_queries(cloud, G.auto_cell(cloud, knn_target(k), device=True))   # 3 and 200 cells of the cell this k searches on
+        want_i, want_d = check_knn(ctx, q, cloud, k)
+        assert (want_i[:, min(k, n):] == -1).all() and np.isinf(want_d[:, min(k, n):]).all()
+        if name == "same70":                                          # equal distances: the lower index first
+            np.testing.assert_array_equal(want_i[:70], np.tile(np.arange(k, dtype=np.int32), (70, 1)))
+
+
+@pytest.mark.parametrize("name", ["one", "two_same"])
+def test_knn_far_from_a_tiny_cloud_equals_numpy(ctx, name):
+    cloud = G.tiny_clouds()[name]
+    q = G.far_queries(cloud)
+    assert 1e5 / float(G.auto_cell(cloud, knn_target(40), device=True)) > 2.0 ** 31   # the coarsest cell any k here searches on
+    for k in RING_K:
+        _, want_d = check_knn(ctx, q, cloud, k)
+        assert np.isfinite(want_d[:, 0]).all()
+
+
+def test_normals_of_outside_queries_equal_the_oracle(ctx, oracle, world, outside):
+    b = world["blob"]
+    pts = np.concatenate([b[::40], outside["q"]])
+    want = oracle.normals_knn(pts, 30, surf=b)
+    same(ctx.normals_knn(cuda(pts.copy()), 30, surf=cuda(b)).cpu().numpy(), want)
+    assert np.isfinite(want[:, 4:7]).all()
+
+
+@pytest.mark.parametrize("name", ["one", "triangle"])
+def test_normals_on_a_tiny_surface_equal_the_oracle(ctx, oracle, name):
+    tiny = G.tiny_clouds()
+    surf = tiny["one"] if name == "one" else np.ascontiguousarray(tiny["plane5"][:3])
+    h = G.auto_cell(surf, 6.0, device=True)                           # lgr_normals_knn_dev: six points per cell under a given surface
+    pts = np.concatenate([G.tiny_queries(surf, h), G.far_queries(surf)])
+    for k in (3, 30):
+        want = oracle.normals_knn(pts, k, surf=surf)
+        same(ctx.normals_knn(cuda(pts.copy()), k, surf=cuda(surf)).cpu().numpy(), want)
+        assert np.isnan(want[:, 4:7]).all() if name == "one" else np.isfinite(want[:, 4:7]).all()
+
+
+@pytest.mark.parametrize("name", ["two_same", "two", "line3", "same70"])
+def test_smoothed_densities_of_tiny_clouds_equal_numpy(ctx, name):
+    cloud = G.tiny_clouds()[name]
+    d = cuda(cloud)
+    for k in [k for k in (2, 3, 8, 40) if k <= len(cloud)]:
+        want_i, want_d = G.knn_numpy(cloud, cloud, k)
+        dk = np.sqrt(want_d[:, k - 1])
+        np.testing.assert_array_equal(bits(ctx.smoothed_densities(d, k).cpu().numpy()), bits(np.minimum(dk, dk[want_i[:, 1]])))

@@ -243,13 +243,9 @@ ROWS = {}
 TWIN = {}
 
 
-# A cloud of ONE point gets the automatic grid cell's floor (1e-6), and lgr_knn_query walks rings of cells outwards from the query's own
-# cell: queries a scene's width away are some 1e5 cells off, the walk is cubic in that, and the call does not come back in minutes (the
-# comment above lgr_nearest_far in csrc/lgr_grid.cuh says as much).  That is the _dev path's behaviour, host form and twin alike; the
-# `one` case of such a count is left out of the row (not_one) rather than run.
-def row(name, counts, optional=True, twin=None, label=None, not_one=()):
+def row(name, counts, optional=True, twin=None, label=None):
     def deco(fn):
-        ROWS[label or name] = (name, fn, counts, optional, not_one)
+        ROWS[label or name] = (name, fn, counts, optional)
         if twin:
             TWIN[name] = twin
         return fn
@@ -279,7 +275,7 @@ def _(s, d):
            None if fp is None else C.addressof(fp), metric_params(s, d, ns, full), s.hout("res", res, skip=result_skip()))
 
 
-@row("lgr_measure", ("ns", "nt"), not_one=("nt",))
+@row("lgr_measure", ("ns", "nt"))
 def _(s, d):
     from lgr_amd import capi
     ps, ns, pt, nt = clouds(s, d)
@@ -316,7 +312,7 @@ def _(s, d):
            s.hout("n2", (C.c_int * 2)(-1, -1)), s.hout("overlap", C.c_float(-1)), s.hout("area", C.c_float(-1), opt))
 
 
-@row("lgr_normal_difference", ("ns", "nt"), optional=False, not_one=("nt",))
+@row("lgr_normal_difference", ("ns", "nt"), optional=False)
 def _(s, d):
     ps, ns, pt, nt = clouds(s, d)
     s.call("lgr_normal_difference", "pipipfpp", ps, ns, pt, nt, s.host(d.Tgt), THR, s.hout("diff", C.c_float(-1)), s.hout("n", C.c_int(-1)))
@@ -330,7 +326,7 @@ def _(s, d):
            s.out("correct", (cc,), np.uint8, opt), s.hout("n3", (C.c_int * 3)(-1, -1, -1)))
 
 
-@row("lgr_evaluate_gt_batch", ("ns", "nt", "c", "n"), not_one=("nt",))
+@row("lgr_evaluate_gt_batch", ("ns", "nt", "c", "n"))
 def _(s, d):
     from lgr_amd import capi
     ps, ns, pt, nt, pc, cc = problem(s, d)
@@ -343,7 +339,7 @@ def _(s, d):
            s.arr(masks) if opt else None, s.hout("out", out), s.out("correct", (cc,), np.uint8, opt))
 
 
-@row("lgr_evaluate_gt", ("ns", "nt", "c"), not_one=("nt",))
+@row("lgr_evaluate_gt", ("ns", "nt", "c"))
 def _(s, d):
     from lgr_amd import capi
     ps, ns, pt, nt, pc, cc = problem(s, d)
@@ -427,7 +423,7 @@ def _(s, d):
     s.keep("out", n_out.value, 48)
 
 
-@row("lgr_normals_knn", ("n", "ns"), not_one=("ns",))
+@row("lgr_normals_knn", ("n", "ns"))
 def _(s, d):
     n, ns = s.case.n("n", 400), s.case.n("ns", N_CLOUD)
     opt = not s.case.absent
@@ -776,15 +772,15 @@ NO_STAGING = {
 NULL_RC = {name: -1 for name in list(ROWS) + list(NO_TWIN)}   # LGR_ERR_INVALID_ARG everywhere
 
 
-def cases_of(counts, optional, not_one=()):
+def cases_of(counts, optional):
     out = [Case("full")] + ([Case("absent")] if optional else [])
     for c in counts:
-        out += [Case("zero", c)] + ([] if c in not_one else [Case("one", c)])
+        out += [Case("zero", c), Case("one", c)]
     return out + [Case("null")]
 
 
-PARAMS = [pytest.param(label, case, id=f"{label}-{case}") for label, (_, _, counts, optional, not_one) in ROWS.items()
-          for case in cases_of(counts, optional, not_one)]
+PARAMS = [pytest.param(label, case, id=f"{label}-{case}") for label, (_, _, counts, optional) in ROWS.items()
+          for case in cases_of(counts, optional)]
 
 
 @pytest.mark.parametrize("label,case", PARAMS)

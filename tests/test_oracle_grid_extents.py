@@ -6,8 +6,13 @@ before tests/test_gpu_grid_extents.py compares the device with it.  No GPU.
   PCL's arithmetic (neighbours by ascending distance), evaluate_plane's pairs, match_local;
 * against brute force: every radius search of match_local finds exactly numpy's candidates' best, and `thin`'s constructed pair -- within
   the radius, two cells apart at the cell the caller asked for -- is found;
-* the ring searches (knn, smoothed_densities, normals) against numpy's lexsort on (d2, index) on room, thin and flat only: the ring walk
-  is cubic in the separation of a query from the points (orc_grid.h knn, as lgr_knn_query on the device)."""
+* the ring searches (knn, smoothed_densities, normals) against numpy's lexsort on (d2, index) on room, thin and flat, with the cloud's
+  own points as queries;
+* the ring searches away from there: queries on and outside the cloud's box (26 directions, three separations, the two corners), clouds of
+  one to five points and of 70 coincident points plus one with k up to more than n, and queries up to 1e5 -- more than 2^31 cells --
+  from a one-point cloud.  Lists against numpy bit for bit, and the walk's cost (orc::Grid::knn's visit counter) against what the grid's
+  dims and the query's cell allow: the walk of orc_grid.h, as lgr_knn_query on the device, visits only cells that exist, from the first
+  ring that touches the grid."""
 import os
 import sys
 
@@ -128,3 +133,86 @@ def test_ring_searches_equal_numpy(oracle, world, name):
         np.testing.assert_array_equal(bits(oracle.smoothed_densities(cloud, k)), bits(np.minimum(dk, dk[want_i[:, 1]])))
     nb = G.N_BLOB
     assert np.array_equal(bits(oracle.normals_knn(cloud, 30)[:nb, 4:7]), bits(oracle.normals_knn(world["scene"][("room", 0.1)], 30)[:nb, 4:7]))
+
+
+# ---- ring searches outside the cloud's box, on tiny clouds and far from them ----------------------------------------------------------
+def check_walk(oracle, q, cloud, k):
+    """oracle.knn(q, cloud, k) == numpy bit for bit, on the grid numpy arrives at, and per query within the cost the grid allows:
+
+        rings walked          == last - first + 1                       (G.ring_walk: from the dims, the query's cell and the rule's end)
+        cells examined        == C, the in-grid cells of those rings     (each exactly once: nothing outside the grid, nothing twice)
+        z and y iterations    <= 3 C + rings                             (a row visited holds a cell of its ring; one jump per z, one per ring)
+
+    so the work per query, iterations + cells, is at most 4 C + rings: the in-grid cells of the rings walked plus the rings walked, up to
+    the constant.  C is at most the whole grid and the rings at most the longest axis, wherever the query lies."""
+    want_i, want_d = G.knn_padded(q, cloud, k)
+    idx, d2, visits, (h, origin, dims) = oracle.knn(q, cloud, k, visits=True)
+    np.testing.assert_array_equal(idx, want_i)
+    np.testing.assert_array_equal(bits(d2), bits(want_d))
+    wh, wo, wd = G.grid_of(cloud, 4.0)
+    assert bits(h) == bits(wh) and np.array_equal(bits(origin), bits(wo)) and list(dims) == list(wd), (h, origin, dims, wh, wo, wd)
+    walk = G.ring_walk(q, cloud, k, h, origin, dims)
+    first, last, cells = walk[:, 0], walk[:, 1], walk[:, 2]
+    rings = last - first + 1
+    np.testing.assert_array_equal(visits[:, 2], rings)
+    np.testing.assert_array_equal(visits[:, 1], cells)
+    assert (visits[:, 0] <= 3 * cells + rings).all(), (visits[visits[:, 0] > 3 * cells + rings], k)
+    assert (cells <= int(dims[0]) * int(dims[1]) * int(dims[2])).all() and (rings <= max(dims)).all()
+    return want_i, want_d, walk
+
+
+@pytest.mark.parametrize("k", [8, 30])
+def test_outside_queries_equal_numpy_at_bounded_cost(oracle, world, k):
+    b = world["blob"]
+    q = G.outside_queries(b)
+    assert len(q) == 80
+    mn, mx = b[:, :3].min(0), b[:, :3].max(0)
+    assert ((q[:78, :3] < mn) | (q[:78, :3] > mx)).any(1).all(), "a query meant to lie outside the box lies inside it"
+    _, _, walk = check_walk(oracle, q, b, k)
+    assert (walk[:78:3, 0] <= 1).all() and (walk[2:78:3, 0] >= 5).all(), "the separations reach neither the first ring outside nor a gap of several"
+    assert (walk[78:, 0] == 0).all()                                # the corners are points of the box
+
+
+TINY = ["one", "two_same", "two", "line3", "plane5", "same70"]
+
+
+@pytest.mark.parametrize("name", TINY)
+def test_tiny_clouds_equal_numpy_at_bounded_cost(oracle, name):
+    cloud = G.tiny_clouds()[name]
+    n = len(cloud)
+    h = G.auto_cell(cloud, 4.0)
+    if name in ("one", "two_same"):
+        assert h == (F(1) if name == "one" else max(np.sqrt(F(F(F(1e-12) * F(4)) / F(2))), F(1e-6)))   # nothing to measure: the floors
+    q = G.tiny_queries(cloud, h)
+    for k in (1, 2, 8):
+        want_i, want_d, walk = check_walk(oracle, q, cloud, k)
+        assert (want_i[:, min(k, n):] == -1).all() and np.isinf(want_d[:, min(k, n):]).all()
+        assert walk[:, 0].max() >= 190, "no query is some 200 cells from the grid"
+        if name == "same70":                                        # equal distances: the lower index first
+            np.testing.assert_array_equal(want_i[:70], np.tile(np.arange(k, dtype=np.int32), (70, 1)))
+        if name == "two_same":
+            assert (want_i[:, :min(k, 2)] == np.arange(min(k, 2))).all()
+    if n > 1:
+        for k in range(2, min(n, 8) + 1):
+            want_i, want_d = G.knn_numpy(cloud, cloud, k)
+            dk = np.sqrt(want_d[:, k - 1])
+            np.testing.assert_array_equal(bits(oracle.smoothed_densities(cloud, k)), bits(np.minimum(dk, dk[want_i[:, 1]])))
+    pts = np.concatenate([cloud, q])
+    got = oracle.normals_knn(pts, 8, surf=cloud)
+    if n < 3:
+        assert np.isnan(got[:, 4:7]).all() and np.isnan(got[:, 9]).all()
+    else:
+        assert np.isfinite(got[:, 9]).all()
+
+
+@pytest.mark.parametrize("name", ["one", "two_same"])
+def test_far_queries_equal_numpy_at_bounded_cost(oracle, name):
+    cloud = G.tiny_clouds()[name]
+    q = G.far_queries(cloud)
+    for k in (1, 2, 8):
+        _, want_d, walk = check_walk(oracle, q, cloud, k)
+        assert (walk[:, 2] == 1).all() and (walk[:, 0] == walk[:, 1]).all()   # one cell, one ring: the ring that reaches it
+    h = G.auto_cell(cloud, 4.0, device=True)
+    assert 1e5 / float(h) > 2.0 ** 31 and np.isfinite(want_d[:, 0]).all()
+    if name == "two_same":
+        assert walk[:, 0].max() == G.RING_CELL_MAX                  # beyond 2^31 cells at the oracle's cell too: the centre is held
