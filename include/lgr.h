@@ -382,23 +382,26 @@ int lgr_match_dense_last_check(lgr_ctx*, double* worst_ratio /* max |f - d2| / e
  *      cv::batchDistance's K-list: the first min(k, entries) rows in ascending (distance, index); the blocks' lists, ascending, go
  *      entry by entry through updateMultivaluedCorrespondence (src/common.cpp:517-529: insert in front of the first entry whose
  *      distance is not smaller, truncate to k), which leaves the first k of their union in (distance ascending, index DESCENDING)
- *      (DESIGN.md section 4).  k = 1 is the one-match entry points' result.  Rows of 135 and 352 floats: an exact dense scan.  Rows of
- *      33 floats: the same scan, or -- lgr_ctx_set_knn_filter -- an MFMA filter that offers every query a proven superset of the rows
- *      its list depends on and runs the same selection on the canonical distances of those rows only: the same bytes either way. ---- */
+ *      (DESIGN.md section 4).  k = 1 is the one-match entry points' result.  Every row length: an exact dense scan, or --
+ *      lgr_ctx_set_knn_filter -- an MFMA filter (f32 operands for 33 floats, f16-split operands for 135 and 352) that offers every query
+ *      a proven superset of the rows its list depends on and runs the same selection on the canonical distances of those rows only: the
+ *      same bytes either way. ---- */
 int lgr_match_knn(lgr_ctx*, int row_len, const float* q, int mq, const float* t, int mt, int block, int k, int32_t* idx, float* dist);
 int lgr_match_knn_dev(lgr_ctx*, int row_len, const float* d_q, int mq, const float* d_t, int mt, int block, int k, int32_t* d_idx, float* d_dist);
 /* both directions; the rows are packed once, each direction sweeps the distances itself */
 int lgr_match_knn2_dev(lgr_ctx*, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block, int k,
                        int32_t* d_ab_idx, float* d_ab_dist, int32_t* d_ba_idx, float* d_ba_dist);
-/* How lgr_match_knn* / lgr_match_ratio* and randomness > 1 / matching ratio inside lgr_correspondences* / lgr_align* / prepared calls
- * sweep 33-float rows; never what they return.  mode: -1 auto (filtered from the measured crossover size), 0 exact scan (the path of
+/* How lgr_match_knn* / lgr_match_ratio* and randomness > 1 / matching ratio inside lgr_correspondences* / lgr_align* / prepared and
+ * multi-scale calls sweep rows of 33, 135 and 352 floats; never what they return.  mode: -1 auto (filtered from the measured crossover size), 0 exact scan (the path of
  * revision 5), 1 filtered at any size.  self_check: 0 / 1 (test sizes): on the device, every pair of regular rows against the proven
  * bound of the filter and every query's candidates against an exact scan; a violation fails the call with LGR_ERR_HIP.  Values outside
- * these: LGR_ERR_INVALID_ARG.  Rows of 135 and 352 floats ignore the mode.
+ * these: LGR_ERR_INVALID_ARG.  Every row length honours the mode, each with its own measured crossover; lgr_ctx_set_dense_filter and the
+ * one-match entry points are independent of this switch.
  * ABI: additions only (these four entry points); no struct changed, lgr_version() stays 5. */
 int lgr_ctx_set_knn_filter(lgr_ctx*, int mode, int self_check);
 int lgr_ctx_get_knn_filter(lgr_ctx*, int* mode, int* self_check);
-/* last k-nearest call of this context on 33-float rows: [0] 1 filtered / 0 exact scan, [1] (query, train) pairs whose canonical distance
+/* last k-nearest call of this context, of any row length (every call writes all slots, an exact scan too: [0] = 0, [1] = all pairs,
+ * [3] = all rows): [0] 1 filtered / 0 exact scan, [1] (query, train) pairs whose canonical distance
  * was computed, [2] query rows answered from candidates, [3] query rows answered by the fallback scan, [4] train rows offered to every
  * query, [5] per-row candidate capacity, [6] self-check violations (~0 = not run), [7] reason code when [0] == 0 under mode 1
  * (1: more than 1024 rows the operands cannot carry, 2: more than half of a direction's rows on the fallback scan, 3: an empty side) */

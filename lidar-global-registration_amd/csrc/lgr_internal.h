@@ -43,7 +43,7 @@ struct lgr_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
-    lgr_buf ws[192];
+    lgr_buf ws[224];
     void* pinned = nullptr;  // small pinned host scratch for read-backs
     size_t pinned_cap = 0;
     hipEvent_t ev[32];       // 0..8 stage timers (lgr_align), 9.. pairs around the match_mfma passes
@@ -69,7 +69,7 @@ struct lgr_ctx {
     unsigned plane_gate[2] = {0, 0};            // lgr_ransac_last_plane_gate: the last RANSAC call of THIS context
     unsigned long long mcover[8] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // lgr_match_last_check_cover
     unsigned long long mpack[2] = {~0ull, ~0ull};   // lgr_match_last_pack_check
-    int knnf_mode = -1, knnf_check = 0;         // lgr_ctx_set_knn_filter: how 33-float rows are swept by the k-nearest matcher
+    int knnf_mode = -1, knnf_check = 0;         // lgr_ctx_set_knn_filter: how the k-nearest matcher sweeps rows of any length
     unsigned long long knnf_last[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0};   // lgr_match_knn_last: the last k-nearest call of THIS context
     double knnf_worst = -1;                     // lgr_match_knn_last_check
     int densef_mode = -1, densef_check = 0;     // lgr_ctx_set_dense_filter: how 135 / 352-float rows are swept by the one-match matcher
@@ -149,13 +149,15 @@ enum {
     // values, widened bounds, candidate counts and lists, fallback list and flags, counters, the fallback rows and their results
     WS_KNNF_OPS_A, WS_KNNF_OPS_B, WS_KNNF_MISC_A, WS_KNNF_MISC_B, WS_KNNF_IRR_A, WS_KNNF_IRR_B, WS_KNNF_PART, WS_KNNF_UW, WS_KNNF_CNT, WS_KNNF_CAND,
     WS_KNNF_FB, WS_KNNF_ISFB, WS_KNNF_DEV, WS_KNNF_FBROWS, WS_KNNF_FBIDX, WS_KNNF_FBDIST, WS_KNNF_CENTRE,
+    // lgr_match_knn_dense_mfma.cuh: the f16 operands of the long rows, the group lists of sweep A; the candidate lists are the WS_KNNF_ slots
+    WS_KNND_OPS_A, WS_KNND_OPS_B, WS_KNND_MISC_A, WS_KNND_MISC_B, WS_KNND_IRR_A, WS_KNND_IRR_B, WS_KNND_CENTRE, WS_KNND_GROUPS,
     // lgr_match_dense_mfma.cuh: the centre and scale; per side the [h1 | h2] operands, norms / norm bounds / tile bounds, irregular rows; per
     // direction the upper bounds, candidate counts and lists, fallback list and flags, counters, the fallback rows and their results
     WS_DENSEF_OPS_A, WS_DENSEF_OPS_B, WS_DENSEF_MISC_A, WS_DENSEF_MISC_B, WS_DENSEF_IRR_A, WS_DENSEF_IRR_B, WS_DENSEF_U, WS_DENSEF_CNT, WS_DENSEF_CAND,
     WS_DENSEF_FB, WS_DENSEF_ISFB, WS_DENSEF_DEV, WS_DENSEF_FBROWS, WS_DENSEF_FBIDX, WS_DENSEF_FBDIST, WS_DENSEF_CENTRE,
     WS_COUNT
 };
-static_assert(WS_COUNT <= 192, "grow lgr_ctx::ws");
+static_assert(WS_COUNT <= 224, "grow lgr_ctx::ws");
 
 // returns device pointer of at least `bytes` (contents undefined unless kept); grows with 25% slack
 int lgr_ws(lgr_ctx* ctx, int slot, size_t bytes, void** out);

@@ -13,6 +13,7 @@
 
 #include "lgr_host.h"
 #include "lgr_match_dense.cuh"
+#include "lgr_match_densef.cuh"
 #include "lgr_cloud.h"
 
 namespace {
@@ -250,34 +251,39 @@ __global__ void ratio_test_kernel(const int32_t* __restrict__ kidx, const float*
 }  // namespace
 
 #include "lgr_match_knn_mfma.cuh"
+#include "lgr_match_knn_dense_mfma.cuh"
 
 namespace {
 
-// 33-float rows under lgr_ctx_set_knn_filter: the filtered path, or the exact scan below with the reason in knnf_last[7]
-int knn_match_33(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int k, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d,
-                 const float* ratio_thr) {
+// a call under lgr_ctx_set_knn_filter: the filtered path of the row length (33 floats: lgr_match_knn_mfma.cuh, 135 and 352 floats:
+// lgr_match_knn_dense_mfma.cuh), or the exact scan with the reason in knnf_last[7].  Every call writes knnf_last fresh.
+template <int NB, int TAIL>
+int knn_match_switched(lgr_ctx* ctx, const float* d_a, int ma, const float* d_b, int mb, int block, int k, int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d,
+                       const float* ratio_thr) {
+    constexpr bool SHORT = NB == 2 && TAIL == 1;
     const unsigned long long fresh[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0};
     memcpy(ctx->knnf_last, fresh, sizeof fresh);
     ctx->knnf_worst = -1;
     const bool args_ok = (d_a || ma == 0) && (d_b || mb == 0) && ma >= 0 && mb >= 0 && block > 0 && (ab_i || ma == 0) && (ab_d || ma == 0);
-    const bool want = ctx->knnf_mode == 1 || (ctx->knnf_mode == -1 && (long long) ma * mb >= KNNF_AUTO_MIN_PAIRS);
+    const bool want = ctx->knnf_mode == 1 || (ctx->knnf_mode == -1 && (long long) ma * mb >= (SHORT ? KNNF_AUTO_MIN_PAIRS : KNND_AUTO_MIN_PAIRS));
     if (want && args_ok) {
         if (ma > 0 && mb > 0) {
             bool done = false;
-            LGR_TRY(knnf_match(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr, &done));
+            if constexpr (SHORT) LGR_TRY(knnf_match(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr, &done));
+            else LGR_TRY((knnd_match<NB, TAIL>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr, &done)));
             if (done) return LGR_OK;
         } else ctx->knnf_last[7] = KNNF_REASON_EMPTY;
     }
-    const int rc = knn_match<2, 1>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    const int rc = knn_match<NB, TAIL>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
     if (rc == LGR_OK && args_ok) { ctx->knnf_last[1] = (unsigned long long) ma * mb * (ba_i ? 2 : 1); ctx->knnf_last[3] = (unsigned long long) ma + (ba_i ? mb : 0); }
     return rc;
 }
 
 int knn_dispatch(lgr_ctx* ctx, int row_len, const float* d_a, int ma, const float* d_b, int mb, int block, int k,
                  int32_t* ab_i, float* ab_d, int32_t* ba_i, float* ba_d, const float* ratio_thr) {
-    if (row_len == 352) return knn_match<22, 0>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
-    if (row_len == 135) return knn_match<8, 7>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
-    if (row_len == 33) return knn_match_33(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    if (row_len == 352) return knn_match_switched<22, 0>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    if (row_len == 135) return knn_match_switched<8, 7>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
+    if (row_len == 33) return knn_match_switched<2, 1>(ctx, d_a, ma, d_b, mb, block, k, ab_i, ab_d, ba_i, ba_d, ratio_thr);
     return lgr_fail(ctx, LGR_ERR_UNSUPPORTED, "row_len == 33 || row_len == 135 || row_len == 352", __FILE__, __LINE__);
 }
 

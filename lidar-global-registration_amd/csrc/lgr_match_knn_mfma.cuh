@@ -243,21 +243,30 @@ __device__ __forceinline__ unsigned long long knnf_wave_min(unsigned long long v
     return v;
 }
 
+// the canonical squared distance at row length 16 NB + TAIL: the long rows (lgr_match_knn_dense_mfma.cuh) share the select and cover kernels
+// below, their candidate lists, irregular rows and fallback flags have the same form
+template <int NB, int TAIL>
+__device__ __forceinline__ float knnf_row_d2(const float* __restrict__ a, const float* __restrict__ b) {
+    if constexpr (NB == 2 && TAIL == 1) return knnf_canon_d2(a, b);
+    else return dense_canon_d2<NB, TAIL>(a, b);
+}
+
 // One wave per query (two per block) that is not on the fallback list: its candidates and the irregular train rows, canonical distances, order P inside
 // each bf block (an entry is in its block's list iff fewer than k entries of the block are in front of it), then the first k members in
 // order F.  Keys as in knn_match_kernel: d bits << 32 | j, and d bits << 32 | ~j.  pairs: canonical distances computed.
-template <bool RATIO>
+template <bool RATIO, int NB = 2, int TAIL = 1>
 __global__ __launch_bounds__(128) void knnf_select_kernel(const float* __restrict__ rows_q, const float* __restrict__ rows_t, int mq, int block, int k,
                                                          const int* __restrict__ cnt, const int* __restrict__ cand, const int* __restrict__ irr, int n_irr,
                                                          const unsigned char* __restrict__ is_fb, float thr, int32_t* __restrict__ idx,
                                                          float* __restrict__ dist, unsigned long long* __restrict__ pairs) {
+    constexpr int LEN = 16 * NB + TAIL;
     __shared__ unsigned long long kp[2][KNNF_NCAND], kf[2][KNNF_NCAND];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, q = blockIdx.x * 2 + w;
     const bool active = q < mq && !is_fb[q];
     const int nc = active ? min(cnt[q], KNNF_CAP) : 0, n = active ? nc + n_irr : 0;
     for (int c = lane; c < n; c += 64) {
         const int j = c < nc ? cand[(size_t) q * KNNF_CAP + c] : irr[1 + c - nc];
-        const float d = sqrtf(knnf_canon_d2(rows_q + (size_t) q * 33, rows_t + (size_t) j * 33));
+        const float d = sqrtf(knnf_row_d2<NB, TAIL>(rows_q + (size_t) q * LEN, rows_t + (size_t) j * LEN));
         kp[w][c] = d < FLT_MAX ? (unsigned long long) __float_as_uint(d) << 32 | (unsigned) j : NONE;
     }
     __syncthreads();
@@ -307,18 +316,20 @@ __global__ __launch_bounds__(128) void knnf_select_kernel(const float* __restric
 
 // the self-check of the candidate sets: one wave per query that is not on the fallback list; S_i from an exact scan (k rounds of the
 // smallest key above the last one give D_k), then every j with d(i, j) <= D_k must be a candidate of i or an irregular train row
+template <int NB = 2, int TAIL = 1>
 __global__ __launch_bounds__(256) void knnf_cover_kernel(const float* __restrict__ rows_q, const float* __restrict__ rows_t, int mq, int mt, int k,
                                                         const int* __restrict__ cnt, const int* __restrict__ cand, const float* __restrict__ xb_t,
                                                         const unsigned char* __restrict__ is_fb, unsigned long long* __restrict__ violations) {
     const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= mq || is_fb[q]) return;
-    const float* a = rows_q + (size_t) q * 33;
+    constexpr int LEN = 16 * NB + TAIL;
+    const float* a = rows_q + (size_t) q * LEN;
     unsigned long long last = 0;
     bool any = false;
     for (int e = 0; e < k; ++e) {
         unsigned long long best = NONE;
         for (int j = lane; j < mt; j += 64) {
-            const float d = sqrtf(knnf_canon_d2(a, rows_t + (size_t) j * 33));
+            const float d = sqrtf(knnf_row_d2<NB, TAIL>(a, rows_t + (size_t) j * LEN));
             const unsigned long long key = d < FLT_MAX ? (unsigned long long) __float_as_uint(d) << 32 | (unsigned) j : NONE;
             if ((!any || key > last) && key < best) best = key;
         }
@@ -330,7 +341,7 @@ __global__ __launch_bounds__(256) void knnf_cover_kernel(const float* __restrict
     const float dk = __uint_as_float((unsigned) (last >> 32));
     const int nc = min(cnt[q], KNNF_CAP);
     for (int j = lane; j < mt; j += 64) {
-        const float d = sqrtf(knnf_canon_d2(a, rows_t + (size_t) j * 33));
+        const float d = sqrtf(knnf_row_d2<NB, TAIL>(a, rows_t + (size_t) j * LEN));
         if (!(d <= dk) || xb_t[j] < 0.f) continue;
         bool found = false;
         for (int c = 0; c < nc; ++c) found = found || cand[(size_t) q * KNNF_CAP + c] == j;
@@ -371,14 +382,16 @@ int knnf_pack_side(lgr_ctx* ctx, const float* rows, const float* centre, int m, 
 }
 
 // the exact scan of one direction on n query rows (all of a side, or the gathered fallback rows)
+template <int NB, int TAIL>
 int knnf_exact(lgr_ctx* ctx, const float* d_q, int n, const float* d_t, int mt, int block, int k, int slot, int32_t* idx, float* dist, const float* ratio_thr) {
+    constexpr int LEN = 16 * NB + TAIL;
     const int mpa = cdiv(n, MT) * MT, mpb = cdiv(mt, MT) * MT;
     float *pa, *pb;
-    LGR_TRY(lgr_ws_t(ctx, WS_DENSE_PACK_A, (size_t) mpa * 33, &pa));
-    LGR_TRY(lgr_ws_t(ctx, WS_DENSE_PACK_B, (size_t) mpb * 33, &pb));
-    dense_pack_kernel<2, 1><<<cdiv((long long) mpa * 33, 256), 256, 0, ctx->stream>>>(d_q, n, mpa, pa);
-    dense_pack_kernel<2, 1><<<cdiv((long long) mpb * 33, 256), 256, 0, ctx->stream>>>(d_t, mt, mpb, pb);
-    return knn_sweep<2, 1>(ctx, pa, n, mpa, pb, mt, mpb, block, k, slot, idx, dist, ratio_thr);
+    LGR_TRY(lgr_ws_t(ctx, WS_DENSE_PACK_A, (size_t) mpa * LEN, &pa));
+    LGR_TRY(lgr_ws_t(ctx, WS_DENSE_PACK_B, (size_t) mpb * LEN, &pb));
+    dense_pack_kernel<NB, TAIL><<<cdiv((long long) mpa * LEN, 256), 256, 0, ctx->stream>>>(d_q, n, mpa, pa);
+    dense_pack_kernel<NB, TAIL><<<cdiv((long long) mpb * LEN, 256), 256, 0, ctx->stream>>>(d_t, mt, mpb, pb);
+    return knn_sweep<NB, TAIL>(ctx, pa, n, mpa, pb, mt, mpb, block, k, slot, idx, dist, ratio_thr);
 }
 
 // One direction.  last: the counters of lgr_match_knn_last, accumulated over the directions of a call.
@@ -413,7 +426,7 @@ int knnf_direction(lgr_ctx* ctx, const KnnfSide& Q, const KnnfSide& T, int block
     if (2ll * n_fb > mq) {   // the documented share: more than half of the rows have no usable candidate list
         last[0] = 0; last[7] = KNNF_REASON_FALLBACK_SHARE;
         last[1] += (unsigned long long) mq * mt; last[3] += mq;
-        return knnf_exact(ctx, Q.rows, mq, T.rows, mt, block, k, WS_KNN_PART_A, idx, dist, ratio_thr);
+        return knnf_exact<2, 1>(ctx, Q.rows, mq, T.rows, mt, block, k, WS_KNN_PART_A, idx, dist, ratio_thr);
     }
     const float thr = ratio_thr ? *ratio_thr : 0.f;
     if (ratio_thr) knnf_select_kernel<true><<<cdiv(mq, 2), 128, 0, ctx->stream>>>(Q.rows, T.rows, mq, block, k, cnt, cand, T.irr, T.n_irr, is_fb, thr, idx, dist, dev);
@@ -422,7 +435,7 @@ int knnf_direction(lgr_ctx* ctx, const KnnfSide& Q, const KnnfSide& T, int block
     if (ctx->knnf_check) {
         const KnnfCheck chk{Q.rows, T.rows, T.xb, (unsigned*) (dev + 3), dev + 1};
         knnf_sweep_kernel<2><<<grid, 256, 0, ctx->stream>>>(Q.op_q, T.op_t, Q.n2, Q.xb, T.ymax, mq, mqp, mt, n_tt, tps, nullptr, nullptr, nullptr, nullptr, chk);
-        knnf_cover_kernel<<<cdiv(mq, 4), 256, 0, ctx->stream>>>(Q.rows, T.rows, mq, mt, k, cnt, cand, T.xb, is_fb, dev + 2);
+        knnf_cover_kernel<><<<cdiv(mq, 4), 256, 0, ctx->stream>>>(Q.rows, T.rows, mq, mt, k, cnt, cand, T.xb, is_fb, dev + 2);
         LGR_HIP(ctx, hipGetLastError());
     }
     if (n_fb) {
@@ -433,7 +446,7 @@ int knnf_direction(lgr_ctx* ctx, const KnnfSide& Q, const KnnfSide& T, int block
         LGR_TRY(lgr_ws_t(ctx, WS_KNNF_FBIDX, (size_t) n_fb * width, &ti));
         LGR_TRY(lgr_ws_t(ctx, WS_KNNF_FBDIST, (size_t) n_fb * width, &td));
         knnf_gather_rows_kernel<<<cdiv((long long) n_fb * 33, 256), 256, 0, ctx->stream>>>(Q.rows, fb + 1, n_fb, rows_fb);
-        LGR_TRY(knnf_exact(ctx, rows_fb, n_fb, T.rows, mt, block, k, WS_KNN_PART_A, ti, td, ratio_thr));
+        LGR_TRY((knnf_exact<2, 1>(ctx, rows_fb, n_fb, T.rows, mt, block, k, WS_KNN_PART_A, ti, td, ratio_thr)));
         knnf_scatter_kernel<<<cdiv((long long) n_fb * width, 256), 256, 0, ctx->stream>>>(ti, td, fb + 1, n_fb, (int) width, idx, dist);
         LGR_HIP(ctx, hipGetLastError());
     }

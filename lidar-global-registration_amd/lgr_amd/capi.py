@@ -827,7 +827,7 @@ class Context:
     # ---- randomness > 1: the k nearest rows (row length 33, 135 or 352) and the vote among a query's candidates ----------------------
     def match_knn(self, q, t, block=10000, k=2):
         """exact matchBF with randomness = k on cuda float32 [m, 33 | 135 | 352] rows: (idx int32 [mq, k], dist float32 [mq, k]),
-        a query's matches in list order, then -1 / 0."""
+        a query's matches in list order, then -1 / 0.  set_knn_filter chooses how every row length is swept, never the result."""
         torch = self.torch
         q = q.contiguous(); t = t.contiguous()
         idx = self.empty((q.shape[0], max(int(k), 0)), torch.int32)
@@ -836,6 +836,8 @@ class Context:
         return idx, dist
 
     def match_knn2(self, a, b, block=10000, k=2):
+        """match_knn in both directions, the rows packed once (under set_knn_filter: one centre and scale for the call):
+        (ab_idx, ab_dist, ba_idx, ba_dist)"""
         torch = self.torch
         a = a.contiguous(); b = b.contiguous()
         kk = max(int(k), 0)
@@ -845,9 +847,11 @@ class Context:
                                            _ptr(ab_i), _ptr(ab_d), _ptr(ba_i), _ptr(ba_d)))
         return ab_i, ab_d, ba_i, ba_d
 
-    # ---- how 33-float rows are swept by the k-nearest matcher (never what it returns) ------------------------------------------------
+    # ---- how the k-nearest matcher sweeps rows of 33, 135 and 352 floats (never what it returns) -----------------------------------------
     def set_knn_filter(self, mode=-1, self_check=0):
-        """mode -1 auto (filtered from the crossover size), 0 exact scan, 1 filtered at any size; self_check 0 / 1 (test sizes)"""
+        """mode -1 auto (filtered from the row length's crossover size), 0 exact scan, 1 filtered at any size; self_check 0 / 1 (test
+        sizes).  Holds for match_knn* / match_ratio* and randomness > 1 / matching ratio in the pipeline, on FPFH, SHOT and RoPS rows;
+        set_dense_filter (the one-match matchers) is a separate switch."""
         self.check(_lib.lgr_ctx_set_knn_filter(self.h, int(mode), int(self_check)))
 
     def knn_filter(self):
@@ -857,7 +861,8 @@ class Context:
         return m.value, c.value
 
     def match_knn_last(self):
-        """the eight counters of lgr_match_knn_last for the last k-nearest call on 33-float rows ([6]: -1 when the self-check did not run)"""
+        """the eight counters of lgr_match_knn_last for the last k-nearest call of any row length, exact scans included ([6]: -1 when the
+        self-check did not run)"""
         out = (C.c_ulonglong * 8)()
         self.check(_lib.lgr_match_knn_last(self.h, out))
         return [-1 if v == 0xFFFFFFFFFFFFFFFF else int(v) for v in out]
@@ -892,6 +897,7 @@ class Context:
         return out.value
 
     def match_knn_host(self, q, t, block=10000, k=2):
+        """match_knn on numpy rows of 33, 135 or 352 floats (uploaded, matched under set_knn_filter, downloaded)"""
         q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
         idx = np.zeros((q.shape[0], max(int(k), 0)), np.int32); dist = np.zeros((q.shape[0], max(int(k), 0)), np.float32)
         self.check(_lib.lgr_match_knn(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), int(k), _ptr(idx), _ptr(dist)))
@@ -914,7 +920,8 @@ class Context:
         return idx, dist
 
     def match_ratio(self, q, t, block=10000, k=2, threshold=MATCHING_RATIO_THRESHOLD):
-        """match_knn and ratio_test in one sweep (the [mq, k] table is never written): (idx int32 [mq], dist float32 [mq])"""
+        """match_knn and ratio_test in one sweep (the [mq, k] table is never written): (idx int32 [mq], dist float32 [mq]); rows of 33,
+        135 or 352 floats, swept as set_knn_filter says"""
         torch = self.torch
         q = q.contiguous(); t = t.contiguous()
         idx = self.empty((q.shape[0],), torch.int32); dist = self.empty((q.shape[0],), torch.float32)
@@ -923,6 +930,7 @@ class Context:
         return idx, dist
 
     def match_ratio_host(self, q, t, block=10000, k=2, threshold=MATCHING_RATIO_THRESHOLD):
+        """match_ratio on numpy rows of 33, 135 or 352 floats"""
         q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
         idx = np.zeros(q.shape[0], np.int32); dist = np.zeros(q.shape[0], np.float32)
         self.check(_lib.lgr_match_ratio(self.h, int(q.shape[1]), _ptr(q), q.shape[0], _ptr(t), t.shape[0], int(block), int(k), C.c_float(threshold),

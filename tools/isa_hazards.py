@@ -363,7 +363,7 @@ def resources(co):
 GATED = ["normals_kernel", "normals_wave_kernel", "refit_kernel", "hypotheses_kernel", "gror_umeyama_kernel", "spfh_tile_kernel", "fpfh_mfma_kernel",
          "count_list_kernel", "match_sweep", "match_tiles", "pack16_kernel", "rs_hyp_kernel", "rs_store_eval_kernel", "rops_kernel",
          "pc_kernel", "seq_sum_kernel", "weights_map_kernel", "nss_hist_kernel", "plane_kernel", "fold_kernel", "mh_order_kernel", "mh_keep_kernel",
-         "refine_dense_kernel", "refine_sum_kernel", "refine_decide_kernel", "dense_match_kernel", "densef_sweep_kernel", "knn_match_kernel", "knn_merge_kernel",
+         "refine_dense_kernel", "refine_sum_kernel", "refine_decide_kernel", "dense_match_kernel", "densef_sweep_kernel", "knn_match_kernel", "knn_merge_kernel", "knnd_kth_kernel", "knnf_select_kernel",
          "vote_matches_kernel", "ratio_test_kernel", "gt_foot_kernel", "gt_batch_kernel", "gt_seqsum_wide_kernel",
          "ho_small_kernel", "ho_act_kernel", "ho_keys_kernel",
          "teaser_adj_kernel", "teaser_clique_kernel", "teaser_rotation_kernel", "teaser_shift_kernel", "teaser_mask_kernel"]

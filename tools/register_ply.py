@@ -100,7 +100,7 @@ def main():
     ap.add_argument("--order", default="canonical", choices=["canonical", "reference"],
                     help="point numbering after the loader: (iz,iy,ix) voxel order, or the reference's hash-container order")
     ap.add_argument("--knn-filter", default="auto", choices=["auto", "on", "off"],
-                    help="how --randomness > 1 / --matching ratio sweep FPFH rows (never what they return): the MFMA filter from the crossover size, always, never")
+                    help="how --randomness > 1 / --matching ratio sweep FPFH, SHOT and RoPS rows (never what they return): the MFMA filter from the crossover size, always, never")
     ap.add_argument("--dense-filter", default="auto", choices=["auto", "on", "off"],
                     help="how SHOT / RoPS rows are matched at --randomness 1 (never what is returned): the MFMA filter from the crossover size, always, never")
     a = ap.parse_args()
