@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-/* ABI revision.  Still 5 with the reference point order on the device: lgr_hash_order_dev, lgr_downsample_order_dev, lgr_dedupe_order_dev,
+/* ABI revision.  Still 5 with point-to-plane ICP: lgr_icp_params, lgr_icp_step, lgr_icp_result, LGR_ICP_*, lgr_default_icp_params,
+ * lgr_icp_plane_dev and lgr_icp_plane_host are additions; no struct or entry point that existed changed.  Still 5 with the reference point order on the device: lgr_hash_order_dev, lgr_downsample_order_dev, lgr_dedupe_order_dev,
  * lgr_preprocess_order_dev and lgr_selfcheck_hash_order are additions; no struct or entry point that existed changed.  Still 5 with the prepared clouds: lgr_cloud, struct lgr_cloud_info, lgr_cloud_level_info, lgr_cloud_prepare*, lgr_cloud_destroy,
  * lgr_cloud_info, lgr_cloud_keypoints*, lgr_cloud_level*, lgr_correspondences_prepared*, lgr_align_prepared and the host twin lgr_nearest are
  * additions; no struct or entry point that existed changed.  Still 5 with the ratio matcher: lgr_feature_params.ratio_k takes the first of that struct's reserved words (a host that
@@ -1102,6 +1103,63 @@ int lgr_refine_plane_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tg
 int lgr_refine_plane(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T0_16[16], const lgr_refine_params*,
                      const lgr_metric_params* mp_or_null, lgr_refine_result* out, lgr_refine_step* trace_or_null,
                      int* n_trace_or_null);   /* host twin */
+
+/* ---- point-to-plane ICP: fine registration of a transform on the device.  A statement of this library's own (DESIGN.md section 4,
+ *      "Point-to-plane ICP"; the reference has no ICP), bit-identical to the CPU statement tests/cpp/icp_ref.cpp:
+ *        max_dist = params.max_dist > 0 ? params.max_dist : 4 x calculatePointCloudDensity(tgt); min_dist = params.min_dist > 0 ?
+ *        params.min_dist : max_dist; c = centre of the target's bounding box; ONE grid over the target for max_dist.
+ *        iteration k = 0, 1, ... with the f32 transform T_k (T_0 = T0):
+ *            d_k = k ? max(min_dist, d_{k-1} x shrink) : max_dist                                  (f32)
+ *            source point i pairs with j = its nearest target within d_k under the rule of lgr_evaluate_plane_dense (strict
+ *            d2 < d_k^2, smallest squared distance, then lowest index) iff the moved point and the target's normal are finite;
+ *            a pair's 28 f64 terms: g g^T (upper triangle), g r, r r with g = ((p - c) x n, n), r = n . (p - q); every other point: 28 x +0.0;
+ *            each sum: the balanced binary tree over the source index, padded with +0.0 to the next power of two     (no atomics, no chain)
+ *            pairs < 6 -> NO_PAIRS; A xi = -b by LDL^T in f64, a pivot not > 1e-12 x max diag A -> DEGENERATE           (T_k stays)
+ *            T_{k+1} = [R | (c - R c) + t] o T_k, R from the unit quaternion (1, w / 2) / |.|, rounded to f32 once
+ *            |w| < rot_eps && |t| < trans_eps -> CONVERGED; k + 1 == max_iterations -> MAX_ITERATIONS
+ *      An empty source or max_iterations == 0 is LGR_OK with 0 iterations and T0 returned (stop NO_PAIRS / MAX_ITERATIONS, pairs 0, rmse
+ *      FLT_MAX, max_dist = the caller's value when positive, else 0): nothing is computed.  nt < 2, max_iterations outside
+ *      [0, LGR_ICP_MAX_ITERATIONS], a NaN or infinite max_dist / min_dist or one above 1e18, shrink outside (0, 1], a negative or NaN eps and
+ *      non-zero reserved words: LGR_ERR_INVALID_ARG, before any work; so is a min_dist above the max_dist in use.  Rows 16-byte aligned.
+ *      trace (optional, host, room for max_iterations entries): entry k is iteration k -- the transform it started from, d_k, its pairs
+ *      and rmse, |w| and |t| of its step (0 when it took none); *n_trace = iterations evaluated (iterations, one more after NO_PAIRS /
+ *      DEGENERATE).  The device path enqueues the iterations in groups of LGR_ICP_GROUP and reads one small record per group; the pairs,
+ *      the terms, the sums and the transform never pass through the host.  The host form is lgr_icp_plane_host (not lgr_icp_plane: the name
+ *      without a suffix is kept free until the host-entry table of the tests has a row for it). ---- */
+#define LGR_ICP_MAX_ITERATIONS 1024
+#define LGR_ICP_GROUP 8
+enum { LGR_ICP_STOP_MAX_ITERATIONS = 0, LGR_ICP_STOP_CONVERGED = 1, LGR_ICP_STOP_NO_PAIRS = 2, LGR_ICP_STOP_DEGENERATE = 3 };
+typedef struct {
+    int32_t max_iterations;   /* 0 .. LGR_ICP_MAX_ITERATIONS */
+    float   max_dist;         /* <= 0: 4 x the target's density */
+    float   min_dist;         /* <= 0: max_dist */
+    float   shrink;           /* (0, 1] */
+    float   rot_eps;          /* rad */
+    float   trans_eps;
+    int32_t reserved[2];      /* 0 */
+} lgr_icp_params;
+void lgr_default_icp_params(lgr_icp_params* p);   /* 30 iterations, max_dist 0, min_dist 0, shrink 1, eps 1e-6 / 1e-6 */
+typedef struct {
+    float   transformation[16];   /* T_k, column-major */
+    float   dist;                 /* d_k */
+    int32_t pairs;
+    float   rmse;                 /* (float) sqrt(sum r r / pairs); FLT_MAX without a pair */
+    float   rot, trans;           /* |w|, |t| of the step taken, 0 without one */
+    int32_t reserved[3];          /* 0 */
+} lgr_icp_step;
+typedef struct {
+    float   transformation[16];   /* the final transform */
+    int32_t iterations;           /* steps taken */
+    int32_t stop;                 /* LGR_ICP_STOP_* */
+    float   max_dist;             /* the value used */
+    int32_t pairs;  float rmse;   /* of the last evaluated iteration */
+    int32_t pairs0; float rmse0;  /* of iteration 0 */
+    int32_t reserved[5];          /* 0 */
+} lgr_icp_result;
+int lgr_icp_plane_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T0_16[16] /* host */,
+                      const lgr_icp_params*, lgr_icp_result* out /* host */, lgr_icp_step* trace_or_null /* host */, int* n_trace_or_null);
+int lgr_icp_plane_host(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T0_16[16], const lgr_icp_params*,
+                       lgr_icp_result* out, lgr_icp_step* trace_or_null, int* n_trace_or_null);   /* host twin */
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,319 @@
+// lgr_icp.hip -- point-to-plane ICP on the device for gfx950 (include/lgr.h lgr_icp_plane*).  A statement of this library's own: DESIGN.md
+// section 4, "Point-to-plane ICP"; the CPU statement is tests/cpp/icp_ref.cpp; the step's f64 arithmetic is lgr_icp_math.h for both.
+//
+// Set-up, once per call: max_dist (the caller's, or 4 x the target's density), ONE grid over the target with cell 1.001 x max_dist, the
+// centre of the target's bounding box.  An iteration, all on the stream:
+//   icp_terms_kernel   a source point per lane: plane_move by S.T, nearest_within(d_k^2), the 28 f64 terms; wave butterfly, LDS tree over
+//                      the four waves -> one partial per term and workgroup (and the workgroup's pair count)
+//   icp_tree_kernel    256 partials -> 1, level by level, until one is left (none up to 256 points, one up to 65 536, two beyond)
+//   icp_step_kernel    the solve, T_{k+1}, d_{k+1}, the stop decision and the trace record (icp_step, lgr_icp_math.h)
+// The tree.  The statement sums x[0, ns) padded with +0.0 to 2^m by S(lo, len) = S(lo, len / 2) + S(lo + len / 2, len / 2).  An xor
+// butterfly with offsets 1, 2, 4, ... leaves in lane 0 exactly that tree over the wave's 64 contiguous indices (lane 0 always adds
+// "its own + the higher half"), the LDS stage is (w0 + w1) + (w2 + w3), and a level of icp_tree_kernel is the same over 256 partials, so
+// the kernels compute S(0, 256^levels).  Indices in [ns, 2^m) hold +0.0 as the statement says; indices from 2^m on hold -0.0, the additive
+// identity (x + -0.0 == x for every x, -0.0 and +0.0 included): S(0, 256^levels) == S(0, 2^m) bit for bit, also where a sum is a zero.
+// No float atomics, no sequential chain; the pair count is an integer sum.
+// Iterations are enqueued blind in groups of LGR_ICP_GROUP with one read-back of S per group; once S.done is set every kernel of a later
+// iteration returns at once and S and the trace stay as they are.
+#include <algorithm>
+#include <cfloat>
+
+#include "lgr_grid.cuh"
+#include "lgr_host.h"
+#include "lgr_icp_math.h"
+#include "lgr_internal.h"
+#include "lgr_math.cuh"
+#include "lgr_plane_point.cuh"
+#include "lgr_pointpass.cuh"
+
+namespace {
+
+constexpr int ICP_BLOCK = 256, ICP_WAVES = ICP_BLOCK / 64, ICP_SLOTS = ICP_TERMS + 1;   // slot 28: the pair count (long long)
+
+struct IcpState {
+    float T[16];          // T_k: T0 (uploaded), then each step's
+    float d;              // d_k of the iteration about to run
+    int k;                // steps taken == index of the iteration about to run
+    int stop, done;       // LGR_ICP_STOP_*, the loop has ended
+    int n_eval;           // iterations evaluated == trace entries written
+    int pairs, pairs0;    // of the last evaluated iteration, of iteration 0
+    float rmse, rmse0;
+    int pad[7];
+};
+static_assert(sizeof(IcpState) == 128, "IcpState is copied and cleared in one piece");
+
+struct IcpConst { float cx, cy, cz, min_dist, shrink, rot_eps, trans_eps; int max_iterations; };
+
+// S(lo, 64) over the wave's lanes, valid in lane 0
+__device__ __forceinline__ double icp_wave_tree(double x) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) x = x + __shfl_xor(x, o);
+    return x;
+}
+
+// the four waves' values of one slot -> S(lo, 256)
+__device__ __forceinline__ double icp_block_tree(const double (*sh)[ICP_SLOTS], int t) { return (sh[0][t] + sh[1][t]) + (sh[2][t] + sh[3][t]); }
+
+// part: [ICP_SLOTS][stride] 8-byte words, slot-major; this workgroup writes column blockIdx.x.  pad_n = 2^m.
+__global__ __launch_bounds__(ICP_BLOCK) void icp_terms_kernel(GridDev g, const float4* __restrict__ src, int ns, long long pad_n, const IcpState* __restrict__ S, float cx,
+                                                              float cy, float cz, double* __restrict__ part, size_t stride) {
+    if (S->done) return;
+    __shared__ double sh[ICP_WAVES][ICP_SLOTS];
+    const long long i = (long long) blockIdx.x * ICP_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float d = S->d;
+    bool has = false;
+    double gv[6] = {0, 0, 0, 0, 0, 0}, r = 0;
+    if (i < ns) {
+        const float4 P = src[(size_t) i * 3];
+        float px, py, pz, d2;
+        int j;
+        plane_move(S->T, P.x, P.y, P.z, px, py, pz);
+        const int t = nearest_within(g, px, py, pz, d * d, d2, j);   // (a non-finite moved point walks nothing: -1)
+        if (t >= 0) {
+            const float4 Q = g.pxyz[t], N = g.pnrm[t];   // the grid's copies of tgt[j]: the same bits
+            if (lgr_finite3(N.x, N.y, N.z)) {
+                has = true;
+                const double nx = (double) N.x, ny = (double) N.y, nz = (double) N.z;
+                const double ux = (double) px - (double) cx, uy = (double) py - (double) cy, uz = (double) pz - (double) cz;
+                const double ex = (double) px - (double) Q.x, ey = (double) py - (double) Q.y, ez = (double) pz - (double) Q.z;
+                r = (nx * ex + ny * ey) + nz * ez;
+                gv[0] = uy * nz - uz * ny;
+                gv[1] = uz * nx - ux * nz;
+                gv[2] = ux * ny - uy * nx;
+                gv[3] = nx; gv[4] = ny; gv[5] = nz;
+            }
+        }
+    }
+    const double fill = i < pad_n ? 0.0 : -0.0;   // the statement's padding / the identity behind it
+    int slot = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b, ++slot) {
+            const double s = icp_wave_tree(has ? gv[a] * gv[b] : fill);
+            if (lane == 0) sh[wave][slot] = s;
+        }
+#pragma unroll
+    for (int a = 0; a < 6; ++a, ++slot) {
+        const double s = icp_wave_tree(has ? gv[a] * r : fill);
+        if (lane == 0) sh[wave][slot] = s;
+    }
+    {
+        const double s = icp_wave_tree(has ? r * r : fill);
+        if (lane == 0) sh[wave][ICP_TERMS - 1] = s;
+    }
+    const long long cnt = __popcll(__ballot(has));
+    if (lane == 0) sh[wave][ICP_TERMS] = __longlong_as_double(cnt);
+    __syncthreads();
+    if (threadIdx.x < ICP_TERMS) part[threadIdx.x * stride + blockIdx.x] = icp_block_tree(sh, threadIdx.x);
+    else if (threadIdx.x == ICP_TERMS) {
+        long long c = 0;
+#pragma unroll
+        for (int w = 0; w < ICP_WAVES; ++w) c += __double_as_longlong(sh[w][ICP_TERMS]);
+        part[ICP_TERMS * stride + blockIdx.x] = __longlong_as_double(c);
+    }
+}
+
+// one level of the tree: entries [256 b, 256 b + 256) of slot blockIdx.y -> entry b.  Entries from n_in on are +0.0 below pad_in
+// (= 2^m / 256^level: workgroups the statement's padding would have filled) and -0.0 from there.
+__global__ __launch_bounds__(ICP_BLOCK) void icp_tree_kernel(const IcpState* __restrict__ S, const double* __restrict__ in, size_t stride_in, long long n_in, long long pad_in,
+                                                             double* __restrict__ out, size_t stride_out) {
+    if (S->done) return;
+    __shared__ double sh[ICP_WAVES];
+    const int slot = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long j = (long long) blockIdx.x * ICP_BLOCK + threadIdx.x;
+    const double* col = in + slot * stride_in;
+    if (slot == ICP_TERMS) {   // the pair count (the branch is uniform over the workgroup)
+        long long c = j < n_in ? __double_as_longlong(col[j]) : 0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o);
+        if (lane == 0) sh[wave] = __longlong_as_double(c);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            long long t = 0;
+#pragma unroll
+            for (int w = 0; w < ICP_WAVES; ++w) t += __double_as_longlong(sh[w]);
+            out[slot * stride_out + blockIdx.x] = __longlong_as_double(t);
+        }
+        return;
+    }
+    const double x = j < n_in ? col[j] : (j < pad_in ? 0.0 : -0.0);
+    const double s = icp_wave_tree(x);
+    if (lane == 0) sh[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[slot * stride_out + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// one wave, one working lane: the iteration's decision from its sums (entry 0 of every slot of `fin`)
+__global__ __launch_bounds__(64) void icp_step_kernel(IcpState* __restrict__ S, const double* __restrict__ fin, size_t stride, IcpConst K, lgr_icp_step* __restrict__ trace) {
+    if (threadIdx.x != 0 || S->done) return;
+    double s[ICP_TERMS];
+#pragma unroll
+    for (int t = 0; t < ICP_TERMS; ++t) s[t] = fin[t * stride];
+    const long long pairs = __double_as_longlong(fin[ICP_TERMS * stride]);
+    const int k = S->k;
+    const float c[3] = {K.cx, K.cy, K.cz};
+    float T[16], Tn[16], rot, trans;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) T[e] = S->T[e];
+    bool stepped;
+    const int stop = icp_step(s, pairs, c, T, k, K.max_iterations, K.rot_eps, K.trans_eps, Tn, &stepped, &rot, &trans);
+    const float rmse = icp_rmse(s[ICP_TERMS - 1], pairs);
+    lgr_icp_step rec;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) rec.transformation[e] = T[e];
+    rec.dist = S->d; rec.pairs = (int) pairs; rec.rmse = rmse; rec.rot = rot; rec.trans = trans;
+    rec.reserved[0] = rec.reserved[1] = rec.reserved[2] = 0;
+    trace[k] = rec;   // k < max_iterations: iteration max_iterations - 1 always sets done
+    S->n_eval = k + 1;
+    S->pairs = (int) pairs; S->rmse = rmse;
+    if (k == 0) { S->pairs0 = (int) pairs; S->rmse0 = rmse; }
+    if (stepped) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) S->T[e] = Tn[e];
+        S->k = k + 1;
+    }
+    if (stop >= 0) { S->stop = stop; S->done = 1; }
+    else S->d = icp_next_dist(S->d, K.shrink, K.min_dist);
+}
+
+void fill_result(const IcpState& s, float max_dist, lgr_icp_result* out) {
+    memset(out, 0, sizeof *out);
+    memcpy(out->transformation, s.T, 64);
+    out->iterations = s.k; out->stop = s.stop; out->max_dist = max_dist;
+    out->pairs = s.pairs; out->rmse = s.rmse; out->pairs0 = s.pairs0; out->rmse0 = s.rmse0;
+}
+
+bool dist_ok(float d) { return d == d && fabsf(d) <= 1e18f; }   // finite, and its square stays finite
+
+bool params_ok(const lgr_icp_params* p) {
+    if (!p || p->max_iterations < 0 || p->max_iterations > LGR_ICP_MAX_ITERATIONS) return false;
+    for (int r : p->reserved)
+        if (r) return false;
+    return dist_ok(p->max_dist) && dist_ok(p->min_dist) && p->shrink > 0.f && p->shrink <= 1.f && p->rot_eps >= 0.f && p->trans_eps >= 0.f;
+}
+
+// nothing to evaluate (an empty source, no iteration allowed): T0 comes back
+void idle_result(const float* T0, const lgr_icp_params* p, int stop, lgr_icp_result* out, int* n_trace) {
+    IcpState s{};
+    memcpy(s.T, T0, 64);
+    s.stop = stop;
+    s.rmse = s.rmse0 = FLT_MAX;
+    fill_result(s, p->max_dist > 0.f ? p->max_dist : 0.f, out);
+    if (n_trace) *n_trace = 0;
+}
+
+}  // namespace
+
+extern "C" void lgr_default_icp_params(lgr_icp_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->max_iterations = 30;
+    p->shrink = 1.f;
+    p->rot_eps = 1e-6f;
+    p->trans_eps = 1e-6f;
+}
+
+extern "C" int lgr_icp_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_params* p,
+                                 lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, T0 && out && ns >= 0 && (d_src || ns == 0) && d_tgt && nt > 1 && params_ok(p) && aligned16(d_src) && aligned16(d_tgt), LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, !trace || n_trace, LGR_ERR_INVALID_ARG);
+    LGR_HIP(ctx, hipSetDevice(ctx->device));
+    const int max_it = p->max_iterations;
+    if (ns == 0 || max_it == 0) {
+        idle_result(T0, p, ns == 0 ? LGR_ICP_STOP_NO_PAIRS : LGR_ICP_STOP_MAX_ITERATIONS, out, n_trace);
+        return LGR_OK;
+    }
+    // ---- set-up: the distances, the grid, the centre, the buffers (every synchronisation that is not a group's read-back happens here)
+    float max_dist = p->max_dist;
+    if (!(max_dist > 0.f)) {
+        float density;
+        LGR_TRY(lgr_cloud_density_dev(ctx, d_tgt, nt, 0.8f, &density));
+        max_dist = 4.f * density;
+    }
+    const float min_dist = p->min_dist > 0.f ? p->min_dist : max_dist;
+    LGR_CHECK(ctx, max_dist > 0.f && dist_ok(max_dist) && min_dist <= max_dist, LGR_ERR_INVALID_ARG);
+    lgr_plane_target pt;   // (its radius is 2 x the threshold it is given: the cell is 1.001 x max_dist, and no d_k exceeds max_dist)
+    LGR_TRY(lgr_plane_target_setup(ctx, d_tgt, nt, max_dist * 0.5f, 1e18f, &pt));
+    LGR_CHECK(ctx, pt.radius == max_dist, LGR_ERR_INVALID_ARG);   // (a max_dist whose half is not representable)
+    const GridDev& g = pt.g;
+    float bb[12];
+    LGR_TRY(lgr_bbox_host(ctx, d_tgt, nt, bb));
+    IcpConst K{};
+    float* c3 = &K.cx;
+    for (int a = 0; a < 3; ++a) {
+        c3[a] = (bb[a] + bb[3 + a]) * 0.5f;
+        if (!(fabsf(c3[a]) <= FLT_MAX)) c3[a] = 0.f;   // no finite target point, or a box whose centre overflows
+    }
+    K.min_dist = min_dist; K.shrink = p->shrink; K.rot_eps = p->rot_eps; K.trans_eps = p->trans_eps; K.max_iterations = max_it;
+    // the levels: nb[0] workgroups of points, then 256 -> 1 until one entry is left
+    long long pad_n = 1;
+    while (pad_n < ns) pad_n <<= 1;
+    size_t nb[5], off[5], words = 0;
+    int levels = 0;
+    for (size_t n = (size_t) ns;;) {
+        n = cdivz(n, ICP_BLOCK);
+        nb[levels] = n; off[levels] = words;
+        words += ICP_SLOTS * n;
+        ++levels;
+        if (n == 1) break;
+    }
+    IcpState* S;
+    double* part;
+    lgr_icp_step* d_trace;
+    char* h;
+    LGR_TRY(lgr_ws_t(ctx, WS_ICP_STATE, 1, &S));
+    LGR_TRY(lgr_ws_t(ctx, WS_ICP_PART, words, &part));
+    LGR_TRY(lgr_ws_t(ctx, WS_ICP_TRACE, (size_t) max_it, &d_trace));
+    const size_t h_trace_off = (sizeof(IcpState) + 63) & ~(size_t) 63;
+    LGR_TRY(lgr_pinned(ctx, h_trace_off + (size_t) max_it * sizeof(lgr_icp_step), (void**) &h));
+    auto iteration = [&]() {
+        icp_terms_kernel<<<(unsigned) nb[0], ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, part, nb[0]);
+        long long pad = pad_n;
+        for (int l = 1; l < levels; ++l) {
+            pad >>= 8;   // >= 2 wherever level l exists: more than 256^l points
+            icp_tree_kernel<<<dim3((unsigned) nb[l], ICP_SLOTS), ICP_BLOCK, 0, ctx->stream>>>(S, part + off[l - 1], nb[l - 1], (long long) nb[l - 1], pad, part + off[l], nb[l]);
+        }
+        icp_step_kernel<<<1, 64, 0, ctx->stream>>>(S, part + off[levels - 1], 1, K, d_trace);
+    };
+    IcpState hs{};
+    memcpy(hs.T, T0, 64);
+    hs.d = max_dist;
+    hs.rmse = hs.rmse0 = FLT_MAX;
+    memcpy(h, &hs, sizeof hs);   // (pinned: the upload reads it in stream order, ahead of the first read-back that overwrites it)
+    LGR_HIP(ctx, hipMemcpyAsync(S, h, sizeof(IcpState), hipMemcpyHostToDevice, ctx->stream));
+    // ---- the iterations, LGR_ICP_GROUP at a time; nothing of an iteration passes through the host
+    int enqueued = 0;
+    for (;;) {
+        const int group = std::min((int) LGR_ICP_GROUP, max_it - enqueued);
+        for (int k = 0; k < group; ++k) iteration();
+        LGR_HIP(ctx, hipGetLastError());
+        LGR_HIP(ctx, hipMemcpyAsync(h, S, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
+        if (trace)   // the entries this group can have written
+            LGR_HIP(ctx, hipMemcpyAsync(h + h_trace_off + (size_t) enqueued * sizeof(lgr_icp_step), d_trace + enqueued, (size_t) group * sizeof(lgr_icp_step),
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        enqueued += group;
+        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(&hs, h, sizeof hs);
+        if (hs.done) break;
+        LGR_CHECK(ctx, enqueued < max_it, LGR_ERR_HIP);   // every iteration was evaluated: the device must have stopped
+    }
+    fill_result(hs, max_dist, out);
+    if (trace) memcpy(trace, h + h_trace_off, (size_t) hs.n_eval * sizeof(lgr_icp_step));
+    if (n_trace) *n_trace = trace ? hs.n_eval : 0;
+    return LGR_OK;
+}
+
+extern "C" int lgr_icp_plane_host(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T0[16], const lgr_icp_params* p,
+                                  lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, T0 && out && ns >= 0 && (src || ns == 0) && tgt && nt > 1 && params_ok(p) && (!trace || n_trace), LGR_ERR_INVALID_ARG);
+    float *ds, *dt;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    return lgr_icp_plane_dev(ctx, ds, ns, dt, nt, T0, p, out, trace, n_trace);
+}

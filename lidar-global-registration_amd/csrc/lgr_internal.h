@@ -155,6 +155,7 @@ enum {
     // direction the upper bounds, candidate counts and lists, fallback list and flags, counters, the fallback rows and their results
     WS_DENSEF_OPS_A, WS_DENSEF_OPS_B, WS_DENSEF_MISC_A, WS_DENSEF_MISC_B, WS_DENSEF_IRR_A, WS_DENSEF_IRR_B, WS_DENSEF_U, WS_DENSEF_CNT, WS_DENSEF_CAND,
     WS_DENSEF_FB, WS_DENSEF_ISFB, WS_DENSEF_DEV, WS_DENSEF_FBROWS, WS_DENSEF_FBIDX, WS_DENSEF_FBDIST, WS_DENSEF_CENTRE,
+    WS_ICP_STATE, WS_ICP_PART, WS_ICP_TRACE,   // lgr_icp.hip: the loop's state, the tree's partials level by level, the trace
     WS_COUNT
 };
 static_assert(WS_COUNT <= 224, "grow lgr_ctx::ws");

@@ -455,6 +455,29 @@ inline Matrix4f refineTransformation(const PointNCloud::ConstPtr& src, const Poi
     return refineTransformation(src, tgt, tn, parameters, max_steps, result);
 }
 
+// ---- not in the reference: point-to-plane ICP from tn (lgr_icp_plane_host).  max_dist <= 0: 4 x the target's
+// density; the other parameters are lgr_default_icp_params' (the overload with `params` takes them all from the caller).
+inline Matrix4f icpPointToPlane(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn, const lgr_icp_params& params,
+                                lgr_icp_result& result) {
+    check(lgr_icp_plane_host(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), tn.data(), &params, &result, nullptr, nullptr),
+          "icpPointToPlane");
+    Matrix4f out;
+    std::memcpy(out.data(), result.transformation, 64);
+    return out;
+}
+inline Matrix4f icpPointToPlane(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn, float max_dist, int max_iterations,
+                                lgr_icp_result& result) {
+    lgr_icp_params ip;
+    lgr_default_icp_params(&ip);
+    ip.max_dist = max_dist;
+    ip.max_iterations = max_iterations;
+    return icpPointToPlane(src, tgt, tn, ip, result);
+}
+inline Matrix4f icpPointToPlane(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn, float max_dist, int max_iterations) {
+    lgr_icp_result result;
+    return icpPointToPlane(src, tgt, tn, max_dist, max_iterations, result);
+}
+
 // ---- include/hypotheses.h:10-12
 inline void updateHypotheses(std::vector<Matrix4f>& transformations, std::vector<float>& metrics, const Matrix4f& new_transformation,
                              float new_metric, const AlignmentParameters& parameters) {

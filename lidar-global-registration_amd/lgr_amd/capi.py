@@ -212,6 +212,47 @@ def refine_params(score_id=None, max_steps=None, threshold=None):
     return p
 
 
+ICP_MAX_ITERATIONS, ICP_GROUP = 1024, 8   # LGR_ICP_MAX_ITERATIONS, LGR_ICP_GROUP
+ICP_STOP_MAX_ITERATIONS, ICP_STOP_CONVERGED, ICP_STOP_NO_PAIRS, ICP_STOP_DEGENERATE = 0, 1, 2, 3
+ICP_STOP_NAMES = ("max_iterations", "converged", "no_pairs", "degenerate")
+
+
+class IcpParams(C.Structure):
+    """lgr_icp_params (include/lgr.h)"""
+    _fields_ = [("max_iterations", C.c_int32), ("max_dist", C.c_float), ("min_dist", C.c_float), ("shrink", C.c_float), ("rot_eps", C.c_float),
+                ("trans_eps", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class IcpStep(C.Structure):
+    """lgr_icp_step (include/lgr.h): one evaluated iteration of a point-to-plane ICP"""
+    _fields_ = [("transformation", C.c_float * 16), ("dist", C.c_float), ("pairs", C.c_int32), ("rmse", C.c_float), ("rot", C.c_float), ("trans", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+    def matrix(self):
+        return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
+
+
+class IcpResult(C.Structure):
+    """lgr_icp_result (include/lgr.h): the final transform, why the loop ended, the pairs and rmse of the last and the first iteration"""
+    _fields_ = [("transformation", C.c_float * 16), ("iterations", C.c_int32), ("stop", C.c_int32), ("max_dist", C.c_float), ("pairs", C.c_int32),
+                ("rmse", C.c_float), ("pairs0", C.c_int32), ("rmse0", C.c_float), ("reserved", C.c_int32 * 5)]
+    trace = None   # list of IcpStep (trace=True), set by Context.icp_plane*
+
+    def matrix(self):
+        return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
+
+
+def icp_params(max_iterations=None, max_dist=None, min_dist=None, shrink=None, rot_eps=None, trans_eps=None):
+    p = IcpParams()
+    _lib.lgr_default_icp_params(C.byref(p))
+    if max_iterations is not None:
+        p.max_iterations = int(max_iterations)
+    for name, v in (("max_dist", max_dist), ("min_dist", min_dist), ("shrink", shrink), ("rot_eps", rot_eps), ("trans_eps", trans_eps)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
 class TemperatureOut(C.Structure):
     """lgr_temperature_out (include/lgr.h): five optional per-point arrays of one temperature map."""
     _fields_ = [("temp_distance", C.c_void_p), ("temp_normal", C.c_void_p), ("color_distance", C.c_void_p), ("color_normal", C.c_void_p), ("nn", C.c_void_p)]
@@ -1593,6 +1634,28 @@ class Context:
         """lgr_refine_plane: numpy in (caller weights in metric_params a numpy float32 [ns]), RefineResult out"""
         src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
         return self._refine(_lib.lgr_refine_plane, src, tgt, T0, score_id, max_steps, threshold, metric_params, trace)
+
+    # ---- point-to-plane ICP (include/lgr.h lgr_icp_plane*) ----
+    def _icp(self, fn, src, tgt, T0, params, trace, kw):
+        p = params if params is not None else icp_params(**kw)
+        out = IcpResult()
+        tr = (IcpStep * max(p.max_iterations, 1))() if trace else None
+        n_tr = C.c_int(0)
+        self.check(fn(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T0), C.byref(p), C.byref(out), tr, C.byref(n_tr) if trace else None))
+        if trace:
+            out.trace = [tr[i] for i in range(n_tr.value)]
+        return out
+
+    def icp_plane(self, src, tgt, T0, params=None, trace=False, **kw):
+        """lgr_icp_plane_dev on cuda clouds [n, 12] (the target with normals): T0 (4x4) refined by point-to-plane ICP -> IcpResult (.matrix(),
+        .iterations, .stop, .max_dist, .pairs, .rmse, .pairs0, .rmse0; .trace with trace=True).  params: an IcpParams, or the keywords of
+        capi.icp_params (max_iterations, max_dist, min_dist, shrink, rot_eps, trans_eps; max_dist <= 0: 4 x the target's density)."""
+        return self._icp(_lib.lgr_icp_plane_dev, src, tgt, T0, params, trace, kw)
+
+    def icp_plane_host(self, src, tgt, T0, params=None, trace=False, **kw):
+        """lgr_icp_plane_host: numpy in, IcpResult out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        return self._icp(_lib.lgr_icp_plane_host, src, tgt, T0, params, trace, kw)
 
     def analysis_metric(self, src, tgt, corr, T, T_gt=None, metric_id=METRIC_UNIFORMITY, score_id=SCORE_MSE, weights=None, weight=None):
         """lgr_analysis_metric_dev: what AlignmentAnalysis::start's first statement and buildCorrectInliers yield under metric_id -> MetricEval

@@ -366,7 +366,8 @@ GATED = ["normals_kernel", "normals_wave_kernel", "refit_kernel", "hypotheses_ke
          "refine_dense_kernel", "refine_sum_kernel", "refine_decide_kernel", "dense_match_kernel", "densef_sweep_kernel", "knn_match_kernel", "knn_merge_kernel", "knnd_kth_kernel", "knnf_select_kernel",
          "vote_matches_kernel", "ratio_test_kernel", "gt_foot_kernel", "gt_batch_kernel", "gt_seqsum_wide_kernel",
          "ho_small_kernel", "ho_act_kernel", "ho_keys_kernel",
-         "teaser_adj_kernel", "teaser_clique_kernel", "teaser_rotation_kernel", "teaser_shift_kernel", "teaser_mask_kernel"]
+         "teaser_adj_kernel", "teaser_clique_kernel", "teaser_rotation_kernel", "teaser_shift_kernel", "teaser_mask_kernel",
+         "icp_terms_kernel", "icp_tree_kernel", "icp_step_kernel"]
 
 
 SCRATCH_ANY = 64   # bytes of scratch memory per work item that no kernel of the library may exceed (the gated ones: none at all)

@@ -5,6 +5,7 @@
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
                                  [--debug-dir DIR] [--hypotheses N [--hypotheses-plane]] [--refine N]
+                                 [--icp N [--icp-max-dist D] [--icp-shrink S [--icp-min-dist M]]]
                                  [--measure N [--measure-seed S0] [--measurements test_measurements.csv]] [--save-features DIR]
                                  [--order canonical|reference] [--alignment ransac|gror|teaser]
 
@@ -29,6 +30,11 @@ With --refine N: after everything above, the found transformation goes through u
 refit, evaluation, while the metric rises) under the run's score -- and the run's weights under weighted_closest_plane; the evaluation before
 and after is printed, the refined transformation is appended to --out as a second row named <name>_refined, and with --ground-truth it is
 analysed like the first (a second results.csv row under that name).
+With --icp N: the found transformation goes through up to N iterations of point-to-plane ICP (lgr_icp_plane) with pairing
+distance D (--icp-max-dist; default 4 x the target's density), shrunk by S per iteration (--icp-shrink, default 1) down to M (--icp-min-dist;
+default with S < 1: half the target's density); the pairs and rmse of the first and the last iteration are printed, the result is appended
+to --out as a row named <name>_icp, and with --ground-truth it is analysed like the first.  --icp and --refine may be combined: the ICP runs
+first and the refinement starts from its result (rows <name>_icp and <name>_icp_refined).
 With --measure N (needs --ground-truth): the reference's `measure` test type (measureTestResults, src/main.cpp:312-382) through lgr_measure --
 N alignments that differ in the RANSAC seed only (S0, S0 + 1, ...; S0 defaults to the profile's seed), one correspondence search for all of
 them, all judged against the ground truth in one batch; one line per run, then the aggregate row, appended to --measurements when given
@@ -91,6 +97,11 @@ def main():
     ap.add_argument("--hypotheses-plane", action="store_true",
                     help="with --hypotheses: build the set through lgr_ransac_multi_ex, which also takes closest_plane, combination and weighted_closest_plane")
     ap.add_argument("--refine", type=int, default=0, metavar="N", help="refine the result by up to N dense closest-plane steps (lgr_refine_plane)")
+    ap.add_argument("--icp", type=int, default=0, metavar="N", help="then up to N iterations of point-to-plane ICP (lgr_icp_plane); runs before --refine")
+    ap.add_argument("--icp-max-dist", type=float, default=0.0, metavar="D", help="pairing distance of the first iteration (<= 0: 4 x the target's density)")
+    ap.add_argument("--icp-shrink", type=float, default=1.0, metavar="S", help="factor on the pairing distance per iteration, in (0, 1]")
+    ap.add_argument("--icp-min-dist", type=float, default=0.0, metavar="M",
+                    help="floor of the pairing distance (<= 0: half the target's density when --icp-shrink < 1, else the first iteration's distance)")
     ap.add_argument("--measure", type=int, default=0, metavar="N",
                     help="the measure test type: N seeded runs judged against --ground-truth, and their test_measurements.csv row")
     ap.add_argument("--measure-seed", type=int, default=None, metavar="S0", help="seed of the first run (default: the profile's seed); run i uses S0 + i")
@@ -116,6 +127,10 @@ def main():
         ap.error("--matching ratio needs --randomness 1")
     if not 0 <= a.refine <= 1024:
         ap.error("--refine takes 0 .. 1024 steps")
+    if not 0 <= a.icp <= 1024:
+        ap.error("--icp takes 0 .. 1024 iterations")
+    if not 0.0 < a.icp_shrink <= 1.0:
+        ap.error("--icp-shrink takes a factor in (0, 1]")
     if a.metrics_csv and not a.ground_truth:
         ap.error("--metrics-csv needs --ground-truth")
     if a.hypotheses_plane and not a.hypotheses:
@@ -169,6 +184,8 @@ def main():
         debug_files(ctx, capi, formats, a, p, clouds, T, lrf)
     if a.hypotheses:
         hypotheses(ctx, capi, formats, a, p, clouds, lrf)
+    if a.icp:
+        T, name = icp(ctx, capi, formats, a, p, clouds, res, T, name, lrf, ld["density_tgt"])
     if a.refine:
         refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf)
     if a.measure:
@@ -263,6 +280,27 @@ def refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
     if a.ground_truth:
         a.metrics_csv = None   # estimateTestMetric's row belongs to the alignment
         analyse(ctx, capi, formats, a, p, clouds, res, Tr, name + "_refined", lrf)
+
+
+def icp(ctx, capi, formats, a, p, clouds, res, T, name, lrf, density_tgt):
+    """the found transformation through lgr_icp_plane; its row in --out and, with a ground truth, its analysis -> (transformation, row name)"""
+    import numpy as np
+    min_dist = a.icp_min_dist if a.icp_min_dist > 0 else (0.5 * density_tgt if a.icp_shrink < 1.0 else 0.0)
+    t = time.perf_counter()
+    r = ctx.icp_plane(clouds[0], clouds[1], T, max_iterations=a.icp, max_dist=a.icp_max_dist, min_dist=min_dist, shrink=a.icp_shrink)
+    dt = time.perf_counter() - t
+    print(f"\nicp in {1e3 * dt:.1f} ms: {r.iterations} iterations of at most {a.icp}, stopped by {capi.ICP_STOP_NAMES[r.stop]} (max_dist {r.max_dist:.6g})")
+    print(f"  first: pairs={r.pairs0} rmse={r.rmse0:.7f}")
+    print(f"   last: pairs={r.pairs} rmse={r.rmse:.7f}")
+    Ti = r.matrix()
+    print(np.array2string(Ti, precision=6, suppress_small=True))
+    if a.out:
+        formats.save_transformation(a.out, name + "_icp", Ti)
+    if a.ground_truth:
+        metrics_csv, a.metrics_csv = a.metrics_csv, None   # estimateTestMetric's row belongs to the alignment
+        analyse(ctx, capi, formats, a, p, clouds, res, Ti, name + "_icp", lrf)
+        a.metrics_csv = metrics_csv
+    return Ti, name + "_icp"
 
 
 def hypotheses(ctx, capi, formats, a, p, clouds, lrf):
