@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-/* ABI revision.  Still 5 with point-to-plane ICP: lgr_icp_params, lgr_icp_step, lgr_icp_result, LGR_ICP_*, lgr_default_icp_params,
+/* ABI revision.  Still 5 with the ICP variants: lgr_icp_ex_params, LGR_ICP_POINT_TO_* / LGR_ICP_PLANE_TO_PLANE, LGR_ICP_ROBUST_*,
+ * lgr_default_icp_ex_params, lgr_icp_ex_dev and lgr_icp_ex_host are additions; lgr_icp_plane* and its structs did not change.  Still 5 with point-to-plane ICP: lgr_icp_params, lgr_icp_step, lgr_icp_result, LGR_ICP_*, lgr_default_icp_params,
  * lgr_icp_plane_dev and lgr_icp_plane_host are additions; no struct or entry point that existed changed.  Still 5 with the reference point order on the device: lgr_hash_order_dev, lgr_downsample_order_dev, lgr_dedupe_order_dev,
  * lgr_preprocess_order_dev and lgr_selfcheck_hash_order are additions; no struct or entry point that existed changed.  Still 5 with the prepared clouds: lgr_cloud, struct lgr_cloud_info, lgr_cloud_level_info, lgr_cloud_prepare*, lgr_cloud_destroy,
  * lgr_cloud_info, lgr_cloud_keypoints*, lgr_cloud_level*, lgr_correspondences_prepared*, lgr_align_prepared and the host twin lgr_nearest are
@@ -1160,6 +1161,52 @@ int lgr_icp_plane_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, 
                       const lgr_icp_params*, lgr_icp_result* out /* host */, lgr_icp_step* trace_or_null /* host */, int* n_trace_or_null);
 int lgr_icp_plane_host(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T0_16[16], const lgr_icp_params*,
                        lgr_icp_result* out, lgr_icp_step* trace_or_null, int* n_trace_or_null);   /* host twin */
+
+/* ---- ICP variants: the loop of lgr_icp_plane* with another contribution per source point ("ICP variants"; CPU
+ *      statement tests/cpp/icp_ex_ref.cpp).  The set-up, d_k, the balanced f64 tree padded with +0.0, the solve, the step, the stop rule,
+ *      the trace and the grouped enqueue are those of lgr_icp_plane*; `base` is read exactly as lgr_icp_plane* reads its parameters.
+ *      What source point i contributes in iteration k, all in f64, one IEEE operation at a time:
+ *        1. p' = plane_move(T_k, p), j = nearest_within(d_k^2) by the rule above; no neighbour or a non-finite p': no pair.
+ *        2. omega = weights ? (double) weights[i] : 1; an omega that is not finite or not > 0: no pair.
+ *        3. n = the target normal of j; m = the source normal of i rotated by T_k's rotation block, m_a = (T[a] nx + T[4+a] ny) + T[8+a] nz.
+ *           POINT_TO_PLANE reads n, PLANE_TO_PLANE n and m, the gate n and m, POINT_TO_POINT without the gate no normal at all.  A normal
+ *           that is read and not finite: no pair.
+ *        4. the gate (on iff min_normal_cos > -1): the pair is kept iff (mx nx + my ny) + mz nz >= (double) min_normal_cos.  It rejects the
+ *           NEAREST neighbour; it does not look for the nearest compatible one.
+ *        5. e = p' - q, u = p' - c, J = [-[u]x | I] with columns j_0 = (0, -uz, uy), j_1 = (uz, 0, -ux), j_2 = (-uy, ux, 0), j_3..5 = unit.
+ *           POINT_TO_PLANE (one row): r = n . e, rho = |r|, g = (u x n, n), as lgr_icp_plane*.
+ *           POINT_TO_POINT (three rows): M = I, rho^2 = e^T M e = e . e.
+ *           PLANE_TO_PLANE (three rows; generalised ICP with covariances from the normals): Sigma = 2 I - (1 - eps)(n n^T + m m^T),
+ *           M = Sigma^-1 by adjugate over determinant (icp_inv_sym3); a determinant that is not finite or not > 0: no pair;
+ *           rho^2 = e^T M e, rho its square root.  Normals are used as given: pass unit normals.
+ *        6. w = icp_robust_weight(robust, rho, k): NONE 1; HUBER rho <= k ? 1 : k / rho; CAUCHY 1 / (1 + rho^2 / k^2); TUKEY rho < k ?
+ *           (1 - rho^2 / k^2)^2 : 0.  W = w omega; a W that is not > 0: no pair (a point Tukey switches off does not count in `pairs`).
+ *        7. the 28 terms.  One row: (W g_a) g_b, (W g_a) r, and r r unweighted.  Three rows: W (j_a . (M j_b)), W (j_a . (M e)), and
+ *           e . (M e) unweighted.  rmse = sqrt(slot 27 / pairs) is the variant's own unweighted residual: the point-to-plane distance, the
+ *           point-to-point distance, and for PLANE_TO_PLANE the Mahalanobis distance under M.  Fewer than 6 pairs: NO_PAIRS, every variant.
+ *      POINT_TO_PLANE / ROBUST_NONE / gate off / weights NULL returns the bytes of lgr_icp_plane* (W == 1 changes no product).
+ *      Refused with LGR_ERR_INVALID_ARG before any work: everything lgr_icp_plane* refuses; an unknown variant or robust; with a robust
+ *      kernel a robust_scale that is not finite or not > 0 (it is not read under ROBUST_NONE); min_normal_cos NaN or outside [-1, 1];
+ *      plane_eps NaN, negative, or non-zero outside [1e-6, 1] (checked under every variant); a non-zero reserved word at either level.
+ *      The idle calls (empty source, max_iterations 0) return what lgr_icp_plane* returns.  Not built: a symmetric objective, a search for
+ *      the nearest compatible neighbour, the information matrix as an output.  The host form is lgr_icp_ex_host for the reason given above. ---- */
+enum { LGR_ICP_POINT_TO_PLANE = 0, LGR_ICP_POINT_TO_POINT = 1, LGR_ICP_PLANE_TO_PLANE = 2 };
+enum { LGR_ICP_ROBUST_NONE = 0, LGR_ICP_ROBUST_HUBER = 1, LGR_ICP_ROBUST_CAUCHY = 2, LGR_ICP_ROBUST_TUKEY = 3 };
+typedef struct {
+    lgr_icp_params base;      /* read exactly as lgr_icp_plane* reads it (reserved words 0) */
+    int32_t variant;          /* LGR_ICP_* */
+    int32_t robust;           /* LGR_ICP_ROBUST_* */
+    float   robust_scale;     /* k, finite and > 0, in units of the variant's residual rho; read only when robust != NONE */
+    float   min_normal_cos;   /* in [-1, 1]; the gate is on iff > -1 (the default filler writes -1) */
+    float   plane_eps;        /* PLANE_TO_PLANE only: 0 = 1e-3, else in [1e-6, 1] */
+    int32_t reserved[3];      /* 0 */
+    const float* weights;     /* NULL, or ns per-source-point weights: device pointer for _dev, host pointer for _host */
+} lgr_icp_ex_params;
+void lgr_default_icp_ex_params(lgr_icp_ex_params* p);   /* base: lgr_default_icp_params; min_normal_cos -1; everything else 0 */
+int lgr_icp_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T0_16[16] /* host */,
+                   const lgr_icp_ex_params*, lgr_icp_result* out /* host */, lgr_icp_step* trace_or_null /* host */, int* n_trace_or_null);
+int lgr_icp_ex_host(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T0_16[16], const lgr_icp_ex_params*,
+                    lgr_icp_result* out, lgr_icp_step* trace_or_null, int* n_trace_or_null);   /* host twin */
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,7 @@
 // lgr_icp.hip -- point-to-plane ICP on the device for gfx950 (include/lgr.h lgr_icp_plane*).  A statement of this library's own: DESIGN.md
 // section 4, "Point-to-plane ICP"; the CPU statement is tests/cpp/icp_ref.cpp; the step's f64 arithmetic is lgr_icp_math.h for both.
+// lgr_icp_ex* (point-to-point, plane-to-plane, robust kernels, the normal gate, point weights; section 4, "ICP variants";
+// tests/cpp/icp_ex_ref.cpp) is the same loop with icp_terms_ex_kernel in the place of icp_terms_kernel.
 //
 // Set-up, once per call: max_dist (the caller's, or 4 x the target's density), ONE grid over the target with cell 1.001 x max_dist, the
 // centre of the target's bounding box.  An iteration, all on the stream:
@@ -115,6 +117,162 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_terms_kernel(GridDev g, const f
     }
 }
 
+// ---- lgr_icp_ex*: the same slots from another contribution per point ("ICP variants"; tests/cpp/icp_ex_ref.cpp)
+struct IcpEx {
+    double k;         // the robust scale
+    double cos_min;   // the gate's cosine
+    double s;         // 1 - eps of plane-to-plane
+    const float* w;   // the point weights
+};
+
+// j_a . v for the columns of J = [-[u]x | I]: the two products of a rotational column, the entry itself of a translational one
+__device__ __forceinline__ double icp_jdot(int a, const double* v, double ux, double uy, double uz) {
+    return a == 0 ? v[2] * uy - v[1] * uz : a == 1 ? v[0] * uz - v[2] * ux : a == 2 ? v[1] * ux - v[0] * uy : v[a - 3];
+}
+
+// As icp_terms_kernel: a source point per lane, one product formed immediately before its butterfly.  Live across the 28 butterflies:
+// one row W g, g and r (13 doubles); three rows u, M j_b (mj: 18 doubles, of which the last nine are M's own entries), M e and W.
+template <int VARIANT, int ROBUST, bool GATE, bool WEIGHTS>
+__global__ __launch_bounds__(ICP_BLOCK) void icp_terms_ex_kernel(GridDev g, const float4* __restrict__ src, int ns, long long pad_n, const IcpState* __restrict__ S, float cx,
+                                                                 float cy, float cz, IcpEx X, double* __restrict__ part, size_t stride) {
+    if (S->done) return;
+    constexpr bool ONE_ROW = VARIANT == ICP_POINT_TO_PLANE, NEED_M = GATE || VARIANT == ICP_PLANE_TO_PLANE, NEED_N = ONE_ROW || NEED_M;
+    __shared__ double sh[ICP_WAVES][ICP_SLOTS];
+    const long long i = (long long) blockIdx.x * ICP_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float d = S->d;
+    bool has = false;
+    double W = 1.0, ux = 0, uy = 0, uz = 0, r = 0, rr = 0;
+    double gv[6] = {0, 0, 0, 0, 0, 0}, wg[6] = {0, 0, 0, 0, 0, 0};   // one row: g, W g
+    double mj[6][3] = {}, me[3] = {0, 0, 0};                         // three rows: M j_b, M e
+    if (i < ns) {
+        const float4 P = src[(size_t) i * 3];
+        float px, py, pz, d2;
+        int j;
+        plane_move(S->T, P.x, P.y, P.z, px, py, pz);
+        const int t = nearest_within(g, px, py, pz, d * d, d2, j);   // (a non-finite moved point walks nothing: -1)
+        bool ok = t >= 0;
+        double om = 1.0;
+        if (WEIGHTS && ok) {
+            om = (double) X.w[i];
+            ok = icp_finite(om) && om > 0.0;
+        }
+        double nx = 0, ny = 0, nz = 0, mx = 0, my = 0, mz = 0;
+        if (NEED_N && ok) {
+            const float4 N = g.pnrm[t];   // the grid's copy of tgt[j]'s normal: the same bits
+            ok = lgr_finite3(N.x, N.y, N.z);
+            nx = (double) N.x; ny = (double) N.y; nz = (double) N.z;
+        }
+        if (NEED_M && ok) {
+            const float4 Ns = src[(size_t) i * 3 + 1];
+            const float* T = S->T;
+            ok = lgr_finite3(Ns.x, Ns.y, Ns.z);
+            const double sx = (double) Ns.x, sy = (double) Ns.y, sz = (double) Ns.z;
+            mx = ((double) T[0] * sx + (double) T[4] * sy) + (double) T[8] * sz;
+            my = ((double) T[1] * sx + (double) T[5] * sy) + (double) T[9] * sz;
+            mz = ((double) T[2] * sx + (double) T[6] * sy) + (double) T[10] * sz;
+            if (GATE) ok = ok && (mx * nx + my * ny) + mz * nz >= X.cos_min;
+        }
+        if (ok) {
+            const float4 Q = g.pxyz[t];
+            ux = (double) px - (double) cx; uy = (double) py - (double) cy; uz = (double) pz - (double) cz;
+            const double ex = (double) px - (double) Q.x, ey = (double) py - (double) Q.y, ez = (double) pz - (double) Q.z;
+            double rho;
+            if (ONE_ROW) {
+                r = (nx * ex + ny * ey) + nz * ez;
+                rr = r * r;
+                rho = __builtin_fabs(r);
+                gv[0] = uy * nz - uz * ny;
+                gv[1] = uz * nx - ux * nz;
+                gv[2] = ux * ny - uy * nx;
+                gv[3] = nx; gv[4] = ny; gv[5] = nz;
+            } else {
+                double M[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};   // (xx, xy, xz, yy, yz, zz); point-to-point: I through the same expressions
+                if (VARIANT == ICP_PLANE_TO_PLANE) {
+                    const double s = X.s;
+                    const double Sg[6] = {2.0 - s * (nx * nx + mx * mx), -(s * (nx * ny + mx * my)), -(s * (nx * nz + mx * mz)),
+                                          2.0 - s * (ny * ny + my * my), -(s * (ny * nz + my * mz)), 2.0 - s * (nz * nz + mz * mz)};
+                    ok = icp_inv_sym3(Sg, M);
+                }
+                const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    mj[0][q] = Mr[q][2] * uy - Mr[q][1] * uz;
+                    mj[1][q] = Mr[q][0] * uz - Mr[q][2] * ux;
+                    mj[2][q] = Mr[q][1] * ux - Mr[q][0] * uy;
+                    mj[3][q] = Mr[q][0]; mj[4][q] = Mr[q][1]; mj[5][q] = Mr[q][2];
+                    me[q] = (Mr[q][0] * ex + Mr[q][1] * ey) + Mr[q][2] * ez;
+                }
+                rr = (ex * me[0] + ey * me[1]) + ez * me[2];
+                rho = ROBUST != ICP_ROBUST_NONE ? __builtin_sqrt(rr) : 0.0;
+            }
+            if (ROBUST != ICP_ROBUST_NONE || WEIGHTS) {
+                W = icp_robust_weight(ROBUST, rho, X.k) * om;
+                ok = ok && W > 0.0;
+            }
+            if (ONE_ROW) {
+#pragma unroll
+                for (int a = 0; a < 6; ++a) wg[a] = W * gv[a];
+            }
+            has = ok;
+        }
+    }
+    const double fill = i < pad_n ? 0.0 : -0.0;   // the statement's padding / the identity behind it
+    int slot = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b, ++slot) {
+            const double x = ONE_ROW ? wg[a] * gv[b] : W * icp_jdot(a, mj[b], ux, uy, uz);
+            const double s = icp_wave_tree(has ? x : fill);
+            if (lane == 0) sh[wave][slot] = s;
+        }
+#pragma unroll
+    for (int a = 0; a < 6; ++a, ++slot) {
+        const double x = ONE_ROW ? wg[a] * r : W * icp_jdot(a, me, ux, uy, uz);
+        const double s = icp_wave_tree(has ? x : fill);
+        if (lane == 0) sh[wave][slot] = s;
+    }
+    {
+        const double s = icp_wave_tree(has ? rr : fill);
+        if (lane == 0) sh[wave][ICP_TERMS - 1] = s;
+    }
+    const long long cnt = __popcll(__ballot(has));
+    if (lane == 0) sh[wave][ICP_TERMS] = __longlong_as_double(cnt);
+    __syncthreads();
+    if (threadIdx.x < ICP_TERMS) part[threadIdx.x * stride + blockIdx.x] = icp_block_tree(sh, threadIdx.x);
+    else if (threadIdx.x == ICP_TERMS) {
+        long long c = 0;
+#pragma unroll
+        for (int w = 0; w < ICP_WAVES; ++w) c += __double_as_longlong(sh[w][ICP_TERMS]);
+        part[ICP_TERMS * stride + blockIdx.x] = __longlong_as_double(c);
+    }
+}
+
+using IcpTermsExFn = void (*)(GridDev, const float4*, int, long long, const IcpState*, float, float, float, IcpEx, double*, size_t);
+
+template <int V, int R>
+IcpTermsExFn icp_ex_pick2(bool gate, bool w) {
+    return gate ? (w ? icp_terms_ex_kernel<V, R, true, true> : icp_terms_ex_kernel<V, R, true, false>)
+                : (w ? icp_terms_ex_kernel<V, R, false, true> : icp_terms_ex_kernel<V, R, false, false>);
+}
+template <int V>
+IcpTermsExFn icp_ex_pick1(int robust, bool gate, bool w) {
+    switch (robust) {
+        case ICP_ROBUST_HUBER: return icp_ex_pick2<V, ICP_ROBUST_HUBER>(gate, w);
+        case ICP_ROBUST_CAUCHY: return icp_ex_pick2<V, ICP_ROBUST_CAUCHY>(gate, w);
+        case ICP_ROBUST_TUKEY: return icp_ex_pick2<V, ICP_ROBUST_TUKEY>(gate, w);
+        default: return icp_ex_pick2<V, ICP_ROBUST_NONE>(gate, w);
+    }
+}
+IcpTermsExFn icp_ex_pick(int variant, int robust, bool gate, bool w) {
+    switch (variant) {
+        case ICP_POINT_TO_POINT: return icp_ex_pick1<ICP_POINT_TO_POINT>(robust, gate, w);
+        case ICP_PLANE_TO_PLANE: return icp_ex_pick1<ICP_PLANE_TO_PLANE>(robust, gate, w);
+        default: return icp_ex_pick1<ICP_POINT_TO_PLANE>(robust, gate, w);
+    }
+}
+
 // one level of the tree: entries [256 b, 256 b + 256) of slot blockIdx.y -> entry b.  Entries from n_in on are +0.0 below pad_in
 // (= 2^m / 256^level: workgroups the statement's padding would have filled) and -0.0 from there.
 __global__ __launch_bounds__(ICP_BLOCK) void icp_tree_kernel(const IcpState* __restrict__ S, const double* __restrict__ in, size_t stride_in, long long n_in, long long pad_in,
@@ -194,6 +352,16 @@ bool params_ok(const lgr_icp_params* p) {
     return dist_ok(p->max_dist) && dist_ok(p->min_dist) && p->shrink > 0.f && p->shrink <= 1.f && p->rot_eps >= 0.f && p->trans_eps >= 0.f;
 }
 
+bool ex_params_ok(const lgr_icp_ex_params* p) {
+    if (!p || !params_ok(&p->base)) return false;
+    if (p->variant < LGR_ICP_POINT_TO_PLANE || p->variant > LGR_ICP_PLANE_TO_PLANE || p->robust < LGR_ICP_ROBUST_NONE || p->robust > LGR_ICP_ROBUST_TUKEY) return false;
+    for (int r : p->reserved)
+        if (r) return false;
+    if (p->robust != LGR_ICP_ROBUST_NONE && !(p->robust_scale > 0.f && p->robust_scale <= FLT_MAX)) return false;
+    if (!(p->min_normal_cos >= -1.f && p->min_normal_cos <= 1.f)) return false;
+    return p->plane_eps == 0.f || (p->plane_eps >= 1e-6f && p->plane_eps <= 1.f);
+}
+
 // nothing to evaluate (an empty source, no iteration allowed): T0 comes back
 void idle_result(const float* T0, const lgr_icp_params* p, int stop, lgr_icp_result* out, int* n_trace) {
     IcpState s{};
@@ -204,23 +372,11 @@ void idle_result(const float* T0, const lgr_icp_params* p, int stop, lgr_icp_res
     if (n_trace) *n_trace = 0;
 }
 
-}  // namespace
-
-extern "C" void lgr_default_icp_params(lgr_icp_params* p) {
-    if (!p) return;
-    memset(p, 0, sizeof *p);
-    p->max_iterations = 30;
-    p->shrink = 1.f;
-    p->rot_eps = 1e-6f;
-    p->trans_eps = 1e-6f;
-}
-
-extern "C" int lgr_icp_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_params* p,
-                                 lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
-    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
-    if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_CHECK(ctx, T0 && out && ns >= 0 && (d_src || ns == 0) && d_tgt && nt > 1 && params_ok(p) && aligned16(d_src) && aligned16(d_tgt), LGR_ERR_INVALID_ARG);
-    LGR_CHECK(ctx, !trace || n_trace, LGR_ERR_INVALID_ARG);
+// The loop behind lgr_icp_plane_dev and lgr_icp_ex_dev, the arguments checked by the caller: the set-up, then the iterations in groups.
+// launch_terms(g, pad_n, S, K, part, stride) enqueues the entry's terms kernel over ceil(ns / 256) workgroups.
+template <class Launch>
+int icp_run(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_params* p, lgr_icp_result* out, lgr_icp_step* trace,
+            int* n_trace, Launch launch_terms) {
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     const int max_it = p->max_iterations;
     if (ns == 0 || max_it == 0) {
@@ -271,7 +427,7 @@ extern "C" int lgr_icp_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const
     const size_t h_trace_off = (sizeof(IcpState) + 63) & ~(size_t) 63;
     LGR_TRY(lgr_pinned(ctx, h_trace_off + (size_t) max_it * sizeof(lgr_icp_step), (void**) &h));
     auto iteration = [&]() {
-        icp_terms_kernel<<<(unsigned) nb[0], ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, part, nb[0]);
+        launch_terms(g, pad_n, S, K, part, nb[0]);
         long long pad = pad_n;
         for (int l = 1; l < levels; ++l) {
             pad >>= 8;   // >= 2 wherever level l exists: more than 256^l points
@@ -307,6 +463,28 @@ extern "C" int lgr_icp_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const
     return LGR_OK;
 }
 
+}  // namespace
+
+extern "C" void lgr_default_icp_params(lgr_icp_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->max_iterations = 30;
+    p->shrink = 1.f;
+    p->rot_eps = 1e-6f;
+    p->trans_eps = 1e-6f;
+}
+
+extern "C" int lgr_icp_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_params* p,
+                                 lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
+    lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, T0 && out && ns >= 0 && (d_src || ns == 0) && d_tgt && nt > 1 && params_ok(p) && aligned16(d_src) && aligned16(d_tgt), LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, !trace || n_trace, LGR_ERR_INVALID_ARG);
+    return icp_run(ctx, d_src, ns, d_tgt, nt, T0, p, out, trace, n_trace, [&](const GridDev& g, long long pad_n, const IcpState* S, const IcpConst& K, double* part, size_t nb0) {
+        icp_terms_kernel<<<(unsigned) nb0, ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, part, nb0);
+    });
+}
+
 extern "C" int lgr_icp_plane_host(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T0[16], const lgr_icp_params* p,
                                   lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
     lgr_turn turn__(ctx);
@@ -316,4 +494,44 @@ extern "C" int lgr_icp_plane_host(lgr_ctx* ctx, const float* src, int ns, const 
     lgr_host_call hc(ctx);
     LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
     return lgr_icp_plane_dev(ctx, ds, ns, dt, nt, T0, p, out, trace, n_trace);
+}
+
+extern "C" void lgr_default_icp_ex_params(lgr_icp_ex_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    lgr_default_icp_params(&p->base);
+    p->min_normal_cos = -1.f;
+}
+
+extern "C" int lgr_icp_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_ex_params* p,
+                              lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, T0 && out && ns >= 0 && (d_src || ns == 0) && d_tgt && nt > 1 && ex_params_ok(p) && aligned16(d_src) && aligned16(d_tgt), LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, !trace || n_trace, LGR_ERR_INVALID_ARG);
+    static_assert(LGR_ICP_POINT_TO_POINT == ICP_POINT_TO_POINT && LGR_ICP_PLANE_TO_PLANE == ICP_PLANE_TO_PLANE && LGR_ICP_ROBUST_HUBER == ICP_ROBUST_HUBER &&
+                      LGR_ICP_ROBUST_CAUCHY == ICP_ROBUST_CAUCHY && LGR_ICP_ROBUST_TUKEY == ICP_ROBUST_TUKEY,
+                  "lgr.h and lgr_icp_math.h number the variants and the robust kernels alike");
+    const float eps = p->plane_eps == 0.f ? 1e-3f : p->plane_eps;
+    const IcpEx X{(double) p->robust_scale, (double) p->min_normal_cos, 1.0 - (double) eps, p->weights};
+    const IcpTermsExFn terms = icp_ex_pick(p->variant, p->robust, p->min_normal_cos > -1.f, p->weights != nullptr);
+    return icp_run(ctx, d_src, ns, d_tgt, nt, T0, &p->base, out, trace, n_trace, [&](const GridDev& g, long long pad_n, const IcpState* S, const IcpConst& K, double* part, size_t nb0) {
+        terms<<<(unsigned) nb0, ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, X, part, nb0);
+    });
+}
+
+extern "C" int lgr_icp_ex_host(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T0[16], const lgr_icp_ex_params* p,
+                               lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, T0 && out && ns >= 0 && (src || ns == 0) && tgt && nt > 1 && ex_params_ok(p) && (!trace || n_trace), LGR_ERR_INVALID_ARG);
+    float *ds, *dt, *dw;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    lgr_icp_ex_params staged = *p;
+    if (p->weights) {
+        LGR_TRY(hc.in(p->weights, (size_t) ns, &dw, 1));   // (one word of room: an empty source stages nothing)
+        staged.weights = dw;
+    }
+    return lgr_icp_ex_dev(ctx, ds, ns, dt, nt, T0, &staged, out, trace, n_trace);
 }

@@ -5,7 +5,8 @@
 //   icp_solve      A xi = -b by LDL^T without pivoting, one fixed operation order, with the pivot rule of the statement;
 //   icp_rotation   R from the unit quaternion (1, w / 2) / |(1, w / 2)|: nine polynomial expressions, no trigonometry;
 //   icp_compose    T' = [R | (c - R c) + t] o T, every entry formed in f64 and rounded to f32 once;
-//   icp_norm3, icp_rmse, icp_next_dist   the scalars of the stop rule, the report and the next iteration's distance.
+//   icp_norm3, icp_rmse, icp_next_dist   the scalars of the stop rule, the report and the next iteration's distance;
+//   icp_inv_sym3, icp_robust_weight      lgr_icp_ex*: the inverse of plane-to-plane's 3 x 3 covariance sum, the M-estimators' weights.
 // Every operation is one IEEE binary64 + - * / sqrt (binary32 where a float is named); compile with -ffp-contract=off on both sides (the
 // Makefile and the tests do).  The pairing, the 28 terms of a point and the balanced tree that sums them are NOT here: the kernels
 // (icp_terms_kernel, icp_tree_kernel) and the statement each write them on their own.
@@ -26,6 +27,36 @@ enum { ICP_TERMS = 28, ICP_STOP_MAX_ITERATIONS = 0, ICP_STOP_CONVERGED = 1, ICP_
 ICP_HD int icp_tri(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }   // a <= b
 
 ICP_HD bool icp_finite(double x) { return __builtin_fabs(x) <= 1.7976931348623157e308; }
+
+// ---- the variants of lgr_icp_ex* ("ICP variants"): the two pieces both sides share; the pairing, the gate and the
+// term products are written once in icp_terms_ex_kernel and once in tests/cpp/icp_ex_ref.cpp
+enum { ICP_POINT_TO_PLANE = 0, ICP_POINT_TO_POINT = 1, ICP_PLANE_TO_PLANE = 2, ICP_ROBUST_NONE = 0, ICP_ROBUST_HUBER = 1, ICP_ROBUST_CAUCHY = 2, ICP_ROBUST_TUKEY = 3 };
+
+// M = S^-1 of the symmetric S = (xx, xy, xz, yy, yz, zz), in the same packing: the adjugate's six entries, each a b - c d, the determinant
+// (xx c00 + xy c01) + xz c02 along the first row, six divisions.  false: the determinant is not finite or not > 0 (M is not written).
+ICP_HD bool icp_inv_sym3(const double* S, double* M) {
+    const double xx = S[0], xy = S[1], xz = S[2], yy = S[3], yz = S[4], zz = S[5];
+    const double c00 = yy * zz - yz * yz, c01 = xz * yz - xy * zz, c02 = xy * yz - xz * yy;
+    const double det = (xx * c00 + xy * c01) + xz * c02;
+    if (!icp_finite(det) || !(det > 0.0)) return false;
+    const double c11 = xx * zz - xz * xz, c12 = xy * xz - xx * yz, c22 = xx * yy - xy * xy;
+    M[0] = c00 / det; M[1] = c01 / det; M[2] = c02 / det;
+    M[3] = c11 / det; M[4] = c12 / det; M[5] = c22 / det;
+    return true;
+}
+
+// w(rho, k) of a residual rho >= 0 under the scale k > 0; q = (rho rho) / (k k).  A NaN rho gives a weight that is not > 0 (NONE excepted).
+//   HUBER  rho <= k ? 1 : k / rho        CAUCHY  1 / (1 + q)        TUKEY  rho < k ? (1 - q) (1 - q) : 0
+ICP_HD double icp_robust_weight(int kind, double rho, double k) {
+    if (kind == ICP_ROBUST_HUBER) return rho <= k ? 1.0 : k / rho;
+    if (kind == ICP_ROBUST_CAUCHY) return 1.0 / (1.0 + (rho * rho) / (k * k));
+    if (kind == ICP_ROBUST_TUKEY) {
+        if (!(rho < k)) return 0.0;
+        const double t = 1.0 - (rho * rho) / (k * k);
+        return t * t;
+    }
+    return 1.0;
+}
 
 // xi = -A^-1 b.  A = L D L^T with unit lower L: for column j, v_k = L(j, k) D(k) (k < j), D(j) = A(j, j) - sum_k L(j, k) v_k and
 // L(i, j) = (A(i, j) - sum_k L(i, k) v_k) / D(j), the sums subtracted one by one in ascending k.  Then L y = -b downwards, z = y / D,

@@ -478,6 +478,22 @@ inline Matrix4f icpPointToPlane(const PointNCloud::ConstPtr& src, const PointNCl
     return icpPointToPlane(src, tgt, tn, max_dist, max_iterations, result);
 }
 
+// ---- not in the reference: the ICP variants from tn (lgr_icp_ex_host; DESIGN.md section 4, "ICP variants").  `options` is the ABI's
+// struct, filled by lgr_default_icp_ex_params and then by the caller: variant, robust kernel and scale, normal gate, plane_eps, per-point
+// weights (host floats, one per source point, or null) and the base parameters of icpPointToPlane.
+inline Matrix4f icpRegistration(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn, const lgr_icp_ex_params& options,
+                                lgr_icp_result& result) {
+    check(lgr_icp_ex_host(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), tn.data(), &options, &result, nullptr, nullptr),
+          "icpRegistration");
+    Matrix4f out;
+    std::memcpy(out.data(), result.transformation, 64);
+    return out;
+}
+inline Matrix4f icpRegistration(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn, const lgr_icp_ex_params& options) {
+    lgr_icp_result result;
+    return icpRegistration(src, tgt, tn, options, result);
+}
+
 // ---- include/hypotheses.h:10-12
 inline void updateHypotheses(std::vector<Matrix4f>& transformations, std::vector<float>& metrics, const Matrix4f& new_transformation,
                              float new_metric, const AlignmentParameters& parameters) {

@@ -253,6 +253,37 @@ def icp_params(max_iterations=None, max_dist=None, min_dist=None, shrink=None, r
     return p
 
 
+ICP_POINT_TO_PLANE, ICP_POINT_TO_POINT, ICP_PLANE_TO_PLANE = 0, 1, 2        # LGR_ICP_*
+ICP_ROBUST_NONE, ICP_ROBUST_HUBER, ICP_ROBUST_CAUCHY, ICP_ROBUST_TUKEY = 0, 1, 2, 3   # LGR_ICP_ROBUST_*
+ICP_VARIANT_IDS = {"plane": 0, "point": 1, "plane2plane": 2}
+ICP_ROBUST_IDS = {"none": 0, "huber": 1, "cauchy": 2, "tukey": 3}
+
+
+class IcpExParams(C.Structure):
+    """lgr_icp_ex_params (include/lgr.h)"""
+    _fields_ = [("base", IcpParams), ("variant", C.c_int32), ("robust", C.c_int32), ("robust_scale", C.c_float), ("min_normal_cos", C.c_float),
+                ("plane_eps", C.c_float), ("reserved", C.c_int32 * 3), ("weights", C.c_void_p)]
+
+
+def icp_ex_params(variant=None, robust=None, robust_scale=None, min_normal_cos=None, plane_eps=None, weights=None, **base_kw):
+    """lgr_default_icp_ex_params, then the given fields.  variant / robust: the LGR_ICP_* value or its name ('plane', 'point', 'plane2plane';
+    'none', 'huber', 'cauchy', 'tukey'); weights: per-source-point weights (a cuda tensor for the _dev entry, numpy for the host entry:
+    keep it alive for the call); base_kw: the keywords of icp_params."""
+    p = IcpExParams()
+    _lib.lgr_default_icp_ex_params(C.byref(p))
+    p.base = icp_params(**base_kw)
+    if variant is not None:
+        p.variant = ICP_VARIANT_IDS[variant] if isinstance(variant, str) else int(variant)
+    if robust is not None:
+        p.robust = ICP_ROBUST_IDS[robust] if isinstance(robust, str) else int(robust)
+    for name, v in (("robust_scale", robust_scale), ("min_normal_cos", min_normal_cos), ("plane_eps", plane_eps)):
+        if v is not None:
+            setattr(p, name, float(v))
+    if weights is not None:
+        p.weights = _ptr(weights).value
+    return p
+
+
 class TemperatureOut(C.Structure):
     """lgr_temperature_out (include/lgr.h): five optional per-point arrays of one temperature map."""
     _fields_ = [("temp_distance", C.c_void_p), ("temp_normal", C.c_void_p), ("color_distance", C.c_void_p), ("color_normal", C.c_void_p), ("nn", C.c_void_p)]
@@ -1639,7 +1670,7 @@ class Context:
     def _icp(self, fn, src, tgt, T0, params, trace, kw):
         p = params if params is not None else icp_params(**kw)
         out = IcpResult()
-        tr = (IcpStep * max(p.max_iterations, 1))() if trace else None
+        tr = (IcpStep * max(getattr(p, "base", p).max_iterations, 1))() if trace else None
         n_tr = C.c_int(0)
         self.check(fn(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T0), C.byref(p), C.byref(out), tr, C.byref(n_tr) if trace else None))
         if trace:
@@ -1656,6 +1687,32 @@ class Context:
         """lgr_icp_plane_host: numpy in, IcpResult out"""
         src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
         return self._icp(_lib.lgr_icp_plane_host, src, tgt, T0, params, trace, kw)
+
+    # ---- ICP variants (include/lgr.h lgr_icp_ex*) ----
+    def _icp_ex(self, fn, src, tgt, T0, params, weights, trace, kw):
+        p = params if params is not None else icp_ex_params(weights=weights, **kw)
+        return self._icp(fn, src, tgt, T0, p, trace, None)
+
+    def icp_ex(self, src, tgt, T0, variant=ICP_POINT_TO_PLANE, robust=ICP_ROBUST_NONE, robust_scale=0.0, min_normal_cos=-1.0, plane_eps=0.0, weights=None, trace=False,
+               params=None, **base_kw):
+        """lgr_icp_ex_dev on cuda clouds [n, 12] (both with normals where the variant or the gate reads them): T0 refined by the chosen ICP
+        variant -> IcpResult as icp_plane's.  variant 'plane' / 'point' / 'plane2plane', robust 'none' / 'huber' / 'cauchy' / 'tukey' with
+        robust_scale k in units of the variant's residual, min_normal_cos > -1 switches the normal gate on, plane_eps the plane-to-plane
+        covariance's thin axis (0: 1e-3), weights a cuda float32 [ns] or None; base_kw: the keywords of capi.icp_params.  params: a ready
+        IcpExParams instead of all of these."""
+        if weights is not None:
+            weights = weights.contiguous()
+        return self._icp_ex(_lib.lgr_icp_ex_dev, src, tgt, T0, params, weights, trace,
+                            dict(base_kw, variant=variant, robust=robust, robust_scale=robust_scale, min_normal_cos=min_normal_cos, plane_eps=plane_eps))
+
+    def icp_ex_host(self, src, tgt, T0, variant=ICP_POINT_TO_PLANE, robust=ICP_ROBUST_NONE, robust_scale=0.0, min_normal_cos=-1.0, plane_eps=0.0, weights=None,
+                    trace=False, params=None, **base_kw):
+        """lgr_icp_ex_host: numpy in (weights a numpy float32 [ns] or None), IcpResult out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.float32)
+        return self._icp_ex(_lib.lgr_icp_ex_host, src, tgt, T0, params, weights, trace,
+                            dict(base_kw, variant=variant, robust=robust, robust_scale=robust_scale, min_normal_cos=min_normal_cos, plane_eps=plane_eps))
 
     def analysis_metric(self, src, tgt, corr, T, T_gt=None, metric_id=METRIC_UNIFORMITY, score_id=SCORE_MSE, weights=None, weight=None):
         """lgr_analysis_metric_dev: what AlignmentAnalysis::start's first statement and buildCorrectInliers yield under metric_id -> MetricEval

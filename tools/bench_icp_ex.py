@@ -1,0 +1,95 @@
+"""GPU timing of the ICP variants (lgr_icp_ex_dev) beside lgr_icp_plane_dev in the same run, by the method of tools/bench_icp.py: the 1M-point
+bench pair at the ground truth perturbed by 0.5 degrees about z and 0.3 x density along (0.6, 0, 0.8), max_dist = 4 x density supplied,
+eps = 0 so that every iteration runs, events on the context's stream around whole calls of 8 and of 24 iterations; the per-iteration
+figure is the slope between the two lengths, so the set-up all share is not in it.  One warm-up per configuration, then --calls timed
+calls each, the configurations ALTERNATING; medians.  Timed: lgr_icp_plane_dev (the yardstick), the neutral lgr_icp_ex_dev (the same
+arithmetic through the other kernel), and each variant with a Huber kernel (k = density for the two distance residuals, 1.0 for
+plane-to-plane's Mahalanobis residual); plane-to-plane also with the gate and weights, the configuration that keeps the most alive.
+
+
+    python tools/bench_icp_ex.py [--points 1000000] [--calls 5] [--out profiles/icp_ex_bench1m.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "lidar-global-registration_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=1_000_000)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "icp_ex_bench1m.json"))
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from lgr_amd import capi, synthetic
+    assert torch.cuda.is_available(), "this is a GPU measurement: there is no CPU figure to fall back to"
+    ctx = capi.Context(0)
+    F = np.float32
+
+    pair = synthetic.make_pair(a.points, seed=synthetic.SEED)   # the bench pair of rank 0
+    src, tgt = torch.from_numpy(pair["src"]).cuda(), torch.from_numpy(pair["tgt"]).cuda()
+    ctx.normals_knn(src, 30, vp=pair["vp_src"])
+    ctx.normals_knn(tgt, 30, vp=pair["vp_tgt"])
+    thr = float(F(ctx.cloud_density(tgt)))
+    ang = np.deg2rad(0.5)
+    dT = np.eye(4)
+    dT[:3, :3] = [[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]]
+    dT[:3, 3] = 0.3 * thr * np.array([0.6, 0.0, 0.8])
+    T0 = (dT @ pair["T_gt"]).astype(F)
+    w = torch.from_numpy(np.random.default_rng(7).uniform(0.25, 1.0, src.shape[0]).astype(F)).cuda()
+    base = dict(max_dist=4 * thr, rot_eps=0.0, trans_eps=0.0)
+    kinds = {
+        "plane": lambda n: ctx.icp_plane(src, tgt, T0, max_iterations=n, **base),
+        "ex_neutral": lambda n: ctx.icp_ex(src, tgt, T0, max_iterations=n, **base),
+        "ex_plane_huber": lambda n: ctx.icp_ex(src, tgt, T0, variant="plane", robust="huber", robust_scale=thr, max_iterations=n, **base),
+        "ex_point_huber": lambda n: ctx.icp_ex(src, tgt, T0, variant="point", robust="huber", robust_scale=thr, max_iterations=n, **base),
+        "ex_plane2plane_huber": lambda n: ctx.icp_ex(src, tgt, T0, variant="plane2plane", robust="huber", robust_scale=1.0, max_iterations=n, **base),
+        "ex_plane2plane_huber_gate_weights": lambda n: ctx.icp_ex(src, tgt, T0, variant="plane2plane", robust="huber", robust_scale=1.0, min_normal_cos=0.9, weights=w,
+                                                                  max_iterations=n, **base),
+    }
+    lengths = (8, 24)
+    configs = [(f"{k}_{n}", f, n) for k, f in kinds.items() for n in lengths]
+    times, last = {k: [] for k, _, _ in configs}, {}
+    for k, f, n in configs:   # warm-up: the workspaces grow here
+        last[k] = f(n)
+        assert last[k].iterations == n and last[k].stop == capi.ICP_STOP_MAX_ITERATIONS, (k, last[k].iterations, last[k].stop)
+    ctx.sync()
+    for _ in range(a.calls):
+        for k, f, n in configs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = f(n)
+            e1.record()
+            e1.synchronize()
+            assert r.iterations == n   # the loops are deterministic
+            times[k].append(e0.elapsed_time(e1))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    slope = {k: (med[f"{k}_{lengths[1]}"] - med[f"{k}_{lengths[0]}"]) / (lengths[1] - lengths[0]) for k in kinds}
+    # the run-to-run spread of the yardstick's own slope: every pairing of a short and a long timed call
+    spread = [(b - s) / (lengths[1] - lengths[0]) for s in times[f"plane_{lengths[0]}"] for b in times[f"plane_{lengths[1]}"]]
+    a_, b_ = last[f"plane_{lengths[1]}"], last[f"ex_neutral_{lengths[1]}"]
+    out = {
+        "what": "ICP variants beside lgr_icp_plane_dev, ms per iteration as the slope between two call lengths (tools/bench_icp_ex.py)",
+        "device": torch.cuda.get_device_name(0), "points": a.points, "density": thr, "max_dist": 4 * thr, "calls": a.calls, "lengths": lengths,
+        "ms_per_iteration": slope, "ratio_to_plane": {k: v / slope["plane"] for k, v in slope.items()},
+        "plane_slope_min_max_over_call_pairings": [min(spread), max(spread)],
+        "neutral_equals_plane_bits": bytes(a_) == bytes(b_),
+        "call_ms_median": med, "call_ms": times,
+        "pairs_first_last": {k: [last[f"{k}_{lengths[1]}"].pairs0, last[f"{k}_{lengths[1]}"].pairs] for k in kinds},
+        "rmse_first_last": {k: [last[f"{k}_{lengths[1]}"].rmse0, last[f"{k}_{lengths[1]}"].rmse] for k in kinds},
+    }
+    print(json.dumps(out))
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -5,7 +5,9 @@
                                  [--feature-radius R] [--distance-thr D] [--out transformations.csv]
                                  [--ground-truth transformations_gt.csv NAME [--results results.csv] [--metrics-csv metrics.csv]]
                                  [--debug-dir DIR] [--hypotheses N [--hypotheses-plane]] [--refine N]
-                                 [--icp N [--icp-max-dist D] [--icp-shrink S [--icp-min-dist M]]]
+                                 [--icp N [--icp-max-dist D] [--icp-shrink S [--icp-min-dist M]]
+                                  [--icp-variant plane|point|plane2plane] [--icp-robust none|huber|cauchy|tukey --icp-robust-scale K]
+                                  [--icp-normal-angle DEG] [--icp-weight WEIGHT_ID] [--icp-plane-eps E]]
                                  [--measure N [--measure-seed S0] [--measurements test_measurements.csv]] [--save-features DIR]
                                  [--order canonical|reference] [--alignment ransac|gror|teaser]
 
@@ -35,6 +37,11 @@ distance D (--icp-max-dist; default 4 x the target's density), shrunk by S per i
 default with S < 1: half the target's density); the pairs and rmse of the first and the last iteration are printed, the result is appended
 to --out as a row named <name>_icp, and with --ground-truth it is analysed like the first.  --icp and --refine may be combined: the ICP runs
 first and the refinement starts from its result (rows <name>_icp and <name>_icp_refined).
+With any of --icp-variant, --icp-robust, --icp-normal-angle, --icp-weight, --icp-plane-eps the iterations run through lgr_icp_ex (DESIGN.md
+section 4, "ICP variants") instead: point-to-plane, point-to-point or plane-to-plane residuals, a Huber / Cauchy / Tukey kernel of scale K (in
+units of the variant's residual: a distance, for plane2plane a Mahalanobis distance), pairs rejected when the angle between the moved source
+normal and the target normal exceeds DEG (the tool hands the cosine to the ABI), and the source's weight map of --icp-weight (the maps of
+lgr_weights; harris and tomasi stay refused) as per-point weights.  Without any of them --icp takes the lgr_icp_plane path as before.
 With --measure N (needs --ground-truth): the reference's `measure` test type (measureTestResults, src/main.cpp:312-382) through lgr_measure --
 N alignments that differ in the RANSAC seed only (S0, S0 + 1, ...; S0 defaults to the profile's seed), one correspondence search for all of
 them, all judged against the ground truth in one batch; one line per run, then the aggregate row, appended to --measurements when given
@@ -102,6 +109,14 @@ def main():
     ap.add_argument("--icp-shrink", type=float, default=1.0, metavar="S", help="factor on the pairing distance per iteration, in (0, 1]")
     ap.add_argument("--icp-min-dist", type=float, default=0.0, metavar="M",
                     help="floor of the pairing distance (<= 0: half the target's density when --icp-shrink < 1, else the first iteration's distance)")
+    ap.add_argument("--icp-variant", default=None, choices=["plane", "point", "plane2plane"], help="the residual of lgr_icp_ex (default with another --icp-* option: plane)")
+    ap.add_argument("--icp-robust", default=None, choices=["none", "huber", "cauchy", "tukey"], help="M-estimator on the variant's residual (needs --icp-robust-scale)")
+    ap.add_argument("--icp-robust-scale", type=float, default=None, metavar="K", help="scale of --icp-robust, in units of the variant's residual")
+    ap.add_argument("--icp-normal-angle", type=float, default=None, metavar="DEG",
+                    help="reject a pair whose moved source normal and target normal differ by more than DEG degrees, 0 .. 180")
+    ap.add_argument("--icp-weight", default=None, choices=["constant", "exp_curvature", "curvedness", "curvature", "nss"],
+                    help="per-point weights of the ICP: the source's weight map of that name (src/weights.cpp)")
+    ap.add_argument("--icp-plane-eps", type=float, default=None, metavar="E", help="plane2plane: the covariance along the normal, 1e-6 .. 1 (default 1e-3)")
     ap.add_argument("--measure", type=int, default=0, metavar="N",
                     help="the measure test type: N seeded runs judged against --ground-truth, and their test_measurements.csv row")
     ap.add_argument("--measure-seed", type=int, default=None, metavar="S0", help="seed of the first run (default: the profile's seed); run i uses S0 + i")
@@ -131,6 +146,17 @@ def main():
         ap.error("--icp takes 0 .. 1024 iterations")
     if not 0.0 < a.icp_shrink <= 1.0:
         ap.error("--icp-shrink takes a factor in (0, 1]")
+    a.icp_ex = any(v is not None for v in (a.icp_variant, a.icp_robust, a.icp_robust_scale, a.icp_normal_angle, a.icp_weight, a.icp_plane_eps))
+    if a.icp_ex and not a.icp:
+        ap.error("the --icp-* options need --icp N")
+    if (a.icp_robust not in (None, "none")) != (a.icp_robust_scale is not None):
+        ap.error("--icp-robust huber|cauchy|tukey and --icp-robust-scale go together")
+    if a.icp_robust_scale is not None and not a.icp_robust_scale > 0.0:
+        ap.error("--icp-robust-scale takes a scale > 0")
+    if a.icp_normal_angle is not None and not 0.0 <= a.icp_normal_angle <= 180.0:
+        ap.error("--icp-normal-angle takes 0 .. 180 degrees")
+    if a.icp_plane_eps is not None and not 1e-6 <= a.icp_plane_eps <= 1.0:
+        ap.error("--icp-plane-eps takes 1e-6 .. 1")
     if a.metrics_csv and not a.ground_truth:
         ap.error("--metrics-csv needs --ground-truth")
     if a.hypotheses_plane and not a.hypotheses:
@@ -283,13 +309,25 @@ def refine(ctx, capi, formats, a, p, clouds, res, T, name, lrf):
 
 
 def icp(ctx, capi, formats, a, p, clouds, res, T, name, lrf, density_tgt):
-    """the found transformation through lgr_icp_plane; its row in --out and, with a ground truth, its analysis -> (transformation, row name)"""
+    """the found transformation through lgr_icp_plane (with an --icp-* option: lgr_icp_ex); its row in --out and, with a ground truth, its
+    analysis -> (transformation, row name)"""
+    import math
     import numpy as np
     min_dist = a.icp_min_dist if a.icp_min_dist > 0 else (0.5 * density_tgt if a.icp_shrink < 1.0 else 0.0)
+    base = dict(max_iterations=a.icp, max_dist=a.icp_max_dist, min_dist=min_dist, shrink=a.icp_shrink)
     t = time.perf_counter()
-    r = ctx.icp_plane(clouds[0], clouds[1], T, max_iterations=a.icp, max_dist=a.icp_max_dist, min_dist=min_dist, shrink=a.icp_shrink)
+    if a.icp_ex:
+        w = ctx.weights(clouds[0], a.icp_weight, with_sum=False)[0] if a.icp_weight is not None else None
+        cos = math.cos(math.radians(a.icp_normal_angle)) if a.icp_normal_angle is not None else -1.0
+        r = ctx.icp_ex(clouds[0], clouds[1], T, variant=a.icp_variant or "plane", robust=a.icp_robust or "none", robust_scale=a.icp_robust_scale or 0.0,
+                       min_normal_cos=max(-1.0, min(1.0, cos)), plane_eps=a.icp_plane_eps or 0.0, weights=w, **base)
+        how = f" ({a.icp_variant or 'plane'}, robust {a.icp_robust or 'none'}" + (f" {a.icp_robust_scale:.6g}" if a.icp_robust_scale else "") + \
+            (f", normals within {a.icp_normal_angle:.6g} deg" if a.icp_normal_angle is not None else "") + (f", weights {a.icp_weight}" if a.icp_weight else "") + ")"
+    else:
+        r = ctx.icp_plane(clouds[0], clouds[1], T, **base)
+        how = ""
     dt = time.perf_counter() - t
-    print(f"\nicp in {1e3 * dt:.1f} ms: {r.iterations} iterations of at most {a.icp}, stopped by {capi.ICP_STOP_NAMES[r.stop]} (max_dist {r.max_dist:.6g})")
+    print(f"\nicp{how} in {1e3 * dt:.1f} ms: {r.iterations} iterations of at most {a.icp}, stopped by {capi.ICP_STOP_NAMES[r.stop]} (max_dist {r.max_dist:.6g})")
     print(f"  first: pairs={r.pairs0} rmse={r.rmse0:.7f}")
     print(f"   last: pairs={r.pairs} rmse={r.rmse:.7f}")
     Ti = r.matrix()
