@@ -1,12 +1,15 @@
-// lgr_icp.hip -- point-to-plane ICP on the device for gfx950 (include/lgr.h lgr_icp_plane*).  A statement of this library's own: DESIGN.md
-// section 4, "Point-to-plane ICP"; the CPU statement is tests/cpp/icp_ref.cpp; the step's f64 arithmetic is lgr_icp_math.h for both.
-// lgr_icp_ex* (point-to-point, plane-to-plane, robust kernels, the normal gate, point weights; section 4, "ICP variants";
-// tests/cpp/icp_ex_ref.cpp) is the same loop with icp_terms_ex_kernel in the place of icp_terms_kernel.
+// lgr_icp.hip -- ICP on the device for gfx950: lgr_icp_ex* (point-to-plane, point-to-point, plane-to-plane, robust kernels, the normal
+// gate, point weights) and lgr_icp_plane*, its neutral configuration (include/lgr.h).  A statement of this library's own: DESIGN.md
+// section 4, "Point-to-plane ICP" and "ICP variants"; the CPU statements are tests/cpp/icp_ref.cpp (the plain algorithm, on its own) and
+// tests/cpp/icp_ex_ref.cpp; the step's f64 arithmetic is lgr_icp_math.h for all of them.
 //
 // Set-up, once per call: max_dist (the caller's, or 4 x the target's density), ONE grid over the target with cell 1.001 x max_dist, the
 // centre of the target's bounding box.  An iteration, all on the stream:
-//   icp_terms_kernel   a source point per lane: plane_move by S.T, nearest_within(d_k^2), the 28 f64 terms; wave butterfly, LDS tree over
-//                      the four waves -> one partial per term and workgroup (and the workgroup's pair count)
+//   icp_terms_kernel   <VARIANT, ROBUST, GATE, WEIGHTS>, one of 48 picked per call.  A source point per lane: plane_move by S.T,
+//                      nearest_within(d_k^2), the pair's values, then the 28 f64 terms, each product formed immediately before its own
+//                      wave butterfly; LDS tree over the four waves -> one partial per term and workgroup (and the workgroup's pair
+//                      count).  Live across the 28 butterflies: one row (point-to-plane) W g, g and r (13 doubles; W g is g where W is
+//                      the constant 1); three rows u, M j_b (mj: 18 doubles, of which the last nine are M's own entries), M e and W.
 //   icp_tree_kernel    256 partials -> 1, level by level, until one is left (none up to 256 points, one up to 65 536, two beyond)
 //   icp_step_kernel    the solve, T_{k+1}, d_{k+1}, the stop decision and the trace record (icp_step, lgr_icp_math.h)
 // The tree.  The statement sums x[0, ns) padded with +0.0 to 2^m by S(lo, len) = S(lo, len / 2) + S(lo + len / 2, len / 2).  An xor
@@ -56,68 +59,7 @@ __device__ __forceinline__ double icp_wave_tree(double x) {
 // the four waves' values of one slot -> S(lo, 256)
 __device__ __forceinline__ double icp_block_tree(const double (*sh)[ICP_SLOTS], int t) { return (sh[0][t] + sh[1][t]) + (sh[2][t] + sh[3][t]); }
 
-// part: [ICP_SLOTS][stride] 8-byte words, slot-major; this workgroup writes column blockIdx.x.  pad_n = 2^m.
-__global__ __launch_bounds__(ICP_BLOCK) void icp_terms_kernel(GridDev g, const float4* __restrict__ src, int ns, long long pad_n, const IcpState* __restrict__ S, float cx,
-                                                              float cy, float cz, double* __restrict__ part, size_t stride) {
-    if (S->done) return;
-    __shared__ double sh[ICP_WAVES][ICP_SLOTS];
-    const long long i = (long long) blockIdx.x * ICP_BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float d = S->d;
-    bool has = false;
-    double gv[6] = {0, 0, 0, 0, 0, 0}, r = 0;
-    if (i < ns) {
-        const float4 P = src[(size_t) i * 3];
-        float px, py, pz, d2;
-        int j;
-        plane_move(S->T, P.x, P.y, P.z, px, py, pz);
-        const int t = nearest_within(g, px, py, pz, d * d, d2, j);   // (a non-finite moved point walks nothing: -1)
-        if (t >= 0) {
-            const float4 Q = g.pxyz[t], N = g.pnrm[t];   // the grid's copies of tgt[j]: the same bits
-            if (lgr_finite3(N.x, N.y, N.z)) {
-                has = true;
-                const double nx = (double) N.x, ny = (double) N.y, nz = (double) N.z;
-                const double ux = (double) px - (double) cx, uy = (double) py - (double) cy, uz = (double) pz - (double) cz;
-                const double ex = (double) px - (double) Q.x, ey = (double) py - (double) Q.y, ez = (double) pz - (double) Q.z;
-                r = (nx * ex + ny * ey) + nz * ez;
-                gv[0] = uy * nz - uz * ny;
-                gv[1] = uz * nx - ux * nz;
-                gv[2] = ux * ny - uy * nx;
-                gv[3] = nx; gv[4] = ny; gv[5] = nz;
-            }
-        }
-    }
-    const double fill = i < pad_n ? 0.0 : -0.0;   // the statement's padding / the identity behind it
-    int slot = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b, ++slot) {
-            const double s = icp_wave_tree(has ? gv[a] * gv[b] : fill);
-            if (lane == 0) sh[wave][slot] = s;
-        }
-#pragma unroll
-    for (int a = 0; a < 6; ++a, ++slot) {
-        const double s = icp_wave_tree(has ? gv[a] * r : fill);
-        if (lane == 0) sh[wave][slot] = s;
-    }
-    {
-        const double s = icp_wave_tree(has ? r * r : fill);
-        if (lane == 0) sh[wave][ICP_TERMS - 1] = s;
-    }
-    const long long cnt = __popcll(__ballot(has));
-    if (lane == 0) sh[wave][ICP_TERMS] = __longlong_as_double(cnt);
-    __syncthreads();
-    if (threadIdx.x < ICP_TERMS) part[threadIdx.x * stride + blockIdx.x] = icp_block_tree(sh, threadIdx.x);
-    else if (threadIdx.x == ICP_TERMS) {
-        long long c = 0;
-#pragma unroll
-        for (int w = 0; w < ICP_WAVES; ++w) c += __double_as_longlong(sh[w][ICP_TERMS]);
-        part[ICP_TERMS * stride + blockIdx.x] = __longlong_as_double(c);
-    }
-}
-
-// ---- lgr_icp_ex*: the same slots from another contribution per point ("ICP variants"; tests/cpp/icp_ex_ref.cpp)
+// what the options of lgr_icp_ex_params add to a point's contribution ("ICP variants")
 struct IcpEx {
     double k;         // the robust scale
     double cos_min;   // the gate's cosine
@@ -130,11 +72,11 @@ __device__ __forceinline__ double icp_jdot(int a, const double* v, double ux, do
     return a == 0 ? v[2] * uy - v[1] * uz : a == 1 ? v[0] * uz - v[2] * ux : a == 2 ? v[1] * ux - v[0] * uy : v[a - 3];
 }
 
-// As icp_terms_kernel: a source point per lane, one product formed immediately before its butterfly.  Live across the 28 butterflies:
-// one row W g, g and r (13 doubles); three rows u, M j_b (mj: 18 doubles, of which the last nine are M's own entries), M e and W.
+// part: [ICP_SLOTS][stride] 8-byte words, slot-major; this workgroup writes column blockIdx.x.  pad_n = 2^m.  A parameter that is off
+// costs nothing: no weight load, no source normal load, no sqrt, and W is the constant 1 (x * 1 == x: the plain algorithm's bits).
 template <int VARIANT, int ROBUST, bool GATE, bool WEIGHTS>
-__global__ __launch_bounds__(ICP_BLOCK) void icp_terms_ex_kernel(GridDev g, const float4* __restrict__ src, int ns, long long pad_n, const IcpState* __restrict__ S, float cx,
-                                                                 float cy, float cz, IcpEx X, double* __restrict__ part, size_t stride) {
+__global__ __launch_bounds__(ICP_BLOCK) void icp_terms_kernel(GridDev g, const float4* __restrict__ src, int ns, long long pad_n, const IcpState* __restrict__ S, float cx,
+                                                              float cy, float cz, IcpEx X, double* __restrict__ part, size_t stride) {
     if (S->done) return;
     constexpr bool ONE_ROW = VARIANT == ICP_POINT_TO_PLANE, NEED_M = GATE || VARIANT == ICP_PLANE_TO_PLANE, NEED_N = ONE_ROW || NEED_M;
     __shared__ double sh[ICP_WAVES][ICP_SLOTS];
@@ -249,27 +191,27 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_terms_ex_kernel(GridDev g, cons
     }
 }
 
-using IcpTermsExFn = void (*)(GridDev, const float4*, int, long long, const IcpState*, float, float, float, IcpEx, double*, size_t);
+using IcpTermsFn = void (*)(GridDev, const float4*, int, long long, const IcpState*, float, float, float, IcpEx, double*, size_t);
 
 template <int V, int R>
-IcpTermsExFn icp_ex_pick2(bool gate, bool w) {
-    return gate ? (w ? icp_terms_ex_kernel<V, R, true, true> : icp_terms_ex_kernel<V, R, true, false>)
-                : (w ? icp_terms_ex_kernel<V, R, false, true> : icp_terms_ex_kernel<V, R, false, false>);
+IcpTermsFn icp_pick2(bool gate, bool w) {
+    return gate ? (w ? icp_terms_kernel<V, R, true, true> : icp_terms_kernel<V, R, true, false>)
+                : (w ? icp_terms_kernel<V, R, false, true> : icp_terms_kernel<V, R, false, false>);
 }
 template <int V>
-IcpTermsExFn icp_ex_pick1(int robust, bool gate, bool w) {
+IcpTermsFn icp_pick1(int robust, bool gate, bool w) {
     switch (robust) {
-        case ICP_ROBUST_HUBER: return icp_ex_pick2<V, ICP_ROBUST_HUBER>(gate, w);
-        case ICP_ROBUST_CAUCHY: return icp_ex_pick2<V, ICP_ROBUST_CAUCHY>(gate, w);
-        case ICP_ROBUST_TUKEY: return icp_ex_pick2<V, ICP_ROBUST_TUKEY>(gate, w);
-        default: return icp_ex_pick2<V, ICP_ROBUST_NONE>(gate, w);
+        case ICP_ROBUST_HUBER: return icp_pick2<V, ICP_ROBUST_HUBER>(gate, w);
+        case ICP_ROBUST_CAUCHY: return icp_pick2<V, ICP_ROBUST_CAUCHY>(gate, w);
+        case ICP_ROBUST_TUKEY: return icp_pick2<V, ICP_ROBUST_TUKEY>(gate, w);
+        default: return icp_pick2<V, ICP_ROBUST_NONE>(gate, w);
     }
 }
-IcpTermsExFn icp_ex_pick(int variant, int robust, bool gate, bool w) {
+IcpTermsFn icp_pick(int variant, int robust, bool gate, bool w) {
     switch (variant) {
-        case ICP_POINT_TO_POINT: return icp_ex_pick1<ICP_POINT_TO_POINT>(robust, gate, w);
-        case ICP_PLANE_TO_PLANE: return icp_ex_pick1<ICP_PLANE_TO_PLANE>(robust, gate, w);
-        default: return icp_ex_pick1<ICP_POINT_TO_PLANE>(robust, gate, w);
+        case ICP_POINT_TO_POINT: return icp_pick1<ICP_POINT_TO_POINT>(robust, gate, w);
+        case ICP_PLANE_TO_PLANE: return icp_pick1<ICP_PLANE_TO_PLANE>(robust, gate, w);
+        default: return icp_pick1<ICP_POINT_TO_PLANE>(robust, gate, w);
     }
 }
 
@@ -372,11 +314,10 @@ void idle_result(const float* T0, const lgr_icp_params* p, int stop, lgr_icp_res
     if (n_trace) *n_trace = 0;
 }
 
-// The loop behind lgr_icp_plane_dev and lgr_icp_ex_dev, the arguments checked by the caller: the set-up, then the iterations in groups.
-// launch_terms(g, pad_n, S, K, part, stride) enqueues the entry's terms kernel over ceil(ns / 256) workgroups.
-template <class Launch>
-int icp_run(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_params* p, lgr_icp_result* out, lgr_icp_step* trace,
-            int* n_trace, Launch launch_terms) {
+// The loop behind lgr_icp_ex_dev, the arguments checked by the caller: the set-up, then the iterations in groups.  `terms` is the call's
+// instantiation of icp_terms_kernel, enqueued over ceil(ns / 256) workgroups with the options X.
+int icp_run(lgr_ctx* ctx, IcpTermsFn terms, const IcpEx& X, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_params* p,
+            lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     const int max_it = p->max_iterations;
     if (ns == 0 || max_it == 0) {
@@ -426,15 +367,6 @@ int icp_run(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt
     LGR_TRY(lgr_ws_t(ctx, WS_ICP_TRACE, (size_t) max_it, &d_trace));
     const size_t h_trace_off = (sizeof(IcpState) + 63) & ~(size_t) 63;
     LGR_TRY(lgr_pinned(ctx, h_trace_off + (size_t) max_it * sizeof(lgr_icp_step), (void**) &h));
-    auto iteration = [&]() {
-        launch_terms(g, pad_n, S, K, part, nb[0]);
-        long long pad = pad_n;
-        for (int l = 1; l < levels; ++l) {
-            pad >>= 8;   // >= 2 wherever level l exists: more than 256^l points
-            icp_tree_kernel<<<dim3((unsigned) nb[l], ICP_SLOTS), ICP_BLOCK, 0, ctx->stream>>>(S, part + off[l - 1], nb[l - 1], (long long) nb[l - 1], pad, part + off[l], nb[l]);
-        }
-        icp_step_kernel<<<1, 64, 0, ctx->stream>>>(S, part + off[levels - 1], 1, K, d_trace);
-    };
     IcpState hs{};
     memcpy(hs.T, T0, 64);
     hs.d = max_dist;
@@ -445,7 +377,15 @@ int icp_run(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt
     int enqueued = 0;
     for (;;) {
         const int group = std::min((int) LGR_ICP_GROUP, max_it - enqueued);
-        for (int k = 0; k < group; ++k) iteration();
+        for (int k = 0; k < group; ++k) {
+            terms<<<(unsigned) nb[0], ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, X, part, nb[0]);
+            long long pad = pad_n;
+            for (int l = 1; l < levels; ++l) {
+                pad >>= 8;   // >= 2 wherever level l exists: more than 256^l points
+                icp_tree_kernel<<<dim3((unsigned) nb[l], ICP_SLOTS), ICP_BLOCK, 0, ctx->stream>>>(S, part + off[l - 1], nb[l - 1], (long long) nb[l - 1], pad, part + off[l], nb[l]);
+            }
+            icp_step_kernel<<<1, 64, 0, ctx->stream>>>(S, part + off[levels - 1], 1, K, d_trace);
+        }
         LGR_HIP(ctx, hipGetLastError());
         LGR_HIP(ctx, hipMemcpyAsync(h, S, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
         if (trace)   // the entries this group can have written
@@ -478,22 +418,22 @@ extern "C" int lgr_icp_plane_dev(lgr_ctx* ctx, const float* d_src, int ns, const
                                  lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
     lgr_turn turn__(ctx);   // contexts of one device take turns (lgr_internal.h)
     if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_CHECK(ctx, T0 && out && ns >= 0 && (d_src || ns == 0) && d_tgt && nt > 1 && params_ok(p) && aligned16(d_src) && aligned16(d_tgt), LGR_ERR_INVALID_ARG);
-    LGR_CHECK(ctx, !trace || n_trace, LGR_ERR_INVALID_ARG);
-    return icp_run(ctx, d_src, ns, d_tgt, nt, T0, p, out, trace, n_trace, [&](const GridDev& g, long long pad_n, const IcpState* S, const IcpConst& K, double* part, size_t nb0) {
-        icp_terms_kernel<<<(unsigned) nb0, ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, part, nb0);
-    });
+    LGR_CHECK(ctx, p, LGR_ERR_INVALID_ARG);
+    lgr_icp_ex_params ex;
+    lgr_default_icp_ex_params(&ex);   // point-to-plane, no robust kernel, gate off, no weights
+    ex.base = *p;                     // every other argument is checked there
+    return lgr_icp_ex_dev(ctx, d_src, ns, d_tgt, nt, T0, &ex, out, trace, n_trace);
 }
 
 extern "C" int lgr_icp_plane_host(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T0[16], const lgr_icp_params* p,
                                   lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
     lgr_turn turn__(ctx);
     if (!ctx) return LGR_ERR_INVALID_ARG;
-    LGR_CHECK(ctx, T0 && out && ns >= 0 && (src || ns == 0) && tgt && nt > 1 && params_ok(p) && (!trace || n_trace), LGR_ERR_INVALID_ARG);
-    float *ds, *dt;
-    lgr_host_call hc(ctx);
-    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
-    return lgr_icp_plane_dev(ctx, ds, ns, dt, nt, T0, p, out, trace, n_trace);
+    LGR_CHECK(ctx, p, LGR_ERR_INVALID_ARG);
+    lgr_icp_ex_params ex;
+    lgr_default_icp_ex_params(&ex);
+    ex.base = *p;
+    return lgr_icp_ex_host(ctx, src, ns, tgt, nt, T0, &ex, out, trace, n_trace);
 }
 
 extern "C" void lgr_default_icp_ex_params(lgr_icp_ex_params* p) {
@@ -514,10 +454,8 @@ extern "C" int lgr_icp_ex_dev(lgr_ctx* ctx, const float* d_src, int ns, const fl
                   "lgr.h and lgr_icp_math.h number the variants and the robust kernels alike");
     const float eps = p->plane_eps == 0.f ? 1e-3f : p->plane_eps;
     const IcpEx X{(double) p->robust_scale, (double) p->min_normal_cos, 1.0 - (double) eps, p->weights};
-    const IcpTermsExFn terms = icp_ex_pick(p->variant, p->robust, p->min_normal_cos > -1.f, p->weights != nullptr);
-    return icp_run(ctx, d_src, ns, d_tgt, nt, T0, &p->base, out, trace, n_trace, [&](const GridDev& g, long long pad_n, const IcpState* S, const IcpConst& K, double* part, size_t nb0) {
-        terms<<<(unsigned) nb0, ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, X, part, nb0);
-    });
+    const IcpTermsFn terms = icp_pick(p->variant, p->robust, p->min_normal_cos > -1.f, p->weights != nullptr);
+    return icp_run(ctx, terms, X, d_src, ns, d_tgt, nt, T0, &p->base, out, trace, n_trace);
 }
 
 extern "C" int lgr_icp_ex_host(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T0[16], const lgr_icp_ex_params* p,

@@ -9,7 +9,7 @@
 //   icp_inv_sym3, icp_robust_weight      lgr_icp_ex*: the inverse of plane-to-plane's 3 x 3 covariance sum, the M-estimators' weights.
 // Every operation is one IEEE binary64 + - * / sqrt (binary32 where a float is named); compile with -ffp-contract=off on both sides (the
 // Makefile and the tests do).  The pairing, the 28 terms of a point and the balanced tree that sums them are NOT here: the kernels
-// (icp_terms_kernel, icp_tree_kernel) and the statement each write them on their own.
+// (icp_terms_kernel, icp_tree_kernel) and the statements each write them on their own.
 #pragma once
 #include <stdint.h>
 
@@ -29,7 +29,7 @@ ICP_HD int icp_tri(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }  
 ICP_HD bool icp_finite(double x) { return __builtin_fabs(x) <= 1.7976931348623157e308; }
 
 // ---- the variants of lgr_icp_ex* ("ICP variants"): the two pieces both sides share; the pairing, the gate and the
-// term products are written once in icp_terms_ex_kernel and once in tests/cpp/icp_ex_ref.cpp
+// term products are written once in icp_terms_kernel and once in tests/cpp/icp_ex_ref.cpp
 enum { ICP_POINT_TO_PLANE = 0, ICP_POINT_TO_POINT = 1, ICP_PLANE_TO_PLANE = 2, ICP_ROBUST_NONE = 0, ICP_ROBUST_HUBER = 1, ICP_ROBUST_CAUCHY = 2, ICP_ROBUST_TUKEY = 3 };
 
 // M = S^-1 of the symmetric S = (xx, xy, xz, yy, yz, zz), in the same packing: the adjugate's six entries, each a b - c d, the determinant

@@ -75,6 +75,18 @@ def test_source_sizes(lgr, pair, ns, shrink):
     check(lgr.icp_plane_host(s, pair["tgt"], pair["T_near"], trace=True, **kw), ref)
 
 
+def test_source_normals_are_not_read(lgr, pair):
+    """every source normal NaN: the plain entries launch the point-to-plane terms with the gate off, which reads the target's normals
+    only -- a source normal that was read would drop its pair.  257 points: two workgroups, as test_source_sizes[257]"""
+    s = pair["src"][:257].copy()
+    s[:, 4:7] = np.nan
+    kw = dict(max_dist=2 * pair["thr"], max_iterations=4)
+    ref = I.icp(s, pair["tgt"], pair["T_near"], **kw)
+    assert ref["iterations"] >= 2 and ref["pairs0"] >= 257 // 4
+    check(lgr.icp_plane(cuda(s), pair["d_tgt"], pair["T_near"], trace=True, **kw), ref)
+    check(lgr.icp_plane_host(s, pair["tgt"], pair["T_near"], trace=True, **kw), ref)
+
+
 @pytest.mark.parametrize("shrink", [False, True])
 def test_three_tree_levels(lgr, pair, shrink):
     """65 537 points: 257 workgroups, 2 partials of the second level, a third launch; over a 1000-point target"""

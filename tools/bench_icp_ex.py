@@ -2,8 +2,9 @@
 bench pair at the ground truth perturbed by 0.5 degrees about z and 0.3 x density along (0.6, 0, 0.8), max_dist = 4 x density supplied,
 eps = 0 so that every iteration runs, events on the context's stream around whole calls of 8 and of 24 iterations; the per-iteration
 figure is the slope between the two lengths, so the set-up all share is not in it.  One warm-up per configuration, then --calls timed
-calls each, the configurations ALTERNATING; medians.  Timed: lgr_icp_plane_dev (the yardstick), the neutral lgr_icp_ex_dev (the same
-arithmetic through the other kernel), and each variant with a Huber kernel (k = density for the two distance residuals, 1.0 for
+calls each, the configurations ALTERNATING; medians.  Timed: lgr_icp_plane_dev (the yardstick), the neutral lgr_icp_ex_dev (`plane` and
+`ex_neutral` time ONE kernel through two entries -- the first forwards to the second --, so their difference is this tool's noise
+floor), and each variant with a Huber kernel (k = density for the two distance residuals, 1.0 for
 plane-to-plane's Mahalanobis residual); plane-to-plane also with the gate and weights, the configuration that keeps the most alive.
 
 
