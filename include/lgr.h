@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-/* ABI revision.  Still 5 with the ICP variants: lgr_icp_ex_params, LGR_ICP_POINT_TO_* / LGR_ICP_PLANE_TO_PLANE, LGR_ICP_ROBUST_*,
+/* ABI revision.  Still 5 with trimmed ICP: lgr_icp_trim_params, lgr_icp_trim_step, lgr_default_icp_trim_params, lgr_icp_trim_dev,
+ * lgr_icp_trim_host, lgr_rank_select_dev and lgr_rank_select_host are additions; lgr_icp_ex*, lgr_icp_plane* and their structs did not
+ * change.  Still 5 with the ICP variants: lgr_icp_ex_params, LGR_ICP_POINT_TO_* / LGR_ICP_PLANE_TO_PLANE, LGR_ICP_ROBUST_*,
  * lgr_default_icp_ex_params, lgr_icp_ex_dev and lgr_icp_ex_host are additions; lgr_icp_plane* and its structs did not change.  Still 5 with point-to-plane ICP: lgr_icp_params, lgr_icp_step, lgr_icp_result, LGR_ICP_*, lgr_default_icp_params,
  * lgr_icp_plane_dev and lgr_icp_plane_host are additions; no struct or entry point that existed changed.  Still 5 with the reference point order on the device: lgr_hash_order_dev, lgr_downsample_order_dev, lgr_dedupe_order_dev,
  * lgr_preprocess_order_dev and lgr_selfcheck_hash_order are additions; no struct or entry point that existed changed.  Still 5 with the prepared clouds: lgr_cloud, struct lgr_cloud_info, lgr_cloud_level_info, lgr_cloud_prepare*, lgr_cloud_destroy,
@@ -1207,6 +1209,54 @@ int lgr_icp_ex_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int
                    const lgr_icp_ex_params*, lgr_icp_result* out /* host */, lgr_icp_step* trace_or_null /* host */, int* n_trace_or_null);
 int lgr_icp_ex_host(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T0_16[16], const lgr_icp_ex_params*,
                     lgr_icp_result* out, lgr_icp_step* trace_or_null, int* n_trace_or_null);   /* host twin */
+
+/* ---- trimmed ICP and median-scaled robust kernels: the loop of lgr_icp_ex* with two additions per iteration, both driven by exact ranks
+ *      of the pairs' residuals found on the device ("Trimmed ICP"; CPU statement tests/cpp/icp_trim_ref.cpp).  Neither
+ *      names an absolute scale.  Everything not said here is lgr_icp_ex*'s; `ex` is read exactly as lgr_icp_ex* reads its parameters.
+ *      Per iteration:
+ *        1. source point i is a candidate iff steps 1 - 5 above give it a pair (a neighbour, a finite p', omega > 0, finite normals where
+ *           read, the gate, a plane-to-plane determinant > 0) and key_i = (float) rho_i is finite without a sign bit, so that its bits
+ *           order as a uint32 (rho is formed under every configuration: |r|, or the square root of e^T M e).  P = the number of
+ *           candidates, ordered by (key_i, i).
+ *        2. K = (long long) floor((double) keep * (double) P); the first K candidates of the order are kept.  cut = the key of the K-th,
+ *           0 when K = 0.
+ *        3. with scale_from_median > 0: k = (double) scale_from_median * (double) key_m, m the candidate of rank (P - 1) / 2 among ALL
+ *           candidates (key_m = 0 without one); a k that is not finite or not > 0 gives w = 1 in that iteration.  Otherwise k =
+ *           ex.robust_scale.  scale = (float) k, or 0 under ROBUST_NONE.
+ *        4. only a kept candidate contributes, with W = w(robust, rho, k) omega and the 28 terms of step 7; a W that is not > 0: no pair.
+ *           pairs, rmse, the tree, the solve, the stop rule, the trace and the grouped enqueue are unchanged; K < 6 ends in NO_PAIRS.
+ *      keep == 1 and scale_from_median == 0 forwards to lgr_icp_ex* and returns its bytes: no select runs, and info holds candidates =
+ *      kept = pairs, cut 0 and scale = ex.robust_scale (0 under ROBUST_NONE).  Refused with LGR_ERR_INVALID_ARG before any work: whatever
+ *      lgr_icp_ex* refuses; keep NaN or outside (0, 1]; scale_from_median NaN, negative or infinite; scale_from_median > 0 with
+ *      ROBUST_NONE; a non-zero reserved word.  With scale_from_median > 0, ex.robust_scale is neither read nor validated.  info receives
+ *      one entry per evaluated iteration, beside the trace's; *n_trace counts both and is required when either is given.  The idle calls
+ *      (empty source, max_iterations 0) return what lgr_icp_ex* returns and write no info.  Not built: a fraction chosen per iteration,
+ *      trimming by a fraction of all source points.  The host form carries _host for the reason given above. ---- */
+typedef struct {
+    lgr_icp_ex_params ex;      /* read exactly as lgr_icp_ex* reads it */
+    float   keep;              /* in (0, 1]; 1 = no trimming */
+    float   scale_from_median; /* 0 = use ex.robust_scale; > 0: k of the iteration = this x the median residual */
+    int32_t reserved[2];       /* 0 */
+} lgr_icp_trim_params;
+typedef struct { int32_t candidates, kept; float cut, scale; } lgr_icp_trim_step;   /* one per evaluated iteration */
+void lgr_default_icp_trim_params(lgr_icp_trim_params* p);   /* ex: lgr_default_icp_ex_params; keep 1; scale_from_median 0 */
+int lgr_icp_trim_dev(lgr_ctx*, const float* d_src, int ns, const float* d_tgt, int nt, const float T0_16[16] /* host */,
+                     const lgr_icp_trim_params*, lgr_icp_result* out /* host */, lgr_icp_step* trace_or_null /* host */,
+                     lgr_icp_trim_step* info_or_null /* host */, int* n_trace_or_null);
+int lgr_icp_trim_host(lgr_ctx*, const float* src, int ns, const float* tgt, int nt, const float T0_16[16], const lgr_icp_trim_params*,
+                      lgr_icp_result* out, lgr_icp_step* trace_or_null, lgr_icp_trim_step* info_or_null, int* n_trace_or_null);   /* host twin */
+
+/* ---- exact rank select, the primitive under trimmed ICP: among the elements with valid[i] != 0 (all when NULL) whose key is finite and
+ *      carries no sign bit (a NaN, an infinite or a negative key is not counted), ordered by (key, i), the element at each of n_ranks (1
+ *      or 2) ranks: its index and key.  below[i] = 1 iff element i is counted and its position is < ranks[0], else 0; *n_valid = the
+ *      number counted.  LGR_ERR_INVALID_ARG for a rank outside [0, n_valid), except that ranks[0] == n_valid is allowed: it sets the flag
+ *      of every counted element, and out_index[0] = -1, out_key[0] = 0.  (*n_valid is written also when a rank is refused.)  n = 0
+ *      launches nothing.  MSB-first radix select over (key bits << 32) | i with integer histograms: deterministic, no sort. ---- */
+int lgr_rank_select_dev(lgr_ctx*, const float* d_keys, const uint8_t* d_valid_or_null, int n, const int64_t* ranks /* host */, int n_ranks,
+                        int32_t* out_index /* host, n_ranks */, float* out_key /* host, n_ranks */, uint8_t* d_below_or_null /* n */,
+                        int64_t* n_valid /* host */);
+int lgr_rank_select_host(lgr_ctx*, const float* keys, const uint8_t* valid_or_null, int n, const int64_t* ranks, int n_ranks,
+                         int32_t* out_index, float* out_key, uint8_t* below_or_null, int64_t* n_valid);   /* host twin */
 
 #ifdef __cplusplus
 }

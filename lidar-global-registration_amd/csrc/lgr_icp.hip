@@ -20,6 +20,8 @@
 // No float atomics, no sequential chain; the pair count is an integer sum.
 // Iterations are enqueued blind in groups of LGR_ICP_GROUP with one read-back of S per group; once S.done is set every kernel of a later
 // iteration returns at once and S and the trace stay as they are.
+// lgr_icp_trim* (trimmed ICP, median-scaled robust kernels) and lgr_rank_select* are further down: the same loop with the terms kernel split
+// around an exact rank select of the pairs' residuals (lgr_rank_select.cuh).
 #include <algorithm>
 #include <cfloat>
 
@@ -30,6 +32,7 @@
 #include "lgr_math.cuh"
 #include "lgr_plane_point.cuh"
 #include "lgr_pointpass.cuh"
+#include "lgr_rank_select.cuh"
 
 namespace {
 
@@ -278,6 +281,206 @@ __global__ __launch_bounds__(64) void icp_step_kernel(IcpState* __restrict__ S, 
     else S->d = icp_next_dist(S->d, K.shrink, K.min_dist);
 }
 
+// ---- trimmed ICP (lgr_icp_trim*; DESIGN.md section 3.1q and section 4, "Trimmed ICP").  The iteration's terms kernel is replaced by
+//   icp_pair_kernel        <VARIANT>: the search and the candidate test, once; stores the pair (grid slot t, p', rho, the key's bits)
+//   sel_hist_kernel x passes, sel_finish_kernel   (lgr_rank_select.cuh): P, the composite at rank K - 1 and at the median rank
+//   icp_trim_terms_kernel  <VARIANT>: the kept candidates' 28 terms from the stored pair, W from k_it; the iteration's info record
+// and feeds the same icp_tree_kernel / icp_step_kernel.  icp_terms_kernel and the path of lgr_icp_ex* are untouched: the per-point
+// values are written here a second time (icp_point_values), with the gate and the weights as run-time switches.
+
+struct IcpPairs {
+    float4* p;        // p' (w unused)
+    double* rho;
+    int* t;           // the neighbour's slot in the grid's copies; -1: no candidate
+    uint32_t* key;    // (float) rho as bits; 0xffffffff: no candidate (the select skips it)
+};
+
+struct IcpTrim { int robust; bool gate; float keep, scale_from_median, robust_scale; };
+
+struct IcpValues {
+    double om, rho, ux, uy, uz, r, rr;
+    double gv[6];             // one row: g
+    double mj[6][3], me[3];   // three rows: M j_b, M e
+};
+
+// the values of source point i moved to p', paired with grid slot t, before any robust weight; false: no pair (steps 2 - 5 of the variants)
+template <int VARIANT>
+__device__ __forceinline__ bool icp_point_values(const GridDev& g, const float4* __restrict__ src, long long i, const float* __restrict__ T, float px, float py, float pz, int t,
+                                                 float cx, float cy, float cz, const IcpEx& X, bool gate, IcpValues& v) {
+    constexpr bool ONE_ROW = VARIANT == ICP_POINT_TO_PLANE;
+    const bool need_m = gate || VARIANT == ICP_PLANE_TO_PLANE, need_n = ONE_ROW || need_m;
+    v.om = 1.0;
+    if (X.w) {
+        v.om = (double) X.w[i];
+        if (!(icp_finite(v.om) && v.om > 0.0)) return false;
+    }
+    double nx = 0, ny = 0, nz = 0, mx = 0, my = 0, mz = 0;
+    if (need_n) {
+        const float4 N = g.pnrm[t];
+        if (!lgr_finite3(N.x, N.y, N.z)) return false;
+        nx = (double) N.x; ny = (double) N.y; nz = (double) N.z;
+    }
+    if (need_m) {
+        const float4 Ns = src[(size_t) i * 3 + 1];
+        if (!lgr_finite3(Ns.x, Ns.y, Ns.z)) return false;
+        const double sx = (double) Ns.x, sy = (double) Ns.y, sz = (double) Ns.z;
+        mx = ((double) T[0] * sx + (double) T[4] * sy) + (double) T[8] * sz;
+        my = ((double) T[1] * sx + (double) T[5] * sy) + (double) T[9] * sz;
+        mz = ((double) T[2] * sx + (double) T[6] * sy) + (double) T[10] * sz;
+        if (gate && !((mx * nx + my * ny) + mz * nz >= X.cos_min)) return false;
+    }
+    const float4 Q = g.pxyz[t];
+    const double ux = (double) px - (double) cx, uy = (double) py - (double) cy, uz = (double) pz - (double) cz;
+    const double ex = (double) px - (double) Q.x, ey = (double) py - (double) Q.y, ez = (double) pz - (double) Q.z;
+    v.ux = ux; v.uy = uy; v.uz = uz;
+    if (ONE_ROW) {
+        v.r = (nx * ex + ny * ey) + nz * ez;
+        v.rr = v.r * v.r;
+        v.rho = __builtin_fabs(v.r);
+        v.gv[0] = uy * nz - uz * ny;
+        v.gv[1] = uz * nx - ux * nz;
+        v.gv[2] = ux * ny - uy * nx;
+        v.gv[3] = nx; v.gv[4] = ny; v.gv[5] = nz;
+        return true;
+    }
+    double M[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};
+    if (VARIANT == ICP_PLANE_TO_PLANE) {
+        const double s = X.s;
+        const double Sg[6] = {2.0 - s * (nx * nx + mx * mx), -(s * (nx * ny + mx * my)), -(s * (nx * nz + mx * mz)),
+                              2.0 - s * (ny * ny + my * my), -(s * (ny * nz + my * mz)), 2.0 - s * (nz * nz + mz * mz)};
+        if (!icp_inv_sym3(Sg, M)) return false;
+    }
+    const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        v.mj[0][q] = Mr[q][2] * uy - Mr[q][1] * uz;
+        v.mj[1][q] = Mr[q][0] * uz - Mr[q][2] * ux;
+        v.mj[2][q] = Mr[q][1] * ux - Mr[q][0] * uy;
+        v.mj[3][q] = Mr[q][0]; v.mj[4][q] = Mr[q][1]; v.mj[5][q] = Mr[q][2];
+        v.me[q] = (Mr[q][0] * ex + Mr[q][1] * ey) + Mr[q][2] * ez;
+    }
+    v.rr = (ex * v.me[0] + ey * v.me[1]) + ez * v.me[2];
+    v.rho = __builtin_sqrt(v.rr);
+    return true;
+}
+
+template <int VARIANT>
+__global__ __launch_bounds__(ICP_BLOCK) void icp_pair_kernel(GridDev g, const float4* __restrict__ src, int ns, const IcpState* __restrict__ S, float cx, float cy, float cz,
+                                                             IcpEx X, bool gate, IcpPairs Pr) {
+    if (S->done) return;
+    const long long i = (long long) blockIdx.x * ICP_BLOCK + threadIdx.x;
+    if (i >= ns) return;
+    const float4 P = src[(size_t) i * 3];
+    const float d = S->d;
+    float px, py, pz, d2;
+    int j;
+    plane_move(S->T, P.x, P.y, P.z, px, py, pz);
+    const int t = nearest_within(g, px, py, pz, d * d, d2, j);
+    IcpValues v;
+    v.rho = 0.0;
+    uint32_t bits = 0xffffffffu;
+    const bool ok = t >= 0 && icp_point_values<VARIANT>(g, src, i, S->T, px, py, pz, t, cx, cy, cz, X, gate, v) && icp_trim_key(v.rho, &bits);
+    Pr.p[i] = make_float4(px, py, pz, 0.f);
+    Pr.rho[i] = v.rho;
+    Pr.t[i] = ok ? t : -1;
+    Pr.key[i] = ok ? bits : 0xffffffffu;
+}
+
+// icp_terms_kernel's second half over the stored pairs: a candidate at or below the cut contributes with W = w(rho, k_it) omega
+template <int VARIANT>
+__global__ __launch_bounds__(ICP_BLOCK) void icp_trim_terms_kernel(GridDev g, const float4* __restrict__ src, int ns, long long pad_n, const IcpState* __restrict__ S, float cx,
+                                                                   float cy, float cz, IcpEx X, IcpTrim A, IcpPairs Pr, const SelWork* __restrict__ sel,
+                                                                   lgr_icp_trim_step* __restrict__ info, double* __restrict__ part, size_t stride) {
+    if (S->done) return;
+    constexpr bool ONE_ROW = VARIANT == ICP_POINT_TO_PLANE;
+    __shared__ double sh[ICP_WAVES][ICP_SLOTS];
+    const long long i = (long long) blockIdx.x * ICP_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const SelState* res = &sel->st[SEL_MAX_PASSES];
+    const long long P = res->P, K = icp_trim_k(A.keep, P);
+    const unsigned long long cut = res->prefix[0];
+    const float key_m = res->ok[1] ? icp_trim_key_value((uint32_t) (res->prefix[1] >> 32)) : 0.f;
+    const double k_it = icp_trim_scale(A.scale_from_median, key_m, A.robust_scale);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        lgr_icp_trim_step rec;
+        rec.candidates = (int) P; rec.kept = (int) K;
+        rec.cut = K > 0 ? icp_trim_key_value((uint32_t) (cut >> 32)) : 0.f;
+        rec.scale = A.robust == ICP_ROBUST_NONE ? 0.f : (float) k_it;
+        info[S->k] = rec;   // k < max_iterations, as the trace
+    }
+    bool has = false;
+    double W = 1.0;
+    IcpValues v;
+    v.ux = v.uy = v.uz = v.r = v.rr = 0.0;
+    double wg[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        v.gv[a] = 0.0;
+        v.mj[a][0] = v.mj[a][1] = v.mj[a][2] = 0.0;
+    }
+    v.me[0] = v.me[1] = v.me[2] = 0.0;
+    if (i < ns) {
+        const int t = Pr.t[i];
+        if (t >= 0 && K > 0 && res->ok[0] && icp_trim_composite(Pr.key[i], (uint32_t) i) <= cut) {
+            const float4 p = Pr.p[i];
+            bool ok = icp_point_values<VARIANT>(g, src, i, S->T, p.x, p.y, p.z, t, cx, cy, cz, X, A.gate, v);   // (true again: the same inputs)
+            W = icp_trim_weight(A.robust, Pr.rho[i], k_it) * v.om;
+            ok = ok && W > 0.0;
+            if (ONE_ROW) {
+#pragma unroll
+                for (int a = 0; a < 6; ++a) wg[a] = W * v.gv[a];
+            }
+            has = ok;
+        }
+    }
+    const double fill = i < pad_n ? 0.0 : -0.0;
+    int slot = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b, ++slot) {
+            const double x = ONE_ROW ? wg[a] * v.gv[b] : W * icp_jdot(a, v.mj[b], v.ux, v.uy, v.uz);
+            const double s = icp_wave_tree(has ? x : fill);
+            if (lane == 0) sh[wave][slot] = s;
+        }
+#pragma unroll
+    for (int a = 0; a < 6; ++a, ++slot) {
+        const double x = ONE_ROW ? wg[a] * v.r : W * icp_jdot(a, v.me, v.ux, v.uy, v.uz);
+        const double s = icp_wave_tree(has ? x : fill);
+        if (lane == 0) sh[wave][slot] = s;
+    }
+    {
+        const double s = icp_wave_tree(has ? v.rr : fill);
+        if (lane == 0) sh[wave][ICP_TERMS - 1] = s;
+    }
+    const long long cnt = __popcll(__ballot(has));
+    if (lane == 0) sh[wave][ICP_TERMS] = __longlong_as_double(cnt);
+    __syncthreads();
+    if (threadIdx.x < ICP_TERMS) part[threadIdx.x * stride + blockIdx.x] = icp_block_tree(sh, threadIdx.x);
+    else if (threadIdx.x == ICP_TERMS) {
+        long long c = 0;
+#pragma unroll
+        for (int w = 0; w < ICP_WAVES; ++w) c += __double_as_longlong(sh[w][ICP_TERMS]);
+        part[ICP_TERMS * stride + blockIdx.x] = __longlong_as_double(c);
+    }
+}
+
+using IcpPairFn = void (*)(GridDev, const float4*, int, const IcpState*, float, float, float, IcpEx, bool, IcpPairs);
+using IcpTrimTermsFn = void (*)(GridDev, const float4*, int, long long, const IcpState*, float, float, float, IcpEx, IcpTrim, IcpPairs, const SelWork*, lgr_icp_trim_step*,
+                                double*, size_t);
+
+IcpPairFn icp_pick_pair(int variant) {
+    return variant == ICP_POINT_TO_POINT ? icp_pair_kernel<ICP_POINT_TO_POINT> : variant == ICP_PLANE_TO_PLANE ? icp_pair_kernel<ICP_PLANE_TO_PLANE> : icp_pair_kernel<ICP_POINT_TO_PLANE>;
+}
+IcpTrimTermsFn icp_pick_trim_terms(int variant) {
+    return variant == ICP_POINT_TO_POINT   ? icp_trim_terms_kernel<ICP_POINT_TO_POINT>
+           : variant == ICP_PLANE_TO_PLANE ? icp_trim_terms_kernel<ICP_PLANE_TO_PLANE>
+                                           : icp_trim_terms_kernel<ICP_POINT_TO_PLANE>;
+}
+
+// what icp_run needs to run the trimmed iteration in place of `terms`
+struct IcpTrimRun { int variant; IcpTrim A; lgr_icp_trim_step* info; };
+
 void fill_result(const IcpState& s, float max_dist, lgr_icp_result* out) {
     memset(out, 0, sizeof *out);
     memcpy(out->transformation, s.T, 64);
@@ -315,9 +518,10 @@ void idle_result(const float* T0, const lgr_icp_params* p, int stop, lgr_icp_res
 }
 
 // The loop behind lgr_icp_ex_dev, the arguments checked by the caller: the set-up, then the iterations in groups.  `terms` is the call's
-// instantiation of icp_terms_kernel, enqueued over ceil(ns / 256) workgroups with the options X.
+// instantiation of icp_terms_kernel, enqueued over ceil(ns / 256) workgroups with the options X.  With `trim` (lgr_icp_trim_dev) the pair
+// kernel, the select and the trimmed terms kernel stand in its place, and n_trace counts the entries of the trace and of trim->info.
 int icp_run(lgr_ctx* ctx, IcpTermsFn terms, const IcpEx& X, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_params* p,
-            lgr_icp_result* out, lgr_icp_step* trace, int* n_trace) {
+            lgr_icp_result* out, lgr_icp_step* trace, int* n_trace, const IcpTrimRun* trim = nullptr) {
     LGR_HIP(ctx, hipSetDevice(ctx->device));
     const int max_it = p->max_iterations;
     if (ns == 0 || max_it == 0) {
@@ -365,6 +569,25 @@ int icp_run(lgr_ctx* ctx, IcpTermsFn terms, const IcpEx& X, const float* d_src, 
     LGR_TRY(lgr_ws_t(ctx, WS_ICP_STATE, 1, &S));
     LGR_TRY(lgr_ws_t(ctx, WS_ICP_PART, words, &part));
     LGR_TRY(lgr_ws_t(ctx, WS_ICP_TRACE, (size_t) max_it, &d_trace));
+    IcpPairs Pr{};
+    SelWork* sel = nullptr;
+    lgr_icp_trim_step* d_info = nullptr;
+    IcpPairFn pair_fn = nullptr;
+    IcpTrimTermsFn trim_terms = nullptr;
+    if (trim) {
+        char* pw;
+        LGR_TRY(lgr_ws_t(ctx, WS_ICP_PAIR, (size_t) ns * 32, &pw));   // 16 + 8 + 4 + 4 bytes a point, the widest first
+        Pr.p = (float4*) pw;
+        Pr.rho = (double*) (pw + (size_t) ns * 16);
+        Pr.t = (int*) (pw + (size_t) ns * 24);
+        Pr.key = (uint32_t*) (pw + (size_t) ns * 28);
+        LGR_TRY(lgr_ws_t(ctx, WS_ICP_SEL, 1, &sel));
+        LGR_TRY(lgr_ws_t(ctx, WS_ICP_INFO, (size_t) max_it, &d_info));
+        LGR_HIP(ctx, hipMemsetAsync(sel, 0, sizeof(SelWork), ctx->stream));
+        pair_fn = icp_pick_pair(trim->variant);
+        trim_terms = icp_pick_trim_terms(trim->variant);
+    }
+    const SelRanks ranks{1, trim ? trim->A.keep : 1.f, {0, 0}};
     const size_t h_trace_off = (sizeof(IcpState) + 63) & ~(size_t) 63;
     LGR_TRY(lgr_pinned(ctx, h_trace_off + (size_t) max_it * sizeof(lgr_icp_step), (void**) &h));
     IcpState hs{};
@@ -378,7 +601,13 @@ int icp_run(lgr_ctx* ctx, IcpTermsFn terms, const IcpEx& X, const float* d_src, 
     for (;;) {
         const int group = std::min((int) LGR_ICP_GROUP, max_it - enqueued);
         for (int k = 0; k < group; ++k) {
-            terms<<<(unsigned) nb[0], ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, X, part, nb[0]);
+            if (trim) {
+                pair_fn<<<(unsigned) nb[0], ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, S, K.cx, K.cy, K.cz, X, trim->A.gate, Pr);
+                sel_enqueue(ctx->stream, &S->done, Pr.key, nullptr, ns, ranks, sel);
+                trim_terms<<<(unsigned) nb[0], ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, X, trim->A, Pr, sel, d_info, part,
+                                                                             nb[0]);
+            } else
+                terms<<<(unsigned) nb[0], ICP_BLOCK, 0, ctx->stream>>>(g, (const float4*) d_src, ns, pad_n, S, K.cx, K.cy, K.cz, X, part, nb[0]);
             long long pad = pad_n;
             for (int l = 1; l < levels; ++l) {
                 pad >>= 8;   // >= 2 wherever level l exists: more than 256^l points
@@ -399,7 +628,11 @@ int icp_run(lgr_ctx* ctx, IcpTermsFn terms, const IcpEx& X, const float* d_src, 
     }
     fill_result(hs, max_dist, out);
     if (trace) memcpy(trace, h + h_trace_off, (size_t) hs.n_eval * sizeof(lgr_icp_step));
-    if (n_trace) *n_trace = trace ? hs.n_eval : 0;
+    if (n_trace) *n_trace = trace || (trim && trim->info) ? hs.n_eval : 0;
+    if (trim && trim->info && hs.n_eval) {   // (after the loop: one small copy, nothing of an iteration)
+        LGR_HIP(ctx, hipMemcpyAsync(trim->info, d_info, (size_t) hs.n_eval * sizeof(lgr_icp_trim_step), hipMemcpyDeviceToHost, ctx->stream));
+        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return LGR_OK;
 }
 
@@ -472,4 +705,133 @@ extern "C" int lgr_icp_ex_host(lgr_ctx* ctx, const float* src, int ns, const flo
         staged.weights = dw;
     }
     return lgr_icp_ex_dev(ctx, ds, ns, dt, nt, T0, &staged, out, trace, n_trace);
+}
+
+// ---- trimmed ICP (include/lgr.h lgr_icp_trim*)
+namespace {
+
+bool trim_params_ok(const lgr_icp_trim_params* p) {
+    if (!p) return false;
+    for (int r : p->reserved)
+        if (r) return false;
+    if (!(p->keep > 0.f && p->keep <= 1.f)) return false;
+    if (!(p->scale_from_median >= 0.f && p->scale_from_median <= FLT_MAX)) return false;
+    lgr_icp_ex_params ex = p->ex;
+    if (p->scale_from_median > 0.f) {
+        if (ex.robust == LGR_ICP_ROBUST_NONE) return false;
+        ex.robust_scale = 1.f;   // not read: not validated
+    }
+    return ex_params_ok(&ex);
+}
+
+bool trim_neutral(const lgr_icp_trim_params* p) { return p->keep == 1.f && p->scale_from_median == 0.f; }
+
+// the neutral call: lgr_icp_ex*'s bytes, and info from its trace
+template <class Fn>
+int trim_forward(lgr_ctx* ctx, Fn fn, const float* src, int ns, const float* tgt, int nt, const float T0[16], const lgr_icp_trim_params* p, lgr_icp_result* out,
+                 lgr_icp_step* trace, lgr_icp_trim_step* info, int* n_trace) {
+    std::vector<lgr_icp_step> own;
+    lgr_icp_step* tr = trace;
+    if (info && !trace) {
+        own.resize((size_t) std::max(p->ex.base.max_iterations, 1));
+        tr = own.data();
+    }
+    int n = 0;
+    LGR_TRY(fn(ctx, src, ns, tgt, nt, T0, &p->ex, out, tr, tr ? &n : nullptr));
+    for (int k = 0; info && k < n; ++k)
+        info[k] = lgr_icp_trim_step{tr[k].pairs, tr[k].pairs, 0.f, p->ex.robust == LGR_ICP_ROBUST_NONE ? 0.f : (float) (double) p->ex.robust_scale};
+    if (n_trace) *n_trace = n;
+    return LGR_OK;
+}
+
+}  // namespace
+
+extern "C" void lgr_default_icp_trim_params(lgr_icp_trim_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    lgr_default_icp_ex_params(&p->ex);
+    p->keep = 1.f;
+}
+
+extern "C" int lgr_icp_trim_dev(lgr_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float T0[16], const lgr_icp_trim_params* p,
+                                lgr_icp_result* out, lgr_icp_step* trace, lgr_icp_trim_step* info, int* n_trace) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, T0 && out && ns >= 0 && (d_src || ns == 0) && d_tgt && nt > 1 && trim_params_ok(p) && aligned16(d_src) && aligned16(d_tgt), LGR_ERR_INVALID_ARG);
+    LGR_CHECK(ctx, (!trace && !info) || n_trace, LGR_ERR_INVALID_ARG);
+    if (trim_neutral(p)) return trim_forward(ctx, lgr_icp_ex_dev, d_src, ns, d_tgt, nt, T0, p, out, trace, info, n_trace);
+    const lgr_icp_ex_params& ex = p->ex;
+    const float eps = ex.plane_eps == 0.f ? 1e-3f : ex.plane_eps;
+    const IcpEx X{(double) ex.robust_scale, (double) ex.min_normal_cos, 1.0 - (double) eps, ex.weights};
+    const IcpTrimRun run{ex.variant, IcpTrim{ex.robust, ex.min_normal_cos > -1.f, p->keep, p->scale_from_median, ex.robust_scale}, info};
+    return icp_run(ctx, nullptr, X, d_src, ns, d_tgt, nt, T0, &ex.base, out, trace, n_trace, &run);
+}
+
+extern "C" int lgr_icp_trim_host(lgr_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float T0[16], const lgr_icp_trim_params* p,
+                                 lgr_icp_result* out, lgr_icp_step* trace, lgr_icp_trim_step* info, int* n_trace) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, T0 && out && ns >= 0 && (src || ns == 0) && tgt && nt > 1 && trim_params_ok(p) && ((!trace && !info) || n_trace), LGR_ERR_INVALID_ARG);
+    if (trim_neutral(p)) return trim_forward(ctx, lgr_icp_ex_host, src, ns, tgt, nt, T0, p, out, trace, info, n_trace);
+    float *ds, *dt, *dw;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.clouds(src, ns, tgt, nt, &ds, &dt));
+    lgr_icp_trim_params staged = *p;
+    if (p->ex.weights) {
+        LGR_TRY(hc.in(p->ex.weights, (size_t) ns, &dw, 1));
+        staged.ex.weights = dw;
+    }
+    return lgr_icp_trim_dev(ctx, ds, ns, dt, nt, T0, &staged, out, trace, info, n_trace);
+}
+
+// ---- the select alone (include/lgr.h lgr_rank_select*)
+extern "C" int lgr_rank_select_dev(lgr_ctx* ctx, const float* d_keys, const uint8_t* d_valid, int n, const int64_t* ranks, int n_ranks, int32_t* out_index,
+                                   float* out_key, uint8_t* d_below, int64_t* n_valid) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, n >= 0 && (d_keys || n == 0) && ranks && n_ranks >= 1 && n_ranks <= 2 && out_index && out_key && n_valid, LGR_ERR_INVALID_ARG);
+    SelState res{};
+    if (n > 0) {
+        LGR_HIP(ctx, hipSetDevice(ctx->device));
+        SelWork* W;
+        char* h;
+        LGR_TRY(lgr_ws_t(ctx, WS_ICP_SEL, 1, &W));
+        LGR_TRY(lgr_pinned(ctx, sizeof(SelState), (void**) &h));
+        LGR_HIP(ctx, hipMemsetAsync(W, 0, sizeof(SelWork), ctx->stream));
+        const SelRanks A{0, 1.f, {(long long) ranks[0], (long long) ranks[n_ranks - 1]}};
+        sel_enqueue(ctx->stream, nullptr, (const uint32_t*) d_keys, d_valid, n, A, W);
+        if (d_below) sel_below_kernel<<<(unsigned) cdivz((size_t) n, SEL_BLOCK), SEL_BLOCK, 0, ctx->stream>>>((const uint32_t*) d_keys, d_valid, n, W, (long long) ranks[0], d_below);
+        LGR_HIP(ctx, hipGetLastError());
+        LGR_HIP(ctx, hipMemcpyAsync(h, &W->st[SEL_MAX_PASSES], sizeof(SelState), hipMemcpyDeviceToHost, ctx->stream));
+        LGR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(&res, h, sizeof res);
+    }
+    *n_valid = res.P;
+    for (int q = 0; q < n_ranks; ++q) {
+        const bool ok = n > 0 && ranks[q] >= 0 && ranks[q] < res.P && res.ok[q];
+        if (!ok) {
+            LGR_CHECK(ctx, q == 0 && ranks[0] == res.P, LGR_ERR_INVALID_ARG);
+            out_index[0] = -1; out_key[0] = 0.f;
+            continue;
+        }
+        out_index[q] = (int32_t) (uint32_t) res.prefix[q];
+        out_key[q] = icp_trim_key_value((uint32_t) (res.prefix[q] >> 32));
+    }
+    return LGR_OK;
+}
+
+extern "C" int lgr_rank_select_host(lgr_ctx* ctx, const float* keys, const uint8_t* valid, int n, const int64_t* ranks, int n_ranks, int32_t* out_index, float* out_key,
+                                    uint8_t* below, int64_t* n_valid) {
+    lgr_turn turn__(ctx);
+    if (!ctx) return LGR_ERR_INVALID_ARG;
+    LGR_CHECK(ctx, n >= 0 && (keys || n == 0) && ranks && n_ranks >= 1 && n_ranks <= 2 && out_index && out_key && n_valid, LGR_ERR_INVALID_ARG);
+    float* dk;
+    uint8_t *dv = nullptr, *db = nullptr;
+    lgr_host_call hc(ctx);
+    LGR_TRY(hc.in(keys, (size_t) n, &dk, 1));
+    if (valid) LGR_TRY(hc.in(valid, (size_t) n, &dv, LGR_PAD_MASK));
+    if (below) LGR_TRY(hc.out((size_t) n, &db, LGR_PAD_MASK));
+    LGR_TRY(lgr_rank_select_dev(ctx, dk, dv, n, ranks, n_ranks, out_index, out_key, db, n_valid));
+    LGR_TRY(hc.fetch(below, db, (size_t) n));
+    return hc.finish();
 }

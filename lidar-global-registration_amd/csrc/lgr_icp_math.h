@@ -6,7 +6,9 @@
 //   icp_rotation   R from the unit quaternion (1, w / 2) / |(1, w / 2)|: nine polynomial expressions, no trigonometry;
 //   icp_compose    T' = [R | (c - R c) + t] o T, every entry formed in f64 and rounded to f32 once;
 //   icp_norm3, icp_rmse, icp_next_dist   the scalars of the stop rule, the report and the next iteration's distance;
-//   icp_inv_sym3, icp_robust_weight      lgr_icp_ex*: the inverse of plane-to-plane's 3 x 3 covariance sum, the M-estimators' weights.
+//   icp_inv_sym3, icp_robust_weight      lgr_icp_ex*: the inverse of plane-to-plane's 3 x 3 covariance sum, the M-estimators' weights;
+//   icp_trim_key, icp_trim_k, icp_trim_median_rank, icp_trim_scale, icp_trim_weight   lgr_icp_trim*: the key that orders the pairs, K from
+//                  keep and P, the median's rank, k of the iteration and the weight under it.
 // Every operation is one IEEE binary64 + - * / sqrt (binary32 where a float is named); compile with -ffp-contract=off on both sides (the
 // Makefile and the tests do).  The pairing, the 28 terms of a point and the balanced tree that sums them are NOT here: the kernels
 // (icp_terms_kernel, icp_tree_kernel) and the statements each write them on their own.
@@ -57,6 +59,42 @@ ICP_HD double icp_robust_weight(int kind, double rho, double k) {
     }
     return 1.0;
 }
+
+// ---- trimmed ICP (lgr_icp_trim*; DESIGN.md section 4, "Trimmed ICP"): the scalar pieces the device and tests/cpp/icp_trim_ref.cpp share.
+// How the ranks are found is NOT here: the device selects by radix (lgr_rank_select.cuh), the statement sorts.
+
+// key = (float) rho as its bit pattern.  true: the key is finite and carries no sign bit, so that its bits order as a uint32 the way the
+// values order as floats -- the point is a candidate.  (A finite rho of this loop stays far below FLT_MAX: max_dist <= 1e18.)
+ICP_HD bool icp_trim_key(double rho, uint32_t* bits) {
+    const float key = (float) rho;
+    uint32_t b;
+    __builtin_memcpy(&b, &key, 4);
+    *bits = b;
+    return b <= 0x7f7fffffu;
+}
+
+ICP_HD float icp_trim_key_value(uint32_t bits) {
+    float key;
+    __builtin_memcpy(&key, &bits, 4);
+    return key;
+}
+
+// what orders the candidates: (key, i)
+ICP_HD unsigned long long icp_trim_composite(uint32_t key_bits, uint32_t i) { return ((unsigned long long) key_bits << 32) | i; }
+
+// K = floor(keep P) of P candidates, keep in (0, 1]
+ICP_HD long long icp_trim_k(float keep, long long P) { return (long long) __builtin_floor((double) keep * (double) P); }
+
+// rank of the median among P >= 1 candidates (the lower one of an even count)
+ICP_HD long long icp_trim_median_rank(long long P) { return (P - 1) / 2; }
+
+// k of the iteration: scale_from_median x the median key (0 without a candidate) where scale_from_median > 0, else the caller's scale
+ICP_HD double icp_trim_scale(float scale_from_median, float key_median, float robust_scale) {
+    return scale_from_median > 0.f ? (double) scale_from_median * (double) key_median : (double) robust_scale;
+}
+
+// w of a kept candidate: a k that is not finite or not > 0 (a median key of 0) weighs every pair 1
+ICP_HD double icp_trim_weight(int kind, double rho, double k) { return icp_finite(k) && k > 0.0 ? icp_robust_weight(kind, rho, k) : 1.0; }
 
 // xi = -A^-1 b.  A = L D L^T with unit lower L: for column j, v_k = L(j, k) D(k) (k < j), D(j) = A(j, j) - sum_k L(j, k) v_k and
 // L(i, j) = (A(i, j) - sum_k L(i, k) v_k) / D(j), the sums subtracted one by one in ascending k.  Then L y = -b downwards, z = y / D,

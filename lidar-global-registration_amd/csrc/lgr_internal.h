@@ -156,6 +156,7 @@ enum {
     WS_DENSEF_OPS_A, WS_DENSEF_OPS_B, WS_DENSEF_MISC_A, WS_DENSEF_MISC_B, WS_DENSEF_IRR_A, WS_DENSEF_IRR_B, WS_DENSEF_U, WS_DENSEF_CNT, WS_DENSEF_CAND,
     WS_DENSEF_FB, WS_DENSEF_ISFB, WS_DENSEF_DEV, WS_DENSEF_FBROWS, WS_DENSEF_FBIDX, WS_DENSEF_FBDIST, WS_DENSEF_CENTRE,
     WS_ICP_STATE, WS_ICP_PART, WS_ICP_TRACE,   // lgr_icp.hip: the loop's state, the tree's partials level by level, the trace
+    WS_ICP_PAIR, WS_ICP_SEL, WS_ICP_INFO,      // lgr_icp.hip, trimmed: the stored pairs, the select's states and histograms, the per-iteration info
     WS_COUNT
 };
 static_assert(WS_COUNT <= 224, "grow lgr_ctx::ws");

@@ -494,6 +494,31 @@ inline Matrix4f icpRegistration(const PointNCloud::ConstPtr& src, const PointNCl
     return icpRegistration(src, tgt, tn, options, result);
 }
 
+// ---- not in the reference: trimmed ICP from tn (lgr_icp_trim_host; DESIGN.md section 4, "Trimmed ICP").  `options` as icpRegistration's;
+// keep in (0, 1]: the fraction of each iteration's pairs, smallest residuals first, that contributes; scale_from_median > 0: the robust
+// kernel's scale is that multiple of the iteration's median residual (1.4826: the MAD rule) and options.robust_scale is not read.
+// keep 1 and scale_from_median 0 is icpRegistration.  info, when given, receives one record per evaluated iteration.
+inline Matrix4f icpRegistrationTrimmed(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn, const lgr_icp_ex_params& options,
+                                       float keep, float scale_from_median, lgr_icp_result& result, std::vector<lgr_icp_trim_step>* info = nullptr) {
+    lgr_icp_trim_params tp;
+    lgr_default_icp_trim_params(&tp);
+    tp.ex = options; tp.keep = keep; tp.scale_from_median = scale_from_median;
+    int n = 0;
+    const int room = options.base.max_iterations < 1 ? 1 : options.base.max_iterations > LGR_ICP_MAX_ITERATIONS ? LGR_ICP_MAX_ITERATIONS : options.base.max_iterations;
+    if (info) info->assign((size_t) room, lgr_icp_trim_step{});   // (a count outside [0, LGR_ICP_MAX_ITERATIONS] is refused by the call)
+    check(lgr_icp_trim_host(context(), raw(*src), (int) src->size(), raw(*tgt), (int) tgt->size(), tn.data(), &tp, &result, nullptr, info ? info->data() : nullptr, &n),
+          "icpRegistrationTrimmed");
+    if (info) info->resize((size_t) n);
+    Matrix4f out;
+    std::memcpy(out.data(), result.transformation, 64);
+    return out;
+}
+inline Matrix4f icpRegistrationTrimmed(const PointNCloud::ConstPtr& src, const PointNCloud::ConstPtr& tgt, const Matrix4f& tn, const lgr_icp_ex_params& options,
+                                       float keep, float scale_from_median) {
+    lgr_icp_result result;
+    return icpRegistrationTrimmed(src, tgt, tn, options, keep, scale_from_median, result);
+}
+
 // ---- include/hypotheses.h:10-12
 inline void updateHypotheses(std::vector<Matrix4f>& transformations, std::vector<float>& metrics, const Matrix4f& new_transformation,
                              float new_metric, const AlignmentParameters& parameters) {

@@ -237,6 +237,7 @@ class IcpResult(C.Structure):
     _fields_ = [("transformation", C.c_float * 16), ("iterations", C.c_int32), ("stop", C.c_int32), ("max_dist", C.c_float), ("pairs", C.c_int32),
                 ("rmse", C.c_float), ("pairs0", C.c_int32), ("rmse0", C.c_float), ("reserved", C.c_int32 * 5)]
     trace = None   # list of IcpStep (trace=True), set by Context.icp_plane*
+    info = None    # list of IcpTrimStep, set by Context.icp_trim*
 
     def matrix(self):
         return np.array(self.transformation, dtype=np.float32).reshape(4, 4).T.copy()
@@ -281,6 +282,28 @@ def icp_ex_params(variant=None, robust=None, robust_scale=None, min_normal_cos=N
             setattr(p, name, float(v))
     if weights is not None:
         p.weights = _ptr(weights).value
+    return p
+
+
+class IcpTrimParams(C.Structure):
+    """lgr_icp_trim_params (include/lgr.h)"""
+    _fields_ = [("ex", IcpExParams), ("keep", C.c_float), ("scale_from_median", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class IcpTrimStep(C.Structure):
+    """lgr_icp_trim_step (include/lgr.h): the candidates, the kept ones, the cut and the robust scale of one evaluated iteration"""
+    _fields_ = [("candidates", C.c_int32), ("kept", C.c_int32), ("cut", C.c_float), ("scale", C.c_float)]
+
+
+def icp_trim_params(keep=None, scale_from_median=None, **ex_and_base):
+    """lgr_default_icp_trim_params, then the given fields; ex_and_base: the keywords of icp_ex_params"""
+    p = IcpTrimParams()
+    _lib.lgr_default_icp_trim_params(C.byref(p))
+    p.ex = icp_ex_params(**ex_and_base)
+    if keep is not None:
+        p.keep = float(keep)
+    if scale_from_median is not None:
+        p.scale_from_median = float(scale_from_median)
     return p
 
 
@@ -1713,6 +1736,57 @@ class Context:
             weights = np.ascontiguousarray(weights, np.float32)
         return self._icp_ex(_lib.lgr_icp_ex_host, src, tgt, T0, params, weights, trace,
                             dict(base_kw, variant=variant, robust=robust, robust_scale=robust_scale, min_normal_cos=min_normal_cos, plane_eps=plane_eps))
+
+    # ---- trimmed ICP and the rank select under it (include/lgr.h lgr_icp_trim*, lgr_rank_select*) ----
+    def _icp_trim(self, fn, src, tgt, T0, params, trace, kw):
+        p = params if params is not None else icp_trim_params(**kw)
+        out = IcpResult()
+        n = max(p.ex.base.max_iterations, 1)
+        tr = (IcpStep * n)() if trace else None
+        info = (IcpTrimStep * n)()
+        n_tr = C.c_int(0)
+        self.check(fn(self.h, _ptr(src), src.shape[0], _ptr(tgt), tgt.shape[0], self._T16(T0), C.byref(p), C.byref(out), tr, info, C.byref(n_tr)))
+        if trace:
+            out.trace = [tr[i] for i in range(n_tr.value)]
+        out.info = [info[i] for i in range(n_tr.value)]
+        return out
+
+    def icp_trim(self, src, tgt, T0, keep=1.0, scale_from_median=0.0, trace=False, weights=None, params=None, **ex_and_base):
+        """lgr_icp_trim_dev on cuda clouds [n, 12]: the loop of icp_ex where each iteration keeps the fraction `keep` of its pairs with the
+        smallest residuals and, with scale_from_median > 0, scales the robust kernel by that multiple of the median residual (1.4826: the
+        MAD rule) -> IcpResult as icp_ex's plus .info, one IcpTrimStep (candidates, kept, cut, scale) per evaluated iteration.
+        ex_and_base: the keywords of capi.icp_ex_params; params: a ready IcpTrimParams instead of all of these."""
+        if weights is not None:
+            weights = weights.contiguous()
+        return self._icp_trim(_lib.lgr_icp_trim_dev, src, tgt, T0, params, trace, dict(ex_and_base, keep=keep, scale_from_median=scale_from_median, weights=weights))
+
+    def icp_trim_host(self, src, tgt, T0, keep=1.0, scale_from_median=0.0, trace=False, weights=None, params=None, **ex_and_base):
+        """lgr_icp_trim_host: numpy in (weights a numpy float32 [ns] or None), IcpResult with .info out"""
+        src = np.ascontiguousarray(src, np.float32); tgt = np.ascontiguousarray(tgt, np.float32)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.float32)
+        return self._icp_trim(_lib.lgr_icp_trim_host, src, tgt, T0, params, trace, dict(ex_and_base, keep=keep, scale_from_median=scale_from_median, weights=weights))
+
+    def _rank_select(self, fn, keys, ranks, valid, below):
+        ranks = [int(r) for r in np.atleast_1d(ranks)]
+        n = int(keys.shape[0])
+        r = (C.c_int64 * len(ranks))(*ranks)
+        idx, key, nv = (C.c_int32 * len(ranks))(), (C.c_float * len(ranks))(), C.c_int64(-1)
+        self.check(fn(self.h, _ptr(keys), _ptr(valid), n, r, len(ranks), idx, key, _ptr(below), C.byref(nv)))
+        return dict(index=list(idx), key=[np.float32(k) for k in key], below=below, n_valid=nv.value)
+
+    def rank_select(self, keys, ranks, valid=None):
+        """lgr_rank_select_dev: keys a cuda float32 [n], valid a cuda uint8 [n] or None, ranks one or two ranks of the order (key, i) over
+        the counted elements -> dict(index, key: per rank; below: cuda uint8 [n], position < ranks[0]; n_valid)"""
+        import torch
+        below = torch.empty(max(int(keys.shape[0]), 1), dtype=torch.uint8, device=keys.device)[:keys.shape[0]]
+        return self._rank_select(_lib.lgr_rank_select_dev, keys.contiguous(), ranks, valid.contiguous() if valid is not None else None, below)
+
+    def rank_select_host(self, keys, ranks, valid=None):
+        """lgr_rank_select_host: numpy in, dict(index, key, below: numpy uint8 [n], n_valid) out"""
+        keys = np.ascontiguousarray(keys, np.float32)
+        valid = np.ascontiguousarray(valid, np.uint8) if valid is not None else None
+        return self._rank_select(_lib.lgr_rank_select_host, keys, ranks, valid, np.zeros(len(keys), np.uint8))
 
     def analysis_metric(self, src, tgt, corr, T, T_gt=None, metric_id=METRIC_UNIFORMITY, score_id=SCORE_MSE, weights=None, weight=None):
         """lgr_analysis_metric_dev: what AlignmentAnalysis::start's first statement and buildCorrectInliers yield under metric_id -> MetricEval

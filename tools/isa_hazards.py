@@ -367,7 +367,7 @@ GATED = ["normals_kernel", "normals_wave_kernel", "refit_kernel", "hypotheses_ke
          "vote_matches_kernel", "ratio_test_kernel", "gt_foot_kernel", "gt_batch_kernel", "gt_seqsum_wide_kernel",
          "ho_small_kernel", "ho_act_kernel", "ho_keys_kernel",
          "teaser_adj_kernel", "teaser_clique_kernel", "teaser_rotation_kernel", "teaser_shift_kernel", "teaser_mask_kernel",
-         "icp_terms_kernel", "icp_tree_kernel", "icp_step_kernel"]
+         "icp_terms_kernel", "icp_tree_kernel", "icp_step_kernel", "icp_pair_kernel", "icp_trim_terms_kernel", "sel_hist_kernel", "sel_finish_kernel"]
 
 
 SCRATCH_ANY = 64   # bytes of scratch memory per work item that no kernel of the library may exceed (the gated ones: none at all)

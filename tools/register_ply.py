@@ -7,7 +7,8 @@
                                  [--debug-dir DIR] [--hypotheses N [--hypotheses-plane]] [--refine N]
                                  [--icp N [--icp-max-dist D] [--icp-shrink S [--icp-min-dist M]]
                                   [--icp-variant plane|point|plane2plane] [--icp-robust none|huber|cauchy|tukey --icp-robust-scale K]
-                                  [--icp-normal-angle DEG] [--icp-weight WEIGHT_ID] [--icp-plane-eps E]]
+                                  [--icp-normal-angle DEG] [--icp-weight WEIGHT_ID] [--icp-plane-eps E]
+                                  [--icp-trim KEEP] [--icp-robust-median MULT]]
                                  [--measure N [--measure-seed S0] [--measurements test_measurements.csv]] [--save-features DIR]
                                  [--order canonical|reference] [--alignment ransac|gror|teaser]
 
@@ -42,6 +43,10 @@ section 4, "ICP variants") instead: point-to-plane, point-to-point or plane-to-p
 units of the variant's residual: a distance, for plane2plane a Mahalanobis distance), pairs rejected when the angle between the moved source
 normal and the target normal exceeds DEG (the tool hands the cosine to the ABI), and the source's weight map of --icp-weight (the maps of
 lgr_weights; harris and tomasi stay refused) as per-point weights.  Without any of them --icp takes the lgr_icp_plane path as before.
+With --icp-trim KEEP or --icp-robust-median MULT the iterations run through lgr_icp_trim ("Trimmed ICP"): each iteration
+keeps the fraction KEEP of its pairs with the smallest residuals, and the kernel of --icp-robust takes MULT x the iteration's median residual as
+its scale (1.4826: the MAD rule; --icp-robust-scale is then not needed).  The tool then also prints the candidates, the kept pairs, the cut and
+the scale of the first and the last iteration.
 With --measure N (needs --ground-truth): the reference's `measure` test type (measureTestResults, src/main.cpp:312-382) through lgr_measure --
 N alignments that differ in the RANSAC seed only (S0, S0 + 1, ...; S0 defaults to the profile's seed), one correspondence search for all of
 them, all judged against the ground truth in one batch; one line per run, then the aggregate row, appended to --measurements when given
@@ -117,6 +122,9 @@ def main():
     ap.add_argument("--icp-weight", default=None, choices=["constant", "exp_curvature", "curvedness", "curvature", "nss"],
                     help="per-point weights of the ICP: the source's weight map of that name (src/weights.cpp)")
     ap.add_argument("--icp-plane-eps", type=float, default=None, metavar="E", help="plane2plane: the covariance along the normal, 1e-6 .. 1 (default 1e-3)")
+    ap.add_argument("--icp-trim", type=float, default=None, metavar="KEEP", help="trimmed ICP (lgr_icp_trim): the fraction of each iteration's pairs that is kept, in (0, 1]")
+    ap.add_argument("--icp-robust-median", type=float, default=None, metavar="MULT",
+                    help="scale of --icp-robust = MULT x the iteration's median residual (1.4826: the MAD rule) instead of --icp-robust-scale")
     ap.add_argument("--measure", type=int, default=0, metavar="N",
                     help="the measure test type: N seeded runs judged against --ground-truth, and their test_measurements.csv row")
     ap.add_argument("--measure-seed", type=int, default=None, metavar="S0", help="seed of the first run (default: the profile's seed); run i uses S0 + i")
@@ -149,7 +157,17 @@ def main():
     a.icp_ex = any(v is not None for v in (a.icp_variant, a.icp_robust, a.icp_robust_scale, a.icp_normal_angle, a.icp_weight, a.icp_plane_eps))
     if a.icp_ex and not a.icp:
         ap.error("the --icp-* options need --icp N")
-    if (a.icp_robust not in (None, "none")) != (a.icp_robust_scale is not None):
+    a.icp_trimmed = a.icp_trim is not None or a.icp_robust_median is not None
+    if a.icp_trimmed and not a.icp:
+        ap.error("the --icp-* options need --icp N")
+    if a.icp_trim is not None and not 0.0 < a.icp_trim <= 1.0:
+        ap.error("--icp-trim takes a fraction in (0, 1]")
+    if a.icp_robust_median is not None:
+        if not a.icp_robust_median > 0.0 or a.icp_robust_median == float("inf"):
+            ap.error("--icp-robust-median takes a finite multiplier > 0")
+        if a.icp_robust in (None, "none") or a.icp_robust_scale is not None:
+            ap.error("--icp-robust-median needs --icp-robust huber|cauchy|tukey and replaces --icp-robust-scale")
+    elif (a.icp_robust not in (None, "none")) != (a.icp_robust_scale is not None):
         ap.error("--icp-robust huber|cauchy|tukey and --icp-robust-scale go together")
     if a.icp_robust_scale is not None and not a.icp_robust_scale > 0.0:
         ap.error("--icp-robust-scale takes a scale > 0")
@@ -316,13 +334,19 @@ def icp(ctx, capi, formats, a, p, clouds, res, T, name, lrf, density_tgt):
     min_dist = a.icp_min_dist if a.icp_min_dist > 0 else (0.5 * density_tgt if a.icp_shrink < 1.0 else 0.0)
     base = dict(max_iterations=a.icp, max_dist=a.icp_max_dist, min_dist=min_dist, shrink=a.icp_shrink)
     t = time.perf_counter()
-    if a.icp_ex:
+    if a.icp_ex or a.icp_trimmed:
         w = ctx.weights(clouds[0], a.icp_weight, with_sum=False)[0] if a.icp_weight is not None else None
         cos = math.cos(math.radians(a.icp_normal_angle)) if a.icp_normal_angle is not None else -1.0
-        r = ctx.icp_ex(clouds[0], clouds[1], T, variant=a.icp_variant or "plane", robust=a.icp_robust or "none", robust_scale=a.icp_robust_scale or 0.0,
-                       min_normal_cos=max(-1.0, min(1.0, cos)), plane_eps=a.icp_plane_eps or 0.0, weights=w, **base)
+        ex = dict(variant=a.icp_variant or "plane", robust=a.icp_robust or "none", robust_scale=a.icp_robust_scale or 0.0, min_normal_cos=max(-1.0, min(1.0, cos)),
+                  plane_eps=a.icp_plane_eps or 0.0, weights=w)
+        if a.icp_trimmed:
+            r = ctx.icp_trim(clouds[0], clouds[1], T, keep=a.icp_trim if a.icp_trim is not None else 1.0, scale_from_median=a.icp_robust_median or 0.0, **ex, **base)
+        else:
+            r = ctx.icp_ex(clouds[0], clouds[1], T, **ex, **base)
         how = f" ({a.icp_variant or 'plane'}, robust {a.icp_robust or 'none'}" + (f" {a.icp_robust_scale:.6g}" if a.icp_robust_scale else "") + \
-            (f", normals within {a.icp_normal_angle:.6g} deg" if a.icp_normal_angle is not None else "") + (f", weights {a.icp_weight}" if a.icp_weight else "") + ")"
+            (f" {a.icp_robust_median:.6g} x median" if a.icp_robust_median else "") + \
+            (f", normals within {a.icp_normal_angle:.6g} deg" if a.icp_normal_angle is not None else "") + (f", weights {a.icp_weight}" if a.icp_weight else "") + \
+            (f", keep {a.icp_trim:.6g}" if a.icp_trim is not None else "") + ")"
     else:
         r = ctx.icp_plane(clouds[0], clouds[1], T, **base)
         how = ""
@@ -330,6 +354,9 @@ def icp(ctx, capi, formats, a, p, clouds, res, T, name, lrf, density_tgt):
     print(f"\nicp{how} in {1e3 * dt:.1f} ms: {r.iterations} iterations of at most {a.icp}, stopped by {capi.ICP_STOP_NAMES[r.stop]} (max_dist {r.max_dist:.6g})")
     print(f"  first: pairs={r.pairs0} rmse={r.rmse0:.7f}")
     print(f"   last: pairs={r.pairs} rmse={r.rmse:.7f}")
+    if a.icp_trimmed:
+        for label, s in (("first", r.info[0]), (" last", r.info[-1])) if r.info else ():
+            print(f"  {label} trim: candidates={s.candidates} kept={s.kept} cut={s.cut:.7f} scale={s.scale:.7f}")
     Ti = r.matrix()
     print(np.array2string(Ti, precision=6, suppress_small=True))
     if a.out:
