@@ -86,10 +86,16 @@ __device__ __forceinline__ float lgr_det3(const float* M) {
 template <bool WANT_U = true>
 __device__ __forceinline__ void lgr_svd3(const float* A, float* U, float* S, float* V) {
     float W[3][3], Vm[3][3];
+    // a matrix whose largest |entry| is below 2^-24 is scaled by the power of two that brings that entry into [0.5, 1) and S is scaled
+    // back (both exact; c_svd3 says why).  ex = 0 everywhere else, and ldexp by 0 returns its argument: no bit changes there.
+    float amax = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { const float a = fabsf(A[i]); amax = (a > amax) ? a : amax; }
+    const int ex = (amax < 0x1p-24f && amax > 0.0f) ? __builtin_amdgcn_frexp_expf(amax) : 0;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { W[i][j] = A[3 * i + j]; Vm[i][j] = (i == j) ? 1.0f : 0.0f; }
+        for (int j = 0; j < 3; ++j) { W[i][j] = __builtin_ldexpf(A[3 * i + j], -ex); Vm[i][j] = (i == j) ? 1.0f : 0.0f; }
     for (int sweep = 0; sweep < 12; ++sweep) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -133,7 +139,7 @@ __device__ __forceinline__ void lgr_svd3(const float* A, float* U, float* S, flo
     if (sgv(o2) > sgv(o1)) { int t = o1; o1 = o2; o2 = t; }
     auto col = [&](const float (&M)[3][3], int i, int o) { return (o == 0) ? M[i][0] : ((o == 1) ? M[i][1] : M[i][2]); };
     const float s0 = sgv(o0), s1 = sgv(o1), s2 = sgv(o2);
-    S[0] = s0; S[1] = s1; S[2] = s2;
+    S[0] = __builtin_ldexpf(s0, ex); S[1] = __builtin_ldexpf(s1, ex); S[2] = __builtin_ldexpf(s2, ex);   // (s0, s1, s2 below: of the scaled matrix)
 #pragma unroll
     for (int i = 0; i < 3; ++i) { V[3 * i + 0] = col(Vm, i, o0); V[3 * i + 1] = col(Vm, i, o1); V[3 * i + 2] = col(Vm, i, o2); }
     if constexpr (WANT_U) {

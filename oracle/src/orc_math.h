@@ -85,10 +85,19 @@ static inline float c_expf(float x) {
 
 // 3x3 SVD by one-sided (Hestenes) Jacobi. A row-major; A = U diag(S) V^T, S descending, U/V row-major, orthonormal.
 // Fixed 12 sweeps over (0,1),(0,2),(1,2); a pair is skipped when gamma^2 <= 1e-14 * alpha * beta.
+// A matrix whose largest |entry| is below 2^-24 is first scaled by the power of two that brings that entry into [0.5, 1), and S is
+// scaled back at the end.  Both scalings are exact, and everything between is invariant under a power of two as long as nothing leaves
+// f32's normal range -- but gamma^2 is of fourth order in the entries and reaches zero (every pair "converged", V = I, U not orthogonal)
+// long before the entries do: a wrong skip at relative size 1e-7 needs gamma < 2^-75, that is entries near 2^-26.  At and above 2^-24
+// nothing is scaled, so nothing there changes by a bit.
 static inline void c_svd3(const float A[9], float U[9], float S[3], float V[9]) {
     float W[3][3], Vm[3][3];
+    float amax = 0.0f;
+    for (int i = 0; i < 9; ++i) { float a = std::fabs(A[i]); if (a > amax) amax = a; }
+    int ex = 0;
+    if (amax < 0x1p-24f && amax > 0.0f) std::frexp(amax, &ex);
     for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) { W[i][j] = A[3 * i + j]; Vm[i][j] = (i == j) ? 1.0f : 0.0f; }
+        for (int j = 0; j < 3; ++j) { W[i][j] = ex ? std::ldexp(A[3 * i + j], -ex) : A[3 * i + j]; Vm[i][j] = (i == j) ? 1.0f : 0.0f; }
     static const int PQ[3][2] = {{0, 1}, {0, 2}, {1, 2}};
     for (int sweep = 0; sweep < 12; ++sweep) {
         for (int k = 0; k < 3; ++k) {
@@ -121,19 +130,21 @@ static inline void c_svd3(const float A[9], float U[9], float S[3], float V[9]) 
         for (int b = a + 1; b < 3; ++b)
             if (sg[ord[b]] > sg[ord[a]]) { int tmp = ord[a]; ord[a] = ord[b]; ord[b] = tmp; }
     float Uc[3][3];  // Uc[j] = j-th column
+    float Ss[3];     // sigma of the scaled matrix
     for (int j = 0; j < 3; ++j) {
         int o = ord[j];
-        S[j] = sg[o];
+        Ss[j] = sg[o];
+        S[j] = ex ? std::ldexp(sg[o], ex) : sg[o];
         for (int i = 0; i < 3; ++i) { V[3 * i + j] = Vm[i][o]; Uc[j][i] = W[i][o]; }
     }
-    float tiny = 1e-5f * S[0];
-    if (!(S[0] > 0.0f)) {  // zero matrix
+    float tiny = 1e-5f * Ss[0];
+    if (!(Ss[0] > 0.0f)) {  // zero matrix
         for (int i = 0; i < 9; ++i) U[i] = (i % 4 == 0) ? 1.0f : 0.0f;
         return;
     }
-    for (int i = 0; i < 3; ++i) Uc[0][i] = Uc[0][i] / S[0];
-    if (S[1] > tiny) {
-        for (int i = 0; i < 3; ++i) Uc[1][i] = Uc[1][i] / S[1];
+    for (int i = 0; i < 3; ++i) Uc[0][i] = Uc[0][i] / Ss[0];
+    if (Ss[1] > tiny) {
+        for (int i = 0; i < 3; ++i) Uc[1][i] = Uc[1][i] / Ss[1];
     } else {
         // rank 1: any unit vector orthogonal to u0: cross with the axis of smallest |component|
         float a0 = std::fabs(Uc[0][0]), a1 = std::fabs(Uc[0][1]), a2 = std::fabs(Uc[0][2]);
@@ -148,8 +159,8 @@ static inline void c_svd3(const float A[9], float U[9], float S[3], float V[9]) 
         float nn = std::sqrt((cx * cx + cy * cy) + cz * cz);
         Uc[1][0] = cx / nn; Uc[1][1] = cy / nn; Uc[1][2] = cz / nn;
     }
-    if (S[2] > tiny) {
-        for (int i = 0; i < 3; ++i) Uc[2][i] = Uc[2][i] / S[2];
+    if (Ss[2] > tiny) {
+        for (int i = 0; i < 3; ++i) Uc[2][i] = Uc[2][i] / Ss[2];
     } else {
         Uc[2][0] = Uc[0][1] * Uc[1][2] - Uc[0][2] * Uc[1][1];
         Uc[2][1] = Uc[0][2] * Uc[1][0] - Uc[0][0] * Uc[1][2];

@@ -396,6 +396,10 @@ void refit(const float* src, const float* tgt, const lgr_orc_corr* corr, int c, 
         for (int a = 0; a < 3; ++a) { cs[a] += p[a]; ct[a] += q[a]; }
         ++n;
     }
+    // no inlier: 0/0 centroids.  Read literally the reference leaves the rotation at the SVD of a zero matrix (identity) beside a NaN
+    // translation; this project records the whole matrix as NaN (orc_ransac's final block, refit_kernel), which no later step can tell
+    // apart: every distance under either is NaN.  Stated here so that the entry and the device kernel have one answer.
+    if (n == 0) { for (int i = 0; i < 16; ++i) T[i] = std::numeric_limits<float>::quiet_NaN(); return; }
     for (int a = 0; a < 3; ++a) { cs[a] /= (float) n; ct[a] /= (float) n; }
     float H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = 0; i < c; ++i) {

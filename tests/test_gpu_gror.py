@@ -4,8 +4,14 @@ src/alignment.cpp:21-35) vs the oracle.
 Bars: node degrees, inlier masks and counts bit-exact (integers); the final 4x4 is a float sequence restated op for
 op, compared bit-exact, and within 1e-2 / 1e-3 of the synthetic ground truth (GROR refines over noisy inliers).
 """
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from fit_ref_lib import same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -67,8 +73,7 @@ def test_gror_no_consistent_set(lgr, oracle):
     res, mask = ctx.gror(cuda(pr["src"]), cuda(pr["tgt"]), pr["corr"], 0.05)
     T_o, d = oracle.gror(pr["src"], pr["tgt"], to_orc_corr(oracle, pr["corr"]), 0.05, 800)
     assert int(res.metric) == d["best_count"] and res.n_inliers == d["n_inliers"]
-    if d["n_inliers"] > 0:
-        assert np.array_equal(bits(res.matrix()), bits(T_o))
+    assert same_bits(res.matrix(), T_o)   # NaN by position: an empty refinement set leaves 0 * inf in every sum
 
 
 def test_gror_host_entry_and_mask(lgr, oracle):
